@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the FEM hot path: fused energy loss + gradient (one pass) on BASELINE.json configs[1]'s mesh.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--settle S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--settle S] [--dump-outputs DIR]
 
 `value` / `ms_per_step`: W untimed warm-up steps, then exactly K timed steps.  The same W + K steps are run a second time after S = 400
 further untimed steps and reported as `steady_state` (for 1.3-10 ms after load onset the part runs every kernel 10-25 % slower, and
@@ -110,6 +110,25 @@ def make_inputs(shape, dev, seed):
         idx[d] = -1
         bc[tuple(idx)] = 1
     return [t.to(dev) if dev is not None else t for t in (u, nu, f, bc)]
+
+
+DUMP_SAMPLE = 1 << 22          # --dump-outputs: elements kept of a larger output (16 MB of float32)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each float32 / float64 tensor of `arrays` as path/<name>.npy.  One of more than DUMP_SAMPLE elements is written
+    as the DUMP_SAMPLE of its flattened elements that a generator seeded with 0 picks (ascending flat indices): the same elements in
+    every run of the same arguments, and under 64 MB in all."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        if a.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"--dump-outputs: {name} is {a.dtype}, not float32 / float64")
+        if a.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a.numpy())
 
 
 def host_cores():
@@ -571,7 +590,15 @@ def main():
     ap.add_argument("--slab-batch", type=int, default=1, help="samples of the slab leg's mesh (BASELINE configs[3] is parametric: the reference trains it with batch 8)")
     ap.add_argument("--slab-timeout", type=float, default=180.0, help="watchdog of the slab leg, seconds")
     ap.add_argument("--no-slab-b8", action="store_true", help="skip the batch-8 repetition of the slab leg (`slab_3d_b8`)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them returned (rank 0) as DIR/<name>.npy: loss (float32 scalar), energy "
+                         "and grad_sumsq (its float64 sums) and grad_u (the gradient wrt u; a fixed seeded sample of %d elements when larger)"
+                         % DUMP_SAMPLE)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.slab and args.dump_outputs:
+        ap.error("--dump-outputs writes the outputs of the default run, not of --slab")
     if args.async_sums:
         args.sums = "async"
     args.sync_sums = args.sums != "async"
@@ -758,6 +785,12 @@ def main():
     # (default 400: 22 ms of the same load), is the steady state a job of more than a few hundred steps is in and the regime of the roofline
     # launches below: reported as `steady_state`.
     dt, region_ms = timed_steps()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the outputs of the last timed step, copied on the device (later launches of the rotation overwrite them); written to files
+        # once the measurements of this path are done, so that the host work does not idle the GPU between them
+        grad, sums, loss = (t.clone() for t in last[0].result)
+        dumped = {"loss": loss, "energy": sums[0], "grad_sumsq": sums[1], "grad_u": grad}
     for _ in range(args.settle):
         step()
     drain()
@@ -893,6 +926,9 @@ def main():
     kern_med_ms = kern_ms[len(kern_ms) // 2]
     alg_bytes = ALG_BYTES_PER_NODE * B * m.geom.nnode_total
     achieved = alg_bytes / (kern_avg_ms * 1e-3) / 1e9
+    if dumped is not None:
+        dump_outputs(args.dump_outputs, dumped)
+        del dumped
 
     traffic, traffic_src = None, None
     try:   # HBM bytes per launch from the committed rocprofv3 PMC summary of this exact workload (profiles/)
