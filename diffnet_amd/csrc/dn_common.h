@@ -76,22 +76,7 @@ struct VecT<4> { using type = float4; };
 #endif
 template <typename V, typename T>
 __device__ __forceinline__ V ld_at(const T* __restrict__ base, unsigned index) {
-#ifdef DN_NT_LOADS          // experiment: non-temporal loads for the streamed fields (profiles/r2_ab2d_nt.txt)
-    const char* a = reinterpret_cast<const char*>(base) + (index * (unsigned)sizeof(T));
-    if constexpr (sizeof(V) == 16) {
-        typedef float v4f __attribute__((ext_vector_type(4)));
-        const v4f t = __builtin_nontemporal_load(reinterpret_cast<const v4f*>(a));
-        return __builtin_bit_cast(V, t);
-    } else if constexpr (sizeof(V) == 8) {
-        typedef float v2f __attribute__((ext_vector_type(2)));
-        const v2f t = __builtin_nontemporal_load(reinterpret_cast<const v2f*>(a));
-        return __builtin_bit_cast(V, t);
-    } else {
-        return __builtin_nontemporal_load(reinterpret_cast<const V*>(a));
-    }
-#else
     return *reinterpret_cast<const V*>(reinterpret_cast<const char*>(base) + (index * (unsigned)sizeof(T)));
-#endif
 }
 template <typename V, typename T>
 __device__ __forceinline__ void st_at(T* __restrict__ base, unsigned index, const V& v) {
@@ -164,80 +149,6 @@ __device__ __forceinline__ void load_seg_stream(const T* __restrict__ base, unsi
         dst[NW] = ld_at<T>(base, rowoff + (unsigned)min(x0 + NW, nx - 1));
     } else {
         load_seg<NW, VEC>(base, rowoff, x0, nx, dst);
-    }
-}
-
-// lane l <- lane l + 1 (whole wave), lane 63 keeps `last`
-__device__ __forceinline__ unsigned dpp_from_right_u32(unsigned v, unsigned last) {
-    return (unsigned)__builtin_amdgcn_update_dpp((int)last, (int)v, 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
-}
-
-// load_seg for NW = 4 aligned rows where the shared node x0 + 4 is the RIGHT NEIGHBOUR LANE's first node: one vector load per
-// lane; the extra value comes over DPP (wave_shl:1) and only lane 63 of each wave loads it from memory (its neighbour is in
-// the next wave).  A per-lane dword / byte load at a stride of 16 bytes touches 16 cache lines per wave-instruction; this form
-// issues it for one lane.  Requires consecutive lanes = consecutive x0 (x0 = 4 * lane + const within the wave).
-template <typename T>
-__device__ __forceinline__ void load_seg4_dpp(const T* __restrict__ base, unsigned rowoff, int x0, int nx, T (&dst)[5]) {
-    const unsigned xl = (unsigned)min(x0, nx - 4);
-    // the node right of the wave's last lane: ONE wave-uniform address -> a scalar (SMEM) load, no divergent branch
-    const unsigned eidx = (unsigned)__builtin_amdgcn_readfirstlane((int)rowoff) +
-                          (unsigned)min(__builtin_amdgcn_readfirstlane(x0) + 256, nx - 1);
-    if constexpr (sizeof(T) == 4) {
-        const float4 v = ld_at<float4>(base, rowoff + xl);
-        const unsigned bits = __float_as_uint(reinterpret_cast<const float&>(v.x));
-        const T lastv = base[eidx];
-        const float last = reinterpret_cast<const float&>(lastv);
-        const unsigned e = dpp_from_right_u32(bits, __float_as_uint(last));
-        const float vf[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dst[k] = reinterpret_cast<const T&>(vf[k]);
-        const float ef = __uint_as_float(e);
-        dst[4] = reinterpret_cast<const T&>(ef);
-    } else {
-        static_assert(sizeof(T) == 1, "load_seg4_dpp: 1- or 4-byte elements");
-        const uint32_t w = ld_at<uint32_t>(base, rowoff + xl);
-        const uint32_t last = (uint32_t)base[eidx];
-        const uint32_t e = dpp_from_right_u32(w, last);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dst[k] = (T)((w >> (8 * k)) & 0xffu);
-        dst[4] = (T)(e & 0xffu);
-    }
-}
-
-// load_seg4_dpp with the lane exchange over ds_bpermute (__shfl_down: 2-3 cycles of a shared SIMD where a DPP move costs 30-36, see
-// DESIGN.md section 4) and, optionally, the 16-byte row vector as a NON-TEMPORAL load.  In this form every byte of a row is requested
-// once per wave (plus one dword through the scalar cache for the wave's last lane): the precondition for non-temporal loads to pay
-// (tools/march_probe.py, profiles/r3_march_probe.txt: the access pattern alone 51.4 -> 47.9 us once nothing is re-read).
-template <bool NT, typename T>
-__device__ __forceinline__ void load_seg4_shfl(const T* __restrict__ base, unsigned rowoff, int x0, int nx, T (&dst)[5]) {
-    const unsigned xl = (unsigned)min(x0, nx - 4);
-    const unsigned eidx = (unsigned)__builtin_amdgcn_readfirstlane((int)rowoff) +
-                          (unsigned)min(__builtin_amdgcn_readfirstlane(x0) + 256, nx - 1);
-    const bool lastlane = (threadIdx.x & 63u) == 63u;
-    if constexpr (sizeof(T) == 4) {
-        typedef float v4f __attribute__((ext_vector_type(4)));
-        const v4f* a = reinterpret_cast<const v4f*>(reinterpret_cast<const char*>(base) + (rowoff + xl) * 4u);
-        const v4f v = NT ? __builtin_nontemporal_load(a) : *a;
-        const T lastv = base[eidx];
-        float e = __shfl_down(v.x, 1, 64);
-        // the exchange must run with every lane active: pinned here, or the compiler sinks it into the `!lastlane` side of the select
-        // below, where lane 63 -- the source of lane 62 -- is masked off and ds_bpermute returns 0 for it
-        asm volatile("" : "+v"(e));
-        const float vf[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dst[k] = reinterpret_cast<const T&>(vf[k]);
-        const float ef = lastlane ? reinterpret_cast<const float&>(lastv) : e;
-        dst[4] = reinterpret_cast<const T&>(ef);
-    } else {
-        static_assert(sizeof(T) == 1, "load_seg4_shfl: 1- or 4-byte elements");
-        const uint32_t w = ld_at<uint32_t>(base, rowoff + xl);
-        const uint32_t last = (uint32_t)base[eidx];
-        uint32_t sh = (uint32_t)__shfl_down((int)w, 1, 64);
-        asm volatile("" : "+v"(sh));          // as above: the exchange stays outside the divergent select
-        const uint32_t e = lastlane ? last : sh;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dst[k] = (T)((w >> (8 * k)) & 0xffu);
-        dst[4] = (T)(e & 0xffu);
     }
 }
 

@@ -23,7 +23,7 @@
 //
 // Measured on MI355X (profiles/r4_fsdt_stencil.txt; 1025^2 nodes, Q2, 3 x 3 points, fp32 mask, in-kernel sums): one sample 27.6 -> 21.3 us, eight
 // samples 95.9 -> 59.4 us against the element form; ~480 VALU instructions (139 packed) per element layer, 117-125 VGPRs.  With the arithmetic removed
-// (-DDN_ST_ABL_MATH) the eight-sample launch takes 52 us: the kernel sits on its access pattern; the in-kernel sums cost 4.5-6.6 us per launch, which
+// (a measurement build) the eight-sample launch took 52 us: the kernel sits on its access pattern; the in-kernel sums cost 4.5-6.6 us per launch, which
 // the loss + gradient pair avoids by deferring them to the second launch (dn_fsdt_args.defer_sums / den_workspace, fsdt_common.h).
 #include <algorithm>
 #include <cstdlib>
@@ -42,15 +42,13 @@ struct FsdtMats {
 
 enum { ST_M = 0, ST_K = 1, ST_C = 2 };
 
-#ifndef DN_ST_VEC2
-#define DN_ST_VEC2 1              // (Q2) the two own nodes of a row as ONE 8-byte access (4-byte aligned on rows of an odd number of nodes: the hardware takes it)
-#endif                            // instead of two 4-byte ones.  Equal where the arrays come out of the 256 MB cache (single launches re-run on the same buffers:
-                                  // 55.1 vs 55.4 us at eight samples), 11-15 % faster where they come from HBM -- the loss + gradient pair at eight samples:
-                                  // 130 -> 116 us with fp32 masks, 127 -> 109 us with uint8 masks (profiles/r4_fsdt_stencil.txt sections 4 and 9)
-// The thread's own nodes of a row.  NW == 2 with DN_ST_VEC2: one access of two elements at min(x0, nx - 2); the closing column (x0 == nx - 1) takes the second half.
+// (Q2) the two own nodes of a row as ONE 8-byte access (4-byte aligned on rows of an odd number of nodes: the hardware takes it)
+// instead of two 4-byte ones.  Equal where the arrays come out of the 256 MB cache (single launches re-run on the same buffers:
+// 55.1 vs 55.4 us at eight samples), 11-15 % faster where they come from HBM -- the loss + gradient pair at eight samples:
+// 130 -> 116 us with fp32 masks, 127 -> 109 us with uint8 masks (profiles/r4_fsdt_stencil.txt sections 4 and 9)
+// The thread's own nodes of a row.  NW == 2: one access of two elements at min(x0, nx - 2); the closing column (x0 == nx - 1) takes the second half.
 template <int NW, typename T>
 __device__ __forceinline__ void st_load_own(const T* __restrict__ base, unsigned rowoff, int x0, int nx, T (&dst)[NW]) {
-#if DN_ST_VEC2
     if constexpr (NW == 2) {
         const unsigned xl = (unsigned)min(x0, nx - 2);
         const bool last = x0 > nx - 2;
@@ -66,18 +64,15 @@ __device__ __forceinline__ void st_load_own(const T* __restrict__ base, unsigned
         }
         return;
     }
-#endif
     load_own<NW, false>(base, rowoff, x0, nx, dst);
 }
 template <int NW>
 __device__ __forceinline__ void st_store_own(float* __restrict__ base, unsigned rowoff, int x0, int nx, const float (&src)[NW]) {
-#if DN_ST_VEC2
     if constexpr (NW == 2) {
         if (x0 + 1 < nx) st_at<float2>(base, rowoff + (unsigned)x0, make_float2(src[0], src[1]));
         else if (x0 < nx) st_at<float>(base, rowoff + (unsigned)x0, src[0]);
         return;
     }
-#endif
     store_seg<NW, false>(base, rowoff, x0, nx, src);
 }
 
@@ -156,14 +151,6 @@ struct StGroups {
 template <int P>
 __device__ __forceinline__ void st_stage(const FsdtParams& p, st_mats_ptr m, const float (&cw)[P + 1], const st_v2f (&cxy)[P + 1], float lf, float okf,
                                          StGroups<P>& G) {
-#ifdef DN_ST_ABL_MATH             // measurement build (tools/variant_build.sh): the access pattern without the arithmetic
-#pragma unroll
-    for (int n = 0; n < P; ++n) {
-        const float t = cw[n] + cxy[n].x + cxy[n].y + cw[P] * lf + okf;
-        G.r1m[n] = G.r1c[n] = G.r1k[n] = G.r2m[n] = G.r2ct[n] = G.r2k[n] = G.r2c[n] = G.r3ct[n] = G.r3m[n] = G.r3c[n] = G.r3k[n] = t;
-    }
-    return;
-#endif
     float wL[P + 1], wR[P + 1];
     st_v2f xyL[P + 1], xyR[P + 1];
 #pragma unroll
@@ -208,11 +195,6 @@ __device__ __forceinline__ void st_stage(const FsdtParams& p, st_mats_ptr m, con
 
 template <int P, int BASE, int JIN>
 __device__ __forceinline__ void st_scatter(st_mats_ptr m, const StGroups<P>& G, float (&acc)[3][2 * P + 1][P]) {
-#ifdef DN_ST_ABL_MATH
-#pragma unroll
-    for (int n = 0; n < P; ++n) { acc[0][BASE][n] += G.r1m[n]; acc[1][BASE + 1][n] += G.r2m[n]; acc[2][BASE][n] -= G.r3m[n]; }
-    return;
-#endif
     st_yscatter<P, ST_M, false, BASE, JIN>(m, G.r1m, acc[0]);
     st_yscatter<P, ST_C, false, BASE, JIN>(m, G.r1c, acc[0]);
     st_yscatter<P, ST_K, false, BASE, JIN>(m, G.r1k, acc[0]);

@@ -24,13 +24,6 @@ namespace dn {
 
 enum : int { FL_NU = 1, FL_F = 2, FL_FGP = 4, FL_BC = 8, FL_BC_U8C = 16 };   // FL_BC_U8C: uint8 masks with constant values only
 
-#ifndef DN_Q1_2D_WAVES
-#define DN_Q1_2D_WAVES 2
-#endif
-#ifndef DN_PRIO_ROT
-#define DN_PRIO_ROT 3      // 0 = off (A/B switch); measured -7 % kernel time at the bench shape
-#endif
-
 template <int E>
 struct RawRow2D {
     float u[E + 1], n[E + 1], f[E + 1];
@@ -40,7 +33,7 @@ struct RawRow2D {
 };
 
 template <int NGP, int E, bool VEC, int FL>
-__global__ void __launch_bounds__(256, DN_Q1_2D_WAVES) poisson2d_q1_raw_kernel(const PoissonParams p) {
+__global__ void __launch_bounds__(256, 2) poisson2d_q1_raw_kernel(const PoissonParams p) {
     constexpr int NW = E;
     constexpr bool HAS_NU = (FL & FL_NU) != 0, HAS_F = (FL & FL_F) != 0, FGP = (FL & FL_FGP) != 0;
     constexpr bool BC_ANY = (FL & (FL_BC | FL_BC_U8C)) != 0, BC_U8C = (FL & FL_BC_U8C) != 0;
@@ -199,14 +192,12 @@ __global__ void __launch_bounds__(256, DN_Q1_2D_WAVES) poisson2d_q1_raw_kernel(c
     };
 
     auto set_prio = [&](int e) {
-#if DN_PRIO_ROT
-        switch (((ey_end - e) >> 1) & 3) {          // progress-dependent wave priority (see the staged form)
+        switch (((ey_end - e) >> 1) & 3) {          // progress-dependent wave priority: measured -7 % kernel time at the bench shape
             case 0: __builtin_amdgcn_s_setprio(0); break;
             case 1: __builtin_amdgcn_s_setprio(1); break;
             case 2: __builtin_amdgcn_s_setprio(2); break;
             default: __builtin_amdgcn_s_setprio(3); break;
         }
-#endif
     };
 
     RawRow2D<E> RA, RB;

@@ -41,47 +41,15 @@ struct CfRow {
     uint32_t bx[2];          //                 box-face bits of those nodes, per condition
 };
 
-#ifndef DN_Q1_2D_WAVES
-#define DN_Q1_2D_WAVES 2
-#endif
-#ifndef DN_PRIO_ROT
-#define DN_PRIO_ROT 3
-#endif
-
-#ifndef DN_CF_DPPX
-#define DN_CF_DPPX 0              // 1: E = 4 takes the shared node x0 + 4 over DPP from the neighbouring lane instead of a strided per-lane load; measured equal (profiles/r2_2d_ab.txt)
-#endif                            // 2: the same over ds_bpermute (load_seg4_shfl)
-#ifndef DN_CF_NT_LD
-#define DN_CF_NT_LD 0             // with DN_CF_DPPX == 2: 1 = non-temporal row loads of nu and f, 2 = of u as well
-#endif
-#ifndef DN_CF_FMASS
-#define DN_CF_FMASS 1
-#endif
-#ifndef DN_CF_NT_COEF
-#define DN_CF_NT_COEF 1           // 1: non-temporal vector loads for nu and f (read once per launch; the node shared with the right neighbour stays a plain
-                                  // load).  Round 2 measured it on ONE re-evaluated batch, where it gives up the Infinity-Cache hits (47 -> 53 us) and left
-                                  // it off; on batches in rotation -- every launch streams from HBM, the regime bench.py now times -- it wins: mask bits
-                                  // 58.3 -> 55.5 us, box 56.5 -> 56.0 (profiles/r3_rotate_nt.txt).  2: u as well (slower: 59.8)
-#endif
-#ifndef DN_CF_REV
-#define DN_CF_REV 0               // 1: neighbouring strips march in opposite directions and share an XCD (see the kernel): the rows two strips share
-#endif                            // are fetched once (measured traffic 1.09x -> 1.002x of the algorithmic bytes).  Faster when one batch is re-evaluated and
-                                  // its arrays partly live in the Infinity Cache (45.4 vs 47.5 us), SLOWER when every launch streams from HBM (different
-                                  // batches in rotation: 59.5 vs 56.4 us, profiles/r2_rotate_variants.txt) -- off.  0: every strip upwards, dispatch order
-#ifndef DN_CF_PF
-#define DN_CF_PF 0                // 1 / 2: software-pipelined rows (one / two raw rows in flight while a layer is computed).  Steady state, box condition
-                                  // (profiles/r2_plan2d_steady.txt): default plan 46.9 us, PF=1 48.1, PF=2 50.6; strips of 32 rows 54.5 / 48.9 / 46.3.  Off: 79 VGPRs
-#endif
-
-#ifndef DN_CF_PK
-#define DN_CF_PK 0                // 1: the element arithmetic of a layer runs on element PAIRS in packed fp32 registers (v_pk_fma_f32 ...; E even): 722 -> 536 VALU
-                                  // instructions per two rows, but 105 -> 154 VGPRs, i.e. 3 instead of 4 waves per SIMD: the 4096 waves of the bench launch no longer fit one
-                                  // round (69 us); with 22-row strips (one round at 3 waves) 55.2 us against 57.4 for the scalar form on that plan and 55.5 for the scalar
-                                  // form on the default plan -- no gain, off (profiles/r3_2d_packed.txt)
-#endif
-#ifndef DN_CF_W
-#define DN_CF_W 4                 // sub-strips CHAINED per workgroup where the launch plan asks for it ("PLAN2D" "T,E,R,W"; not the default, see plan2d in
-#endif                            // poisson_fused.hip): W x 2 waves march W neighbouring strips; a strip takes the row it shares with the strip below / above
+// Measured and removed (code in the history):
+//  - the shared node x0 + 4 from the neighbouring lane instead of a strided per-lane load: over DPP equal (profiles/r2_2d_ab.txt), over ds_bpermute
+//    with non-temporal row loads slower, 60-69 us
+//  - neighbouring strips marching in opposite directions on one XCD: traffic 1.09x -> 1.002x of the algorithmic bytes, but slower where every
+//    launch streams from HBM (59.5 vs 56.4 us, profiles/r2_rotate_variants.txt)
+//  - software-pipelined rows (one / two raw rows in flight): 48.1 / 50.6 us against 46.9 on the default plan (profiles/r2_plan2d_steady.txt)
+//  - element pairs in packed fp32 registers: 722 -> 536 VALU instructions per two rows, 105 -> 154 VGPRs, no gain (profiles/r3_2d_packed.txt)
+constexpr int CF_W = 4;           // sub-strips CHAINED per workgroup where the launch plan asks for it ("PLAN2D" "T,E,R,W"; not the default, see plan2d in
+                                  // poisson_fused.hip): W x 2 waves march W neighbouring strips; a strip takes the row it shares with the strip below / above
                                   // through LDS instead of re-reading it from HBM and recomputing the seam layer: a workgroup of W strips of R rows reads
                                   // W R + 2 rows instead of W (R + 2)
 constexpr int CF_TS = 128;        // threads per chained sub-strip (two waves: 128 x 4 elements = one 512-node row segment)
@@ -117,54 +85,18 @@ __device__ __forceinline__ void lds_wait(float (&v)[N]) {
     else { static_assert(N == 1, "lds_wait: 1..5 values"); asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[0])::"memory"); }
 }
 
-#ifdef DN_STAMP2D
-// Diagnostic build only (tools/clock2d.py): shader-clock ticks (s_memtime) and constant-100-MHz ticks (s_memrealtime) of every workgroup's
-// lifetime -> the clock the kernel really ran at (the MI355X lowers it under load: profiles/r2_clock_under_load.txt)
-__device__ unsigned long long dn_stamp2d_buf[8192 * 4];      // per workgroup: shader ticks of its march, then constant-clock (10 ns) stamps: start, end of the march, end of the kernel
-extern "C" int dn_debug_stamps2d(void* dst, size_t bytes) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(dn_stamp2d_buf), bytes); }
-#endif
-
 template <int E, bool VEC, int FL, int W>
-__global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : DN_Q1_2D_WAVES) poisson2d_q1_cf_kernel(const PoissonParams p) {
-#ifdef DN_STAMP2D
-    const unsigned long long stamp_t0 = __builtin_amdgcn_s_memtime(), stamp_rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
+__global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : 2) poisson2d_q1_cf_kernel(const PoissonParams p) {
     constexpr int NW = E;
     constexpr bool HAS_NU = (FL & CF_NU) != 0, HAS_F = (FL & CF_F) != 0;
     constexpr bool BC_ANY = (FL & (CF_BC | CF_BC_U8C | CF_BC_PACKED)) != 0, BC_U8C = (FL & CF_BC_U8C) != 0, BC_PACKED = (FL & CF_BC_PACKED) != 0;
     constexpr bool UA = (FL & CF_UA) != 0;
-    static_assert(!UA || (E == 4 && VEC && W == 1 && !DN_CF_REV && !DN_CF_PF && DN_CF_DPPX == 0), "CF_UA: four elements per thread, vector accesses, plain upward march");
-    static_assert(W == 1 || (!DN_CF_REV && !DN_CF_PF), "chained sub-strips: plain upward march only");
+    static_assert(!UA || (E == 4 && VEC && W == 1), "CF_UA: four elements per thread, vector accesses, one strip per workgroup");
     // W > 1: the workgroup holds W sub-strips of CF_TS threads each; sub (wave-uniform) is this thread's sub-strip
     const int T = W > 1 ? CF_TS : (int)blockDim.x;
     const int sub = W > 1 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x / CF_TS) : 0;       // wave-uniform: everything derived from it stays scalar
     const int tid = W > 1 ? (int)threadIdx.x - sub * CF_TS : (int)threadIdx.x;
-#if DN_CF_REV
-    // Workgroup -> (chunk, strip, sample) so that NEIGHBOURING strips run on the same XCD (one L2) at the same time: the dispatcher
-    // hands consecutive workgroups (x fastest, then y, z) to consecutive XCDs; XCD k takes the k-th contiguous range of strips.
-    unsigned lid = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-#if defined(DN_CF_REV_PAIRS)          // (round 4 experiment) only the two strips of a PAIR share an XCD, dispatched 8 workgroups apart; consecutive pairs go round the
-    {                                 // XCDs in dispatch order as in the default launch (no contiguous range of samples per XCD)
-        const unsigned nwg = gridDim.x * gridDim.y * gridDim.z;
-        if ((nwg & 15u) == 0u) {
-            const unsigned xcd = lid & 7u, member = (lid >> 3) & 1u, q = lid >> 4;
-#if DN_CF_REV_PAIRS == 2              // pairs (2 k + 1, 2 k + 2): the strips that read their shared rows at their START (all workgroups start together: the second read
-            lid = (2u * (8u * q + xcd) + member + nwg - 1u) % nwg;     // meets the first in the L2; at the ends the two marches are microseconds apart)
-#else
-            lid = 2u * (8u * q + xcd) + member;
-#endif
-        }
-    }
-#elif !defined(DN_CF_REV_NOXCD)       // (round 4 experiment NOXCD: opposite marches in plain dispatch order -- the second read of a shared row then meets the first in the Infinity Cache, not in an L2)
-    {
-        const unsigned nwg = gridDim.x * gridDim.y * gridDim.z, xcd = lid & 7u, idx = lid >> 3, base = nwg >> 3, rem = nwg & 7u;
-        lid = xcd * base + min(xcd, rem) + idx;
-    }
-#endif
-    const int chunk = (int)(lid % gridDim.x), strip = (int)((lid / gridDim.x) % gridDim.y), b = (int)(lid / (gridDim.x * gridDim.y));
-#else
     const int chunk = blockIdx.x, strip = W > 1 ? (int)blockIdx.y * W + sub : selected_strip(p, (int)blockIdx.y), b = blockIdx.z;      // (chained launches cover every strip)
-#endif
     const bool active = W == 1 || strip < p.nstrips;                         // the last workgroup of a sample may hold fewer than W strips
     const bool chain_dn = W > 1 && sub > 0;                                  // the strip below is in this workgroup
     const bool chain_up = W > 1 && sub + 1 < W && strip + 1 < p.nstrips;     // the strip above is
@@ -178,19 +110,13 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : DN_Q1_2D_
     const int R = p.rows_per_strip;
     // The strip owns the node rows [sb0, sc0) (the last strip also the top row of the domain) and the element layers between them; it
     // also computes the layer below its first row (the seam: that row's other half), so it reads the node rows sb0 - 1 .. sc0.
-    // DN_CF_REV: odd strips march DOWNWARDS, in the mirrored row coordinate y' = nely - y (the element is mirror-symmetric: the rule's
-    // moments of b and of 1 - b are the same numbers, so the same formulas apply with lower / upper rows exchanged).  An even strip and
-    // the odd one above it then read the two rows they share at the same time (both at their end), the odd strip and the even one above
-    // it both at their start: with the strips of a pair on one XCD the second read is an L2 hit instead of HBM traffic.
     const int sb0 = strip * R, sc0 = min(sb0 + R, p.nely);
-    const bool rev = DN_CF_REV && (strip & 1);
-    const int ysgn = rev ? -1 : 1, yoff = rev ? p.nely : 0;                  // physical row of the logical row y: ysgn * y + yoff
-    // logical layers [ey_begin, ey_end); energy counted for layers e_from <= ey <= e_until, rows stored for ey >= r_from
-    const int ey_begin = rev ? p.nely - sc0 : ((sb0 > 0 && !chain_dn) ? sb0 - 1 : sb0);     // chain_dn: no seam layer, the carry comes from the strip below
-    const int ey_end = rev ? (sb0 > 0 ? p.nely - sb0 + 1 : p.nely) : sc0;
-    const int r_from = rev ? (sc0 == p.nely ? ey_begin : ey_begin + 1) : sb0;
-    const int e_from = rev ? 0 : sb0, e_until = rev ? p.nely - 1 - sb0 : p.nely;
-    const bool top_row = rev ? sb0 == 0 : sc0 == p.nely;                     // the strip also finishes the last logical row (no layer above it)
+    // layers [ey_begin, ey_end); energy counted for layers e_from <= ey <= e_until, rows stored for ey >= r_from
+    const int ey_begin = (sb0 > 0 && !chain_dn) ? sb0 - 1 : sb0;          // chain_dn: no seam layer, the carry comes from the strip below
+    const int ey_end = sc0;
+    const int r_from = sb0;
+    const int e_from = sb0, e_until = p.nely;
+    const bool top_row = sc0 == p.nely;                                      // the strip also finishes the last row (no layer above it)
 
     __shared__ float xch[2][256];
     __shared__ double red[W > 1 ? 4 * W : 8];
@@ -278,43 +204,23 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : DN_Q1_2D_
         for (int k = 0; k < 2; ++k) r.bx[k] = (yc == ylo[k] || yc == yhi[k]) ? NBITS : boxx[k];
     };
 
-    auto lseg = [&](auto base, unsigned rowoff, auto& dst, auto nt) {
-        if constexpr (E == 4 && VEC && DN_CF_DPPX == 2) load_seg4_shfl<decltype(nt)::value>(base, rowoff, x0, p.nx, dst);
-        else if constexpr (E == 4 && VEC && DN_CF_DPPX) load_seg4_dpp(base, rowoff, x0, p.nx, dst);
-        else load_seg<NW, VEC>(base, rowoff, x0, p.nx, dst);
-    };
-    constexpr std::integral_constant<bool, (DN_CF_NT_LD >= 2)> NT_U{};
-    constexpr std::integral_constant<bool, (DN_CF_NT_LD >= 1)> NT_C{};
-    constexpr std::false_type NT_NO{};
     auto row_issue = [&](int yr, CfRow<E>& r) {
-        const int yp = ysgn * min(yr, p.ny - 1) + yoff;
+        const int yp = min(yr, p.ny - 1);
         const unsigned rowoff = (unsigned)yp * (unsigned)p.nx;
-#if DN_CF_NT_COEF >= 2
-        load_seg_stream<NW, VEC>(sb.u, rowoff, x0, p.nx, r.u);
-#else
-        lseg(sb.u, rowoff, r.u, NT_U);
-#endif
-#if DN_CF_NT_COEF
+        load_seg<NW, VEC>(sb.u, rowoff, x0, p.nx, r.u);
+        // nu and f (read once per launch) as non-temporal vector loads, the node shared with the right neighbour as a plain load.  On one
+        // re-evaluated batch this gives up the Infinity-Cache hits (47 -> 53 us); on batches in rotation -- every launch streams from HBM, the
+        // regime bench.py times -- it wins: mask bits 58.3 -> 55.5 us, box 56.5 -> 56.0; u as well was slower: 59.8 (profiles/r3_rotate_nt.txt)
         if constexpr (HAS_NU) load_seg_stream<NW, VEC>(sb.nu, rowoff, x0, p.nx, r.n);
         if constexpr (HAS_F) load_seg_stream<NW, VEC>(sb.f, rowoff, x0, p.nx, r.f);
-#else
-        if constexpr (HAS_NU) lseg(sb.nu, rowoff, r.n, NT_C);
-        if constexpr (HAS_F) lseg(sb.f, rowoff, r.f, NT_C);
-#endif
         if constexpr (BC_PACKED) {
             packed_issue(yp, r);
         } else if constexpr (BC_U8C) {
-            // both mask slots are loaded unconditionally (an absent one re-reads the other and is ignored): a load inside a
-            // wave-uniform branch makes the compiler wait vmcnt(0) where the branch joins, which would drain the pipelined rows
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                if (DN_CF_PF || has_mask[k]) {        // not pipelined: an absent condition costs no load (wave-uniform branch)
+                if (has_mask[k]) {                    // an absent condition costs no load (wave-uniform branch)
                     uint8_t t[NW + 1];
-#if DN_NT_MASK
                     load_seg_stream<NW, VEC>(mask8[k], rowoff, x0, p.nx, t);
-#else
-                    lseg(mask8[k], rowoff, t, NT_NO);
-#endif
                     uint32_t w = 0u;
 #pragma unroll
                     for (int n = 0; n < NW; ++n) w |= (uint32_t)t[n] << (8 * n);
@@ -346,7 +252,7 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : DN_Q1_2D_
         } else if constexpr (BC_U8C) {
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                if (DN_CF_PF || has_mask[k]) {
+                if (has_mask[k]) {
                     const float val = p.bc[k].value;
 #pragma unroll
                     for (int n = 0; n <= NW; ++n) {
@@ -373,9 +279,9 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : DN_Q1_2D_
     float e1_acc = 0.f, e2_acc = 0.f, sq_acc = 0.f;
     int par = 0;
 
-    // The finished row is stored by flush_store(), after the next row has been consumed and the one after it requested: a store
-    // issued here would be younger than the loads the next consumer waits for, and because it sits in a divergent branch the
-    // compiler turns that wait into vmcnt(0), i.e. into a wait for the store itself.
+    // emit_row stages the finished row in pend_* and writes it through flush_store().  (The software-pipelined march, since removed, used
+    // the staging to issue the store after the next row's loads: a store in a divergent branch that is younger than the loads the next
+    // consumer waits for turns that wait into vmcnt(0), i.e. into a wait for the store itself.)
     float pend_v[NW];
     unsigned pend_row = 0u;
     bool pend_st = false;
@@ -422,9 +328,9 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : DN_Q1_2D_
             sq_acc = (st && lastcol) ? fmaf(t, t, sq_acc) : sq_acc;
             pend_x = t * p.out_scale;
         }
-        pend_row = (unsigned)(ysgn * yr + yoff) * (unsigned)p.nx;
+        pend_row = (unsigned)yr * (unsigned)p.nx;
         pend_st = st && sb.out != nullptr;
-        if (!DN_CF_PF) flush_store();
+        flush_store();
     };
 
     const float mx0 = p.T.mxs[0], mx1 = p.T.mxs[1], mx2 = p.T.mxs[2], mx3 = p.T.mxs[3];
@@ -434,7 +340,7 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : DN_Q1_2D_
     // forcing term as a tensor-product mass matrix applied row by row (14 instead of 28 instructions per element: -11 % VALU instructions,
     // time unchanged -- the kernel moves its ~312 MB at 5.45 TB/s whatever the arithmetic costs, profiles/r2_ab2d_fmass.txt); not in the
     // generic mask / value-field form, whose register budget it would push from 4 to 3 waves per SIMD
-    constexpr bool FMASS = HAS_F && DN_CF_FMASS && (FL & CF_BC) == 0;
+    constexpr bool FMASS = HAS_F && (FL & CF_BC) == 0;
     const float cx00 = p.T.q1mx[0], cx01 = p.T.q1mx[1], cx11 = p.T.q1mx[2], cy00 = p.T.q1my[0], cy01 = p.T.q1my[1], cy11 = p.T.q1my[2];
     // sum_g W_g f_g N_a(g) with f bilinear is (mass_x (x) mass_y) f.  x-stage, once per node row: g[n] = the row's forcing seen through
     // the thread's own elements (elements beyond the mesh excluded; the node shared with the right neighbour gets the rest over the
@@ -459,7 +365,7 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : DN_Q1_2D_
     auto layer = [&](auto fresh, int ey, const CfRow<E>& L, CfRow<E>& U, const float (&cin)[NW + 1], float (&cout)[NW + 1]) {
         const bool own_layer = ey >= e_from && ey <= e_until;
         const float cnt = (own_layer && col_owner) ? 1.f : 0.f;
-        if (!DN_CF_PF && decltype(fresh)::value) { row_bc(U); fstage(U); }
+        if constexpr (decltype(fresh)::value) { row_bc(U); fstage(U); }
         float o[NW + 1], le1 = 0.f, le2 = 0.f;
 #pragma unroll
         for (int n = 0; n <= NW; ++n) { o[n] = cin[n]; cout[n] = 0.f; }
@@ -472,56 +378,6 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : DN_Q1_2D_
                 le2 = fmaf(U.u[n], tup, fmaf(L.u[n], tlo, le2));
             }
         }
-        if constexpr (E % 2 == 0 && DN_CF_PK) {
-            // two elements per instruction: .x = element e, .y = element e + 1 (v2f: poisson_elem.h).  Elements beyond the mesh take part with
-            // their differences of u (and their forcing) zeroed -- every contribution is linear in those --, on data clamped into the mesh
-            v2f le1v = 0.f, le2v = 0.f;
-#pragma unroll
-            for (int e = 0; e < E; e += 2) {
-                const v2f ok = {ex0 + e < p.nelx ? 1.f : 0.f, ex0 + e + 1 < p.nelx ? 1.f : 0.f};
-                const v2f Ll = {L.u[e], L.u[e + 1]}, Lr = {L.u[e + 1], L.u[e + 2]}, Ul = {U.u[e], U.u[e + 1]}, Ur = {U.u[e + 1], U.u[e + 2]};
-                const v2f UX = ok * (Lr - Ll), UY = ok * (Ul - Ll), UXY = ok * (Ur - Ul) - UX;
-                v2f P = mx0, Q = 0.f, Pp = my0, Qp = 0.f;
-                if constexpr (HAS_NU) {
-                    const v2f N0 = {L.n[e], L.n[e + 1]}, Nr = {L.n[e + 1], L.n[e + 2]}, Nu = {U.n[e], U.n[e + 1]}, Nur = {U.n[e + 1], U.n[e + 2]};
-                    const v2f NX = Nr - N0, NY = Nu - N0, NXY = (Nur - Nu) - NX;
-                    P = vfma(mx1, NX, mx0 * N0);
-                    Q = vfma(mx1, NXY, mx0 * NY);
-                    Pp = vfma(my1, NY, my0 * N0);
-                    Qp = vfma(my1, NXY, my0 * NX);
-                }
-                const v2f A0 = vfma(my1, Q, my0 * P), A1 = vfma(my2, Q, my1 * P), A2 = vfma(my3, Q, my2 * P);
-                const v2f B0 = vfma(mx1, Qp, mx0 * Pp), B1 = vfma(mx2, Qp, mx1 * Pp), B2 = vfma(mx3, Qp, mx2 * Pp);
-                const v2f tX0 = vfma(UXY, A1, UX * A0), tX1 = vfma(UXY, A2, UX * A1);
-                const v2f tY0 = vfma(UXY, B1, UY * B0), tY1 = vfma(UXY, B2, UY * B1);
-                le1v += vfma(h1, vfma(UXY, tY1, UY * tY0), h0 * vfma(UXY, tX1, UX * tX0));
-                v2f cU0 = 0.f, cUX = k0 * tX0, cUY = k1 * tY0, cUXY = vfma(k0, tX1, k1 * tY1);
-                if constexpr (HAS_F && !FMASS) {
-                    const v2f U0 = Ll;
-                    const v2f Fl = {L.f[e], L.f[e + 1]}, Fr = {L.f[e + 1], L.f[e + 2]}, Fu = {U.f[e], U.f[e + 1]}, Fur = {U.f[e + 1], U.f[e + 2]};
-                    const v2f F0 = ok * Fl, FX = ok * (Fr - Fl), FY = ok * (Fu - Fl), FXY = ok * (Fur - Fu) - FX;
-                    const v2f S0 = vfma(mx1, FX, mx0 * F0), S1 = vfma(mx1, FXY, mx0 * FY);
-                    const v2f T0 = vfma(mx2, FX, mx1 * F0), T1 = vfma(mx2, FXY, mx1 * FY);
-                    const v2f L0 = vfma(my1, S1, my0 * S0), LX = vfma(my1, T1, my0 * T0);
-                    const v2f LY = vfma(my2, S1, my1 * S0), LXY = vfma(my2, T1, my1 * T0);
-                    le2v += vfma(LXY, UXY, vfma(LY, UY, vfma(LX, UX, L0 * U0)));
-                    cU0 = nb * L0;
-                    cUX = vfma(nb, LX, cUX);
-                    cUY = vfma(nb, LY, cUY);
-                    cUXY = vfma(nb, LXY, cUXY);
-                }
-                const v2f g01 = cUX - cUXY, g10 = cUY - cUXY, g00 = (cU0 - cUX) - g10;
-                o[e] += g00.x;
-                o[e + 1] += g01.x + g00.y;
-                o[e + 2] += g01.y;
-                cout[e] += g10.x;
-                cout[e + 1] += cUXY.x + g10.y;
-                cout[e + 2] += cUXY.y;
-                __builtin_amdgcn_sched_barrier(0);      // one pair at a time: interleaving the pairs doubles the live set
-            }
-            le1 += le1v.x + le1v.y;
-            le2 += le2v.x + le2v.y;
-        } else {
 #pragma unroll
         for (int e = 0; e < E; ++e) {
             if (ex0 + e < p.nelx) {       // elements beyond the domain are skipped (and: scheduling fence between elements)
@@ -558,7 +414,6 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : DN_Q1_2D_
                 cout[e] += g10;
                 cout[e + 1] += cUXY;
             }
-        }
         }
         e1_acc = fmaf(cnt, le1, e1_acc);
         e2_acc = fmaf(cnt, le2, e2_acc);
@@ -616,14 +471,12 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : DN_Q1_2D_
     };
 
     auto set_prio = [&](int e) {
-#if DN_PRIO_ROT
         switch (((ey_end - e) >> 1) & 3) {          // progress-dependent wave priority (profiles/README.md)
             case 0: __builtin_amdgcn_s_setprio(0); break;
             case 1: __builtin_amdgcn_s_setprio(1); break;
             case 2: __builtin_amdgcn_s_setprio(2); break;
             default: __builtin_amdgcn_s_setprio(3); break;
         }
-#endif
     };
 
     constexpr std::true_type FRESH{};
@@ -641,69 +494,6 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : DN_Q1_2D_
     }
     int ey = ey_begin;
     bool odd = false;
-#if DN_CF_PF == 2
-    {
-        // software pipeline, two raw rows ahead: WR0 / WR1 hold rows k + 1 and k + 2 while layer k - 1 runs.  Rows past the strip's last one
-        // are re-reads of that row (cache hits, no HBM traffic; a wave-uniform branch around the loads would drain the pipeline)
-        CfRow<E> WR0, WR1;
-        auto consume = [&](CfRow<E>& r, const CfRow<E>& WR) {
-            r = WR;
-            row_bc(r);
-            fstage(r);
-        };
-        row_issue(min(ey_begin + 1, ey_end), WR0);
-        row_issue(min(ey_begin + 2, ey_end), WR1);
-        for (; ey + 1 < ey_end; ey += 2) {
-            set_prio(ey);
-            consume(RB, WR0);
-            row_issue(min(ey + 3, ey_end), WR0);
-            flush_store();
-            layer(FRESH, ey, RA, RB, carryA, carryB);
-            consume(RA, WR1);
-            row_issue(min(ey + 4, ey_end), WR1);
-            flush_store();
-            layer(FRESH, ey + 1, RB, RA, carryB, carryA);
-        }
-        if (ey < ey_end) {
-            set_prio(ey);
-            consume(RB, WR0);
-            flush_store();
-            layer(FRESH, ey, RA, RB, carryA, carryB);
-            odd = true;
-        }
-        flush_store();
-    }
-#elif DN_CF_PF
-    {
-        // software pipeline: WR holds the raw row k + 2 while layer k runs; consume = Dirichlet select + copy into the row state
-        CfRow<E> WR;
-        auto consume = [&](CfRow<E>& r) {
-            r = WR;
-            row_bc(r);
-            fstage(r);
-        };
-        row_issue(min(ey_begin + 1, ey_end), WR);
-        for (; ey + 1 < ey_end; ey += 2) {
-            set_prio(ey);
-            consume(RB);
-            row_issue(min(ey + 2, ey_end), WR);
-            flush_store();
-            layer(FRESH, ey, RA, RB, carryA, carryB);
-            consume(RA);
-            row_issue(min(ey + 3, ey_end), WR);
-            flush_store();
-            layer(FRESH, ey + 1, RB, RA, carryB, carryA);
-        }
-        if (ey < ey_end) {
-            set_prio(ey);
-            consume(RB);
-            flush_store();
-            layer(FRESH, ey, RA, RB, carryA, carryB);
-            odd = true;
-        }
-        flush_store();
-    }
-#else
     const int n_main = chain_up ? ey_end - 1 : ey_end;         // chain_up: the strip's last layer takes its upper row from the strip above (LDS)
     for (; ey + 1 < n_main; ey += 2) {
         set_prio(ey);
@@ -726,8 +516,7 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : DN_Q1_2D_
             else { fetch_row(RB); layer(LANDED, ey, RA, RB, carryA, carryB); publish_carry(carryB); }
         }
     }
-#endif
-    if (top_row) {                // the last logical row of the domain: only the layer below it contributes
+    if (top_row) {                // the last row of the domain: only the layer below it contributes
         float o[NW + 1], keep[NW];
 #pragma unroll
         for (int n = 0; n <= NW; ++n) o[n] = odd ? carryB[n] : carryA[n];
@@ -758,36 +547,20 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : DN_Q1_2D_
     }
     }                                 // active
 
-#ifdef DN_STAMP2D
-    if (tid == 0) {
-        const unsigned slot = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        if (slot < 8192u) {
-            dn_stamp2d_buf[4 * slot] = __builtin_amdgcn_s_memtime() - stamp_t0;
-            dn_stamp2d_buf[4 * slot + 1] = stamp_rt0;
-            dn_stamp2d_buf[4 * slot + 2] = __builtin_amdgcn_s_memrealtime();
-        }
-    }
-#endif
     if constexpr (W > 1) {            // a hand-over poll that ran into its bound: NaN sums + the sticky error word (never silent)
         e1_acc += spin_poison;
         sq_acc += spin_poison;
         if (spin_poison != spin_poison && p.counter != nullptr && (threadIdx.x & 63u) == 0u) atomicOr(p.counter + DN_WS_ERRWORD, 1u);
     }
     if (p.want_sums) finish_sums(p, e1_acc, e2_acc, sq_acc, (int)threadIdx.x, (int)blockDim.x, red, &last_flag);
-#ifdef DN_STAMP2D
-    if (tid == 0) {
-        const unsigned slot = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        if (slot < 8192u) dn_stamp2d_buf[4 * slot + 3] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
 }
 
 template <int E, bool VEC, int FL>
 static void cf_launch_one(const PoissonParams& pp, const Geom2D& g, int batch, hipStream_t s) {
-    if constexpr (E == 4 && VEC && DN_CF_W > 1 && (FL & CF_UA) == 0 && !DN_CF_REV && !DN_CF_PF) {
-        if (g.W == DN_CF_W) {         // chained sub-strips (plan2d): W strips per workgroup
-            hipLaunchKernelGGL((poisson2d_q1_cf_kernel<E, VEC, FL, DN_CF_W>), dim3(g.chunks, (g.strips + DN_CF_W - 1) / DN_CF_W, batch),
-                               dim3(CF_TS * DN_CF_W), 0, s, pp);
+    if constexpr (E == 4 && VEC && (FL & CF_UA) == 0) {
+        if (g.W == CF_W) {            // chained sub-strips (plan2d): W strips per workgroup
+            hipLaunchKernelGGL((poisson2d_q1_cf_kernel<E, VEC, FL, CF_W>), dim3(g.chunks, (g.strips + CF_W - 1) / CF_W, batch),
+                               dim3(CF_TS * CF_W), 0, s, pp);
             return;
         }
     }
@@ -820,18 +593,14 @@ static void cf_launch_flags(const PoissonParams& pp, const Geom2D& g, int batch,
 #undef DN_CF
 }
 
-int poisson2d_q1_cf_chain() { return DN_CF_W > 1 && !DN_CF_REV && !DN_CF_PF ? DN_CF_W : 1; }       // what plan2d may put into Geom2D::W
+int poisson2d_q1_cf_chain() { return CF_W; }       // what plan2d may put into Geom2D::W
 
 int launch_poisson2d_q1_cf(const PoissonParams& pp, const Geom2D& g, int batch, bool vec, hipStream_t s) {
     if (g.W > 1 && !(g.W == poisson2d_q1_cf_chain() && g.E == 4 && vec && g.T == CF_TS && g.R + 3 <= CF_NSLOT)) return DN_E_BADARG;
     if (g.ua) {                   // rows of 4 k + 1 nodes (plan2d): the vector kernel on 4-byte aligned rows, last node column in the last thread column
         if (g.E != 4 || g.W != 1 || (pp.nx & 3) != 1 || pp.nx < 9) return DN_E_BADARG;
-#if DN_CF_REV || DN_CF_PF || DN_CF_DPPX
-        return DN_E_UNSUPPORTED;  // (experiment builds: no 4 k + 1 form)
-#else
         cf_launch_flags<4, true, CF_UA>(pp, g, batch, s);
         return 0;
-#endif
     }
     if (g.E == 4 && vec) { cf_launch_flags<4, true>(pp, g, batch, s); return 0; }
     if (g.E == 2 && vec) { cf_launch_flags<2, true>(pp, g, batch, s); return 0; }

@@ -24,22 +24,6 @@ struct PlaneState3D {
 // pure 1-D weight of Gauss point g (1 at compile time for the unit-weight rule)
 #define T_W(T, g, UW) ((UW) ? 1.f : (T).w[g])
 
-#ifndef DN_Q1W_WAVES_T16
-#define DN_Q1W_WAVES_T16 5        // 16-wide one-element form with the next plane's loads in flight: <= 96 VGPRs
-#endif
-#ifndef DN_Q1W_WAVES_E1
-#define DN_Q1W_WAVES_E1 6         // one element per thread at 2 x 2 x 2 points: <= 80 VGPRs (6 waves per SIMD)
-#endif
-#ifndef DN_Q1W_WAVES
-#define DN_Q1W_WAVES 4            // second-generation kernel: <= 128 VGPRs (4 waves per SIMD)
-#endif
-#ifndef DN_Q1_3D_WAVES
-#define DN_Q1_3D_WAVES 2
-#endif
-#ifndef DN_PRIO_ROT3D
-#define DN_PRIO_ROT3D 0
-#endif
-
 // =============================================================================================================
 // Second-generation kernel (the round-1 kernel it replaced -- poisson3d_q1m_kernel, ~1/3 more VALU instructions per element -- is no longer
 // in the tree; its numbers stay in profiles/r1_*): same mapping, hand-over and reductions.
@@ -103,34 +87,14 @@ struct __attribute__((packed, aligned(1))) B2U { uint8_t a, b; };
 // instruction costs a SIMD ~33 cycles (about 14 plain VALU instructions) as soon as two or more waves share it, while a
 // ds_bpermute_b32 / ds_swizzle_b32 costs ~3 (tools/micro/valu_mem.hip, profiles/r2_valu_mem.txt).  `from` is the byte address of the
 // source lane ((lane - 1) & 63) * 4, `nf` is 0 for the first lane of a row and 1 elsewhere.
-#ifndef DN_T16_DPP
-#define DN_T16_DPP 0
-#endif
-#ifndef DN_T16_PAIRED
-#define DN_T16_PAIRED 1
-#endif
 __device__ __forceinline__ float lane_from_left(float v, int from, float nf) {
-#if DN_T16_DPP
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, true));
-#else
     return nf * __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(from, __builtin_bit_cast(int, v)));
-#endif
 }
 
-#if defined(DN_STAMP3D) && DN_NGP == 2
-// Diagnostic build only (tools/stamp3d.py): per-wave cycle budget of the T16 loop, accumulated in scalar registers with s_memtime
-// and written once at the end of the kernel by every 61st workgroup.  Phases per layer: A = wait for the prefetched plane + stage
-// it, B = request the next plane + deferred store, C = layer arithmetic, D = hand-over write + barrier wait, E = hand-over read +
-// finish the node value.
-__device__ unsigned long long dn_stamp_buf[8192 * 8];
-extern "C" int dn_debug_stamps(void* dst, size_t bytes) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(dn_stamp_buf), bytes); }
-#define DN_STAMP(var) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t__ = __builtin_amdgcn_s_memtime(); var += t__ - stamp_last; stamp_last = t__; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define DN_STAMP(var) do { } while (0)
-#endif
-
+// Waves per SIMD asked of the compiler: 5 = the 16-wide one-element form with the next plane's loads in flight (<= 96 VGPRs), 6 = one element
+// per thread at 2 x 2 x 2 points (<= 80 VGPRs), 4 = the second-generation kernel (<= 128 VGPRs)
 template <int NGP, int E, bool VEC, int FL, bool UW, bool T16>
-__global__ void __launch_bounds__(256, NGP == 4 ? 2 : (T16 ? (NGP == 2 ? ((FL & (FL3_BC | FL3_FGP)) ? 4 : DN_Q1W_WAVES_T16) : 3) : ((E == 1 && NGP == 2) ? ((FL & (FL3_BC | FL3_FGP)) ? 4 : DN_Q1W_WAVES_E1) : DN_Q1W_WAVES))) poisson3d_q1w_kernel(const PoissonParams p, const int chunks_x, const int tiles_y,
+__global__ void __launch_bounds__(256, NGP == 4 ? 2 : (T16 ? (NGP == 2 ? ((FL & (FL3_BC | FL3_FGP)) ? 4 : 5) : 3) : ((E == 1 && NGP == 2) ? ((FL & (FL3_BC | FL3_FGP)) ? 4 : 6) : 4))) poisson3d_q1w_kernel(const PoissonParams p, const int chunks_x, const int tiles_y,
                                                                             const int strips_z) {
     static_assert(!T16 || E == 1, "T16 is the one-element-per-thread form");
     constexpr int NW = E;
@@ -176,10 +140,6 @@ __global__ void __launch_bounds__(256, NGP == 4 ? 2 : (T16 ? (NGP == 2 ? ((FL & 
 #pragma unroll
     for (int e = 0; e < E; ++e) okf[e] = (row_ok && (ex0 + e < p.nelx)) ? 1.f : 0.f;
 
-#if defined(DN_STAMP3D) && DN_NGP == 2
-    unsigned long long stamp_A = 0, stamp_B = 0, stamp_C = 0, stamp_D = 0, stamp_E = 0, stamp_n = 0, stamp_last = 0;
-    const unsigned long long stamp_t0 = __builtin_amdgcn_s_memtime();
-#endif
     __shared__ float xch[2][T16 ? 1 : NW + 2][256];
     __shared__ double red[2 * (256 / 64)];      // block_sum2: two sums per wave
     __shared__ int last_flag;
@@ -222,11 +182,7 @@ __global__ void __launch_bounds__(256, NGP == 4 ? 2 : (T16 ? (NGP == 2 ? ((FL & 
         uint8_t m8[2][2][NW + 1];
     };
     auto plane_issue = [&](int zreq, RawPlane& W) {
-#ifdef DN_ABL_ZFIX3D                       // timing experiment only: every plane re-reads the strip's first plane (cache hits)
-        const unsigned zoff = (unsigned)ez_begin * npl + (unsigned)(zreq & 1) * 4u * (unsigned)p.nx;
-#else
         const unsigned zoff = (unsigned)min(zreq, p.nz - 1) * npl;
-#endif
         const unsigned rowoff[2] = {zoff + row0, zoff + row1};
         float (&ru)[2][NW + 1] = W.ru;
         float (&rn)[2][NW + 1] = W.rn;
@@ -238,67 +194,19 @@ __global__ void __launch_bounds__(256, NGP == 4 ? 2 : (T16 ? (NGP == 2 ? ((FL & 
             if constexpr (T16) {
                 // both nodes of the row in one load; threads right of the mesh read the last valid pair (their element is masked)
                 const unsigned o2 = rowoff[jb] + x0c;
-#ifdef DN_ABL_NX4                          // timing experiment only: DN_ABL_NX4 aligned dwordx4 loads per layer and thread, nothing else
-                if (jb == 0) {
-                    float4 a = ld_at<float4>(sb.u, o2 & ~3u);
-                    if (DN_ABL_NX4 > 1) { const float4 t = ld_at<float4>(sb.nu, o2 & ~3u); a.y += t.x; a.z += t.y; }
-                    if (DN_ABL_NX4 > 2) { const float4 t = ld_at<float4>(sb.f, o2 & ~3u); a.w += t.z; a.x += t.w; }
-                    ru[0][0] = a.x; ru[0][1] = a.y; ru[1][0] = a.z; ru[1][1] = a.w;
-                    rn[0][0] = a.y; rn[0][1] = a.z; rn[1][0] = a.w; rn[1][1] = a.x;
-                    rf[0][0] = a.z; rf[0][1] = a.w; rf[1][0] = a.x; rf[1][1] = a.y;
-                    if constexpr (BC_U8C) {
-                        const uint8_t mz = (uint8_t)(a.x == 123.456f);
-                        m8[0][0][0] = m8[0][0][1] = m8[0][1][0] = m8[0][1][1] = m8[1][0][0] = m8[1][0][1] = m8[1][1][0] = m8[1][1][1] = mz;
-                    }
-                }
-                continue;
-#endif
-#ifdef DN_ABL_ROW0DWORD                    // timing experiment only: one aligned dword / byte per field for row 0
-                if (jb == 0) {
-                    const float a0 = ld_at<float>(sb.u, o2);
-                    ru[jb][0] = a0; ru[jb][1] = a0 + 0.5f;
-                    if constexpr (HAS_NU) { const float t = ld_at<float>(sb.nu, o2); rn[jb][0] = t; rn[jb][1] = t; }
-                    if constexpr (HAS_F) { const float t = ld_at<float>(sb.f, o2); rf[jb][0] = t; rf[jb][1] = t; }
-                    if constexpr (BC_U8C) {
-#pragma unroll
-                        for (int k = 0; k < 2; ++k) { const uint8_t t = ld_at<uint8_t>(mask8[k], o2); m8[jb][k][0] = t; m8[jb][k][1] = t; }
-                    }
-                    continue;
-                }
-#endif
-#if defined(DN_ABL_LOADS3D) || defined(DN_ABL_ROW0ONLY) || defined(DN_ABL_ROW0DWORD)   // timing experiment only: no VMEM loads (all rows / row 1 only); values made up from the offset
-#if !defined(DN_ABL_LOADS3D)
-                if (jb == 1)
-#endif
-                {
-                    const float t = __uint_as_float((o2 & 0xffffu) | 0x3f800000u);
-                    ru[jb][0] = t; ru[jb][1] = t + 0.5f;
-                    rn[jb][0] = t; rn[jb][1] = t; rf[jb][0] = t; rf[jb][1] = t;
-                    if constexpr (BC_U8C) { m8[jb][0][0] = m8[jb][0][1] = m8[jb][1][0] = m8[jb][1][1] = (uint8_t)(o2 == 0xffffffffu); }
-                    continue;
-                }
-#endif
-#if DN_T16_PAIRED          // one 4-byte-aligned dwordx2 / ushort per node pair; two aligned dword loads instead (DN_T16_PAIRED=0) measured 165 -> 249 us at 256^3: the second load hits lines still in flight (profiles/r2_3d_bottleneck.md)
+                // one 4-byte-aligned dwordx2 / ushort per node pair; two aligned dword loads instead measured 165 -> 249 us at 256^3: the second
+                // load hits lines still in flight (profiles/r2_3d_bottleneck.md)
                 const F2U a = ld_at<F2U>(sb.u, o2);
                 ru[jb][0] = a.a; ru[jb][1] = a.b;
                 if constexpr (HAS_NU) { const F2U t = ld_at<F2U>(sb.nu, o2); rn[jb][0] = t.a; rn[jb][1] = t.b; }
                 if constexpr (HAS_F) { const F2U t = ld_at<F2U>(sb.f, o2); rf[jb][0] = t.a; rf[jb][1] = t.b; }
-#else
-                ru[jb][0] = ld_at<float>(sb.u, o2); ru[jb][1] = ld_at<float>(sb.u, o2 + 1u);
-                if constexpr (HAS_NU) { rn[jb][0] = ld_at<float>(sb.nu, o2); rn[jb][1] = ld_at<float>(sb.nu, o2 + 1u); }
-                if constexpr (HAS_F) { rf[jb][0] = ld_at<float>(sb.f, o2); rf[jb][1] = ld_at<float>(sb.f, o2 + 1u); }
-#endif
                 if constexpr (BC_U8C) {
                     // unconditional loads (an absent mask reads the other one and is ignored): a load inside a uniform branch makes
                     // the compiler wait vmcnt(0) at the end of the branch, which serialises every load of the plane behind it
 #pragma unroll
                     for (int k = 0; k < 2; ++k) {
-#if DN_T16_PAIRED
                         const B2U t = ld_at<B2U>(mask8[k], o2);
                         m8[jb][k][0] = t.a; m8[jb][k][1] = t.b;
-#else
-                        m8[jb][k][0] = ld_at<uint8_t>(mask8[k], o2); m8[jb][k][1] = ld_at<uint8_t>(mask8[k], o2 + 1u);
-#endif
                     }
                 } else if constexpr (BC_ANY) {
                     bc_issue<NW, false>(p, sb, rowoff[jb], (int)x0c, braw[jb]);
@@ -394,30 +302,18 @@ __global__ void __launch_bounds__(256, NGP == 4 ? 2 : (T16 ? (NGP == 2 ? ((FL & 
     unsigned pend_off = 0u;
     bool pend_st = false;
     auto flush_store = [&]() {
-#ifdef DN_ABL_STORE3D                      // timing experiment only
-        if (pend_st && pend_v == 123.456f) st_at<float>(sb.out, pend_off, pend_v);
-#else
         if (pend_st) st_at<float>(sb.out, pend_off, pend_v);
-#endif
         pend_st = false;
     };
     auto emit_plane = [&](const float (&o)[2][NW + 1], const float (&keep)[NW], int z, bool owned_plane) {
         if constexpr (T16) {
             const float left = lane_from_left(o[0][1], from_left, nfirst);          // right-hand contribution of the thread to the left
-#ifdef DN_ABL_XCH3D                        // timing experiment only: no LDS hand-over, no barrier
-            float t = o[0][0] + left + o[1][0] + lane_from_left(o[1][1], from_left, nfirst);
-#else
-            DN_STAMP(stamp_C);
             xch[par][0][tid] = o[1][0] + lane_from_left(o[1][1], from_left, nfirst);        // up slot with the up-right part of the left thread folded in
-#ifndef DN_ABLATE_BAR3D                    // timing experiment only: results are wrong without the barrier
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
-            DN_STAMP(stamp_D);
             // the value is stored by flush_store(), AFTER the next plane has been consumed and the one after it requested: a
             // store issued here would be younger than those loads' consumer wait, which the compiler turns into vmcnt(0)
             float t = o[0][0] + left;
             if (ty > 0) t += xch[par][0][tid - 16];
-#endif
             t *= keep[0];
             const bool st = owned_plane && owner && noderow_ok;
             sq_acc = st ? fmaf(t, t, sq_acc) : sq_acc;
@@ -487,28 +383,16 @@ __global__ void __launch_bounds__(256, NGP == 4 ? 2 : (T16 ? (NGP == 2 ? ((FL & 
         RawPlane W;
         plane_issue(ez_begin + 1, W);
         int ez = ez_begin;
-#if defined(DN_STAMP3D) && DN_NGP == 2
-        stamp_last = __builtin_amdgcn_s_memtime();
-#endif
 #pragma nounroll
         for (; ez + 1 < ez_end; ez += 2) {
             plane_consume(W, SB);
-            DN_STAMP(stamp_A);
             plane_issue(ez + 2, W);
             flush_store();
-            DN_STAMP(stamp_B);
             layer(ez, SA, SB);
-            DN_STAMP(stamp_E);
             plane_consume(W, SA);
-            DN_STAMP(stamp_A);
             plane_issue(ez + 3, W);
             flush_store();
-            DN_STAMP(stamp_B);
             layer(ez + 1, SB, SA);
-            DN_STAMP(stamp_E);
-#if defined(DN_STAMP3D) && DN_NGP == 2
-            stamp_n += 2;
-#endif
         }
         if (ez < ez_end) {
             plane_consume(W, SB);
@@ -543,18 +427,6 @@ __global__ void __launch_bounds__(256, NGP == 4 ? 2 : (T16 ? (NGP == 2 ? ((FL & 
         if constexpr (T16) flush_store();
     }
 
-#if defined(DN_STAMP3D) && DN_NGP == 2
-    if constexpr (T16) {
-        if (blockIdx.x % 61u == 0u && (tid & 63) == 0) {
-            const unsigned slot = (blockIdx.x / 61u) * 4u + (unsigned)(tid >> 6);
-            if (slot < 8192u) {
-                unsigned long long* d = dn_stamp_buf + slot * 8u;
-                d[0] = stamp_A; d[1] = stamp_B; d[2] = stamp_C; d[3] = stamp_D; d[4] = stamp_E; d[5] = stamp_n;
-                d[6] = stamp_t0; d[7] = __builtin_amdgcn_s_memtime();
-            }
-        }
-    }
-#endif
     if (p.want_sums) finish_sums(p, e1_acc, e2_acc, sq_acc, tid, TX * TY, red, &last_flag, (double)p.T.esc);
 }
 
@@ -568,17 +440,10 @@ __global__ void __launch_bounds__(256, NGP == 4 ? 2 : (T16 ? (NGP == 2 ? ((FL & 
 // the hand-over needs anyway, a thread reads the four records of its element with ds_read_b128.  One barrier per layer:
 //     request plane k + 2  ->  gather + stage plane k + 1 from LDS  ->  layer k  ->  publish plane k + 2, hand-over  ->  barrier  ->  finish plane k
 // =============================================================================================================
-#ifndef DN_TAB_VGPR
-#define DN_TAB_VGPR 0             // 1: 1-D tables in vector registers (103 VGPRs, 4 waves): measured equal (profiles/r2_prio3d.txt), off
-#endif
-#ifndef DN_Q1N_WAVES
-#define DN_Q1N_WAVES 5            // 2 x 2 x 2 points: <= 96 VGPRs.  The 3- and 4-point rules get 3 / 2 waves per SIMD (<= 168 / 256 VGPRs): at 5 they spilled 100-500 bytes of scratch per thread
-#endif
-#ifndef DN_PRIO3D
-#define DN_PRIO3D 0               // 1 / 2: static / rotating wave priorities per workgroup: measured equal (profiles/r2_prio3d.txt), off
-#endif
+// 2 x 2 x 2 points: 5 waves per SIMD (<= 96 VGPRs).  The 3- and 4-point rules get 3 / 2 (<= 168 / 256 VGPRs): at 5 they spilled 100-500 bytes of
+// scratch per thread
 template <int NGP, int FL, bool UW>
-__global__ void __launch_bounds__(256, NGP == 2 ? DN_Q1N_WAVES : (NGP == 3 ? 3 : 2)) poisson3d_q1n_kernel(const PoissonParams p, const int chunks_x, const int tiles_y, const int strips_z) {
+__global__ void __launch_bounds__(256, NGP == 2 ? 5 : (NGP == 3 ? 3 : 2)) poisson3d_q1n_kernel(const PoissonParams p, const int chunks_x, const int tiles_y, const int strips_z) {
     constexpr bool HAS_NU = (FL & FL3_NU) != 0, HAS_F = (FL & FL3_F) != 0, BC_U8C = (FL & FL3_BC_U8C) != 0;
     constexpr int NMASK = !BC_U8C ? 0 : ((FL & FL3_BC_ONE) ? 1 : 2);
     constexpr bool MASK_F32 = (FL & FL3_BC_F32) != 0;
@@ -612,27 +477,9 @@ __global__ void __launch_bounds__(256, NGP == 2 ? DN_Q1N_WAVES : (NGP == 3 ? 3 :
     const bool noderow_ok = ey < p.ny;
     const float okf = (ey < p.nely && x0 < p.nelx) ? 1.f : 0.f;         // elements beyond the mesh: computed on clamped data, scaled by 0
 
-    // DN_TAB_VGPR: the 1-D tables the loop multiplies with in VECTOR registers.  In isolation a VALU instruction with an SGPR operand
-    // does not pair with another wave's instruction on gfx950 (3.8 SIMD-cycles per instruction at 90 % SGPR-operand share against
-    // 2.3 with none, tools/micro/valu_sgpr.hip, profiles/r2_valu_sgpr.txt) and half of this loop's instructions read a table
-    // entry -- but this kernel's waves do not pair anyway (its layer period is the sum of its phases), so the switch measured equal.
+    // (The 1-D tables the loop multiplies with in VECTOR registers instead of SGPR operands measured equal, 103 VGPRs: this kernel's waves do
+    // not pair anyway, its layer period is the sum of its phases -- profiles/r2_prio3d.txt, profiles/r2_valu_sgpr.txt.)
     ElemTab TV = p.T;
-#if DN_TAB_VGPR
-#define DN_V(x) asm volatile("" : "+v"(x))
-#pragma unroll
-    for (int j = 0; j < NGP; ++j) {
-        DN_V(TV.b[j][1]);
-        if constexpr (!UW) { DN_V(TV.w[j]); DN_V(TV.wb[j]); }
-    }
-    DN_V(TV.m[1]); DN_V(TV.m01);
-    if constexpr (HAS_F) { DN_V(TV.m[2]); DN_V(TV.m12); DN_V(TV.nbw); }
-    DN_V(TV.kap[0]); DN_V(TV.kap[1]); DN_V(TV.kap[2]);
-#undef DN_V
-#endif
-#if defined(DN_STAMP3D) && DN_NGP == 2
-    unsigned long long stamp_A = 0, stamp_B = 0, stamp_C = 0, stamp_D = 0, stamp_E = 0, stamp_n = 0, stamp_last = 0;
-    const unsigned long long stamp_t0 = __builtin_amdgcn_s_memtime(), stamp_rt0 = __builtin_amdgcn_s_memrealtime();   // shader clock / constant 100 MHz clock
-#endif
     __shared__ float4 rec[2][17 * 17];            // [plane parity][node row * 17 + node column] = {u after Dirichlet, nu, f, keep}
     __shared__ float xch[2][256];
     __shared__ double red[2 * (256 / 64)];      // block_sum2: two sums per wave
@@ -756,12 +603,10 @@ __global__ void __launch_bounds__(256, NGP == 2 ? DN_Q1N_WAVES : (NGP == 3 ? 3 :
     };
     // hand the finished contributions over, (optionally) publish the plane requested at the top of the layer, ONE barrier, finish the node
     auto emit_plane = [&](const float (&o)[2][2], float keep, float uown, int z, bool owned_plane, const RawNodes* W, int zpub) {
-        DN_STAMP(stamp_C);
         const float left = lane_from_left(o[0][1], from_left, nfirst);
         xch[par][tid] = o[1][0] + lane_from_left(o[1][1], from_left, nfirst);
         if (W != nullptr) plane_publish(*W, zpub);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        DN_STAMP(stamp_D);
         float t = o[0][0] + left;
         if (ty > 0) t += xch[par][tid - 16];
         const bool st = owned_plane && owner && noderow_ok;
@@ -811,56 +656,17 @@ __global__ void __launch_bounds__(256, NGP == 2 ? DN_Q1N_WAVES : (NGP == 3 ? 3 :
     plane_gather(ez_begin, SA, keep_lo, u_lo);
     __syncthreads();              // every thread has read plane ez_begin before the first layer publishes plane ez_begin + 2 into its slot
     int ez = ez_begin;
-    // Wave priorities against lock-step: workgroups that start together and do identical work fall into phase (all request, then all
-    // gather, then all compute: the layer period becomes the SUM of the VALU, TA and LDS times instead of their maximum).  Different
-    // priorities for the workgroups resident on a CU let one run ahead through its arithmetic while the others use the memory paths.
-    const int prio_hash = (int)((blockIdx.x >> 8) & 3u);
-    auto set_prio = [&](int step) {
-#if DN_PRIO3D == 1
-        (void)step;
-        switch (prio_hash) {
-            case 0: __builtin_amdgcn_s_setprio(0); break;
-            case 1: __builtin_amdgcn_s_setprio(1); break;
-            case 2: __builtin_amdgcn_s_setprio(2); break;
-            default: __builtin_amdgcn_s_setprio(3); break;
-        }
-#elif DN_PRIO3D == 2
-        switch ((prio_hash + (step >> 1)) & 3) {
-            case 0: __builtin_amdgcn_s_setprio(0); break;
-            case 1: __builtin_amdgcn_s_setprio(1); break;
-            case 2: __builtin_amdgcn_s_setprio(2); break;
-            default: __builtin_amdgcn_s_setprio(3); break;
-        }
-#else
-        (void)step;
-#endif
-    };
-    set_prio(0);
-#if defined(DN_STAMP3D) && DN_NGP == 2
-    stamp_last = __builtin_amdgcn_s_memtime();
-#endif
+    // (Static or rotating wave priorities per workgroup, against workgroups falling into lock-step, measured equal: profiles/r2_prio3d.txt.)
 #pragma nounroll
     for (; ez + 1 < ez_end; ez += 2) {
-#if DN_PRIO3D == 2
-        set_prio(ez - ez_begin);
-#endif
         plane_request(ez + 2, W);                 // lands while this layer is computed; published before the layer's barrier
         flush_store();
-        DN_STAMP(stamp_A);
         plane_gather(ez + 1, SB, keep_up, u_up);
-        DN_STAMP(stamp_B);
         layer(ez, SA, SB, keep_lo, u_lo, &W);
-        DN_STAMP(stamp_E);
         plane_request(ez + 3, W);
         flush_store();
-        DN_STAMP(stamp_A);
         plane_gather(ez + 2, SA, keep_lo, u_lo);
-        DN_STAMP(stamp_B);
         layer(ez + 1, SB, SA, keep_up, u_up, &W);
-        DN_STAMP(stamp_E);
-#if defined(DN_STAMP3D) && DN_NGP == 2
-        stamp_n += 2;
-#endif
     }
     bool odd = false;
     if (ez < ez_end) {
@@ -877,20 +683,6 @@ __global__ void __launch_bounds__(256, NGP == 2 ? DN_Q1N_WAVES : (NGP == 3 ? 3 :
         flush_store();
     }
 
-#if defined(DN_STAMP3D) && DN_NGP == 2
-    if (tid == 0) {                               // node-owner build: wave 0 of EVERY workgroup (per-CU timelines, tools/stamp3d.py)
-        const unsigned slot = blockIdx.x;
-        if (slot < 8192u) {
-            unsigned long long* d = dn_stamp_buf + slot * 8u;
-            // where the wave ran: HW_REG_HW_ID (4: wave / SIMD / CU / SH / SE ids) and HW_REG_XCC_ID (20), whole registers
-            const unsigned long long hwid = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11));
-            d[0] = stamp_A; d[1] = stamp_B; d[2] = stamp_C; d[3] = stamp_D;
-            d[4] = stamp_E | ((__builtin_amdgcn_s_memrealtime() - stamp_rt0) << 40);          // lifetime in 10-ns ticks in the upper bits
-            d[5] = stamp_n | (hwid << 16) | ((xcc & 0xffull) << 48);
-            d[6] = stamp_t0; d[7] = __builtin_amdgcn_s_memtime();
-        }
-    }
-#endif
     if constexpr (E1G) e1_acc = (ut_acc / p.T.esc + p.T.beta * e2_acc) / p.T.alpha;       // per-thread share of sum W nu |grad u|^2 (the identity holds for the total)
     if (p.want_sums) finish_sums(p, e1_acc, e2_acc, sq_acc, tid, 256, red, &last_flag, (double)p.T.esc);
 }
@@ -905,14 +697,8 @@ __global__ void __launch_bounds__(256, NGP == 2 ? DN_Q1N_WAVES : (NGP == 3 ? 3 :
 // odd node columns, so that the three records a thread reads per node row are conflict-free b128 reads (lane stride 16 bytes).  The halo -- node
 // row 16 (33 nodes) and node column 32 (16 nodes) -- is loaded 13 nodes per wave.  Needs an even nx (8-byte aligned pairs).
 // =============================================================================================================
-#ifndef DN_Q1N2_WAVES
-#define DN_Q1N2_WAVES 3
-#endif
-#ifndef DN_Q1N2_LOAD_WAVES
-#define DN_Q1N2_LOAD_WAVES 3      // waves per SIMD asked of the load-vector instantiations (no staged forcing planes: 141-151 VGPRs with nu)
-#endif
-template <int FL>
-__global__ void __launch_bounds__(256, (FL & FL3_LOAD) ? DN_Q1N2_LOAD_WAVES : DN_Q1N2_WAVES) poisson3d_q1n2_kernel(const PoissonParams p, const int chunks_x, const int tiles_y, const int strips_z) {
+template <int FL>     // 3 waves per SIMD, the load-vector instantiations included (no staged forcing planes: 141-151 VGPRs with nu)
+__global__ void __launch_bounds__(256, 3) poisson3d_q1n2_kernel(const PoissonParams p, const int chunks_x, const int tiles_y, const int strips_z) {
     constexpr int NGP = 2;
     constexpr bool UW = true;
     // LOADV: the forcing arrives as the assembled load vector (one value per node, used by the node's owner only: no staging, no element
@@ -948,10 +734,6 @@ __global__ void __launch_bounds__(256, (FL & FL3_LOAD) ? DN_Q1N2_LOAD_WAVES : DN
     const bool noderow_ok = ey < p.ny;
     const float okf[2] = {(ey < p.nely && x0 < p.nelx) ? 1.f : 0.f, (ey < p.nely && x0 + 1 < p.nelx) ? 1.f : 0.f};
     const ElemTab& TV = p.T;
-#if defined(DN_STAMP3D)
-    unsigned long long stamp_A = 0, stamp_B = 0, stamp_C = 0, stamp_D = 0, stamp_E = 0, stamp_n = 0, stamp_last = 0;
-    const unsigned long long stamp_t0 = __builtin_amdgcn_s_memtime(), stamp_rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
 
     __shared__ float4 recE[2][17][17];            // [plane parity][node row][even node column / 2] = {u after Dirichlet, nu, f, keep}
     __shared__ float4 recO[2][17][16];
@@ -1123,7 +905,6 @@ __global__ void __launch_bounds__(256, (FL & FL3_LOAD) ? DN_Q1N2_LOAD_WAVES : DN
     // o[node row][node column of the element]: contributions of the thread's two elements (.x, .y) to their 2 x 2 nodes in the plane being
     // finished.  The thread's node columns: c0 = o[.][0].x (+ the left thread's o[.][1].y), c1 = o[.][1].x + o[.][0].y; o[.][1].y goes right.
     auto emit_plane = [&](const v2f (&o)[2][2], int z, bool owned_plane, const RawNodes2* W, int zpub) {
-        DN_STAMP(stamp_C);
         // keep and (E1G) the value of the own node pair in the plane being finished: re-read from the thread's own records rather than carried in
         // eight registers through the layer (the kernel sits at its register cap).  The reads are issued BEFORE this call's publish overwrites the
         // records of the same parity (a wave's LDS accesses execute in order) and land under the barrier.
@@ -1134,7 +915,6 @@ __global__ void __launch_bounds__(256, (FL & FL3_LOAD) ? DN_Q1N2_LOAD_WAVES : DN
         xch[par][tid] = make_float2(o[1][0].x + lane_from_left(o[1][1].y, from_left, nfirst), o[1][1].x + o[1][0].y);
         if (W != nullptr) plane_publish(*W, zpub);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        DN_STAMP(stamp_D);
         v2f t = {o[0][0].x + left0, o[0][1].x + o[0][0].y};
         if (ty > 0) {
             const float2 up = xch[par][tid - 16];
@@ -1194,28 +974,16 @@ __global__ void __launch_bounds__(256, (FL & FL3_LOAD) ? DN_Q1N2_LOAD_WAVES : DN
     plane_gather(ez_begin, SA);
     __syncthreads();
     int ez = ez_begin;
-#if defined(DN_STAMP3D)
-    stamp_last = __builtin_amdgcn_s_memtime();
-#endif
 #pragma nounroll
     for (; ez + 1 < ez_end; ez += 2) {
         plane_request(ez + 2, W);                 // lands while this layer is computed; published before the layer's barrier
         flush_store();
-        DN_STAMP(stamp_A);
         plane_gather(ez + 1, SB);
-        DN_STAMP(stamp_B);
         layer(ez, SA, SB, &W);
-        DN_STAMP(stamp_E);
         plane_request(ez + 3, W);
         flush_store();
-        DN_STAMP(stamp_A);
         plane_gather(ez + 2, SA);
-        DN_STAMP(stamp_B);
         layer(ez + 1, SB, SA, &W);
-        DN_STAMP(stamp_E);
-#if defined(DN_STAMP3D)
-        stamp_n += 2;
-#endif
     }
     bool odd = false;
     if (ez < ez_end) {
@@ -1231,30 +999,10 @@ __global__ void __launch_bounds__(256, (FL & FL3_LOAD) ? DN_Q1N2_LOAD_WAVES : DN
         emit_plane(o, p.nz - 1, true, nullptr, 0);
         flush_store();
     }
-#if defined(DN_STAMP3D)
-    if (tid == 0) {                               // wave 0 of every workgroup (tools/stamp3d.py)
-        const unsigned slot = blockIdx.x;
-        if (slot < 8192u) {
-            unsigned long long* d = dn_stamp_buf + slot * 8u;
-            const unsigned long long hwid = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11));
-            d[0] = stamp_A; d[1] = stamp_B; d[2] = stamp_C; d[3] = stamp_D;
-            d[4] = stamp_E | ((__builtin_amdgcn_s_memrealtime() - stamp_rt0) << 40);
-            d[5] = stamp_n | (hwid << 16) | ((xcc & 0xffull) << 48);
-            d[6] = stamp_t0; d[7] = __builtin_amdgcn_s_memtime();
-        }
-    }
-#endif
     float e1_acc = e1_acc2.x + e1_acc2.y;
     const float e2_acc = e2_acc2.x + e2_acc2.y, sq_acc = sq_acc2.x + sq_acc2.y;
     if constexpr (E1G) e1_acc = ((ut_acc.x + ut_acc.y) / p.T.esc + p.T.beta * e2_acc) / p.T.alpha;
     if (p.want_sums) finish_sums(p, e1_acc, e2_acc, sq_acc, tid, 256, red, &last_flag, (double)p.T.esc);
-}
-
-// diagnostic: resident workgroups per CU the runtime grants the default 3-D kernel (tools/occ3d.py prints it)
-extern "C" int dn_debug_occupancy_q1n(void) {
-    int n = -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, poisson3d_q1n_kernel<2, FL3_NU | FL3_F | FL3_BC_U8C | FL3_BC_ONE, true>, 256, 0) != hipSuccess) return -1;
-    return n;
 }
 #endif
 

@@ -27,8 +27,8 @@
 // oracle; tests/test_gpu_q1cf3d.py: this kernel against the oracle and against the round-3 kernels).
 // Measured (profiles/r4_3d_cf_times.txt): 256^3 121 -> 95 us, 128^3 26 -> 22 us.  With the arithmetic cut down the launch is bound by its ACCESS
 // PATTERN (89.6 us with every LDS access, hand-over, barrier and all arithmetic removed: pair loads 44.5 + store 22 + mask bytes 7 + halo 16) and,
-// right behind it, by the per-layer chain of publish / hand-over / finish; the DN_CF3_ABL_* switches below are the timing experiments that showed it
-// (their results are wrong by construction; none is defined in the library build).
+// right behind it, by the per-layer chain of publish / hand-over / finish.  Timing builds with parts of the kernel cut out (results wrong by
+// construction) and a per-phase cycle budget of the loop (profiles/r4_stamp3d_cf.txt) showed it; they were removed from the source.
 #include <cmath>
 
 #include "poisson_common.h"
@@ -52,24 +52,6 @@ struct Cf3Consts {
     float inv_esc, beta, inv_alpha;
 };
 
-#ifndef DN_CF3_PF
-#define DN_CF3_PF 1                   // planes in flight per thread (raw register sets): 1, or 2 (9 VGPRs more; measured equal: profiles/r4_3d_cf_times.txt)
-#endif
-#ifndef DN_Q1CF_WAVES
-#define DN_Q1CF_WAVES 3               // waves per SIMD asked of the compiler (<= 168 VGPRs)
-#endif
-
-#if defined(DN_STAMP3D)
-// Diagnostic build only (tools/stamp3d.py): per-wave cycle budget of the loop, accumulated in scalar registers with s_memtime and written once
-// at the end of the kernel by wave 0 of every workgroup.  Phases per layer: A = request the next plane + deferred store, B = gather the upper
-// plane from LDS + stage it, C = layer arithmetic + adjoint, D = hand-over + publish + barrier, E = hand-over read + finish the node values.
-__device__ unsigned long long dn_stamp_buf[8192 * 8];
-extern "C" int dn_debug_stamps(void* dst, size_t bytes) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(dn_stamp_buf), bytes); }
-#define DN_STAMP(var) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t__ = __builtin_amdgcn_s_memtime(); var += t__ - stamp_last; stamp_last = t__; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define DN_STAMP(var) do { } while (0)
-#endif
-
 // lane l <- lane l - 1 of the wave, 0 for the first lane of a row of 16.  ds_bpermute, not DPP: on gfx950 a DPP move costs a shared SIMD ~33
 // cycles, a ds_bpermute ~3 (tools/micro/valu_mem.hip, profiles/r2_valu_mem.txt).
 __device__ __forceinline__ float cf3_from_left(float v, int from, float nf) {
@@ -88,8 +70,8 @@ __device__ __forceinline__ float cf3_usel_lt(int a, int b, float x, float y) {
     return __builtin_bit_cast(float, r);
 }
 
-template <int FL>
-__global__ void __launch_bounds__(256, DN_Q1CF_WAVES) poisson3d_q1_cf_kernel(const PoissonParams p, const Cf3Consts k, const int chunks_x, const int tiles_y, const int strips_z) {
+template <int FL>     // 3 waves per SIMD asked of the compiler (<= 168 VGPRs)
+__global__ void __launch_bounds__(256, 3) poisson3d_q1_cf_kernel(const PoissonParams p, const Cf3Consts k, const int chunks_x, const int tiles_y, const int strips_z) {
     constexpr bool HAS_NU = (FL & CF3_NU) != 0, F_ARR = (FL & CF3_F) != 0, LOADV = F_ARR && (FL & CF3_LOAD) != 0, HAS_F = F_ARR && !LOADV;
     constexpr bool IMG = (FL & CF3_IMG) != 0, BOX = (FL & CF3_BOX) != 0;
     constexpr int NMASK = !IMG ? 0 : ((FL & CF3_ONE) ? 1 : 2);
@@ -124,10 +106,6 @@ __global__ void __launch_bounds__(256, DN_Q1CF_WAVES) poisson3d_q1_cf_kernel(con
 
     const v2f okv = {(ey < p.nely && x0 < p.nelx) ? 1.f : 0.f, (ey < p.nely && x0 + 1 < p.nelx) ? 1.f : 0.f};
     const v2f okown = owner ? okv : zero2;         // elements this workgroup counts in the element sums
-#if defined(DN_STAMP3D)
-    unsigned long long stamp_A = 0, stamp_A1 = 0, stamp_B = 0, stamp_C = 0, stamp_D = 0, stamp_E = 0, stamp_n = 0, stamp_last = 0;
-    const unsigned long long stamp_t0 = __builtin_amdgcn_s_memtime(), stamp_rt0 = __builtin_amdgcn_s_memrealtime();
-#endif
 
     // The node planes in LDS: ONE block, two slots; per slot 17 node rows, per row the three fields one after the other, per field the EVEN node
     // columns (17 floats, padded to 18) followed by the ODD ones (16, padded to 18).  A thread's element pair needs the node pairs (x0, x0 + 1)
@@ -212,33 +190,17 @@ __global__ void __launch_bounds__(256, DN_Q1CF_WAVES) poisson3d_q1_cf_kernel(con
         const unsigned zoff_f = HAS_F ? (unsigned)min(zreq + 1, p.nz - 1) * npl : zoff;
         const unsigned oo = zoff + own_off, oh = zoff + halo_off + (halo_fmask & (zoff_f - zoff));
         W.u = ld_pair(sb.u, oo);
-#ifdef DN_CF3_ABL_REQ                      // timing experiment only (results are wrong): u is the one array requested, the other values are made up from it
-        W.n = W.u + 0.5f; W.f = W.u; W.h = W.u.x;
-        W.m[0] = W.m[1] = (uint16_t)(W.u.x == 123.456f); W.hm[0] = W.hm[1] = (uint8_t)W.m[0];
-        W.mf[0] = W.mf[1] = 0.f; W.hmf[0] = W.hmf[1] = 0.f;
-        return;
-#endif
         if constexpr (HAS_NU) W.n = ld_pair(sb.nu, oo);
         if constexpr (F_ARR) W.f = ld_pair(sb.f, zoff_f + own_off);
-#ifdef DN_CF3_ABL_HALO                     // timing experiment only (results are wrong): no halo requests
-        W.h = W.u.x; W.hm[0] = W.hm[1] = 0; W.hmf[0] = W.hmf[1] = 0.f;
-#else
         W.h = halo_src[oh];
-#endif
         if constexpr (IMG) {
             const unsigned ohm = zoff + halo_off;
 #pragma unroll
             for (int kk = 0; kk < NMASK; ++kk) {
-#ifdef DN_CF3_ABL_MASK                     // timing experiment only (results are wrong): no mask requests for the own pair
-                W.m[kk] = (uint16_t)(W.u.x == 123.456f); W.mf[kk] = 0.f;
-#else
                 if constexpr (MASK_F32) W.mf[kk] = ld_pair(mask32[kk], oo);
                 else W.m[kk] = ld_at<uint16_t>(mask8[kk], oo);
-#endif
-#ifndef DN_CF3_ABL_HALO
                 if constexpr (MASK_F32) W.hmf[kk] = ld_at<float>(mask32[kk], ohm);
                 else W.hm[kk] = ld_at<uint8_t>(mask8[kk], ohm);
-#endif
             }
         }
     };
@@ -416,26 +378,19 @@ __global__ void __launch_bounds__(256, DN_Q1CF_WAVES) poisson3d_q1_cf_kernel(con
     const int from_left = (int)(((unsigned)tid - 1u) & 63u) << 2;
     const float nfirst = tx > 0 ? 1.f : 0.f;
     float2 pend_v = make_float2(0.f, 0.f);
-#ifdef DN_CF3_ABL_PUB
-    float abl_sink = 0.f;
-#endif
     unsigned pend_off = 0u;
     bool pend_st = false;
     // (The store as one asm block that selects the owning lanes through the exec mask -- no branch, so that the compiler's vmcnt waits for the raw
     // plane's loads stay exact instead of vmcnt(0) -- was built and measured, with one and two planes in flight: equal, profiles/r4_3d_cf_times.txt.)
     auto flush_store = [&]() {
-#ifdef DN_CF3_ABL_STORE                    // timing experiment only (results are wrong): nothing is stored
-        if (pend_st && pend_v.x == 123.456f) st_at<float2>(sb.out, pend_off, pend_v);
-#else
         if (pend_st) st_at<float2>(sb.out, pend_off, pend_v);
-#endif
         pend_st = false;
     };
     // One element layer between the staged plane L (lower, plane ez, LDS slot zslot) and the plane above (slot 1 - zslot), whose node pairs were
     // requested from LDS right after the previous layer's barrier.  Order of a layer (every step overlaps the latencies of the ones before it):
     //   1  request the node pairs of the upper plane from LDS (asm, not waited for yet); read the own pair's load vector of plane ez
-    //   2  publish plane ez + 2 (requested from memory two layers ago) into slot zslot: every thread gathered plane ez before the previous barrier
-    //   3  request plane ez + 4 from memory into the raw set just published; the deferred store of plane ez - 1
+    //   2  publish plane ez + 2 (requested from memory one layer ago) into slot zslot: every thread gathered plane ez before the previous barrier
+    //   3  request plane ez + 3 from memory into the raw set just published; the deferred store of plane ez - 1
     //   4  stage the upper plane (its LDS reads have had steps 2-3 to land), element arithmetic, adjoint of the in-plane stage
     //   5  hand-over: right-hand contributions to the lane on the right (ds_bpermute), the upper node row's to the thread above (LDS slot)
     //   6  ONE barrier (LDS only): it publishes plane ez + 2 and the hand-over slots
@@ -452,23 +407,11 @@ __global__ void __launch_bounds__(256, DN_Q1CF_WAVES) poisson3d_q1_cf_kernel(con
     };
     // steps 5-8
     auto emit_plane = [&](const v2f (&o)[2][2], const v2f uown, const OwnVals& ov, int z, int zslot, bool owned_plane) {
-        DN_STAMP(stamp_C);
-#ifdef DN_CF3_ABL_XCH                      // timing experiment only (results are wrong): no lane exchange, no hand-over slot
-        const float left0 = o[0][1].y;
-#else
         const float left0 = cf3_from_left(o[0][1].y, from_left, nfirst);
         lds_st2(lds_pair, OFF_X + zslot * 512, o[1][0].x + cf3_from_left(o[1][1].y, from_left, nfirst), o[1][1].x + o[1][0].y);
-#endif
-#ifdef DN_CF3_ABL_BAR                      // timing experiment only (results are wrong): no workgroup barrier
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
-        DN_STAMP(stamp_D);
         v2f up = {0.f, 0.f};
-#ifndef DN_CF3_ABL_XCH
         if (ty > 0) up = lds_ld2(lds_pair, OFF_X + zslot * 512 - 32);       // the hand-over of the thread one node row below (tid - 16)
-#endif
         v2f keep = {1.f, 1.f};
         if constexpr (IMG) keep = lds_ld2(lds_pair + (z & 3) * 2048, OFF_K);
         if constexpr (BOX && !IMG) {           // in-plane faces: per thread; a plane on a fixed z face: every node
@@ -496,9 +439,6 @@ __global__ void __launch_bounds__(256, DN_Q1CF_WAVES) poisson3d_q1_cf_kernel(con
         if constexpr (IMG || BOX) t *= keep;
         sq_acc = fmaf(t.x, t.x, fmaf(t.y, t.y, sq_acc));
         pend_v = make_float2(t.x * p.out_scale, t.y * p.out_scale);
-#ifdef DN_CF3_ABL_PUB
-        pend_v.x += abl_sink;
-#endif
         pend_off = (unsigned)z * npl + out_base;
         pend_st = st && sb.out != nullptr && x0 < p.nx;
     };
@@ -507,44 +447,16 @@ __global__ void __launch_bounds__(256, DN_Q1CF_WAVES) poisson3d_q1_cf_kernel(con
         const bool own_layer = ez >= ez_own;
         // (the reads are issued and waited for inside ONE layer: carried over the loop's back edge, their target registers could be copied by the
         // compiler before the data has landed -- it does not know that an asm LDS read completes later)
-#ifndef DN_CF3_ABL_GATHER                  // timing experiment only (with DN_CF3_ABL_MATH; results are wrong): no LDS gather
         gather_issue(1 - zslot);
-#endif
         OwnVals ov;
         own_read(zslot, ov);
         if (W != nullptr) {
-#ifndef DN_CF3_ABL_PUB                     // timing experiment only (results are wrong): nothing is published into LDS -- the loaded values only feed the stored value
             plane_publish(*W, ez + 2, zslot);
-#else
-            abl_sink += W->u.x + W->u.y + W->h;
-            if constexpr (HAS_NU) abl_sink += W->n.x + W->n.y;
-            if constexpr (F_ARR) abl_sink += W->f.x + W->f.y;
-            if constexpr (IMG && !MASK_F32) abl_sink += (float)(W->m[0] + W->hm[0]);
-#endif
-            DN_STAMP(stamp_A1);
-            plane_request(ez + 2 + DN_CF3_PF, *W);
+            plane_request(ez + 3, *W);
         }
         flush_store();
-        DN_STAMP(stamp_A);
         v2f F[2][2];
-#ifdef DN_CF3_ABL_MATH                     // timing experiment only (results are wrong): the memory side alone -- every load, LDS access, hand-over, barrier and store, no element arithmetic
-        {
-#ifdef DN_CF3_ABL_GATHER
-            RP.u00 = RP.u10 = RP.u01 = RP.u11 = RP.n00 = RP.n10 = RP.n01 = RP.n11 = RP.f00 = RP.f10 = RP.f01 = RP.f11 = L.own;
-#endif
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(RP.u00), "+v"(RP.u10), "+v"(RP.u01), "+v"(RP.u11));
-            v2f acc = RP.u00 + RP.u10 + RP.u01 + RP.u11;
-            if constexpr (HAS_NU) { asm volatile("" : "+v"(RP.n00), "+v"(RP.n10), "+v"(RP.n01), "+v"(RP.n11)); acc += RP.n00 + RP.n10 + RP.n01 + RP.n11; }
-            if constexpr (HAS_F) { asm volatile("" : "+v"(RP.f00), "+v"(RP.f10), "+v"(RP.f01), "+v"(RP.f11)); acc += RP.f00 + RP.f10 + RP.f01 + RP.f11; }
-            v2f oa[2][2] = {{acc, acc * 0.5f}, {acc * 0.25f, acc * 0.125f}};
-            Up.own = RP.u00;
-            emit_plane(oa, L.own, ov, ez, zslot, own_layer);
-            DN_STAMP(stamp_E);
-            return;
-        }
-#endif
         gather_stage(Up, F);
-        DN_STAMP(stamp_B);
         v2f GX[2], GY[2], GU[2][2], Sz[2][2];
 #pragma unroll
         for (int j = 0; j < 2; ++j)
@@ -579,12 +491,11 @@ __global__ void __launch_bounds__(256, DN_Q1CF_WAVES) poisson3d_q1_cf_kernel(con
         v2f o[2][2];
         plane_adjoint(GX, GY, GU, o);
         emit_plane(o, L.own, ov, ez, zslot, own_layer);
-        DN_STAMP(stamp_E);
     };
 
     // prologue: planes ez_begin (slot 0) and ez_begin + 1 (slot 1) into LDS (requested together), the lower one staged
-    // DN_CF3_PF planes are in flight per thread: the plane published at the start of a layer was requested DN_CF3_PF layers earlier (with two, WA
-    // carries the even and WB the odd planes after the first; measured equal to one, which is the default)
+    // One plane is in flight per thread: the plane published at the start of a layer was requested one layer earlier, into WA (two planes in flight
+    // measured equal, with 9 VGPRs more: profiles/r4_3d_cf_times.txt)
     RawNodes WA, WB;
     {
         RawNodes& W0 = WA;
@@ -599,9 +510,6 @@ __global__ void __launch_bounds__(256, DN_Q1CF_WAVES) poisson3d_q1_cf_kernel(con
         plane_publish(W0, ez_begin, 0);
         plane_publish(W, ez_begin + 1, 1);
         plane_request(ez_begin + 2, WA);
-#if DN_CF3_PF == 2
-        plane_request(ez_begin + 3, WB);
-#endif
     }
     __syncthreads();
     {
@@ -628,20 +536,10 @@ __global__ void __launch_bounds__(256, DN_Q1CF_WAVES) poisson3d_q1_cf_kernel(con
     // every thread has read plane ez_begin (slot 0) before the first layer publishes plane ez_begin + 2 into that slot
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     int ez = ez_begin;
-#if defined(DN_STAMP3D)
-    stamp_last = __builtin_amdgcn_s_memtime();
-#endif
 #pragma nounroll
     for (; ez + 1 < ez_end; ez += 2) {
-        layer(ez, 0, SA, SB, &WA);                // publishes plane ez + 2 (requested two layers ago), requests plane ez + 4
-#if DN_CF3_PF == 2
-        layer(ez + 1, 1, SB, SA, &WB);
-#else
+        layer(ez, 0, SA, SB, &WA);                // publishes plane ez + 2 (requested one layer ago), requests plane ez + 3
         layer(ez + 1, 1, SB, SA, &WA);
-#endif
-#if defined(DN_STAMP3D)
-        stamp_n += 2;
-#endif
     }
     // the last strip owns the top boundary plane: only the layer below contributes -- take back one of the plane's two products.  (Called on SA
     // or SB by name: selecting between the two states through a reference would put both into scratch memory.)
@@ -666,19 +564,6 @@ __global__ void __launch_bounds__(256, DN_Q1CF_WAVES) poisson3d_q1_cf_kernel(con
         flush_store();
         if (ez_end == p.nelz) top_plane(SA, 0);
     }
-#if defined(DN_STAMP3D)
-    if (tid == 0) {                               // wave 0 of every workgroup (tools/stamp3d.py)
-        const unsigned slot = blockIdx.x;
-        if (slot < 8192u) {
-            unsigned long long* d = dn_stamp_buf + slot * 8u;
-            const unsigned long long hwid = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11));
-            d[0] = stamp_A | (stamp_A1 << 32); d[1] = stamp_B; d[2] = stamp_C; d[3] = stamp_D;       // A1 (gather issue + publish) in the upper half
-            d[4] = stamp_E | ((__builtin_amdgcn_s_memrealtime() - stamp_rt0) << 40);
-            d[5] = stamp_n | (hwid << 16) | ((xcc & 0xffull) << 48);
-            d[6] = stamp_t0; d[7] = __builtin_amdgcn_s_memtime();
-        }
-    }
-#endif
     if (p.want_sums) {
         // sum_a u_a out_a = wscale ( alpha sum nu |grad u|^2 - beta sum f u ): this thread's share of the stiffness sum (the identity holds for the total)
         const float e1_acc = (ut_acc * k.inv_esc + k.beta * e2_acc) * k.inv_alpha;

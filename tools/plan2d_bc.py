@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Launch-plan sweep (dn_config_set("PLAN2D", "T,E,R")) of the 2-D headline launch for the box / u8 Dirichlet forms, in steady state:
 40 ms of load first (tools/ramp2d.py), then 200 prepared launches back to back between ONE pair of events, plans interleaved over rounds.
-usage: plan2d_bc.py [plan ...]   (DN_LIB_PATH selects a variant build)"""
+usage: plan2d_bc.py [plan ...]"""
 import os
 import sys
 import time

@@ -1,6 +1,6 @@
 #!/bin/bash
 # round 4 evidence in one call: GPU test suite, bench line (default and with the driver's arguments), rocprofv3 kernel stats of the bench command,
-# counter passes of the 2-D bench kernel (mask bits, folded sums) and of the closed-form 3-D kernel at 256^3 / 128^3, phase stamps of the 3-D kernel
+# counter passes of the 2-D bench kernel (mask bits, folded sums) and of the closed-form 3-D kernel at 256^3 / 128^3
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 root=$(pwd)
@@ -15,10 +15,6 @@ rm -rf $O/kt
 DN_BC_FORM=bits DN_SUMS=fold tools/prof_case.sh r4_2d_bits 2 512 64 3 "" 12 > /dev/null 2>&1; echo "pmc 2d bits rc=$?"
 tools/prof_case.sh r4_3d_256_cf 3 256 1 2 "" 12 > /dev/null 2>&1; echo "pmc 3d 256 rc=$?"
 tools/prof_case.sh r4_3d_128_cf 3 128 1 2 "" 12 > /dev/null 2>&1; echo "pmc 3d 128 rc=$?"
-if [ -f variants/libdn_stamp.so ]; then
-  DN_LIB_PATH=variants/libdn_stamp.so python tools/stamp3d.py 256 1 2>&1 | grep -v amdgpu.ids | head -12 > $O/stamp256.txt
-  DN_LIB_PATH=variants/libdn_stamp.so python tools/stamp3d.py 128 1 2>&1 | grep -v amdgpu.ids | head -12 > $O/stamp128.txt
-fi
 # second half of the round: FSDT stencil form against the element form (single launches, rotation-free: B = 8 fits the 256 MB cache, see the pair), the loss + gradient
 # pair with deferred sums, the cost of the in-kernel sums, the generic operators through the raw launches, the 3-D generator's training step
 (python tools/time_fsdt.py 1025 2; DN_FSDT_FORM=elem python tools/time_fsdt.py 1025 2) 2>&1 | grep -v amdgpu.ids > $O/fsdt_forms.txt

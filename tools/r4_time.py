@@ -2,7 +2,7 @@
 """Round-4 timing harness: one fused Poisson launch (2-D or 3-D Q1) over NSETS field sets in rotation, prepared launches back to back,
 steady state.  usage: r4_time.py <2|3> <n> <B> <bc: none|u8|f32|bits|box> [key=value ...]
 keys: sums=1|0|defer|fold (in-kernel final reduction / no sums / per-workgroup partials only / partials folded by the next launch), load=1 (forcing as LoadVector), nsets=4, plan=<PLAN2D|PLAN3D override>,
-      nu=1|0, f=1|0, pad=<bytes> (stagger the fields' start addresses), reps=3, iters=400, tag=<label>, cfg=KEY:VALUE[,...] (dn_config_set).  DN_LIB_PATH selects a variant build."""
+      nu=1|0, f=1|0, pad=<bytes> (stagger the fields' start addresses), reps=3, iters=400, tag=<label>, cfg=KEY:VALUE[,...] (dn_config_set)."""
 import os, sys, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from diffnet_amd import BoxFaces, DiffNet2DFEM, DiffNet3DFEM, LoadVector, PackedMask, _lib, ops

@@ -15,7 +15,7 @@ for k in range(int(os.environ.get('NSETS', '8'))):
     u, nu, f = (torch.rand(shape, generator=g).to(dev) for _ in range(3))
     nu += 0.5
     sets.append((u, nu, f))
-# usage: rotate_batches.py [PLAN2D override | default] [box | bits | u8]   (DN_LIB_PATH selects a variant build)
+# usage: rotate_batches.py [PLAN2D override | default] [box | bits | u8]
 if len(sys.argv) > 1 and sys.argv[1] != "default":
     _lib.config_set("PLAN2D", sys.argv[1])
 form = sys.argv[2] if len(sys.argv) > 2 else "box"
