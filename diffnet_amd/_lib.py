@@ -9,7 +9,7 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DN_LIB_PATH") or os.path.join(HERE, "libdiffnet_hip.so")     # DN_LIB_PATH: another build of the library
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 DN_E = {-1: "DN_E_BADARG", -2: "DN_E_UNSUPPORTED", -3: "DN_E_WORKSPACE", -4: "DN_E_HANDOVER"}
 
@@ -54,6 +54,16 @@ class DnFsdtArgs(C.Structure):
                 ("defer_sums", C.c_int32), ("den_ticket", C.c_int32), ("den_workspace", C.c_void_p)]
 
 
+class DnStokesArgs(C.Structure):
+    _fields_ = [("u", C.c_void_p), ("v", C.c_void_p), ("p", C.c_void_p),
+                ("bc_mask", C.c_void_p * 3), ("mask_is_u8", C.c_int32 * 3), ("mask_batched", C.c_int32 * 3),
+                ("bc_field", C.c_void_p * 3), ("bc_field_batched", C.c_int32 * 3), ("bc_value", C.c_float * 3),
+                ("f_gp", C.c_void_p * 2), ("f_batched", C.c_int32 * 2), ("f_value", C.c_float * 2),
+                ("visco", C.c_float), ("pspg", C.c_float), ("wscale", C.c_float), ("transpose", C.c_int32),
+                ("out", C.c_void_p * 3), ("sumsq", C.c_void_p), ("norms", C.c_void_p), ("in_num", C.c_void_p), ("in_den", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 I32x3 = C.c_int32 * 3
 
 # name -> (restype, argtypes); must list every symbol of include/diffnet_hip.h
@@ -87,6 +97,8 @@ SYMBOLS = {
                                    C.c_float, C.c_float, C.c_void_p]),
     "dn_fsdt_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
     "dn_fsdt_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnFsdtArgs), C.c_void_p]),
+    "dn_stokes_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
+    "dn_stokes_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnStokesArgs), C.c_void_p]),
     "dn_upconv_out_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "dn_upconv_out_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                     C.c_void_p, C.c_int64, C.c_void_p]),

@@ -34,8 +34,10 @@ struct FsdtParams {
 constexpr int FSDT_WS_NBLOCKS_WORD = 4;    // word of the workspace header in which a deferring launch leaves its number of workgroups
 constexpr int FSDT_WS_TICKET_WORD = 5;     // ... and its ticket (0 after any launch that reduced in the kernel)
 
-// Deterministic in-kernel final reduction of three scalars (same protocol as finish_sums in poisson_common.h).
-__device__ __forceinline__ void finish_sums3(const FsdtParams& p, const float (&sq)[3], int tid, int nthreads, double* red, int* flag) {
+// Deterministic in-kernel final reduction of three scalars (same protocol as finish_sums in poisson_common.h).  Params: any kernel
+// parameter struct with the members part, counter, sumsq and norms of FsdtParams (FsdtParams, StokesParams in stokes.hip).
+template <class Params>
+__device__ __forceinline__ void finish_sums3(const Params& p, const float (&sq)[3], int tid, int nthreads, double* red, int* flag) {
     const int nblocks = gridDim.x * gridDim.y * gridDim.z;
     const int blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     double s[3];

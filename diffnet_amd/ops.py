@@ -11,7 +11,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import DnDirichlet, DnFsdtArgs, DnMesh, DnPoissonArgs, I32x3, DiffNetHipError
+from ._lib import DnDirichlet, DnFsdtArgs, DnMesh, DnPoissonArgs, DnStokesArgs, I32x3, DiffNetHipError
 
 
 def _require(t, name, ndim=None, strict=False):
@@ -578,9 +578,11 @@ def call_cache_clear():
     with _WS_LOCK:
         _CALL_CACHE.clear()
         _FSDT_CACHE.clear()
+        _STOKES_CACHE.clear()
         _PACK_CACHE.clear()
     _POISSON_WS_BYTES.clear()
     _FSDT_WS_BYTES.clear()
+    _STOKES_WS_BYTES.clear()
 
 
 class PoissonPlan:
@@ -1298,6 +1300,222 @@ class FsdtPlan:
                 _lib.check(rc, "dn_fsdt_apply")
         return self.result
 
+
+
+# ---- fused 2-D Stokes (PSPG) residuals: dn_stokes_apply -------------------------------------------------------------------------
+# The launch has a reduction workspace of its OWN per (device, stream), never the one of _workspace: an FSDT launch with defer_norms leaves
+# its partials in that one for a later consumer, and a Stokes launch issued in between must not overwrite them.
+_STOKES_WS = {}
+_STOKES_WS_BYTES = {}
+_STOKES_CACHE = __import__("collections").OrderedDict()
+_STOKES_LAUNCH_LOCK = _threading.Lock()
+
+
+def _stokes_workspace(dev, nbytes):
+    key = (dev.index, _raw_stream(dev))
+    with _WS_LOCK:
+        ws = _STOKES_WS.get(key)
+        if ws is None or ws.numel() < nbytes:
+            ws = torch.zeros(max(nbytes, 1 << 16), dtype=torch.uint8, device=dev)   # ABI: zero-filled once
+            _STOKES_WS[key] = ws
+    return ws
+
+
+def stokes_bc3(bc):
+    """The three Dirichlet masks of a Stokes call: `bc` is one mask shared by u, v and p, or a sequence of three (None: no condition)."""
+    if bc is None or isinstance(bc, torch.Tensor):
+        return (bc, bc, bc)
+    bc = tuple(bc)
+    if len(bc) != 3:
+        raise ValueError(f"stokes: bc must be one mask or three (got {len(bc)})")
+    return bc
+
+
+def stokes_f2(f_gp):
+    """The two forcing terms of a Stokes call: None (no forcing), or a pair of None / float / Gauss-point tensor (Bf, G, nely, nelx)."""
+    if f_gp is None:
+        return (0.0, 0.0)
+    f_gp = tuple(f_gp)
+    if len(f_gp) != 2:
+        raise ValueError(f"stokes: f_gp must be a pair (f1, f2) (got {len(f_gp)})")
+    return tuple(0.0 if f is None else f for f in f_gp)
+
+
+def _stokes_check_mesh(geom):
+    if geom.nsd != 2 or geom.deg != 1 or not 2 <= geom.ngp_1d <= 4:
+        raise DiffNetHipError(f"stokes_apply: 2-D Q1 meshes with 2..4 Gauss points per axis only (nsd {geom.nsd}, degree {geom.deg}, ngp {geom.ngp_1d})")
+
+
+def _stokes_key(geom, flds, bc3, vals, f2, consts, in_num, in_den, flags):
+    """Key of a cached prepared dn_stokes_apply call (see _call_key); None when an argument needs a conversion copy."""
+    parts = [geom.key, flds[0].device.index, _raw_stream(flds[0].device), consts, flags]
+    for t in flds:
+        k = _tkey(t)
+        if k is None or k == 0 or k[1] != torch.float32:
+            return None
+        parts.append(k)
+    for m in bc3:
+        k = _tkey(m)
+        if k is None or (k != 0 and k[1] not in (torch.float32, torch.uint8, torch.bool)):
+            return None
+        parts.append(k)
+    for v in tuple(vals) + tuple(f2):
+        if isinstance(v, torch.Tensor) and v.numel() > 1:
+            k = _tkey(v)
+            if k is None or k[1] != torch.float32:
+                return None
+            parts.append(k)
+        else:
+            parts.append(float(v))
+    for t in (in_num, in_den):
+        k = _tkey(t)
+        if k is None or (k != 0 and (k[1] != torch.float32 or k[2] != (3,))):
+            return None
+        parts.append(k)
+    return tuple(parts)
+
+
+def _prepare_stokes(geom, u, v, p, bc3, vals, f2, consts, in_num, in_den, want_red):
+    """Validation + argument struct of a dn_stokes_apply call, outputs left unset: (mesh, args, tensors to keep alive, field shape)."""
+    _stokes_check_mesh(geom)
+    flds = [_require(t, n, 4) for t, n in ((u, "u"), (v, "v"), (p, "p"))]
+    B = flds[0].shape[0]
+    shape = (B, 1, *geom.node_shape)
+    for t in flds:
+        if tuple(t.shape) != shape:
+            raise ValueError(f"stokes_apply: field shape {tuple(t.shape)} != {shape}")
+    keep = list(flds)
+    args = DnStokesArgs()
+    args.u, args.v, args.p = (t.data_ptr() for t in flds)
+    nn = geom.nnode_total
+
+    def batched(t, name):
+        if tuple(t.shape[-2:]) != tuple(geom.node_shape) or t.numel() not in (B * nn, nn):
+            raise ValueError(f"stokes_apply: {name} shape {tuple(t.shape)} does not match the mesh {shape}")
+        return 1 if (t.numel() == B * nn and B > 1) else 0
+
+    for k, m in enumerate(bc3):
+        if m is None:
+            continue
+        if not isinstance(m, torch.Tensor):
+            raise TypeError(f"stokes_apply: bc[{k}] must be a tensor or None")
+        if not m.is_cuda:
+            raise DiffNetHipError(f"stokes_apply: bc[{k}] is on {m.device}: the FEM ops run on the GPU only (no CPU fallback)")
+        if m.dtype in (torch.bool, torch.uint8):
+            m = m.contiguous()
+            m = m.view(torch.uint8) if m.dtype == torch.bool else m
+            args.mask_is_u8[k] = 1
+        else:
+            m = _require(m, f"bc[{k}]")
+        args.mask_batched[k] = batched(m, f"bc[{k}]")
+        args.bc_mask[k] = m.data_ptr()
+        keep.append(m)
+    for k, val in enumerate(vals):
+        if isinstance(val, torch.Tensor) and val.numel() > 1:
+            if bc3[k] is None:
+                raise ValueError(f"stokes_apply: bc_values[{k}] is a field but field {k} has no Dirichlet mask")
+            val = _require(val, f"bc_values[{k}]")
+            args.bc_field_batched[k] = batched(val, f"bc_values[{k}]")
+            args.bc_field[k] = val.data_ptr()
+            keep.append(val)
+        else:
+            args.bc_value[k] = float(val)
+    G, nel = geom.ngp_total, geom.nelem_total
+    for k, f in enumerate(f2):
+        if isinstance(f, torch.Tensor) and f.numel() > 1:
+            f = _require(f, f"f_gp[{k}]")
+            if tuple(f.shape[-3:]) != (G, *geom.elem_shape) or f.numel() not in (G * nel, B * G * nel):
+                raise ValueError(f"stokes_apply: f_gp[{k}] shape {tuple(f.shape)} is not (B | 1, {G}, {geom.elem_shape[0]}, {geom.elem_shape[1]})")
+            args.f_batched[k] = 1 if (f.numel() == B * G * nel and B > 1) else 0
+            args.f_gp[k] = f.data_ptr()
+            keep.append(f)
+        else:
+            args.f_value[k] = float(f)
+    args.visco, args.pspg, args.wscale, transpose = consts
+    args.transpose = 1 if transpose else 0
+    if (in_num is None) != (in_den is None):
+        raise ValueError("stokes_apply: in_num and in_den go together")
+    for name, t in (("in_num", in_num), ("in_den", in_den)):
+        if t is not None:
+            t = _require(t, name, 1)
+            if t.numel() != 3:
+                raise ValueError(f"{name} must hold 3 floats")
+            setattr(args, name, t.data_ptr())
+            keep.append(t)
+    mesh = geom.mesh_struct(B)
+    if want_red:
+        key = (mesh.nx, mesh.ny, mesh.ngp, B)
+        nbytes = _STOKES_WS_BYTES.get(key)
+        if nbytes is None:
+            nbytes = _lib.lib().dn_stokes_workspace_bytes(C.byref(mesh))
+            if nbytes < 0:
+                _lib.check(int(nbytes), "dn_stokes_workspace_bytes")
+            _STOKES_WS_BYTES[key] = nbytes
+        ws = _stokes_workspace(flds[0].device, nbytes)
+        keep.append(ws)
+        args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    return mesh, args, keep, shape
+
+
+def stokes_apply(geom, u, v, p, bc=None, bc_values=(0.0, 0.0, 0.0), visco=1.0, pspg=0.0, f_gp=None, wscale=1.0, want_out=True,
+                 want_sums=True, want_norms=False, in_num=None, in_den=None, transpose=False):
+    """One launch of dn_stokes_apply (include/diffnet_hip.h): the three assembled Stokes (PSPG) residuals of the fields u, v, p
+    (B,1,ny,nx) and / or the float64 device tensor of their three sums of squares.  `bc`: one Dirichlet mask shared by the three fields or
+    three (None: no condition), fp32 (`>= 0.5`) or bool / uint8, per sample or shared; `bc_values[k]`: float or tensor field k and
+    residual k take there; `f_gp`: None or (f1, f2), each None, a float or a Gauss-point tensor (B | 1, G, nely, nelx); `in_num` / `in_den`:
+    float32 device tensors of 3, field k is scaled by in_num[k] / in_den[k] (0 where in_den[k] <= 0) as it is loaded; `want_norms`: a third
+    result, the float32 tensor of the three Frobenius norms written by the same launch; `transpose`: the adjoint J_R^T = S J_R S (forcing and
+    Dirichlet values ignored).  Returns (outs | None, sums | None[, norms]).  Calls on the same buffers reuse their prepared argument structs
+    (small LRU, fresh outputs per call: see poisson_apply)."""
+    _stokes_check_mesh(geom)
+    bc3, f2, vals = stokes_bc3(bc), stokes_f2(f_gp), tuple(bc_values)
+    if len(vals) != 3:
+        raise ValueError("stokes_apply: bc_values must hold three entries")
+    consts = (float(visco), float(pspg), float(wscale), bool(transpose))
+    flds = (u, v, p)
+    want_red = want_sums or want_norms
+    key = None
+    if all(isinstance(t, torch.Tensor) and t.is_cuda for t in flds) and tuple(u.shape[1:]) == (1, *geom.node_shape) and u.shape == v.shape == p.shape:
+        key = _stokes_key(geom, flds, bc3, vals, f2, consts, in_num, in_den, (want_out, want_sums, want_norms))
+    ent = None
+    if key is not None:
+        with _WS_LOCK:
+            ent = _STOKES_CACHE.get(key)
+            if ent is not None:
+                _STOKES_CACHE.move_to_end(key)
+    if ent is None:
+        _CALL_STATS["miss" if key is not None else "uncached"] += 1
+        mesh, args, keep, shape = _prepare_stokes(geom, u, v, p, bc3, vals, f2, consts, in_num, in_den, want_red)
+        with _WS_LOCK:
+            live_ws = list(_STOKES_WS.values())
+        ent = (mesh, args, C.byref(mesh), C.byref(args), shape, [t for t in keep if any(t is x for x in live_ws)])
+        if key is not None:
+            with _WS_LOCK:
+                _STOKES_CACHE[key] = ent
+                while len(_STOKES_CACHE) > _CALL_CACHE_MAX:
+                    _STOKES_CACHE.popitem(last=False)
+    else:
+        _CALL_STATS["hit"] += 1
+    mesh, args, mref, aref, shape = ent[:5]
+    dev = u.device
+    outs = sums = norms = None
+    if want_out:
+        o3 = torch.empty((3, *shape), dtype=torch.float32, device=dev)      # one allocation, three views
+        outs = list(o3.unbind(0))
+    if want_sums:
+        sums = torch.empty(3, dtype=torch.float64, device=dev)
+    if want_norms:
+        norms = torch.empty(3, dtype=torch.float32, device=dev)
+    with _STOKES_LAUNCH_LOCK:          # pointer patch + launch of the (possibly shared, cached) argument struct as one step
+        if want_out:
+            p0, step = o3.data_ptr(), 4 * o3[0].numel()
+            args.out[0], args.out[1], args.out[2] = p0, p0 + step, p0 + 2 * step
+        args.sumsq = sums.data_ptr() if want_sums else None
+        args.norms = norms.data_ptr() if want_norms else None
+        rc = _lib.lib().dn_stokes_apply(mref, aref, _stream(u))
+    if rc:
+        _lib.check(rc, "dn_stokes_apply")
+    return (outs, sums, norms) if want_norms else (outs, sums)
 
 def compute_winding_nodes(points, normals, area, q):
     """Drop-in for `compute_winding_nodes` of IBN/poisson-2d/parametric/IBN_2D.py:89-104 (same argument shapes:

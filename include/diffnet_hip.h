@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define DN_ABI_VERSION 9
+#define DN_ABI_VERSION 10
 
 #define DN_E_BADARG (-1)    /* null pointer / non-positive size / unsupported combination   */
 #define DN_E_UNSUPPORTED (-2) /* (nsd, degree, ngp) outside the compiled instantiations      */
@@ -293,6 +293,54 @@ typedef struct dn_fsdt_args {
 } dn_fsdt_args;
 int64_t dn_fsdt_workspace_bytes(const dn_mesh *mesh);
 int dn_fsdt_apply(const dn_mesh *mesh, const dn_fsdt_args *args, void *stream);
+
+/* ---- fused 2-D Stokes (PSPG) residuals -------------------------------------------------------------------------
+ * Replaces the residual body of the three-field Stokes scripts of the reference:
+ * examples/stokes/single_instance/e2_stokes_ldc_resmin.py:151-240, e1_stokes_mms_resmin.py:122-217,
+ * e1_stokes_mms_resmin_loss2.py:158-247, and the Stokes stage of the Navier-Stokes scripts
+ * (examples/navier-stokes/single_instance/e2_ns_fps_resmin.py:193 calc_residuals_stokes, e2_ns_fps_af_bcmask.py:199,
+ * e2_ns_fps_af_pc.py:234, b1_stokes_ns_resmin_base.py:181): Dirichlet substitution, 9 Gauss-point evaluations, three weak
+ * forms, three assemblies, the Dirichlet rows and the three Frobenius sums, in ONE launch.  Mesh: nsd = 2, degree 1, ngp 2..4.
+ *   u~ = where(bc1, u_bc, u), v~ = where(bc2, v_bc, v), p~ = where(bc3, p_bc, p)      (mask: fp32 >= 0.5, u8 != 0)
+ *   R1_a = sum_e sum_g J w_g [ visco (Nx_a u~_x + Ny_a u~_y) - Nx_a p~ - N_a f1 ]
+ *   R2_a = sum_e sum_g J w_g [ visco (Nx_a v~_x + Ny_a v~_y) - Ny_a p~ - N_a f2 ]
+ *   R3_a = sum_e sum_g J w_g [ N_a (u~_x + v~_y) + pspg (Nx_a p~_x + Ny_a p~_y) ]
+ *   R_k = where(bc_k, value_k, R_k)   (Dirichlet rows take the VALUE, as in the scripts),  J = wscale
+ * Fields (B,1,ny,nx) fp32.  Per field k: bc_mask[k] NULL (no condition) or an fp32 / u8 image, shared (1,1,ny,nx) or per sample;
+ * the value is bc_field[k] (shared or per sample) or the constant bc_value[k].  Forcing k: f_gp[k] at the Gauss points
+ * (Bf,G,nely,nelx) with Bf = 1 (f_batched 0) or B, else the constant f_value[k] (0: none).
+ * out[k] may be NULL; sumsq (3 doubles) / norms (3 floats, sqrt of sumsq): fixed-order fp64 reduction in the kernel, needs
+ * `workspace` (zero-filled once before first use, dn_stokes_workspace_bytes; one per stream, not shared with other operators).
+ * in_num / in_den (both or neither): field k is scaled by in_num[k] / in_den[k] as it is loaded (0 where in_den[k] <= 0).
+ * transpose != 0: the adjoint J_R^T = S J_R S, S = diag(1, 1, -1) -- p is negated as it is loaded and R3 before its Dirichlet
+ * rows, the forcing is dropped and the Dirichlet values are zero (bc_field / bc_value / f_gp / f_value are ignored).  The VJP of
+ * the three norms is this launch on the residuals with in_num = cotangents of the norms, in_den = the norms.
+ * Coefficients of the scripts: e2_stokes_ldc_resmin / e1_stokes_mms_resmin_loss2: visco = 1/Re, pspg = h^2 Re / 12, J = (h/2)^2;
+ * e1_stokes_mms_resmin: visco = Re; the Navier-Stokes Stokes stage: visco = 1/Re, pspg = hx hy Re / 12, J = 1, no forcing.
+ * DN_E_UNSUPPORTED for nsd != 2, degree != 1, ngp outside 2..4; DN_E_BADARG for NULL fields, no output at all, in_num without
+ * in_den, flags outside {0, 1} or a bc_field without its mask; nothing is launched then. */
+typedef struct dn_stokes_args {
+    const float *u, *v, *p;
+    const void *bc_mask[3];
+    int32_t mask_is_u8[3];
+    int32_t mask_batched[3];
+    const float *bc_field[3];
+    int32_t bc_field_batched[3];
+    float bc_value[3];
+    const float *f_gp[2];
+    int32_t f_batched[2];
+    float f_value[2];
+    float visco, pspg, wscale;
+    int32_t transpose;
+    float *out[3];
+    double *sumsq;
+    float *norms;
+    const float *in_num, *in_den;
+    void *workspace;
+    int64_t workspace_bytes;
+} dn_stokes_args;
+int64_t dn_stokes_workspace_bytes(const dn_mesh *mesh);
+int dn_stokes_apply(const dn_mesh *mesh, const dn_stokes_args *args, void *stream);
 
 /* ---- fused output block of the 2-D U-Net generator ----------------------------------------------------------
  * Upsample(x2, nearest) -> ZeroPad2d((1,0,1,0)) -> Conv2d(C -> 1, 4x4, padding 1, bias) -> Sigmoid
