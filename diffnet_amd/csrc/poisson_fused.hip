@@ -308,8 +308,9 @@ static Geom2D plan2d_env(const dn_mesh* m, int P, bool allow_e4 = true, bool cha
     Geom2D g = plan2d(m, P, allow_e4, chain_ok, allow_ua);
     const char* e = config(CFG_PLAN2D);
     int T, E, R, W = 0;
+    // (Q2 / Q3 kernels exist for E * P <= 4 only: a larger E is ignored there, like the E values the Q1 closed form lacks)
     if (e && sscanf(e, "%d,%d,%d,%d", &T, &E, &R, &W) >= 3 && T >= 64 && T <= 256 && (E == 1 || E == 2 || E == 4) && R >= 1 &&
-        !(P == 1 && (E == 1 || (E == 4 && !g.ua && (m->nx % 4 != 0 || !allow_e4)) || (g.ua && E != 4)))) {
+        !(P == 1 && (E == 1 || (E == 4 && !g.ua && (m->nx % 4 != 0 || !allow_e4)) || (g.ua && E != 4))) && !(P > 1 && E * P > 4)) {
         const int nely = (m->ny - 1) / P;
         g.T = T; g.E = E; g.R = R > nely ? nely : R;
         g.chunks = chunks_for(g.ua ? (m->nx - 1) / 4 : (m->nx - 1) / (E * P) + 1, T);
@@ -320,12 +321,14 @@ static Geom2D plan2d_env(const dn_mesh* m, int P, bool allow_e4 = true, bool cha
     return g;
 }
 
-static Geom3D plan3d_env(const dn_mesh* m, bool allow_e2 = false) {
+// need_e2: the launch reads box faces, folds an earlier launch's partials or takes a load vector -- only the two-element form has those
+// paths, so an E = 1 override is ignored there (it would drop the condition / the fold, or refuse the load vector)
+static Geom3D plan3d_env(const dn_mesh* m, bool allow_e2 = false, bool need_e2 = false) {
     Geom3D g = plan3d(m, allow_e2);
     const char* e = config(CFG_PLAN3D);
     int TX, TY, E, R;
     if (e && sscanf(e, "%d,%d,%d,%d", &TX, &TY, &E, &R) == 4 && TX * TY >= 64 && (E == 1 || (E == 2 && allow_e2 && TX == 16 && TY == 16)) && R >= 1 &&
-        TX * TY <= 256) {
+        TX * TY <= 256 && !(need_e2 && allow_e2 && E == 1)) {
         const int nelz = m->nz - 1;
         g.TX = TX; g.TY = TY; g.E = E; g.R = R > nelz ? nelz : R;
         g.chunks = chunks_for((m->nx - 1) / E + 1, TX);
@@ -346,8 +349,9 @@ static long long num_workgroups(const dn_mesh* m, bool allow_e4 = true) {
     const Geom3D g = plan3d_env(m, false);
     long long n = (long long)g.chunks * g.tiles * g.strips * m->batch;
     if (m->ngp == 2) {
-        const Geom3D g2 = plan3d_env(m, true);
+        const Geom3D g2 = plan3d_env(m, true), g2n = plan3d_env(m, true, true);
         n = std::max(n, (long long)g2.chunks * g2.tiles * g2.strips * m->batch);
+        n = std::max(n, (long long)g2n.chunks * g2n.tiles * g2n.strips * m->batch);
     }
     return n;
 }
@@ -430,6 +434,14 @@ static bool q1n2_ok(const dn_mesh* m, const dn_poisson_args* a) {
         else return false;
     }
     return kinds != 3;
+}
+
+// Does the launch of (mesh, args) need the 3-D two-element form (plan3d_env: need_e2)?  Box faces, a fold of an earlier launch and a load
+// vector have no one-element path.
+static bool q1n2_needed(const dn_poisson_args* a) {
+    for (int k = 0; k < 2; ++k)
+        if (a->bc[k].mask_kind == DN_MASK_BOX && a->bc[k].box_faces != 0) return true;
+    return a->fold_prev != nullptr || (a->f_is_load && a->f);
 }
 
 namespace dn {
@@ -611,6 +623,15 @@ extern "C" int dn_poisson_apply(const dn_mesh* m, const dn_poisson_args* a, void
     pp.acc_sums = (a->accumulate_sums && want_red && !a->defer_sums) ? 1 : 0;      // (deferred: dn_poisson_finish_sums accumulates)
     pp.defer_sums = (a->defer_sums && want_red) ? 1 : 0;
     auto launched = [&](int total) { return a->strip_select == 1 ? std::min(total, 2) : (a->strip_select == 2 ? std::max(total - 2, 0) : total); };
+    // a split launch left without strips still closes the evaluation it folds: the one-workgroup finish kernel forms prev's scalars
+    auto no_strips = [&]() {
+        if (pp.fold_n > 0) {
+            hipLaunchKernelGGL(poisson_finish_sums_kernel, dim3(1), dim3(256), 0, s, pp.fold_pe, pp.fold_ps, pp.fold_n, pp.fold_energy, pp.fold_sumsq,
+                               pp.fold_energy_f32, pp.fold_scale, pp.fold_acc);
+            DN_LAUNCH_CHECK();
+        }
+        return 0;
+    };
     if (gen3d) {
         if (a->strip_select != 0 || a->accumulate_sums || a->defer_sums) return DN_E_UNSUPPORTED;      // no split evaluation of this form
         rc = launch_poisson3d_gen(pp, m, a->workspace, a->workspace_bytes, s);
@@ -627,18 +648,18 @@ extern "C" int dn_poisson_apply(const dn_mesh* m, const dn_poisson_args* a, void
         pp.rows_per_strip = g.R;
         pp.nstrips = g.strips;
         g.strips = launched(g.strips);
-        if (g.strips == 0) return 0;                         // fewer than three strips: the other launch did everything
+        if (g.strips == 0) return no_strips();               // fewer than three strips: the other launch did everything
         // (the partial-sum arrays were laid out for nwg workgroups: never launch more than that)
         if (want_red && (long long)g.chunks * ((g.strips + g.W - 1) / g.W) * m->batch > nwg) return DN_E_WORKSPACE;
         const int NW = g.E * P;
         const bool vec = vec_ok(NW);
         rc = launch2d(pp, g, P, m->ngp, m->batch, vec, s);
     } else {
-        Geom3D g = plan3d_env(m, q1n2_ok(m, a));
+        Geom3D g = plan3d_env(m, q1n2_ok(m, a), q1n2_needed(a));
         pp.rows_per_strip = g.R;
         pp.nstrips = g.strips;
         g.strips = launched(g.strips);
-        if (g.strips == 0) return 0;
+        if (g.strips == 0) return no_strips();
         if (want_red && (long long)g.chunks * g.tiles * g.strips * m->batch > nwg) return DN_E_WORKSPACE;
         const int NW = g.E;
         const bool vec = vec_ok(NW);
@@ -665,7 +686,7 @@ static long long launched_workgroups(const dn_mesh* m, const dn_poisson_args* a)
         if (!chain_ok) g.W = 1;
         return (long long)g.chunks * ((sel(g.strips) + g.W - 1) / g.W) * m->batch;
     }
-    Geom3D g = plan3d_env(m, q1n2_ok(m, a));
+    Geom3D g = plan3d_env(m, q1n2_ok(m, a), q1n2_needed(a));
     return (long long)g.chunks * g.tiles * sel(g.strips) * m->batch;
 }
 

@@ -360,9 +360,13 @@ def _mask_image(m, like):
 # The reference keeps Dirichlet masks as fp32 images and hands them to loss() every step (IBN_2D.py:69-73, 119-121); read as they are they
 # cost the fused 2-D kernel 4 B per node and launch (72 against 54-56 us at 512^2 x 64), as uint8 images 1 B.  A one-shot call
 # (energy_loss / energy_loss_and_grad / residual*) therefore packs a mask image to one bit per node the FIRST time it sees it and finds the
-# bits again on later calls: the cache is keyed on the mask's storage (address, offset, shape, strides, dtype) AND its version counter -- an
-# in-place write to the mask (or to any view of its storage) changes the version and the image is packed again -- and an entry holds the
-# mask tensor itself, so that the address cannot be handed to another tensor while the entry lives.  Small LRU; `AUTO_PACK_MASKS = False`
+# bits again on later calls: the cache is keyed on the mask's storage (address, offset, shape, strides, dtype) and the current stream (an
+# entry packed on one stream is not read by launches on another, which are not ordered behind the pack) AND checked against the mask's
+# version counter -- an in-place write to the mask (or to any view of its storage) changes the version and the image is packed again -- and
+# an entry holds the mask tensor itself, so that the address cannot be handed to another tensor while the entry lives.  Masks without a
+# version counter (inference tensors, made under torch.inference_mode()) are not packed: the call reads the image.  LIMIT: writes that
+# bypass autograd's version counter -- through `mask.data`, DLPack / CuPy views, or a kernel writing the storage by pointer -- are not seen,
+# and the stale bits are used; after such a write call `call_cache_clear()` (or pack explicitly).  Small LRU; `AUTO_PACK_MASKS = False`
 # turns it off.  Prepared launches (PoissonPlan) take what they are given: pack explicitly with PackedMask.pack there.
 AUTO_PACK_MASKS = True
 _PACK_CACHE = __import__("collections").OrderedDict()
@@ -370,18 +374,32 @@ _PACK_CACHE_MAX = 8
 _PACK_STATS = {"hit": 0, "pack": 0}
 
 
+def _version_of(m):
+    """The tensor's version counter, None where it has none (inference tensors raise on the read)."""
+    if m.is_inference():
+        return None
+    try:
+        return m._version
+    except RuntimeError:
+        return None
+
+
 def _packed_on_first_use(m):
-    key = (m.untyped_storage().data_ptr(), m.storage_offset(), tuple(m.shape), tuple(m.stride()), m.dtype)
+    """The cached PackedMask of image `m`, packed now if needed; None where the image cannot be tracked (no version counter)."""
+    ver = _version_of(m)
+    if ver is None:
+        return None
+    key = (m.untyped_storage().data_ptr(), m.storage_offset(), tuple(m.shape), tuple(m.stride()), m.dtype, _raw_stream(m.device))
     with _WS_LOCK:
         ent = _PACK_CACHE.get(key)
-        if ent is not None and ent[1] == m._version:
+        if ent is not None and ent[1] == ver:
             _PACK_CACHE.move_to_end(key)
             _PACK_STATS["hit"] += 1
             return ent[2]
     pm = PackedMask.pack(m)
     _PACK_STATS["pack"] += 1
     with _WS_LOCK:
-        _PACK_CACHE[key] = (m, m._version, pm)
+        _PACK_CACHE[key] = (m, ver, pm)
         _PACK_CACHE.move_to_end(key)
         while len(_PACK_CACHE) > _PACK_CACHE_MAX:
             _PACK_CACHE.popitem(last=False)
@@ -406,6 +424,8 @@ def _auto_pack(geom, u, f_gp, dl):
                 m.dtype in (torch.float32, torch.uint8, torch.bool) and m.dim() == u.dim() and tuple(m.shape[1:]) == want and
                 m.shape[0] in (1, u.shape[0])):
             return dl
+    if any(isinstance(d.mask, torch.Tensor) and _version_of(d.mask) is None for d in dl):
+        return dl
     return [d if isinstance(d.mask, (PackedMask, BoxFaces)) else Dirichlet(_packed_on_first_use(d.mask), d.value) for d in dl]
 
 
@@ -459,7 +479,7 @@ def workspace_status(device=None):
     NaN -- never silently wrong).  Cheap enough for once per epoch; not for the launch path."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     with _WS_LOCK:
-        items = [(k, w) for k, w in _WS.items() if k[0] == dev.index]
+        items = [(k, w) for d in (_WS, _FSDT_WS) for k, w in d.items() if k[0] == dev.index]
     for (_, stream), ws in items:
         _lib.check(_lib.lib().dn_workspace_status(C.c_void_p(ws.data_ptr()), C.c_void_p(stream)), "dn_workspace_status")
 
@@ -700,14 +720,23 @@ class PoissonPlan:
         return self.result
 
     def fold(self, prev):
-        """This launch closes the evaluation of `prev` (a pipelined_sums plan on the same mesh whose launch precedes this one on the stream):
-        its first workgroup adds up prev's partial sums and writes prev's scalars.  fold(None) clears."""
+        """This launch closes the evaluation of `prev` (a pipelined_sums plan on the same mesh and batch, prepared on the same stream, whose launch
+        precedes this one there): its first workgroup adds up prev's partial sums and writes prev's scalars (a split launch left without strips
+        runs the one-workgroup finish kernel for that).  Raises DiffNetHipError for a plan of another mesh, batch, device or stream.
+        fold(None) clears."""
         if prev is None:
             self.args.fold_prev = None
             self._folds = None
             return self
         if not getattr(prev, "pipelined_sums", False):
             raise DiffNetHipError("PoissonPlan.fold: the other plan must be prepared with pipelined_sums=True")
+        # the library counts prev's partial sums and finds their stride from THIS launch's mesh struct (batch included): they must be identical
+        if C.string_at(C.addressof(prev.mesh), C.sizeof(prev.mesh)) != C.string_at(C.addressof(self.mesh), C.sizeof(self.mesh)):
+            raise DiffNetHipError("PoissonPlan.fold: the other plan was prepared for another mesh or batch size; only a plan on the same mesh "
+                                  "and batch can be folded")
+        if prev.device != self.device or prev.stream != self.stream:
+            raise DiffNetHipError("PoissonPlan.fold: the other plan was prepared on another device or stream; its launch must precede this one "
+                                  "on the same stream")
         self._folds = prev                                    # keeps its argument struct and workspace alive
         self.args.fold_prev = C.addressof(prev.args)
         return self
@@ -1054,6 +1083,20 @@ def residual_loss(geom, u, nu=None, f=None, f_gp=None, dirichlet=(), jac=1.0):
 
 _FSDT_WS_BYTES = {}
 _FSDT_CACHE = __import__("collections").OrderedDict()
+# The FSDT launches have a reduction workspace of their OWN per (device, stream), never the one of _workspace: a launch with defer_norms leaves its
+# partials there for a later `norms_from` consumer, and a reducing dn_poisson_apply launch issued in between must not overwrite them while the
+# pair's ticket still matches (only FSDT's own reductions clear the ticket).  Another reducing FSDT launch in between clears it: NaN, never stale.
+_FSDT_WS = {}
+
+
+def _fsdt_workspace(dev, nbytes):
+    key = (dev.index, _raw_stream(dev))
+    with _WS_LOCK:
+        ws = _FSDT_WS.get(key)
+        if ws is None or ws.numel() < nbytes:
+            ws = torch.zeros(max(nbytes, 1 << 16), dtype=torch.uint8, device=dev)   # ABI: zero-filled once
+            _FSDT_WS[key] = ws
+    return ws
 
 
 def _fsdt_key(geom, flds, bc, bc_values, consts, in_scale, in_num, in_den, flags):
@@ -1085,9 +1128,10 @@ def _fsdt_key(geom, flds, bc, bc_values, consts, in_scale, in_num, in_den, flags
 
 
 class DeferredNorms:
-    """Handle of a dn_fsdt_apply launch that left its partial sums of squares in the stream's reduction workspace (`defer_norms=True`): pass it as
-    `norms_from` to the NEXT FSDT launch on that stream, which forms the norms itself.  Any other reducing FSDT launch in between overwrites the
-    partials -- the pair is meant to be issued back to back (elasticity.fsdt_loss_and_grad, FsdtPlan)."""
+    """Handle of a dn_fsdt_apply launch that left its partial sums of squares in the stream's FSDT reduction workspace (`defer_norms=True`): pass it
+    as `norms_from` to the NEXT FSDT launch on that stream, which forms the norms itself.  Any other reducing FSDT launch in between overwrites the
+    partials (the consumer's norms and outputs come out NaN); Poisson and Stokes launches use workspaces of their own and change nothing -- the
+    pair is meant to be issued back to back (elasticity.fsdt_loss_and_grad, FsdtPlan)."""
 
     _next = [1]
 
@@ -1135,7 +1179,7 @@ def fsdt_apply(geom, w, phi_x, phi_y, bc=None, bc_values=(0.0, 0.0, 0.0), D11=1.
         mesh, args, keep, shape = _prepare_fsdt(geom, w, phi_x, phi_y, bc, bc_values, consts, in_scale, in_num, in_den,
                                                 (want_sums or want_norms or defer_norms) and norms_from is None, defer_norms, norms_from)
         with _WS_LOCK:
-            live_ws = list(_WS.values())
+            live_ws = list(_FSDT_WS.values())
         ent = (mesh, args, C.byref(mesh), C.byref(args), shape, [t for t in keep if any(t is x for x in live_ws)],
                next((t for t in keep if any(t is x for x in live_ws)), None))
         if key is not None:
@@ -1237,7 +1281,7 @@ def _prepare_fsdt(geom, w, phi_x, phi_y, bc, bc_values, consts, in_scale, in_num
             if nbytes < 0:
                 _lib.check(int(nbytes), "dn_fsdt_workspace_bytes")
             _FSDT_WS_BYTES[key] = nbytes
-        ws = _workspace(flds[0].device, nbytes)
+        ws = _fsdt_workspace(flds[0].device, nbytes)
         keep.append(ws)
         args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
     return mesh, args, keep, shape
@@ -1303,8 +1347,8 @@ class FsdtPlan:
 
 
 # ---- fused 2-D Stokes (PSPG) residuals: dn_stokes_apply -------------------------------------------------------------------------
-# The launch has a reduction workspace of its OWN per (device, stream), never the one of _workspace: an FSDT launch with defer_norms leaves
-# its partials in that one for a later consumer, and a Stokes launch issued in between must not overwrite them.
+# The launch has a reduction workspace of its OWN per (device, stream), never the one of _workspace or _fsdt_workspace: an FSDT launch with
+# defer_norms leaves its partials in its workspace for a later consumer, and a Stokes launch issued in between must not overwrite them.
 _STOKES_WS = {}
 _STOKES_WS_BYTES = {}
 _STOKES_CACHE = __import__("collections").OrderedDict()

@@ -37,7 +37,8 @@ extern "C" {
  * is loaded, from the environment variables DN_<KEY>; afterwards the environment is never read again (no getenv on the
  * launch path) and the only way to change a switch is this call.  Keys (the table kKeys in csrc/dn_api.hip):
  *   "PLAN2D" ("T,E,R[,W]": threads per strip, elements per thread, node rows per strip, W >= 2 = chain strips per workgroup
- *   where the closed-form Q1 kernel can), "PLAN3D" ("TX,TY,E,R"), "PLAN_FSDT" ("T,R"),
+ *   where the closed-form Q1 kernel can), "PLAN3D" ("TX,TY,E,R"; E = 1 is ignored by launches only the two-element form serves: box faces,
+ *   fold_prev, f_is_load), "PLAN_FSDT" ("T,R"),
  *   "Q1_RULE_KERNEL" (non-empty: per-Gauss-point 2-D Q1 kernels instead of the closed form),
  *   "GPE_GATHER" (non-empty: per-node gather adjoint of gauss_pt_eval), "GPE_TILED" (non-empty: tiled LDS adjoint instead of the
  *   marching 3-D Q1 adjoint), "Q1_3D_T16" (non-empty: the 3-D Q1 kernel form in which every thread loads its own nodes),
@@ -159,7 +160,9 @@ typedef struct dn_poisson_args {
      * energy_f32 -- what dn_poisson_finish_sums would do -- before it starts its own strip: the final reduction of evaluation k leaves
      * the critical path (no tail at the end of launch k, no extra kernel, no event) and rides at the start of launch k + 1, where one
      * of ~2000 workgroups doing 1-2 us of extra work delays nothing.  A loop therefore gets the loss of step k when launch k + 1 has
-     * run (a training loop only logs it); the last evaluation is closed with dn_poisson_finish_sums.  Kernels without the path (anything
+     * run (a training loop only logs it); the last evaluation is closed with dn_poisson_finish_sums.  The earlier call's partial count
+     * and layout are derived from THIS call's mesh: it must have been made with an identical dn_mesh (batch included) on the same
+     * stream.  A split launch (strip_select 2) left without strips runs the one-workgroup finish kernel for it.  Kernels without the path (anything
      * but the 2-D closed-form Q1 kernel and the 3-D Q1 two-element node-owner kernel) return DN_E_UNSUPPORTED.  Read at call time only. */
     const struct dn_poisson_args *fold_prev;
     /* f_is_load != 0 (round 4): `f` does not hold nodal forcing values but the ASSEMBLED load vector b_a = sum_e sum_g w_g N_a(g) f_g
@@ -284,7 +287,9 @@ typedef struct dn_fsdt_args {
                               a third of the 1025^2 Q2 launch at one sample); sumsq and norms are ignored.  The value is the pair's TICKET: it is
                               left in the workspace next to the partials, and any launch that reduces in the kernel clears it */
     int32_t den_ticket;    /* with den_workspace: the ticket the producer was launched with; if the workspace holds another one (some other reducing
-                              launch used it in between) the scales, this call's outputs and the norms come out NaN -- never silently stale */
+                              dn_fsdt_apply launch used it in between) the scales, this call's outputs and the norms come out NaN.  Only FSDT
+                              launches clear the ticket: other entry points must not be handed the producer's workspace in between (the Python
+                              layer gives FSDT, Poisson and Stokes launches separate workspaces) */
     const void *den_workspace; /* (round 4) the `workspace` of an earlier launch with defer_sums on the same mesh, stream and launch plan: every
                               workgroup of THIS launch reduces those partials (fixed order: bitwise the sums the producer would have formed)
                               and uses their square roots where it would have read in_den (in_num required, in_den NULL); if sumsq / norms of
