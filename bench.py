@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the FEM hot path: fused energy loss + gradient (one pass) on BASELINE.json configs[1]'s mesh.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--settle S] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--settle S]]
 
-`value` / `ms_per_step`: W untimed warm-up steps, then exactly K timed steps.  The same W + K steps are run a second time after S = 400
+`value` / `ms_per_step`: W untimed warm-up steps, then exactly K timed steps.  A plain run does only that: set-up, the W + K steps, the
+--dump-outputs files, the line.  Everything else is measured with --full only: the same W + K steps run a second time after S = 400
 further untimed steps and reported as `steady_state` (for 1.3-10 ms after load onset the part runs every kernel 10-25 % slower, and
-W = 5, K = 20 is 1.4 ms of load: a job of more than a few hundred steps is in the second regime, and so are the roofline launches).
+W = 5, K = 20 is 1.4 ms of load: a job of more than a few hundred steps is in the second regime, and so are the roofline launches),
+and the extra objects listed below.
 
 N > 1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (the driver's form:
 RANK / LOCAL_RANK / WORLD_SIZE come from the environment), or run plainly -- then this process, which has not touched the GPU
@@ -24,7 +26,7 @@ therefore one regime; the one-batch kernel time is a side field, and so are the 
 left in the cache at its next turn; with 4, part of u still is) and over 3 streams (`roofline.deeper_rotation`).  The Dirichlet mask is held as a general
 per-sample mask array (one bit per node, diffnet_amd.PackedMask); the geometry-derived form is a side field.
 
-Prints ONE JSON line (rank 0).  Extra objects: `roofline` (time of the dominant kernel between timing-only HIP events over the
+Prints ONE JSON line (rank 0).  Extra objects (--full): `roofline` (time of the dominant kernel between timing-only HIP events over the
 rotation vs the HBM peak of MI355X_MICROARCH.md, plus `stream_ceiling`: a plain 3-read / 1-write streaming kernel over the same
 arrays), `cpu_baseline` (the CPU oracle = port of the reference formulation, timed on this box's host cores on a bounded sample
 of the same workload), `configs` (device time of every BASELINE.json config) and `slab_3d` (configs[3] over the same ranks).
@@ -561,8 +563,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=5, help="untimed steps directly before the timed ones")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: steady_state, roofline, cpu_baseline, configs, slab_3d, slab_3d_b8 "
+                         "(--settle, --no-cpu, --no-configs, --slab-size and the other options of the slab leg act on these only).  Without it the "
+                         "run ends after the timed steps and --dump-outputs")
     ap.add_argument("--settle", type=int, default=400,
-                    help="untimed steps before the SECOND run of the warm-up + timed steps, reported as `steady_state` (about 22 ms of load: between about 1.3 and "
+                    help="(--full) untimed steps before the SECOND run of the warm-up + timed steps, reported as `steady_state` (about 22 ms of load: between about 1.3 and "
                          "10 ms after the GPU leaves idle the launch runs 10-25 %% slower -- power-management transient, tools/ramp2d.py, "
                          "profiles/r2_ramp2d.txt).  `value` is the W + K steps run first, from idle; this second run is reported as `steady_state`; "
                          "--settle 0 makes the two the same thing")
@@ -779,10 +785,10 @@ def main():
         return float(tmax), region[0].elapsed_time(region[1]) / args.steps
 
     # The GPU leaves idle when the first launch arrives, and between 1.3 and 10 ms after that every kernel runs 10-25 % slower (power-management
-    # ramp, tools/ramp2d.py): the driver's W = 5, K = 20 is 1.4 ms of load, i.e. entirely inside that transient.  The W + K steps are therefore
-    # run twice.  `value` / `ms_per_step` are the FIRST run -- exactly the contract: W untimed warm-up steps, then K timed steps, nothing before
-    # them (round 4; rounds 2-3 reported the second run as `value` and this one as `cold_start`).  The second run, after --settle untimed steps
-    # (default 400: 22 ms of the same load), is the steady state a job of more than a few hundred steps is in and the regime of the roofline
+    # ramp, tools/ramp2d.py): the driver's W = 5, K = 20 is 1.4 ms of load, i.e. entirely inside that transient.  With --full the W + K steps are
+    # therefore run twice.  `value` / `ms_per_step` are the FIRST run -- exactly the contract: W untimed warm-up steps, then K timed steps, nothing
+    # before them (round 4; rounds 2-3 reported the second run as `value` and this one as `cold_start`).  The second run, after --settle untimed
+    # steps (default 400: 22 ms of the same load), is the steady state a job of more than a few hundred steps is in and the regime of the roofline
     # launches below: reported as `steady_state`.
     dt, region_ms = timed_steps()
     dumped = None
@@ -791,6 +797,34 @@ def main():
         # once the measurements of this path are done, so that the host work does not idle the GPU between them
         grad, sums, loss = (t.clone() for t in last[0].result)
         dumped = {"loss": loss, "energy": sums[0], "grad_sumsq": sums[1], "grad_u": grad}
+
+    def headline():
+        """The line of a plain run: the result of the W + K steps and the workload they ran."""
+        mask_note = {'bits': 'held as one bit per node and sample (a general mask array)', 'u8': 'held as a uint8 image', 'f32': 'held as an fp32 image',
+                     'box': 'derived from the geometry (no array)'}[bc_form]
+        return {
+            "metric": "elements*gauss_pts/sec (FEM loss+grad)", "value": units_per_step * world * args.steps / dt, "unit": "elements*gauss_pts/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{args.nsd}-D Poisson energy loss + gradient wrt u, Q1, {args.size}^{args.nsd} nodes, "
+                                   f"{args.ngp}^{args.nsd} Gauss pts, batch {B}/GPU, nu+f nodal fields, Dirichlet mask on all boundary faces "
+                                   + mask_note + f", fused single pass (BASELINE.json configs[1] mesh); every step evaluates the next of {NROT} "
+                                   "different batches in rotation (nu, f and the mask stream from HBM with non-temporal loads; of the 4 x 67 MB of u a part may survive in the 256 MB "
+                                   "Infinity Cache until the batch's next turn: roofline.deeper_rotation of a --full run has the 16-batch figure)"
+                                   + ("; 2-D Q1 element evaluated in closed form: the rule's sums as polynomials of its moments, same value "
+                                      "as the per-point sum (dn_config_set(\"Q1_RULE_KERNEL\") runs the per-point kernel)" if args.nsd == 2 else ""),
+                       "batch_per_gpu": B, "nodes": list(m.geom.node_shape), "parallelism": f"batch-sharded x{world}",
+                       "batches_in_rotation": NROT, "mask_format": bc_form}}
+
+    if not args.full:
+        if dumped is not None:
+            dump_outputs(args.dump_outputs, dumped)
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     for _ in range(args.settle):
         step()
     drain()
@@ -941,22 +975,10 @@ def main():
 
     out = None
     if rank == 0:
-        value = units_per_step * world * args.steps / dt
-        mask_note = {'bits': 'held as one bit per node and sample (a general mask array)', 'u8': 'held as a uint8 image', 'f32': 'held as an fp32 image',
-                     'box': 'derived from the geometry (no array)'}[bc_form]
-        out = {
-            "metric": "elements*gauss_pts/sec (FEM loss+grad)", "value": value, "unit": "elements*gauss_pts/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "settle": args.settle, "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{args.nsd}-D Poisson energy loss + gradient wrt u, Q1, {args.size}^{args.nsd} nodes, "
-                                   f"{args.ngp}^{args.nsd} Gauss pts, batch {B}/GPU, nu+f nodal fields, Dirichlet mask on all boundary faces "
-                                   + mask_note + f", fused single pass (BASELINE.json configs[1] mesh); every step evaluates the next of {NROT} "
-                                   "different batches in rotation (nu, f and the mask stream from HBM with non-temporal loads; of the 4 x 67 MB of u a part may survive in the 256 MB "
-                                   "Infinity Cache until the batch's next turn: roofline.deeper_rotation has the 16-batch figure)"
-                                   + ("; 2-D Q1 element evaluated in closed form: the rule's sums as polynomials of its moments, same value "
-                                      "as the per-point sum (dn_config_set(\"Q1_RULE_KERNEL\") runs the per-point kernel)" if args.nsd == 2 else ""),
-                       "batch_per_gpu": B, "nodes": list(m.geom.node_shape), "parallelism": f"batch-sharded x{world}",
-                       "batches_in_rotation": NROT, "mask_format": bc_form},
+        out = headline()
+        value = out["value"]
+        out.update({
+            "settle": args.settle,
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                          "kernel": "poisson fused kernel (one launch per dn_poisson_apply)", "kernel_avg_ms": kern_avg_ms,
@@ -994,7 +1016,7 @@ def main():
                                      "the driver's W = 5, K = 20 all of it falls into the 1.3-10 ms power-management transient after load onset, tools/ramp2d.py) "
                                      "says what a 25-step job sees, this what a job of more than a few hundred steps sees.  Rounds 2-3 reported this one as "
                                      "`value` and the other as `cold_start`"},
-        }
+        })
         if not args.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(kw, c)
             out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]

@@ -1,5 +1,5 @@
 """bench.py --dump-outputs: the files hold what the last timed step computed (checked against the CPU oracle on the batch that step
-evaluated), and two runs with the same arguments write the same files."""
+evaluated), two runs with the same arguments write the same files, and a --full run writes them too."""
 import json
 import os
 import subprocess
@@ -16,9 +16,9 @@ pytestmark = pytest.mark.gpu
 N, B, STEPS, WARMUP = 64, 2, 6, 1
 
 
-def run_bench(out):
+def run_bench(out, *extra):
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(STEPS), "--warmup", str(WARMUP), "--settle", "3",
-                        "--batch", str(B), "--size", str(N), "--no-cpu", "--dump-outputs", str(out)],
+                        "--batch", str(B), "--size", str(N), "--no-cpu", "--dump-outputs", str(out), *extra],
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -51,3 +51,16 @@ def test_dump_outputs_hold_the_last_timed_step(tmp_path):
     _, again = run_bench(tmp_path / "b")
     for name in got:
         assert np.array_equal(got[name], again[name]), name
+
+
+def test_full_run_adds_side_fields_and_dumps_the_same(tmp_path):
+    """A plain run stops after the timed steps; --full measures the side fields after them and still dumps the last timed step."""
+    plain, a = run_bench(tmp_path / "a")
+    full, b = run_bench(tmp_path / "b", "--full")
+    assert not {"settle", "roofline", "steady_state"} & set(plain)
+    for key in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "config"):
+        assert plain[key] == full[key], key
+    assert full["settle"] == 3 and full["steady_state"]["ms_per_step"] > 0 and full["roofline"]["kernel_avg_ms"] > 0
+    assert sorted(a) == sorted(b)
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name

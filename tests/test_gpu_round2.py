@@ -400,7 +400,7 @@ def test_bench_spawns_its_own_ranks_world2_gloo_rehearsal():
     env = dict(os.environ, DN_DIST_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--batch", "4",
-                        "--slab-size", "64", "--slab-steps", "3", "--no-cpu"], env=env, capture_output=True, text=True, timeout=600)
+                        "--slab-size", "64", "--slab-steps", "3", "--no-cpu", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1                                             # ONE JSON line, from rank 0

@@ -6,10 +6,10 @@ export TMPDIR=/tmp
 root=$(pwd)
 O=gpurun_out/r3_ev
 mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
-python bench.py --gpus 1 --steps 20 --warmup 5 --no-configs > $O/bench_driver_args.json 2>/dev/null; echo "bench (driver args) rc=$?"
+python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-configs > $O/bench_driver_args.json 2>/dev/null; echo "bench (driver args) rc=$?"
 rm -rf $O/kt
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $root/$O/kt -- python3 $root/bench.py --no-cpu --slab-size 0 --no-configs > $root/$O/kt.log 2>&1); echo "kt rc=$?"
+(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $root/$O/kt -- python3 $root/bench.py --full --no-cpu --slab-size 0 --no-configs > $root/$O/kt.log 2>&1); echo "kt rc=$?"
 rm -rf $O/kt_slab
 (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $root/$O/kt_slab -- python3 $root/tools/slab_timeline.py > $root/$O/slab_timeline.txt 2>&1); echo "slab kt rc=$?"
 DN_BC_FORM=bits tools/prof_case.sh r3_2d_bits 2 512 64 3 "" 12 > /dev/null 2>&1; echo "pmc bits rc=$?"

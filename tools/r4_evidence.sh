@@ -8,10 +8,10 @@ O=gpurun_out/r4_ev
 mkdir -p $O
 python -c "from diffnet_amd import _lib; print(_lib.lib().dn_build_info().decode())"
 timeout -k 10 1000 python -m pytest tests -x -q -m gpu > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -2 $O/pytest.log
-python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
-python bench.py --gpus 1 --steps 20 --warmup 5 --no-configs > $O/bench_driver_args.json 2>/dev/null; echo "bench (driver args) rc=$?"
+python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-configs > $O/bench_driver_args.json 2>/dev/null; echo "bench (driver args) rc=$?"
 rm -rf $O/kt
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $root/$O/kt -- python3 $root/bench.py --no-cpu --slab-size 0 --no-configs > $root/$O/kt.log 2>&1); echo "kt rc=$?"
+(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $root/$O/kt -- python3 $root/bench.py --full --no-cpu --slab-size 0 --no-configs > $root/$O/kt.log 2>&1); echo "kt rc=$?"
 DN_BC_FORM=bits DN_SUMS=fold tools/prof_case.sh r4_2d_bits 2 512 64 3 "" 12 > /dev/null 2>&1; echo "pmc 2d bits rc=$?"
 tools/prof_case.sh r4_3d_256_cf 3 256 1 2 "" 12 > /dev/null 2>&1; echo "pmc 3d 256 rc=$?"
 tools/prof_case.sh r4_3d_128_cf 3 128 1 2 "" 12 > /dev/null 2>&1; echo "pmc 3d 128 rc=$?"

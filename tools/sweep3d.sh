@@ -3,7 +3,7 @@
 run() { # size batch plans...
   local size=$1 batch=$2; shift 2
   for plan in "$@"; do
-    out=$(env DN_PLAN3D=$plan python bench.py --nsd 3 --size $size --ngp 2 --batch $batch --no-cpu --steps 40 --warmup 5 2>/dev/null | tail -1)
+    out=$(env DN_PLAN3D=$plan python bench.py --full --nsd 3 --size $size --ngp 2 --batch $batch --no-cpu --steps 40 --warmup 5 2>/dev/null | tail -1)
     echo "n=$size B=$batch plan=$plan $(echo "$out" | python -c 'import sys,json; d=json.loads(sys.stdin.read()); r=d["roofline"]; print("kern_us=%.1f min_us=%.1f frac=%.3f" % (r["kernel_avg_ms"]*1e3, r["kernel_min_ms"]*1e3, r["frac"]))')"
   done
 }
