@@ -64,6 +64,17 @@ class DnStokesArgs(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class DnNsArgs(C.Structure):
+    _fields_ = [("u", C.c_void_p), ("v", C.c_void_p), ("p", C.c_void_p),
+                ("bc_mask", C.c_void_p * 3), ("mask_is_u8", C.c_int32 * 3), ("mask_batched", C.c_int32 * 3),
+                ("bc_field", C.c_void_p * 3), ("bc_field_batched", C.c_int32 * 3), ("bc_value", C.c_float * 3),
+                ("f_gp", C.c_void_p * 2), ("f_batched", C.c_int32 * 2), ("f_value", C.c_float * 2),
+                ("visco", C.c_float), ("wscale", C.c_float), ("tau_h", C.c_float * 2), ("cinv", C.c_float), ("vjp", C.c_int32),
+                ("cot", C.c_void_p * 3),
+                ("out", C.c_void_p * 3), ("sumsq", C.c_void_p), ("norms", C.c_void_p), ("in_num", C.c_void_p), ("in_den", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 I32x3 = C.c_int32 * 3
 
 # name -> (restype, argtypes); must list every symbol of include/diffnet_hip.h
@@ -99,6 +110,8 @@ SYMBOLS = {
     "dn_fsdt_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnFsdtArgs), C.c_void_p]),
     "dn_stokes_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
     "dn_stokes_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnStokesArgs), C.c_void_p]),
+    "dn_ns_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
+    "dn_ns_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnNsArgs), C.c_void_p]),
     "dn_upconv_out_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "dn_upconv_out_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                     C.c_void_p, C.c_int64, C.c_void_p]),

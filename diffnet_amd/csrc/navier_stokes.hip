@@ -1,0 +1,497 @@
+// Fused 2-D Navier-Stokes (VMS) residuals on Q1 meshes and their VJP: dn_ns_apply (include/diffnet_hip.h).
+//
+// The nonlinear residual body of examples/navier-stokes/single_instance/e1_ns_ldc_resmin.py:147-308 of the reference (calc_tau,
+// calc_residuals) and of e2_ns_fps_resmin.py:293 calc_residuals_ns and its siblings: Dirichlet substitution of u, v, p, the Gauss-point
+// evaluations, the variational-multiscale weak forms with the detached stabilisation parameters tau_m / tau_c, their assembly, the Dirichlet
+// rows (which take the boundary VALUE) and the three sums of squares -- in one launch.
+//
+// Flux form: at a Gauss point every weak form is  T_k,a = N_a A_k + Nx_a B_k + Ny_a C_k  with nine pointwise coefficients
+//     A1 = a1 - f1 - tm (r1 u_x + r2 u_y)    B1 = visco u_x - p + tm u r1 - tm^2 r1 r1 + tc d    C1 = visco u_y + tm v r1 - tm^2 r1 r2
+//     A2 = a2 - f2 - tm (r1 v_x + r2 v_y)    B2 = visco v_x + tm u r2 - tm^2 r2 r1               C2 = visco v_y - p + tm v r2 - tm^2 r2 r2 + tc d
+//     A3 = d                                 B3 = tm r1                                          C3 = tm r2
+// (a1 = u u_x + v u_y, a2 = u v_x + v v_y, d = u_x + v_y, r1 = a1 + p_x - f1, r2 = a2 + p_y - f2).  The VJP mode has the same form: with the
+// cotangents evaluated like fields (L_k, L_k,x, L_k,y) the pullback of s = sum_k (L_k A_k + L_k,x B_k + L_k,y C_k) with tau held fixed is
+// again N_a G + Nx_a G_x + Ny_a G_y per field (ns_vjp_flux below; DESIGN.md section 3.2 has the derivation), so both modes share the march.
+//
+// Element-owner march: one wave = 62 owner columns + two ghost lanes; lane q owns node column q and the element to its right.  A lane
+// marches the node rows of a strip, loads every node row once (the x neighbour comes over ds_bpermute), computes its element's four local
+// contributions, hands the two right-hand ones to its neighbour lane (shuffle) and carries the top pair in registers into the next element
+// row.  A strip recomputes one halo element row under it, so every output node is written once, by its owner lane, with the same additions
+// in any launch plan: no atomics on the data path, results bitwise independent of the plan and of the other samples of the batch.
+// Sums of squares: fixed-order fp64 reduction (finish_sums3).
+#include <algorithm>
+
+#include "fsdt_common.h"
+
+namespace dn {
+
+struct NsParams {
+    float bx[4][2], dx[4][2];              // 1-D Q1 basis / derivative (times 2 / hx) at the Gauss points along x
+    float by[4][2], dy[4][2];              // along y
+    float wg[16];                          // wscale w_ig w_jg, point jg * ngp + ig
+    float visco;
+    float Gx, Gy, diff, gg_inv;            // tau: Gx = 4 / hx^2, Gy = 4 / hy^2, diff = cinv visco^2 (Gx^2 + Gy^2), gg_inv = 1 / (gx^2 + gy^2)
+    float fconst[2];                       // constant forcing (where fgp[k] is NULL)
+    const float* fld[3];                   // u, v, p (the linearisation point in the VJP mode)
+    const float* cot[3];                   // VJP: the cotangents of R1..R3
+    const void* mask[3];
+    int mask_kind[3];                      // 0: none, 1: uint8 (!= 0), 2: fp32 (>= 0.5)
+    int mask_batched[3];
+    const float* bcf[3];
+    int bcf_batched[3];
+    float bcv[3];
+    const float* fgp[2];                   // (B | 1, G, nely, nelx)
+    int fgp_batched[2];
+    const float* in_num;                   // optional, VJP: cotangent k is scaled by in_num[k] / in_den[k] (0 where in_den[k] <= 0)
+    const float* in_den;
+    float* out[3];
+    double* part;                          // [3][nblocks] partial sums of squares (finish_sums3)
+    unsigned* counter;
+    double* sumsq;
+    float* norms;
+    int nx, ny, nelx, nely, chunks, rows_per_strip, strips, want_sums;
+};
+
+constexpr int NS_OWNERS = 62;              // owner lanes per wave (lanes 1 .. 62); lanes 0 and 63 are ghosts
+
+// Raw loads of one node row r (clamped into the mesh) and, with the Gauss-point forcing, of the element layer r - 1 under it
+template <int G, bool MASK, bool BCF, bool FGP, bool VJP>
+struct NsRaw {
+    float v[3];
+    float l[VJP ? 3 : 1];
+    float mf[MASK ? 3 : 1];
+    uint8_t mb[MASK ? 3 : 1];
+    float bf[BCF ? 3 : 1];
+    float f[FGP ? 2 : 1][FGP ? G : 1];
+};
+
+// A landed node row: substituted values of the lane's node (c) and of its right neighbour (n); VJP: the cotangents likewise
+template <bool VJP>
+struct NsRow {
+    float c[3], n[3];
+    float lc[VJP ? 3 : 1], ln[VJP ? 3 : 1];
+    unsigned fixed;
+    float bv[3];
+};
+
+// value and derivatives at one point from the element's four nodal values (local node ly * 2 + lx)
+__device__ __forceinline__ void ns_eval(float bx0, float bx1, float dx0, float dx1, float by0, float by1, float dy0, float dy1,
+                                        float f0, float f1, float f2, float f3, float& val, float& fx, float& fy) {
+    const float vb = fmaf(bx0, f0, bx1 * f1), vt = fmaf(bx0, f2, bx1 * f3);
+    const float db = fmaf(dx0, f0, dx1 * f1), dt = fmaf(dx0, f2, dx1 * f3);
+    val = fmaf(by0, vb, by1 * vt);
+    fx = fmaf(by0, db, by1 * dt);
+    fy = fmaf(dy0, vb, dy1 * vt);
+}
+
+// forward coefficients (A, B, C) of the three weak forms at a point
+__device__ __forceinline__ void ns_fwd_flux(const NsParams& p, float u, float ux, float uy, float v, float vx, float vy, float pg, float px,
+                                            float py, float f1, float f2, float (&A)[3], float (&B)[3], float (&Cc)[3]) {
+    const float a1 = fmaf(u, ux, v * uy), a2 = fmaf(u, vx, v * vy), d = ux + vy;
+    const float r1 = a1 + px - f1, r2 = a2 + py - f2;
+    const float temp = sqrtf(fmaf(p.Gx, u * u, p.Gy * (v * v)) + p.diff);     // calc_tau; tau is detached
+    const float tm = 1.f / temp, tc = temp * p.gg_inv, tm2 = tm * tm;
+    const float tr1 = tm * r1, tr2 = tm * r2, qr1 = tm2 * r1, qr2 = tm2 * r2;
+    A[0] = a1 - f1 - tm * fmaf(r1, ux, r2 * uy);
+    B[0] = fmaf(p.visco, ux, -pg) + fmaf(u, tr1, -qr1 * r1) + tc * d;
+    Cc[0] = fmaf(p.visco, uy, fmaf(v, tr1, -qr1 * r2));
+    A[1] = a2 - f2 - tm * fmaf(r1, vx, r2 * vy);
+    B[1] = fmaf(p.visco, vx, fmaf(u, tr2, -qr2 * r1));
+    Cc[1] = fmaf(p.visco, vy, -pg) + fmaf(v, tr2, -qr2 * r2) + tc * d;
+    A[2] = d;
+    B[2] = tr1;
+    Cc[2] = tr2;
+}
+
+// VJP coefficients: d/d(u, u_x, u_y | v, v_x, v_y | p, p_x, p_y) of sum_k (L_k A_k + Lx_k B_k + Ly_k C_k), tau held fixed
+__device__ __forceinline__ void ns_vjp_flux(const NsParams& p, float u, float ux, float uy, float v, float vx, float vy, float px, float py,
+                                            float f1, float f2, const float (&L)[3], const float (&Lx)[3], const float (&Ly)[3],
+                                            float (&A)[3], float (&B)[3], float (&Cc)[3]) {
+    const float a1 = fmaf(u, ux, v * uy), a2 = fmaf(u, vx, v * vy);
+    const float r1 = a1 + px - f1, r2 = a2 + py - f2;
+    const float temp = sqrtf(fmaf(p.Gx, u * u, p.Gy * (v * v)) + p.diff);
+    const float tm = 1.f / temp, tc = temp * p.gg_inv, tm2 = tm * tm;
+    const float tu = tm * u, tv = tm * v, qr1 = tm2 * r1, qr2 = tm2 * r2;
+    // partials with respect to the strong residuals r1, r2 (r1 = a1 + p_x - f1: also the p_x, p_y coefficients)
+    const float g1 = -tm * fmaf(L[0], ux, L[1] * vx) + Lx[0] * (tu - 2.f * qr1) + Ly[0] * (tv - qr2) - Lx[1] * qr2 + Lx[2] * tm;
+    const float g2 = -tm * fmaf(L[0], uy, L[1] * vy) - Ly[0] * qr1 + Lx[1] * (tu - qr1) + Ly[1] * (tv - 2.f * qr2) + Ly[2] * tm;
+    const float h1 = L[0] + g1, h2 = L[1] + g2;                         // with respect to a1, a2
+    const float hd = fmaf(tc, Lx[0] + Ly[1], L[2]);                     // with respect to d
+    A[0] = fmaf(h1, ux, h2 * vx) + tm * fmaf(Lx[0], r1, Lx[1] * r2);
+    B[0] = fmaf(h1, u, -tm * r1 * L[0]) + fmaf(p.visco, Lx[0], hd);
+    Cc[0] = fmaf(h1, v, -tm * r2 * L[0]) + p.visco * Ly[0];
+    A[1] = fmaf(h1, uy, h2 * vy) + tm * fmaf(Ly[0], r1, Ly[1] * r2);
+    B[1] = fmaf(h2, u, -tm * r1 * L[1]) + p.visco * Lx[1];
+    Cc[1] = fmaf(h2, v, -tm * r2 * L[1]) + fmaf(p.visco, Ly[1], hd);
+    A[2] = -(Lx[0] + Ly[1]);
+    B[2] = g1;
+    Cc[2] = g2;
+}
+
+template <int NGP, bool MASK, bool BCF, bool FGP, bool VJP>
+__global__ void __launch_bounds__(256) ns2d_kernel(const NsParams p) {
+    constexpr int G = NGP * NGP;
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int lane = (int)threadIdx.x & 63;
+    const int wid = (int)blockIdx.x * ((int)blockDim.x >> 6) + wave;
+    const int b = blockIdx.y;
+    const int chunk = wid % p.chunks, strip = wid / p.chunks;
+
+    __shared__ double red[16];
+    __shared__ int last_flag;
+    float sq[3] = {0.f, 0.f, 0.f};
+
+    if (strip < p.strips) {
+        const int nx = p.nx, ny = p.ny;
+        const int q = chunk * NS_OWNERS + lane - 1;                        // node column of the lane
+        const bool owner = lane >= 1 && lane <= NS_OWNERS && q < nx;
+        const unsigned qc = (unsigned)min(max(q, 0), nx - 1);
+        const int64_t nps = (int64_t)nx * ny;
+        const int nel = p.nelx * p.nely;
+        const bool elem_x = q >= 0 && q < p.nelx;                          // the element to the right of the lane's column exists
+        const unsigned qe = (unsigned)min(max(q, 0), p.nelx - 1);
+
+        const float* fb[3];
+        const float* cb[3];
+        const float* bcf[3];
+        const float* mfp[3];
+        const uint8_t* mbp[3];
+        float* ob[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            fb[k] = p.fld[k] + (int64_t)b * nps;
+            cb[k] = VJP ? p.cot[k] + (int64_t)b * nps : fb[k];
+            bcf[k] = p.bcf[k] ? p.bcf[k] + (p.bcf_batched[k] ? (int64_t)b * nps : 0) : fb[k];
+            const int64_t mo = p.mask_batched[k] ? (int64_t)b * nps : 0;
+            mfp[k] = reinterpret_cast<const float*>(p.mask[k]) + (p.mask_kind[k] == 2 ? mo : 0);
+            mbp[k] = reinterpret_cast<const uint8_t*>(p.mask[k]) + (p.mask_kind[k] == 1 ? mo : 0);
+            ob[k] = p.out[k] ? p.out[k] + (int64_t)b * nps : nullptr;
+        }
+        const float* fg[2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) fg[k] = p.fgp[k] ? p.fgp[k] + (p.fgp_batched[k] ? (int64_t)b * G * nel : 0) : nullptr;
+
+        float lscale[3] = {1.f, 1.f, 1.f};
+        if (VJP && p.in_num) {        // cotangent of the norms over the norms (the VJP of ||R_k||), torch's convention at ||R_k|| == 0: zero
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float den = p.in_den[k];
+                lscale[k] = den > 0.f ? p.in_num[k] / den : (den == den ? 0.f : den);
+            }
+        }
+
+        using Raw = NsRaw<G, MASK, BCF, FGP, VJP>;
+        using Row = NsRow<VJP>;
+        auto issue = [&](int r, Raw& w) {
+            const unsigned rowoff = (unsigned)min(max(r, 0), ny - 1) * (unsigned)nx + qc;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) w.v[k] = ld_at<float>(fb[k], rowoff);
+            if constexpr (VJP) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) w.l[k] = ld_at<float>(cb[k], rowoff);
+            }
+            if constexpr (MASK) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    w.mf[k] = 0.f;
+                    w.mb[k] = 0;
+                    if (p.mask_kind[k] == 2) w.mf[k] = ld_at<float>(mfp[k], rowoff);
+                    else if (p.mask_kind[k] == 1) w.mb[k] = ld_at<uint8_t>(mbp[k], rowoff);
+                }
+            }
+            if constexpr (BCF) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    w.bf[k] = 0.f;
+                    if (p.bcf[k]) w.bf[k] = ld_at<float>(bcf[k], rowoff);
+                }
+            }
+            if constexpr (FGP) {
+                const unsigned eoff = (unsigned)min(max(r - 1, 0), p.nely - 1) * (unsigned)p.nelx + qe;
+#pragma unroll
+                for (int k = 0; k < 2; ++k)
+#pragma unroll
+                    for (int g = 0; g < G; ++g) w.f[k][g] = fg[k] ? ld_at<float>(fg[k], eoff + (unsigned)(g * nel)) : 0.f;
+            }
+        };
+
+        // Dirichlet substitution of a landed row (the cotangent of a Dirichlet row is zero) and the right neighbours
+        auto consume = [&](const Raw& w, Row& R) {
+            R.fixed = 0u;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                float val = w.v[k];
+                float lv = 0.f;
+                if constexpr (VJP) lv = w.l[k] * lscale[k];
+                R.bv[k] = p.bcv[k];
+                if constexpr (MASK) {
+                    const bool fx = p.mask_kind[k] == 2 ? (w.mf[k] >= 0.5f) : (p.mask_kind[k] == 1 ? (w.mb[k] != 0) : false);
+                    if constexpr (BCF) R.bv[k] = p.bcf[k] ? w.bf[k] : R.bv[k];
+                    val = fx ? R.bv[k] : val;
+                    lv = fx ? 0.f : lv;
+                    R.fixed |= fx ? (1u << k) : 0u;
+                }
+                R.c[k] = val;
+                R.n[k] = __shfl_down(val, 1, 64);
+                if constexpr (VJP) {
+                    R.lc[k] = lv;
+                    R.ln[k] = __shfl_down(lv, 1, 64);
+                }
+            }
+        };
+
+        // the lane's element in element row e (node rows e, e + 1: Bm, Tp): its four local contributions per weak form, zero where the
+        // element does not exist; returns the parts that belong to the lane's node in rows e (bot) and e + 1 (top)
+        auto element = [&](const Row& Bm, const Row& Tp, const Raw& w, int e, float (&bot)[3], float (&top)[3]) {
+            float acc[3][4];
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+#pragma unroll
+                for (int a = 0; a < 4; ++a) acc[k][a] = 0.f;
+#pragma unroll
+            for (int jg = 0; jg < NGP; ++jg) {
+                const float by0 = p.by[jg][0], by1 = p.by[jg][1], dy0 = p.dy[jg][0], dy1 = p.dy[jg][1];
+#pragma unroll
+                for (int ig = 0; ig < NGP; ++ig) {
+                    const int g = jg * NGP + ig;
+                    const float bx0 = p.bx[ig][0], bx1 = p.bx[ig][1], dx0 = p.dx[ig][0], dx1 = p.dx[ig][1];
+                    float val[3], gx[3], gy[3];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k)
+                        ns_eval(bx0, bx1, dx0, dx1, by0, by1, dy0, dy1, Bm.c[k], Bm.n[k], Tp.c[k], Tp.n[k], val[k], gx[k], gy[k]);
+                    float f1 = p.fconst[0], f2 = p.fconst[1];
+                    if constexpr (FGP) {
+                        f1 = p.fgp[0] ? w.f[0][g] : f1;
+                        f2 = p.fgp[1] ? w.f[1][g] : f2;
+                    }
+                    float A[3], Bc[3], Cc[3];
+                    if constexpr (VJP) {
+                        float L[3], Lx[3], Ly[3];
+#pragma unroll
+                        for (int k = 0; k < 3; ++k)
+                            ns_eval(bx0, bx1, dx0, dx1, by0, by1, dy0, dy1, Bm.lc[k], Bm.ln[k], Tp.lc[k], Tp.ln[k], L[k], Lx[k], Ly[k]);
+                        ns_vjp_flux(p, val[0], gx[0], gy[0], val[1], gx[1], gy[1], gx[2], gy[2], f1, f2, L, Lx, Ly, A, Bc, Cc);
+                    } else {
+                        ns_fwd_flux(p, val[0], gx[0], gy[0], val[1], gx[1], gy[1], val[2], gx[2], gy[2], f1, f2, A, Bc, Cc);
+                    }
+                    const float wq = p.wg[g];
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        const float Aw = wq * A[k], Bw = wq * Bc[k], Cw = wq * Cc[k];
+                        const float s0 = fmaf(by0, Aw, dy0 * Cw), s1 = fmaf(by1, Aw, dy1 * Cw);     // per ly: N_ly A + N'_ly C
+                        const float t0 = by0 * Bw, t1 = by1 * Bw;
+                        acc[k][0] = fmaf(bx0, s0, fmaf(dx0, t0, acc[k][0]));
+                        acc[k][1] = fmaf(bx1, s0, fmaf(dx1, t0, acc[k][1]));
+                        acc[k][2] = fmaf(bx0, s1, fmaf(dx0, t1, acc[k][2]));
+                        acc[k][3] = fmaf(bx1, s1, fmaf(dx1, t1, acc[k][3]));
+                    }
+                }
+            }
+            const bool ok = elem_x && e >= 0 && e < p.nely;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                float c[4];
+#pragma unroll
+                for (int a = 0; a < 4; ++a) c[a] = ok ? acc[k][a] : 0.f;
+                // the node's own element (right) as local node lx = 0, the left neighbour's element as lx = 1
+                bot[k] = c[0] + __shfl_up(c[1], 1, 64);
+                top[k] = c[2] + __shfl_up(c[3], 1, 64);
+            }
+        };
+
+        const int j0 = strip * p.rows_per_strip, j1 = min(j0 + p.rows_per_strip, ny);
+        Row prev, cur;
+        float carry[3] = {0.f, 0.f, 0.f};
+        // two rows in flight ahead of the element row being computed (W0, W1 alternate; unrolled by two so that no register with a load
+        // outstanding is ever copied)
+        Raw W0, W1;
+        {
+            Raw A;
+            issue(j0 - 1, A);
+            issue(j0, W0);
+            issue(j0 + 1, W1);
+            consume(A, prev);
+        }
+        // element row e (from e = j0 - 1, the halo row): W holds the raw node row e + 1 and the element layer e; refilled with row e + 3.
+        // Node row e is finished here.
+        auto step = [&](int e, Raw& W) {
+            consume(W, cur);
+            float bot[3], top[3];
+            element(prev, cur, W, e, bot, top);
+            issue(e + 3, W);
+            if (e >= j0) {
+                const unsigned rowoff = (unsigned)e * (unsigned)nx + qc;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    float r = carry[k] + bot[k];
+                    if constexpr (MASK) {
+                        // forward: Dirichlet rows take the boundary value (the scripts' torch.where); VJP: no gradient reaches a substituted node
+                        const bool fx = (prev.fixed & (1u << k)) != 0u;
+                        r = fx ? (VJP ? 0.f : prev.bv[k]) : r;
+                    }
+                    sq[k] = owner ? fmaf(r, r, sq[k]) : sq[k];
+                    if (owner && ob[k]) st_at<float>(ob[k], rowoff, r);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) carry[k] = top[k];
+            prev = cur;
+        };
+        for (int e = j0 - 1; e < j1; e += 2) {
+            step(e, W0);
+            if (e + 1 < j1) step(e + 1, W1);
+        }
+    }
+    if (p.want_sums) finish_sums3(p, sq, (int)threadIdx.x, (int)blockDim.x, red, &last_flag);
+}
+
+static constexpr int64_t NS_WS_HEADER = 64 * (1 + 64);     // top counter + DN_NSHARD shard counters (finish_sums3)
+
+struct NsGeom { int chunks, strips, R, wpb, gx; };
+
+static int ns_validate(const dn_mesh* m) {
+    if (!m) return DN_E_BADARG;
+    if (m->nsd != 2 || m->degree != 1 || m->ngp < 2 || m->ngp > 4) return DN_E_UNSUPPORTED;
+    if (m->batch < 1 || m->batch > 65535 || m->nx < 2 || m->ny < 2) return DN_E_BADARG;
+    const int64_t nps = (int64_t)m->nx * m->ny, nel = (int64_t)(m->nx - 1) * (m->ny - 1);
+    if (nps >= (1ll << 30) || nel * m->ngp * m->ngp >= (1ll << 30)) return DN_E_UNSUPPORTED;     // 32-bit byte offsets within a sample
+    return 0;
+}
+
+// One wave per (62-column chunk, strip of R node rows, sample); strips of at least 8 rows (a strip recomputes one halo element row) until
+// the launch has ~4096 waves (16 per CU).
+static NsGeom ns_plan(const dn_mesh* m) {
+    NsGeom g;
+    g.chunks = (m->nx + NS_OWNERS - 1) / NS_OWNERS;
+    const int64_t per_row = (int64_t)g.chunks * m->batch;
+    int strips = (int)std::min<int64_t>((4096 + per_row - 1) / per_row, (m->ny + 7) / 8);
+    strips = std::max(strips, 1);
+    g.R = (m->ny + strips - 1) / strips;
+    g.strips = (m->ny + g.R - 1) / g.R;
+    const int waves = g.chunks * g.strips;
+    g.wpb = std::min(waves, 4);
+    g.gx = (waves + g.wpb - 1) / g.wpb;
+    return g;
+}
+
+template <int NGP, bool VJP>
+static void ns_launch_k(const NsParams& pp, const NsGeom& g, int batch, bool mask, bool bcf, bool fgp, hipStream_t s) {
+    dim3 grid(g.gx, batch), block(64 * g.wpb);
+    const int sel = (mask ? (bcf ? 2 : 1) : 0);
+    if (fgp) {
+        switch (sel) {
+            case 0: hipLaunchKernelGGL((ns2d_kernel<NGP, false, false, true, VJP>), grid, block, 0, s, pp); return;
+            case 1: hipLaunchKernelGGL((ns2d_kernel<NGP, true, false, true, VJP>), grid, block, 0, s, pp); return;
+            default: hipLaunchKernelGGL((ns2d_kernel<NGP, true, true, true, VJP>), grid, block, 0, s, pp); return;
+        }
+    }
+    switch (sel) {
+        case 0: hipLaunchKernelGGL((ns2d_kernel<NGP, false, false, false, VJP>), grid, block, 0, s, pp); return;
+        case 1: hipLaunchKernelGGL((ns2d_kernel<NGP, true, false, false, VJP>), grid, block, 0, s, pp); return;
+        default: hipLaunchKernelGGL((ns2d_kernel<NGP, true, true, false, VJP>), grid, block, 0, s, pp); return;
+    }
+}
+
+template <int NGP>
+static void ns_launch_ngp(const NsParams& pp, const NsGeom& g, int batch, bool mask, bool bcf, bool fgp, bool vjp, hipStream_t s) {
+    if (vjp) ns_launch_k<NGP, true>(pp, g, batch, mask, bcf, fgp, s);
+    else ns_launch_k<NGP, false>(pp, g, batch, mask, bcf, fgp, s);
+}
+
+}  // namespace dn
+
+using namespace dn;
+
+extern "C" int64_t dn_ns_workspace_bytes(const dn_mesh* m) {
+    if (ns_validate(m) != 0) return DN_E_BADARG;
+    const NsGeom g = ns_plan(m);
+    return NS_WS_HEADER + (int64_t)(3 * sizeof(double)) * g.gx * m->batch;
+}
+
+extern "C" int dn_ns_apply(const dn_mesh* m, const dn_ns_args* a, void* stream) {
+    int rc = ns_validate(m);
+    if (rc) return rc;
+    if (!a || !a->u || !a->v || !a->p) return DN_E_BADARG;
+    if (!a->out[0] && !a->out[1] && !a->out[2] && !a->sumsq && !a->norms) return DN_E_BADARG;
+    if ((a->in_num != nullptr) != (a->in_den != nullptr)) return DN_E_BADARG;
+    if (a->vjp & ~1) return DN_E_BADARG;
+    const bool vjp = a->vjp != 0;
+    if (vjp && (!a->cot[0] || !a->cot[1] || !a->cot[2])) return DN_E_BADARG;     // a VJP without its cotangents
+    if (!vjp && a->in_num) return DN_E_BADARG;                                    // the scaling applies to the cotangents only
+    for (int k = 0; k < 3; ++k) {
+        if ((a->mask_is_u8[k] | a->mask_batched[k] | a->bc_field_batched[k]) & ~1) return DN_E_BADARG;
+        if (a->bc_field[k] && !a->bc_mask[k]) return DN_E_BADARG;           // a value field without a condition
+    }
+    for (int k = 0; k < 2; ++k)
+        if (a->f_batched[k] & ~1) return DN_E_BADARG;
+    if (!(a->tau_h[0] > 0.f) || !(a->tau_h[1] > 0.f)) return DN_E_BADARG;
+    const bool want_red = a->sumsq || a->norms;
+    const NsGeom g = ns_plan(m);
+    const int64_t nwg = (int64_t)g.gx * m->batch;
+    if (want_red && (!a->workspace || a->workspace_bytes < NS_WS_HEADER + (int64_t)(3 * sizeof(double)) * nwg)) return DN_E_WORKSPACE;
+
+    NsParams pp;
+    const int ngp = m->ngp;
+    const double sx = m->scale[0], sy = m->scale[1], J = a->wscale;
+    for (int ig = 0; ig < 4; ++ig)
+        for (int i = 0; i < 2; ++i) {
+            const bool in = ig < ngp;
+            pp.bx[ig][i] = in ? m->basis[ig][i] : 0.f;
+            pp.by[ig][i] = in ? m->basis[ig][i] : 0.f;
+            pp.dx[ig][i] = in ? (float)(m->dbasis[ig][i] * sx) : 0.f;
+            pp.dy[ig][i] = in ? (float)(m->dbasis[ig][i] * sy) : 0.f;
+        }
+    for (int gq = 0; gq < 16; ++gq) {
+        const int ig = gq % ngp, jg = gq / ngp;
+        pp.wg[gq] = gq < ngp * ngp ? (float)(J * m->gpw[ig] * m->gpw[jg]) : 0.f;
+    }
+    // calc_tau of the scripts: g and G are float32 tensors, the diffusion part a float32 product
+    const float visco = a->visco;
+    const double hx = a->tau_h[0], hy = a->tau_h[1];
+    const float gx = (float)(2.0 / hx), gy = (float)(2.0 / hy);
+    const float Gx = (float)(4.0 / (hx * hx)), Gy = (float)(4.0 / (hy * hy));
+    pp.visco = visco;
+    pp.Gx = Gx;
+    pp.Gy = Gy;
+    pp.diff = (float)((double)a->cinv * (double)visco * (double)visco) * (Gx * Gx + Gy * Gy);
+    pp.gg_inv = 1.f / (gx * gx + gy * gy);
+    pp.fld[0] = a->u; pp.fld[1] = a->v; pp.fld[2] = a->p;
+    bool any_mask = false, any_bcf = false;
+    for (int k = 0; k < 3; ++k) {
+        pp.cot[k] = vjp ? a->cot[k] : nullptr;
+        pp.mask[k] = a->bc_mask[k];
+        pp.mask_kind[k] = !a->bc_mask[k] ? 0 : (a->mask_is_u8[k] ? 1 : 2);
+        pp.mask_batched[k] = a->mask_batched[k];
+        any_mask = any_mask || a->bc_mask[k];
+        pp.bcf[k] = a->bc_field[k];
+        pp.bcf_batched[k] = a->bc_field_batched[k];
+        pp.bcv[k] = a->bc_value[k];
+        any_bcf = any_bcf || pp.bcf[k];
+        pp.out[k] = a->out[k];
+    }
+    bool any_fgp = false;
+    for (int k = 0; k < 2; ++k) {
+        pp.fgp[k] = a->f_gp[k];
+        pp.fgp_batched[k] = a->f_batched[k];
+        pp.fconst[k] = a->f_gp[k] ? 0.f : a->f_value[k];
+        any_fgp = any_fgp || pp.fgp[k];
+    }
+    pp.in_num = a->in_num;
+    pp.in_den = a->in_den;
+    pp.counter = reinterpret_cast<unsigned*>(a->workspace);
+    pp.part = a->workspace ? reinterpret_cast<double*>(reinterpret_cast<char*>(a->workspace) + NS_WS_HEADER) : nullptr;
+    pp.sumsq = a->sumsq;
+    pp.norms = a->norms;
+    pp.nx = m->nx; pp.ny = m->ny;
+    pp.nelx = m->nx - 1; pp.nely = m->ny - 1;
+    pp.chunks = g.chunks; pp.rows_per_strip = g.R; pp.strips = g.strips;
+    pp.want_sums = want_red ? 1 : 0;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    switch (ngp) {
+        case 2: ns_launch_ngp<2>(pp, g, m->batch, any_mask, any_bcf, any_fgp, vjp, s); break;
+        case 3: ns_launch_ngp<3>(pp, g, m->batch, any_mask, any_bcf, any_fgp, vjp, s); break;
+        default: ns_launch_ngp<4>(pp, g, m->batch, any_mask, any_bcf, any_fgp, vjp, s); break;
+    }
+    DN_LAUNCH_CHECK();
+    return 0;
+}

@@ -11,7 +11,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import DnDirichlet, DnFsdtArgs, DnMesh, DnPoissonArgs, DnStokesArgs, I32x3, DiffNetHipError
+from ._lib import DnDirichlet, DnFsdtArgs, DnMesh, DnNsArgs, DnPoissonArgs, DnStokesArgs, I32x3, DiffNetHipError
 
 
 def _require(t, name, ndim=None, strict=False):
@@ -599,10 +599,12 @@ def call_cache_clear():
         _CALL_CACHE.clear()
         _FSDT_CACHE.clear()
         _STOKES_CACHE.clear()
+        _NS_CACHE.clear()
         _PACK_CACHE.clear()
     _POISSON_WS_BYTES.clear()
     _FSDT_WS_BYTES.clear()
     _STOKES_WS_BYTES.clear()
+    _NS_WS_BYTES.clear()
 
 
 class PoissonPlan:
@@ -1560,6 +1562,199 @@ def stokes_apply(geom, u, v, p, bc=None, bc_values=(0.0, 0.0, 0.0), visco=1.0, p
     if rc:
         _lib.check(rc, "dn_stokes_apply")
     return (outs, sums, norms) if want_norms else (outs, sums)
+
+# ---- fused 2-D Navier-Stokes (VMS) residuals and their VJP: dn_ns_apply ------------------------------------------------------------
+# A reduction workspace of its OWN per (device, stream), for the reason given at _STOKES_WS.
+_NS_WS = {}
+_NS_WS_BYTES = {}
+_NS_CACHE = __import__("collections").OrderedDict()
+_NS_LAUNCH_LOCK = _threading.Lock()
+
+
+def _ns_workspace(dev, nbytes):
+    key = (dev.index, _raw_stream(dev))
+    with _WS_LOCK:
+        ws = _NS_WS.get(key)
+        if ws is None or ws.numel() < nbytes:
+            ws = torch.zeros(max(nbytes, 1 << 16), dtype=torch.uint8, device=dev)   # ABI: zero-filled once
+            _NS_WS[key] = ws
+    return ws
+
+
+def _ns_check_mesh(geom):
+    if geom.nsd != 2 or geom.deg != 1 or not 2 <= geom.ngp_1d <= 4:
+        raise DiffNetHipError(f"ns_apply: 2-D Q1 meshes with 2..4 Gauss points per axis only (nsd {geom.nsd}, degree {geom.deg}, ngp {geom.ngp_1d})")
+
+
+def _ns_key(geom, flds, cot, bc3, vals, f2, consts, in_num, in_den, flags):
+    """Key of a cached prepared dn_ns_apply call: the Stokes key of the shared arguments and the cotangents; None when an argument needs a
+    conversion copy."""
+    base = _stokes_key(geom, flds, bc3, vals, f2, consts, in_num, in_den, flags)
+    if base is None:
+        return None
+    parts = [base]
+    for t in (cot if cot is not None else (None, None, None)):
+        k = _tkey(t)
+        if k is None or (k != 0 and k[1] != torch.float32):
+            return None
+        parts.append(k)
+    return tuple(parts)
+
+
+def _prepare_ns(geom, u, v, p, cot, bc3, vals, f2, consts, in_num, in_den, want_red):
+    """Validation + argument struct of a dn_ns_apply call, outputs left unset: (mesh, args, tensors to keep alive, field shape)."""
+    _ns_check_mesh(geom)
+    flds = [_require(t, n, 4) for t, n in ((u, "u"), (v, "v"), (p, "p"))]
+    if cot is not None:
+        flds += [_require(t, f"cot[{k}]", 4) for k, t in enumerate(cot)]
+    B = flds[0].shape[0]
+    shape = (B, 1, *geom.node_shape)
+    for t in flds:
+        if tuple(t.shape) != shape:
+            raise ValueError(f"ns_apply: field shape {tuple(t.shape)} != {shape}")
+    keep = list(flds)
+    args = DnNsArgs()
+    args.u, args.v, args.p = (t.data_ptr() for t in flds[:3])
+    if cot is not None:
+        for k in range(3):
+            args.cot[k] = flds[3 + k].data_ptr()
+    nn = geom.nnode_total
+
+    def batched(t, name):
+        if tuple(t.shape[-2:]) != tuple(geom.node_shape) or t.numel() not in (B * nn, nn):
+            raise ValueError(f"ns_apply: {name} shape {tuple(t.shape)} does not match the mesh {shape}")
+        return 1 if (t.numel() == B * nn and B > 1) else 0
+
+    for k, m in enumerate(bc3):
+        if m is None:
+            continue
+        if not isinstance(m, torch.Tensor):
+            raise TypeError(f"ns_apply: bc[{k}] must be a tensor or None")
+        if not m.is_cuda:
+            raise DiffNetHipError(f"ns_apply: bc[{k}] is on {m.device}: the FEM ops run on the GPU only (no CPU fallback)")
+        if m.dtype in (torch.bool, torch.uint8):
+            m = m.contiguous()
+            m = m.view(torch.uint8) if m.dtype == torch.bool else m
+            args.mask_is_u8[k] = 1
+        else:
+            m = _require(m, f"bc[{k}]")
+        args.mask_batched[k] = batched(m, f"bc[{k}]")
+        args.bc_mask[k] = m.data_ptr()
+        keep.append(m)
+    for k, val in enumerate(vals):
+        if isinstance(val, torch.Tensor) and val.numel() > 1:
+            if bc3[k] is None:
+                raise ValueError(f"ns_apply: bc_values[{k}] is a field but field {k} has no Dirichlet mask")
+            val = _require(val, f"bc_values[{k}]")
+            args.bc_field_batched[k] = batched(val, f"bc_values[{k}]")
+            args.bc_field[k] = val.data_ptr()
+            keep.append(val)
+        else:
+            args.bc_value[k] = float(val)
+    G, nel = geom.ngp_total, geom.nelem_total
+    for k, f in enumerate(f2):
+        if isinstance(f, torch.Tensor) and f.numel() > 1:
+            f = _require(f, f"f_gp[{k}]")
+            if tuple(f.shape[-3:]) != (G, *geom.elem_shape) or f.numel() not in (G * nel, B * G * nel):
+                raise ValueError(f"ns_apply: f_gp[{k}] shape {tuple(f.shape)} is not (B | 1, {G}, {geom.elem_shape[0]}, {geom.elem_shape[1]})")
+            args.f_batched[k] = 1 if (f.numel() == B * G * nel and B > 1) else 0
+            args.f_gp[k] = f.data_ptr()
+            keep.append(f)
+        else:
+            args.f_value[k] = float(f)
+    args.visco, args.wscale, args.tau_h[0], args.tau_h[1], args.cinv = consts
+    args.vjp = 1 if cot is not None else 0
+    if (in_num is None) != (in_den is None):
+        raise ValueError("ns_apply: in_num and in_den go together")
+    if in_num is not None and cot is None:
+        raise ValueError("ns_apply: in_num / in_den scale the cotangents of a VJP (cot)")
+    for name, t in (("in_num", in_num), ("in_den", in_den)):
+        if t is not None:
+            t = _require(t, name, 1)
+            if t.numel() != 3:
+                raise ValueError(f"{name} must hold 3 floats")
+            setattr(args, name, t.data_ptr())
+            keep.append(t)
+    mesh = geom.mesh_struct(B)
+    if want_red:
+        key = (mesh.nx, mesh.ny, mesh.ngp, B)
+        nbytes = _NS_WS_BYTES.get(key)
+        if nbytes is None:
+            nbytes = _lib.lib().dn_ns_workspace_bytes(C.byref(mesh))
+            if nbytes < 0:
+                _lib.check(int(nbytes), "dn_ns_workspace_bytes")
+            _NS_WS_BYTES[key] = nbytes
+        ws = _ns_workspace(flds[0].device, nbytes)
+        keep.append(ws)
+        args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    return mesh, args, keep, shape
+
+
+def ns_apply(geom, u, v, p, bc=None, bc_values=(0.0, 0.0, 0.0), visco=1.0, f_gp=None, wscale=1.0, tau_h=None, cinv=36.0, cot=None,
+             want_out=True, want_sums=True, want_norms=False, in_num=None, in_den=None):
+    """One launch of dn_ns_apply (include/diffnet_hip.h): the three assembled Navier-Stokes (VMS) residuals of the fields u, v, p
+    (B,1,ny,nx) and / or the float64 device tensor of their three sums of squares.  `bc`, `bc_values`, `f_gp`, `in_num` / `in_den`,
+    `want_norms` as in stokes_apply; `tau_h`: the (hx, hy) of the stabilisation parameters (default: the mesh spacing); `cinv`: their
+    constant.  `cot` (three fields like u): the VJP launch instead -- the gradient of sum_k <cot_k, R_k> with respect to (u, v, p) at the
+    point (u, v, p), tau held fixed, with cot_k scaled by in_num[k] / in_den[k] where those are given.  Returns (outs | None, sums | None[,
+    norms]).  Calls on the same buffers reuse their prepared argument structs (small LRU, fresh outputs per call: see poisson_apply)."""
+    _ns_check_mesh(geom)
+    bc3, f2, vals = stokes_bc3(bc), stokes_f2(f_gp), tuple(bc_values)
+    if len(vals) != 3:
+        raise ValueError("ns_apply: bc_values must hold three entries")
+    if cot is not None:
+        cot = tuple(cot)
+        if len(cot) != 3:
+            raise ValueError("ns_apply: cot must hold three fields")
+    th = geom.hs[:2] if tau_h is None else tuple(tau_h)
+    consts = (float(visco), float(wscale), float(th[0]), float(th[1]), float(cinv))
+    flds = (u, v, p)
+    want_red = want_sums or want_norms
+    key = None
+    if all(isinstance(t, torch.Tensor) and t.is_cuda for t in flds) and tuple(u.shape[1:]) == (1, *geom.node_shape) and u.shape == v.shape == p.shape:
+        key = _ns_key(geom, flds, cot, bc3, vals, f2, consts, in_num, in_den, (want_out, want_sums, want_norms))
+    ent = None
+    if key is not None:
+        with _WS_LOCK:
+            ent = _NS_CACHE.get(key)
+            if ent is not None:
+                _NS_CACHE.move_to_end(key)
+    if ent is None:
+        _CALL_STATS["miss" if key is not None else "uncached"] += 1
+        mesh, args, keep, shape = _prepare_ns(geom, u, v, p, cot, bc3, vals, f2, consts, in_num, in_den, want_red)
+        with _WS_LOCK:
+            live_ws = list(_NS_WS.values())
+        ent = (mesh, args, C.byref(mesh), C.byref(args), shape, [t for t in keep if any(t is x for x in live_ws)])
+        if key is not None:
+            with _WS_LOCK:
+                _NS_CACHE[key] = ent
+                while len(_NS_CACHE) > _CALL_CACHE_MAX:
+                    _NS_CACHE.popitem(last=False)
+    else:
+        _CALL_STATS["hit"] += 1
+    mesh, args, mref, aref, shape = ent[:5]
+    dev = u.device
+    outs = sums = norms = None
+    if want_out:
+        o3 = torch.empty((3, *shape), dtype=torch.float32, device=dev)      # one allocation, three views
+        outs = list(o3.unbind(0))
+    if want_sums:
+        sums = torch.empty(3, dtype=torch.float64, device=dev)
+    if want_norms:
+        norms = torch.empty(3, dtype=torch.float32, device=dev)
+    with _NS_LAUNCH_LOCK:              # pointer patch + launch of the (possibly shared, cached) argument struct as one step
+        if want_out:
+            p0, step = o3.data_ptr(), 4 * o3[0].numel()
+            args.out[0], args.out[1], args.out[2] = p0, p0 + step, p0 + 2 * step
+        else:
+            args.out[0] = args.out[1] = args.out[2] = None
+        args.sumsq = sums.data_ptr() if want_sums else None
+        args.norms = norms.data_ptr() if want_norms else None
+        rc = _lib.lib().dn_ns_apply(mref, aref, _stream(u))
+    if rc:
+        _lib.check(rc, "dn_ns_apply")
+    return (outs, sums, norms) if want_norms else (outs, sums)
+
 
 def compute_winding_nodes(points, normals, area, q):
     """Drop-in for `compute_winding_nodes` of IBN/poisson-2d/parametric/IBN_2D.py:89-104 (same argument shapes:

@@ -347,6 +347,63 @@ typedef struct dn_stokes_args {
 int64_t dn_stokes_workspace_bytes(const dn_mesh *mesh);
 int dn_stokes_apply(const dn_mesh *mesh, const dn_stokes_args *args, void *stream);
 
+/* ---- fused 2-D Navier-Stokes (VMS) residuals and their VJP --------------------------------------------------------
+ * Replaces the nonlinear residual body of the Navier-Stokes scripts of the reference:
+ * examples/navier-stokes/single_instance/e1_ns_ldc_resmin.py:147-308 (calc_tau, calc_residuals), e2_ns_fps_resmin.py:293
+ * calc_residuals_ns, e2_ns_fps_af_bcmask.py:299, e2_ns_fps_af_pc.py:341, b1_stokes_ns_resmin_base.py, e4_stokes_ns_cases.py:
+ * Dirichlet substitution, the Gauss-point evaluations, the variational-multiscale weak forms, three assemblies, the Dirichlet rows
+ * and the three Frobenius sums, in ONE launch.  Mesh: nsd = 2, degree 1 (the scripts' Laplacian terms vanish), ngp 2..4.
+ *   u~ = where(bc1, u_bc, u), v~ = where(bc2, v_bc, v), p~ = where(bc3, p_bc, p)      (mask: fp32 >= 0.5, u8 != 0)
+ *   at every Gauss point, from u~, v~, p~:  a1 = u u_x + v u_y,  a2 = u v_x + v v_y,  d = u_x + v_y,
+ *     r1 = a1 + p_x - f1,  r2 = a2 + p_y - f2,
+ *     tau_m = 1 / sqrt(Gx u^2 + Gy v^2 + cinv visco^2 (Gx^2 + Gy^2)),  tau_c = sqrt(...) / (gx^2 + gy^2),
+ *     gx = 2 / tau_h[0], gy = 2 / tau_h[1], Gx = gx^2, Gy = gy^2 (float32, as the scripts' calc_tau); tau is DETACHED (no gradient)
+ *   T1_a = N a1 + visco (Nx u_x + Ny u_y) - Nx p - N f1 + tau_m (u Nx + v Ny) r1 - tau_m N (r1 u_x + r2 u_y)
+ *          - tau_m^2 r1 (r1 Nx + r2 Ny) + tau_c Nx d
+ *   T2_a = N a2 + visco (Nx v_x + Ny v_y) - Ny p - N f2 + tau_m (u Nx + v Ny) r2 - tau_m N (r1 v_x + r2 v_y)
+ *          - tau_m^2 r2 (r1 Nx + r2 Ny) + tau_c Ny d
+ *   T3_a = N d + tau_m (Nx r1 + Ny r2)
+ *   R_k = assemble(sum_g wscale w_g T_k),  R_k = where(bc_k, value_k, R_k)   (Dirichlet rows take the VALUE, as in the scripts)
+ * Fields (B,1,ny,nx) fp32.  Masks, value fields and forcing as in dn_stokes_args.  out[k] may be NULL; sumsq (3 doubles) / norms
+ * (3 floats): fixed-order fp64 reduction in the kernel, needs `workspace` (zero-filled once before first use, dn_ns_workspace_bytes;
+ * one per stream, not shared with other operators).  out[k] is bitwise independent of the batch it is computed in; sumsq / norms are
+ * reproducible for a given mesh and batch size, but their fp32 per-lane partial sums follow the launch plan, which depends on B, so
+ * they (and, through in_den, the gradients of the norms) may differ in the last bits between batch sizes -- as in dn_stokes_apply.
+ * vjp != 0: the vector-Jacobian product at the linearisation point (u, v, p) -- with the same masks, values and forcing -- of the
+ * cotangents cot[0..2] of (R1, R2, R3), tau held fixed: out[k] = d/d(field k) sum_j <cot_j, R_j>, zero on field k's Dirichlet nodes
+ * (the cotangent of a Dirichlet row of R_j is dropped).  in_num / in_den (both or neither, VJP only): cot[k] is scaled by
+ * in_num[k] / in_den[k] as it is loaded (0 where in_den[k] <= 0); the VJP of the three norms is this launch on the saved residuals
+ * with in_num = cotangents of the norms, in_den = the norms.
+ * Coefficients of the scripts: visco = 1/Re, wscale = (hx/2)(hy/2), tau_h = (hx, hy) the mesh spacing, cinv = 36.
+ * DN_E_UNSUPPORTED for nsd != 2, degree != 1, ngp outside 2..4; DN_E_BADARG for NULL fields, no output at all, in_num without
+ * in_den, in_num outside the VJP mode, a VJP without its three cotangents, flags outside {0, 1}, tau_h not positive or a bc_field
+ * without its mask; nothing is launched then. */
+typedef struct dn_ns_args {
+    const float *u, *v, *p;
+    const void *bc_mask[3];
+    int32_t mask_is_u8[3];
+    int32_t mask_batched[3];
+    const float *bc_field[3];
+    int32_t bc_field_batched[3];
+    float bc_value[3];
+    const float *f_gp[2];
+    int32_t f_batched[2];
+    float f_value[2];
+    float visco, wscale;
+    float tau_h[2];
+    float cinv;
+    int32_t vjp;
+    const float *cot[3];
+    float *out[3];
+    double *sumsq;
+    float *norms;
+    const float *in_num, *in_den;
+    void *workspace;
+    int64_t workspace_bytes;
+} dn_ns_args;
+int64_t dn_ns_workspace_bytes(const dn_mesh *mesh);
+int dn_ns_apply(const dn_mesh *mesh, const dn_ns_args *args, void *stream);
+
 /* ---- fused output block of the 2-D U-Net generator ----------------------------------------------------------
  * Upsample(x2, nearest) -> ZeroPad2d((1,0,1,0)) -> Conv2d(C -> 1, 4x4, padding 1, bias) -> Sigmoid
  * (DiffNet/networks/unets.py:68-74, `self.final`) without materialising the upsampled tensor.
