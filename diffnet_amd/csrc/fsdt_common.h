@@ -35,7 +35,7 @@ constexpr int FSDT_WS_NBLOCKS_WORD = 4;    // word of the workspace header in wh
 constexpr int FSDT_WS_TICKET_WORD = 5;     // ... and its ticket (0 after any launch that reduced in the kernel)
 
 // Deterministic in-kernel final reduction of three scalars (same protocol as finish_sums in poisson_common.h).  Params: any kernel
-// parameter struct with the members part, counter, sumsq and norms of FsdtParams (FsdtParams, StokesParams in stokes.hip).
+// parameter struct with the members part, counter, sumsq and norms of FsdtParams (FsdtParams, Flow2dParams in flow2d_common.h).
 template <class Params>
 __device__ __forceinline__ void finish_sums3(const Params& p, const float (&sq)[3], int tid, int nthreads, double* red, int* flag) {
     const int nblocks = gridDim.x * gridDim.y * gridDim.z;

@@ -19,50 +19,17 @@
 // row.  A strip recomputes one halo element row under it, so every output node is written once, by its owner lane, with the same additions
 // in any launch plan: no atomics on the data path, results bitwise independent of the plan and of the other samples of the batch.
 // Sums of squares: fixed-order fp64 reduction (finish_sums3).
-#include <algorithm>
-
-#include "fsdt_common.h"
+#include "flow2d_common.h"      // everything the kernel shares with stokes.hip: parameters, lane set-up, row loader, plan, checks, launch switch
 
 namespace dn {
 
-struct NsParams {
+struct NsParams : Flow2dParams {
     float bx[4][2], dx[4][2];              // 1-D Q1 basis / derivative (times 2 / hx) at the Gauss points along x
     float by[4][2], dy[4][2];              // along y
     float wg[16];                          // wscale w_ig w_jg, point jg * ngp + ig
     float visco;
     float Gx, Gy, diff, gg_inv;            // tau: Gx = 4 / hx^2, Gy = 4 / hy^2, diff = cinv visco^2 (Gx^2 + Gy^2), gg_inv = 1 / (gx^2 + gy^2)
-    float fconst[2];                       // constant forcing (where fgp[k] is NULL)
-    const float* fld[3];                   // u, v, p (the linearisation point in the VJP mode)
-    const float* cot[3];                   // VJP: the cotangents of R1..R3
-    const void* mask[3];
-    int mask_kind[3];                      // 0: none, 1: uint8 (!= 0), 2: fp32 (>= 0.5)
-    int mask_batched[3];
-    const float* bcf[3];
-    int bcf_batched[3];
-    float bcv[3];
-    const float* fgp[2];                   // (B | 1, G, nely, nelx)
-    int fgp_batched[2];
-    const float* in_num;                   // optional, VJP: cotangent k is scaled by in_num[k] / in_den[k] (0 where in_den[k] <= 0)
-    const float* in_den;
-    float* out[3];
-    double* part;                          // [3][nblocks] partial sums of squares (finish_sums3)
-    unsigned* counter;
-    double* sumsq;
-    float* norms;
-    int nx, ny, nelx, nely, chunks, rows_per_strip, strips, want_sums;
-};
-
-constexpr int NS_OWNERS = 62;              // owner lanes per wave (lanes 1 .. 62); lanes 0 and 63 are ghosts
-
-// Raw loads of one node row r (clamped into the mesh) and, with the Gauss-point forcing, of the element layer r - 1 under it
-template <int G, bool MASK, bool BCF, bool FGP, bool VJP>
-struct NsRaw {
-    float v[3];
-    float l[VJP ? 3 : 1];
-    float mf[MASK ? 3 : 1];
-    uint8_t mb[MASK ? 3 : 1];
-    float bf[BCF ? 3 : 1];
-    float f[FGP ? 2 : 1][FGP ? G : 1];
+    const float* cot[3];                   // VJP: the cotangents of R1..R3 (fld: the linearisation point)
 };
 
 // A landed node row: substituted values of the lane's node (c) and of its right neighbour (n); VJP: the cotangents likewise
@@ -131,11 +98,8 @@ __device__ __forceinline__ void ns_vjp_flux(const NsParams& p, float u, float ux
 template <int NGP, bool MASK, bool BCF, bool FGP, bool VJP>
 __global__ void __launch_bounds__(256) ns2d_kernel(const NsParams p) {
     constexpr int G = NGP * NGP;
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    const int lane = (int)threadIdx.x & 63;
-    const int wid = (int)blockIdx.x * ((int)blockDim.x >> 6) + wave;
-    const int b = blockIdx.y;
-    const int chunk = wid % p.chunks, strip = wid / p.chunks;
+    int lane, chunk, strip;
+    flow2d_wave(p, lane, chunk, strip);
 
     __shared__ double red[16];
     __shared__ int last_flag;
@@ -143,77 +107,22 @@ __global__ void __launch_bounds__(256) ns2d_kernel(const NsParams p) {
 
     if (strip < p.strips) {
         const int nx = p.nx, ny = p.ny;
-        const int q = chunk * NS_OWNERS + lane - 1;                        // node column of the lane
-        const bool owner = lane >= 1 && lane <= NS_OWNERS && q < nx;
-        const unsigned qc = (unsigned)min(max(q, 0), nx - 1);
-        const int64_t nps = (int64_t)nx * ny;
-        const int nel = p.nelx * p.nely;
-        const bool elem_x = q >= 0 && q < p.nelx;                          // the element to the right of the lane's column exists
-        const unsigned qe = (unsigned)min(max(q, 0), p.nelx - 1);
-
-        const float* fb[3];
-        const float* cb[3];
-        const float* bcf[3];
-        const float* mfp[3];
-        const uint8_t* mbp[3];
-        float* ob[3];
+        constexpr int NX = VJP ? 3 : 0;             // a row of the VJP carries the three cotangents
+        Flow2dLane<NX> L;
+        flow2d_lane(p, chunk, lane, L);
+        const int b = blockIdx.y;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            fb[k] = p.fld[k] + (int64_t)b * nps;
-            cb[k] = VJP ? p.cot[k] + (int64_t)b * nps : fb[k];
-            bcf[k] = p.bcf[k] ? p.bcf[k] + (p.bcf_batched[k] ? (int64_t)b * nps : 0) : fb[k];
-            const int64_t mo = p.mask_batched[k] ? (int64_t)b * nps : 0;
-            mfp[k] = reinterpret_cast<const float*>(p.mask[k]) + (p.mask_kind[k] == 2 ? mo : 0);
-            mbp[k] = reinterpret_cast<const uint8_t*>(p.mask[k]) + (p.mask_kind[k] == 1 ? mo : 0);
-            ob[k] = p.out[k] ? p.out[k] + (int64_t)b * nps : nullptr;
+            flow2d_field_base<G>(p, b, k, L);
+            if constexpr (VJP) L.xb[k] = p.cot[k] + (int64_t)b * ((int64_t)nx * ny);
         }
-        const float* fg[2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) fg[k] = p.fgp[k] ? p.fgp[k] + (p.fgp_batched[k] ? (int64_t)b * G * nel : 0) : nullptr;
 
         float lscale[3] = {1.f, 1.f, 1.f};
-        if (VJP && p.in_num) {        // cotangent of the norms over the norms (the VJP of ||R_k||), torch's convention at ||R_k|| == 0: zero
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const float den = p.in_den[k];
-                lscale[k] = den > 0.f ? p.in_num[k] / den : (den == den ? 0.f : den);
-            }
-        }
+        if constexpr (VJP) flow2d_in_scale(p, lscale);       // in_num / in_den scales the cotangents
 
-        using Raw = NsRaw<G, MASK, BCF, FGP, VJP>;
+        using Raw = Flow2dRaw<G, MASK, BCF, FGP, NX>;
         using Row = NsRow<VJP>;
-        auto issue = [&](int r, Raw& w) {
-            const unsigned rowoff = (unsigned)min(max(r, 0), ny - 1) * (unsigned)nx + qc;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) w.v[k] = ld_at<float>(fb[k], rowoff);
-            if constexpr (VJP) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) w.l[k] = ld_at<float>(cb[k], rowoff);
-            }
-            if constexpr (MASK) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    w.mf[k] = 0.f;
-                    w.mb[k] = 0;
-                    if (p.mask_kind[k] == 2) w.mf[k] = ld_at<float>(mfp[k], rowoff);
-                    else if (p.mask_kind[k] == 1) w.mb[k] = ld_at<uint8_t>(mbp[k], rowoff);
-                }
-            }
-            if constexpr (BCF) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    w.bf[k] = 0.f;
-                    if (p.bcf[k]) w.bf[k] = ld_at<float>(bcf[k], rowoff);
-                }
-            }
-            if constexpr (FGP) {
-                const unsigned eoff = (unsigned)min(max(r - 1, 0), p.nely - 1) * (unsigned)p.nelx + qe;
-#pragma unroll
-                for (int k = 0; k < 2; ++k)
-#pragma unroll
-                    for (int g = 0; g < G; ++g) w.f[k][g] = fg[k] ? ld_at<float>(fg[k], eoff + (unsigned)(g * nel)) : 0.f;
-            }
-        };
+        auto issue = [&](int r, Raw& w) { flow2d_issue(p, L, r, w); };
 
         // Dirichlet substitution of a landed row (the cotangent of a Dirichlet row is zero) and the right neighbours
         auto consume = [&](const Raw& w, Row& R) {
@@ -222,10 +131,10 @@ __global__ void __launch_bounds__(256) ns2d_kernel(const NsParams p) {
             for (int k = 0; k < 3; ++k) {
                 float val = w.v[k];
                 float lv = 0.f;
-                if constexpr (VJP) lv = w.l[k] * lscale[k];
+                if constexpr (VJP) lv = w.x[k] * lscale[k];
                 R.bv[k] = p.bcv[k];
                 if constexpr (MASK) {
-                    const bool fx = p.mask_kind[k] == 2 ? (w.mf[k] >= 0.5f) : (p.mask_kind[k] == 1 ? (w.mb[k] != 0) : false);
+                    const bool fx = flow2d_fixed(p, w, k);
                     if constexpr (BCF) R.bv[k] = p.bcf[k] ? w.bf[k] : R.bv[k];
                     val = fx ? R.bv[k] : val;
                     lv = fx ? 0.f : lv;
@@ -287,7 +196,7 @@ __global__ void __launch_bounds__(256) ns2d_kernel(const NsParams p) {
                     }
                 }
             }
-            const bool ok = elem_x && e >= 0 && e < p.nely;
+            const bool ok = L.elem_x && e >= 0 && e < p.nely;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 float c[4];
@@ -320,7 +229,7 @@ __global__ void __launch_bounds__(256) ns2d_kernel(const NsParams p) {
             element(prev, cur, W, e, bot, top);
             issue(e + 3, W);
             if (e >= j0) {
-                const unsigned rowoff = (unsigned)e * (unsigned)nx + qc;
+                const unsigned rowoff = (unsigned)e * (unsigned)nx + L.qc;
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
                     float r = carry[k] + bot[k];
@@ -329,8 +238,8 @@ __global__ void __launch_bounds__(256) ns2d_kernel(const NsParams p) {
                         const bool fx = (prev.fixed & (1u << k)) != 0u;
                         r = fx ? (VJP ? 0.f : prev.bv[k]) : r;
                     }
-                    sq[k] = owner ? fmaf(r, r, sq[k]) : sq[k];
-                    if (owner && ob[k]) st_at<float>(ob[k], rowoff, r);
+                    sq[k] = L.owner ? fmaf(r, r, sq[k]) : sq[k];
+                    if (L.owner && L.ob[k]) st_at<float>(L.ob[k], rowoff, r);
                 }
             }
 #pragma unroll
@@ -345,90 +254,42 @@ __global__ void __launch_bounds__(256) ns2d_kernel(const NsParams p) {
     if (p.want_sums) finish_sums3(p, sq, (int)threadIdx.x, (int)blockDim.x, red, &last_flag);
 }
 
-static constexpr int64_t NS_WS_HEADER = 64 * (1 + 64);     // top counter + DN_NSHARD shard counters (finish_sums3)
-
-struct NsGeom { int chunks, strips, R, wpb, gx; };
-
-static int ns_validate(const dn_mesh* m) {
-    if (!m) return DN_E_BADARG;
-    if (m->nsd != 2 || m->degree != 1 || m->ngp < 2 || m->ngp > 4) return DN_E_UNSUPPORTED;
-    if (m->batch < 1 || m->batch > 65535 || m->nx < 2 || m->ny < 2) return DN_E_BADARG;
-    const int64_t nps = (int64_t)m->nx * m->ny, nel = (int64_t)(m->nx - 1) * (m->ny - 1);
-    if (nps >= (1ll << 30) || nel * m->ngp * m->ngp >= (1ll << 30)) return DN_E_UNSUPPORTED;     // 32-bit byte offsets within a sample
-    return 0;
-}
-
-// One wave per (62-column chunk, strip of R node rows, sample); strips of at least 8 rows (a strip recomputes one halo element row) until
-// the launch has ~4096 waves (16 per CU).
-static NsGeom ns_plan(const dn_mesh* m) {
-    NsGeom g;
-    g.chunks = (m->nx + NS_OWNERS - 1) / NS_OWNERS;
-    const int64_t per_row = (int64_t)g.chunks * m->batch;
-    int strips = (int)std::min<int64_t>((4096 + per_row - 1) / per_row, (m->ny + 7) / 8);
-    strips = std::max(strips, 1);
-    g.R = (m->ny + strips - 1) / strips;
-    g.strips = (m->ny + g.R - 1) / g.R;
-    const int waves = g.chunks * g.strips;
-    g.wpb = std::min(waves, 4);
-    g.gx = (waves + g.wpb - 1) / g.wpb;
-    return g;
-}
-
 template <int NGP, bool VJP>
-static void ns_launch_k(const NsParams& pp, const NsGeom& g, int batch, bool mask, bool bcf, bool fgp, hipStream_t s) {
-    dim3 grid(g.gx, batch), block(64 * g.wpb);
-    const int sel = (mask ? (bcf ? 2 : 1) : 0);
-    if (fgp) {
-        switch (sel) {
-            case 0: hipLaunchKernelGGL((ns2d_kernel<NGP, false, false, true, VJP>), grid, block, 0, s, pp); return;
-            case 1: hipLaunchKernelGGL((ns2d_kernel<NGP, true, false, true, VJP>), grid, block, 0, s, pp); return;
-            default: hipLaunchKernelGGL((ns2d_kernel<NGP, true, true, true, VJP>), grid, block, 0, s, pp); return;
-        }
+struct NsFamily {
+    template <bool MASK, bool BCF, bool FGP>
+    static void launch(dim3 grid, dim3 block, hipStream_t s, const NsParams& pp) {
+        hipLaunchKernelGGL((ns2d_kernel<NGP, MASK, BCF, FGP, VJP>), grid, block, 0, s, pp);
     }
-    switch (sel) {
-        case 0: hipLaunchKernelGGL((ns2d_kernel<NGP, false, false, false, VJP>), grid, block, 0, s, pp); return;
-        case 1: hipLaunchKernelGGL((ns2d_kernel<NGP, true, false, false, VJP>), grid, block, 0, s, pp); return;
-        default: hipLaunchKernelGGL((ns2d_kernel<NGP, true, true, false, VJP>), grid, block, 0, s, pp); return;
-    }
-}
+};
 
 template <int NGP>
-static void ns_launch_ngp(const NsParams& pp, const NsGeom& g, int batch, bool mask, bool bcf, bool fgp, bool vjp, hipStream_t s) {
-    if (vjp) ns_launch_k<NGP, true>(pp, g, batch, mask, bcf, fgp, s);
-    else ns_launch_k<NGP, false>(pp, g, batch, mask, bcf, fgp, s);
+static void ns_launch_ngp(const NsParams& pp, const Flow2dGeom& g, int batch, bool vjp, hipStream_t s) {
+    if (vjp) flow2d_launch<NsFamily<NGP, true>>(pp, g, batch, s);
+    else flow2d_launch<NsFamily<NGP, false>>(pp, g, batch, s);
 }
+
+constexpr int NS_MIN_ROWS = 8;          // shortest strip (flow2d_plan): a strip recomputes one halo element row
 
 }  // namespace dn
 
 using namespace dn;
 
 extern "C" int64_t dn_ns_workspace_bytes(const dn_mesh* m) {
-    if (ns_validate(m) != 0) return DN_E_BADARG;
-    const NsGeom g = ns_plan(m);
-    return NS_WS_HEADER + (int64_t)(3 * sizeof(double)) * g.gx * m->batch;
+    if (flow2d_validate(m) != 0) return DN_E_BADARG;
+    return flow2d_workspace_bytes(flow2d_plan(m, NS_MIN_ROWS), m->batch);
 }
 
 extern "C" int dn_ns_apply(const dn_mesh* m, const dn_ns_args* a, void* stream) {
-    int rc = ns_validate(m);
+    int rc = flow2d_validate(m);
     if (rc) return rc;
-    if (!a || !a->u || !a->v || !a->p) return DN_E_BADARG;
-    if (!a->out[0] && !a->out[1] && !a->out[2] && !a->sumsq && !a->norms) return DN_E_BADARG;
-    if ((a->in_num != nullptr) != (a->in_den != nullptr)) return DN_E_BADARG;
+    if ((rc = flow2d_check_args(a))) return rc;
     if (a->vjp & ~1) return DN_E_BADARG;
     const bool vjp = a->vjp != 0;
     if (vjp && (!a->cot[0] || !a->cot[1] || !a->cot[2])) return DN_E_BADARG;     // a VJP without its cotangents
     if (!vjp && a->in_num) return DN_E_BADARG;                                    // the scaling applies to the cotangents only
-    for (int k = 0; k < 3; ++k) {
-        if ((a->mask_is_u8[k] | a->mask_batched[k] | a->bc_field_batched[k]) & ~1) return DN_E_BADARG;
-        if (a->bc_field[k] && !a->bc_mask[k]) return DN_E_BADARG;           // a value field without a condition
-    }
-    for (int k = 0; k < 2; ++k)
-        if (a->f_batched[k] & ~1) return DN_E_BADARG;
     if (!(a->tau_h[0] > 0.f) || !(a->tau_h[1] > 0.f)) return DN_E_BADARG;
-    const bool want_red = a->sumsq || a->norms;
-    const NsGeom g = ns_plan(m);
-    const int64_t nwg = (int64_t)g.gx * m->batch;
-    if (want_red && (!a->workspace || a->workspace_bytes < NS_WS_HEADER + (int64_t)(3 * sizeof(double)) * nwg)) return DN_E_WORKSPACE;
+    const Flow2dGeom g = flow2d_plan(m, NS_MIN_ROWS);
+    if ((rc = flow2d_check_workspace(a, g, m->batch))) return rc;
 
     NsParams pp;
     const int ngp = m->ngp;
@@ -455,42 +316,13 @@ extern "C" int dn_ns_apply(const dn_mesh* m, const dn_ns_args* a, void* stream) 
     pp.Gy = Gy;
     pp.diff = (float)((double)a->cinv * (double)visco * (double)visco) * (Gx * Gx + Gy * Gy);
     pp.gg_inv = 1.f / (gx * gx + gy * gy);
-    pp.fld[0] = a->u; pp.fld[1] = a->v; pp.fld[2] = a->p;
-    bool any_mask = false, any_bcf = false;
-    for (int k = 0; k < 3; ++k) {
-        pp.cot[k] = vjp ? a->cot[k] : nullptr;
-        pp.mask[k] = a->bc_mask[k];
-        pp.mask_kind[k] = !a->bc_mask[k] ? 0 : (a->mask_is_u8[k] ? 1 : 2);
-        pp.mask_batched[k] = a->mask_batched[k];
-        any_mask = any_mask || a->bc_mask[k];
-        pp.bcf[k] = a->bc_field[k];
-        pp.bcf_batched[k] = a->bc_field_batched[k];
-        pp.bcv[k] = a->bc_value[k];
-        any_bcf = any_bcf || pp.bcf[k];
-        pp.out[k] = a->out[k];
-    }
-    bool any_fgp = false;
-    for (int k = 0; k < 2; ++k) {
-        pp.fgp[k] = a->f_gp[k];
-        pp.fgp_batched[k] = a->f_batched[k];
-        pp.fconst[k] = a->f_gp[k] ? 0.f : a->f_value[k];
-        any_fgp = any_fgp || pp.fgp[k];
-    }
-    pp.in_num = a->in_num;
-    pp.in_den = a->in_den;
-    pp.counter = reinterpret_cast<unsigned*>(a->workspace);
-    pp.part = a->workspace ? reinterpret_cast<double*>(reinterpret_cast<char*>(a->workspace) + NS_WS_HEADER) : nullptr;
-    pp.sumsq = a->sumsq;
-    pp.norms = a->norms;
-    pp.nx = m->nx; pp.ny = m->ny;
-    pp.nelx = m->nx - 1; pp.nely = m->ny - 1;
-    pp.chunks = g.chunks; pp.rows_per_strip = g.R; pp.strips = g.strips;
-    pp.want_sums = want_red ? 1 : 0;
+    flow2d_fill(pp, m, a, g);
+    for (int k = 0; k < 3; ++k) pp.cot[k] = vjp ? a->cot[k] : nullptr;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     switch (ngp) {
-        case 2: ns_launch_ngp<2>(pp, g, m->batch, any_mask, any_bcf, any_fgp, vjp, s); break;
-        case 3: ns_launch_ngp<3>(pp, g, m->batch, any_mask, any_bcf, any_fgp, vjp, s); break;
-        default: ns_launch_ngp<4>(pp, g, m->batch, any_mask, any_bcf, any_fgp, vjp, s); break;
+        case 2: ns_launch_ngp<2>(pp, g, m->batch, vjp, s); break;
+        case 3: ns_launch_ngp<3>(pp, g, m->batch, vjp, s); break;
+        default: ns_launch_ngp<4>(pp, g, m->batch, vjp, s); break;
     }
     DN_LAUNCH_CHECK();
     return 0;

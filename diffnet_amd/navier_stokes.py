@@ -26,6 +26,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import ops
+from .stokes import _fix, _forcing, _ones3, _vals, _weak_form
 
 
 def _coef(fem, wscale, tau_h, visco, cinv):
@@ -34,13 +35,6 @@ def _coef(fem, wscale, tau_h, visco, cinv):
     if len(th) != 2:
         raise ValueError("tau_h must hold two entries (hx, hy)")
     return dict(visco=float(visco), wscale=ws, tau_h=th, cinv=float(cinv))
-
-
-def _vals(bc_values):
-    vals = tuple(bc_values)
-    if len(vals) != 3:
-        raise ValueError("bc_values must hold three entries (u, v, p)")
-    return vals
 
 
 class _NsResiduals(torch.autograd.Function):
@@ -102,9 +96,6 @@ def ns_total_loss(fem, u, v, p, bc, bc_values=(0.0, 0.0, 0.0), visco=1.0, f_gp=N
     return _NsNorms.apply(u, v, p, fem, bc, _vals(bc_values), f_gp, _coef(fem, wscale, tau_h, visco, cinv), True)
 
 
-_ONES = {}
-
-
 def ns_loss_and_grad(fem, u, v, p, bc, bc_values=(0.0, 0.0, 0.0), visco=1.0, f_gp=None, wscale=None, tau_h=None, cinv=36.0, weights=None):
     """(norms, grads): the three residual norms as one (3,) tensor and the gradient of sum_k weights[k] * ||R_k|| (weights: a (3,) float32
     device tensor, default ones) with respect to (u, v, p) -- what `ns_total_loss(...).backward()` leaves in the fields' .grad -- from two
@@ -113,20 +104,9 @@ def ns_loss_and_grad(fem, u, v, p, bc, bc_values=(0.0, 0.0, 0.0), visco=1.0, f_g
     with torch.no_grad():
         Rs, _, norms = ops.ns_apply(fem.geom, u, v, p, bc, vals, f_gp=f_gp, want_sums=False, want_norms=True, **coef)
         if weights is None:
-            key = (u.device.type, u.device.index)
-            weights = _ONES.get(key)
-            if weights is None:
-                weights = _ONES[key] = torch.ones(3, dtype=torch.float32, device=u.device)
+            weights = _ones3(u.device)
         grads, _ = ops.ns_apply(fem.geom, u, v, p, bc, vals, f_gp=f_gp, cot=Rs, want_sums=False, in_num=weights, in_den=norms, **coef)
     return norms, grads
-
-
-def _condition(m):
-    if m.dtype == torch.bool:
-        return m
-    if m.dtype == torch.uint8:
-        return m != 0
-    return m >= 0.5
 
 
 def ns_residuals_composed(fem, u, v, p, bc, bc_values=(0.0, 0.0, 0.0), visco=1.0, f_gp=None, wscale=None, tau_h=None, cinv=36.0):
@@ -135,27 +115,11 @@ def ns_residuals_composed(fem, u, v, p, bc, bc_values=(0.0, 0.0, 0.0), visco=1.0
     c = _coef(fem, wscale, tau_h, visco, cinv)
     visco, wscale, (hx, hy), cinv = c["visco"], c["wscale"], c["tau_h"], c["cinv"]
     bc3, vals, f2 = ops.stokes_bc3(bc), _vals(bc_values), ops.stokes_f2(f_gp)
-
-    def fix(t, m, val):
-        if m is None:
-            return t
-        return torch.where(_condition(m), val if isinstance(val, torch.Tensor) else torch.full_like(t, float(val)), t)
-
-    u, v, p = (fix(t, m, val) for t, m, val in zip((u, v, p), bc3, vals))
+    u, v, p = (_fix(t, m, val) for t, m, val in zip((u, v, p), bc3, vals))
     ev, dx, dy = fem.gauss_pt_evaluation, fem.gauss_pt_evaluation_der_x, fem.gauss_pt_evaluation_der_y
     ug, vg, pg = ev(u), ev(v), ev(p)
     ux, uy, vx, vy, px, py = dx(u), dy(u), dx(v), dy(v), dx(p), dy(p)
-    dev = u.device
-    N, Nx, Ny = (t.to(dev) for t in (fem.Nvalues, fem.dN_x_values, fem.dN_y_values))       # (1, nbf, ngp, 1, 1)
-    jxw = (fem.gpw.to(dev) * wscale).reshape(1, 1, -1, 1, 1)
-    G, eshape = fem.geom.ngp_total, fem.geom.elem_shape
-
-    def forcing(f):
-        if isinstance(f, torch.Tensor) and f.numel() > 1:
-            return f.to(dev).reshape(-1, G, *eshape)
-        return torch.full_like(pg, float(f))
-
-    f1, f2 = forcing(f2[0]).expand_as(pg), forcing(f2[1]).expand_as(pg)
+    f1, f2 = _forcing(f2[0], pg, fem.geom).expand_as(pg), _forcing(f2[1], pg, fem.geom).expand_as(pg)
     a1, a2, d = ug * ux + vg * uy, ug * vx + vg * vy, ux + vy
     r1, r2 = a1 + px - f1, a2 + py - f2
     # calc_tau of the scripts (float32 g and G), on detached values
@@ -165,16 +129,11 @@ def ns_residuals_composed(fem, u, v, p, bc, bc_values=(0.0, 0.0, 0.0), visco=1.0
     temp = torch.sqrt(Gx * ug.detach() ** 2 + Gy * vg.detach() ** 2 + diff)
     tm, tc = 1.0 / temp, temp * float(np.float32(1.0) / (gx * gx + gy * gy))
     tm2 = tm * tm
-
-    def weak(a_x, a_y, a_0):
-        """sum_g JxW ( dN_x a_x + dN_y a_y + N a_0 ), per local basis function -> (B, nbf, nelY, nelX)"""
-        t = Nx * a_x.unsqueeze(1) + Ny * a_y.unsqueeze(1) + N * a_0.unsqueeze(1)
-        return torch.sum(t * jxw, 2)
-
+    weak = _weak_form(fem, u.device, wscale)
     # the test-function coefficients of T1..T3 (N, Nx, Ny terms of the scripts' temp1..temp3)
     R1 = fem.assemble(weak(visco * ux - pg + tm * ug * r1 - tm2 * r1 * r1 + tc * d, visco * uy + tm * vg * r1 - tm2 * r1 * r2,
                            a1 - f1 - tm * (r1 * ux + r2 * uy)))
     R2 = fem.assemble(weak(visco * vx + tm * ug * r2 - tm2 * r2 * r1, visco * vy - pg + tm * vg * r2 - tm2 * r2 * r2 + tc * d,
                            a2 - f2 - tm * (r1 * vx + r2 * vy)))
     R3 = fem.assemble(weak(tm * r1, tm * r2, d))
-    return tuple(fix(R, m, val) for R, m, val in zip((R1, R2, R3), bc3, vals))
+    return tuple(_fix(R, m, val) for R, m, val in zip((R1, R2, R3), bc3, vals))

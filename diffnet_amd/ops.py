@@ -598,13 +598,13 @@ def call_cache_clear():
     with _WS_LOCK:
         _CALL_CACHE.clear()
         _FSDT_CACHE.clear()
-        _STOKES_CACHE.clear()
-        _NS_CACHE.clear()
+        _STOKES.cache.clear()
+        _NS.cache.clear()
         _PACK_CACHE.clear()
     _POISSON_WS_BYTES.clear()
     _FSDT_WS_BYTES.clear()
-    _STOKES_WS_BYTES.clear()
-    _NS_WS_BYTES.clear()
+    _STOKES.ws_bytes.clear()
+    _NS.ws_bytes.clear()
 
 
 class PoissonPlan:
@@ -1348,22 +1348,39 @@ class FsdtPlan:
 
 
 
-# ---- fused 2-D Stokes (PSPG) residuals: dn_stokes_apply -------------------------------------------------------------------------
-# The launch has a reduction workspace of its OWN per (device, stream), never the one of _workspace or _fsdt_workspace: an FSDT launch with
-# defer_norms leaves its partials in its workspace for a later consumer, and a Stokes launch issued in between must not overwrite them.
-_STOKES_WS = {}
-_STOKES_WS_BYTES = {}
-_STOKES_CACHE = __import__("collections").OrderedDict()
-_STOKES_LAUNCH_LOCK = _threading.Lock()
+# ---- the two three-field 2-D flow operators: dn_stokes_apply (PSPG) and dn_ns_apply (VMS residuals and their VJP) ------------------
+# Each operator has a reduction workspace of its OWN per (device, stream), never the one of _workspace or _fsdt_workspace nor the other
+# operator's: an FSDT launch with defer_norms leaves its partials in its workspace for a later consumer, and a launch issued in between
+# must not overwrite them.  _Flow2dOp holds an operator's workspaces, their sizes, its prepared-call cache and its launch lock.
+class _Flow2dOp:
+    def __init__(self, name, args_type):
+        self.name, self.args_type = name, args_type          # name: "stokes_apply" / "ns_apply", the prefix of its messages
+        self.fn, self.ws_fn = "dn_" + name, "dn_" + name.replace("_apply", "_workspace_bytes")      # the C entry points
+        self.ws = {}
+        self.ws_bytes = {}
+        self.cache = __import__("collections").OrderedDict()
+        self.launch_lock = _threading.Lock()
 
 
-def _stokes_workspace(dev, nbytes):
+_STOKES = _Flow2dOp("stokes_apply", DnStokesArgs)
+_NS = _Flow2dOp("ns_apply", DnNsArgs)
+
+
+def _flow2d_workspace(op, mesh, B, dev):
+    """The operator's reduction workspace on the current stream of `dev`, large enough for `mesh`."""
+    key = (mesh.nx, mesh.ny, mesh.ngp, B)
+    nbytes = op.ws_bytes.get(key)
+    if nbytes is None:
+        nbytes = getattr(_lib.lib(), op.ws_fn)(C.byref(mesh))
+        if nbytes < 0:
+            _lib.check(int(nbytes), op.ws_fn)
+        op.ws_bytes[key] = nbytes
     key = (dev.index, _raw_stream(dev))
     with _WS_LOCK:
-        ws = _STOKES_WS.get(key)
+        ws = op.ws.get(key)
         if ws is None or ws.numel() < nbytes:
             ws = torch.zeros(max(nbytes, 1 << 16), dtype=torch.uint8, device=dev)   # ABI: zero-filled once
-            _STOKES_WS[key] = ws
+            op.ws[key] = ws
     return ws
 
 
@@ -1387,13 +1404,17 @@ def stokes_f2(f_gp):
     return tuple(0.0 if f is None else f for f in f_gp)
 
 
-def _stokes_check_mesh(geom):
+def _flow2d_check_mesh(op, geom):
     if geom.nsd != 2 or geom.deg != 1 or not 2 <= geom.ngp_1d <= 4:
-        raise DiffNetHipError(f"stokes_apply: 2-D Q1 meshes with 2..4 Gauss points per axis only (nsd {geom.nsd}, degree {geom.deg}, ngp {geom.ngp_1d})")
+        raise DiffNetHipError(f"{op.name}: 2-D Q1 meshes with 2..4 Gauss points per axis only (nsd {geom.nsd}, degree {geom.deg}, ngp {geom.ngp_1d})")
 
 
-def _stokes_key(geom, flds, bc3, vals, f2, consts, in_num, in_den, flags):
-    """Key of a cached prepared dn_stokes_apply call (see _call_key); None when an argument needs a conversion copy."""
+def _flow2d_key(geom, flds, bc3, vals, f2, consts, in_num, in_den, flags, cot=()):
+    """Key of a cached prepared call (see _call_key) from the arguments the two operators share and the operator's own fields `cot`
+    (each a tensor or None); None when an argument needs a conversion copy."""
+    u, v, p = flds
+    if not (all(isinstance(t, torch.Tensor) and t.is_cuda for t in flds) and tuple(u.shape[1:]) == (1, *geom.node_shape) and u.shape == v.shape == p.shape):
+        return None
     parts = [geom.key, flds[0].device.index, _raw_stream(flds[0].device), consts, flags]
     for t in flds:
         k = _tkey(t)
@@ -1418,35 +1439,43 @@ def _stokes_key(geom, flds, bc3, vals, f2, consts, in_num, in_den, flags):
         if k is None or (k != 0 and (k[1] != torch.float32 or k[2] != (3,))):
             return None
         parts.append(k)
+    for t in cot:
+        k = _tkey(t)
+        if k is None or (k != 0 and k[1] != torch.float32):
+            return None
+        parts.append(k)
     return tuple(parts)
 
 
-def _prepare_stokes(geom, u, v, p, bc3, vals, f2, consts, in_num, in_den, want_red):
-    """Validation + argument struct of a dn_stokes_apply call, outputs left unset: (mesh, args, tensors to keep alive, field shape)."""
-    _stokes_check_mesh(geom)
-    flds = [_require(t, n, 4) for t, n in ((u, "u"), (v, "v"), (p, "p"))]
+def _prepare_flow2d(op, geom, flds, bc3, vals, f2, in_num, in_den, want_red):
+    """Validation + the members dn_stokes_args and dn_ns_args have in common (fields, masks, values, forcing, in_num / in_den, workspace),
+    outputs left unset: (mesh, args, tensors to keep alive, field shape).  `flds`: (name, tensor) pairs, u, v, p first; any further ones
+    are checked like them and head the keep list in the same order, for the caller to place."""
+    name = op.name
+    _flow2d_check_mesh(op, geom)
+    flds = [_require(t, n, 4) for n, t in flds]
     B = flds[0].shape[0]
     shape = (B, 1, *geom.node_shape)
     for t in flds:
         if tuple(t.shape) != shape:
-            raise ValueError(f"stokes_apply: field shape {tuple(t.shape)} != {shape}")
+            raise ValueError(f"{name}: field shape {tuple(t.shape)} != {shape}")
     keep = list(flds)
-    args = DnStokesArgs()
-    args.u, args.v, args.p = (t.data_ptr() for t in flds)
+    args = op.args_type()
+    args.u, args.v, args.p = (t.data_ptr() for t in flds[:3])
     nn = geom.nnode_total
 
-    def batched(t, name):
+    def batched(t, what):
         if tuple(t.shape[-2:]) != tuple(geom.node_shape) or t.numel() not in (B * nn, nn):
-            raise ValueError(f"stokes_apply: {name} shape {tuple(t.shape)} does not match the mesh {shape}")
+            raise ValueError(f"{name}: {what} shape {tuple(t.shape)} does not match the mesh {shape}")
         return 1 if (t.numel() == B * nn and B > 1) else 0
 
     for k, m in enumerate(bc3):
         if m is None:
             continue
         if not isinstance(m, torch.Tensor):
-            raise TypeError(f"stokes_apply: bc[{k}] must be a tensor or None")
+            raise TypeError(f"{name}: bc[{k}] must be a tensor or None")
         if not m.is_cuda:
-            raise DiffNetHipError(f"stokes_apply: bc[{k}] is on {m.device}: the FEM ops run on the GPU only (no CPU fallback)")
+            raise DiffNetHipError(f"{name}: bc[{k}] is on {m.device}: the FEM ops run on the GPU only (no CPU fallback)")
         if m.dtype in (torch.bool, torch.uint8):
             m = m.contiguous()
             m = m.view(torch.uint8) if m.dtype == torch.bool else m
@@ -1459,7 +1488,7 @@ def _prepare_stokes(geom, u, v, p, bc3, vals, f2, consts, in_num, in_den, want_r
     for k, val in enumerate(vals):
         if isinstance(val, torch.Tensor) and val.numel() > 1:
             if bc3[k] is None:
-                raise ValueError(f"stokes_apply: bc_values[{k}] is a field but field {k} has no Dirichlet mask")
+                raise ValueError(f"{name}: bc_values[{k}] is a field but field {k} has no Dirichlet mask")
             val = _require(val, f"bc_values[{k}]")
             args.bc_field_batched[k] = batched(val, f"bc_values[{k}]")
             args.bc_field[k] = val.data_ptr()
@@ -1471,36 +1500,82 @@ def _prepare_stokes(geom, u, v, p, bc3, vals, f2, consts, in_num, in_den, want_r
         if isinstance(f, torch.Tensor) and f.numel() > 1:
             f = _require(f, f"f_gp[{k}]")
             if tuple(f.shape[-3:]) != (G, *geom.elem_shape) or f.numel() not in (G * nel, B * G * nel):
-                raise ValueError(f"stokes_apply: f_gp[{k}] shape {tuple(f.shape)} is not (B | 1, {G}, {geom.elem_shape[0]}, {geom.elem_shape[1]})")
+                raise ValueError(f"{name}: f_gp[{k}] shape {tuple(f.shape)} is not (B | 1, {G}, {geom.elem_shape[0]}, {geom.elem_shape[1]})")
             args.f_batched[k] = 1 if (f.numel() == B * G * nel and B > 1) else 0
             args.f_gp[k] = f.data_ptr()
             keep.append(f)
         else:
             args.f_value[k] = float(f)
-    args.visco, args.pspg, args.wscale, transpose = consts
-    args.transpose = 1 if transpose else 0
     if (in_num is None) != (in_den is None):
-        raise ValueError("stokes_apply: in_num and in_den go together")
-    for name, t in (("in_num", in_num), ("in_den", in_den)):
+        raise ValueError(f"{name}: in_num and in_den go together")
+    for what, t in (("in_num", in_num), ("in_den", in_den)):
         if t is not None:
-            t = _require(t, name, 1)
+            t = _require(t, what, 1)
             if t.numel() != 3:
-                raise ValueError(f"{name} must hold 3 floats")
-            setattr(args, name, t.data_ptr())
+                raise ValueError(f"{what} must hold 3 floats")
+            setattr(args, what, t.data_ptr())
             keep.append(t)
     mesh = geom.mesh_struct(B)
     if want_red:
-        key = (mesh.nx, mesh.ny, mesh.ngp, B)
-        nbytes = _STOKES_WS_BYTES.get(key)
-        if nbytes is None:
-            nbytes = _lib.lib().dn_stokes_workspace_bytes(C.byref(mesh))
-            if nbytes < 0:
-                _lib.check(int(nbytes), "dn_stokes_workspace_bytes")
-            _STOKES_WS_BYTES[key] = nbytes
-        ws = _stokes_workspace(flds[0].device, nbytes)
+        ws = _flow2d_workspace(op, mesh, B, flds[0].device)
         keep.append(ws)
         args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
     return mesh, args, keep, shape
+
+
+def _flow2d_call(op, key, prepare, u, want_out, want_sums, want_norms):
+    """Look up the prepared call `key` (None: not cacheable) or prepare() it, allocate fresh outputs, patch their three pointers into the
+    (possibly shared, cached) argument struct and launch.  Returns (outs | None, sums | None[, norms])."""
+    ent = None
+    if key is not None:
+        with _WS_LOCK:
+            ent = op.cache.get(key)
+            if ent is not None:
+                op.cache.move_to_end(key)
+    if ent is None:
+        _CALL_STATS["miss" if key is not None else "uncached"] += 1
+        mesh, args, keep, shape = prepare()
+        with _WS_LOCK:
+            live_ws = list(op.ws.values())
+        ent = (mesh, args, C.byref(mesh), C.byref(args), shape, [t for t in keep if any(t is x for x in live_ws)])
+        if key is not None:
+            with _WS_LOCK:
+                op.cache[key] = ent
+                while len(op.cache) > _CALL_CACHE_MAX:
+                    op.cache.popitem(last=False)
+    else:
+        _CALL_STATS["hit"] += 1
+    mesh, args, mref, aref, shape = ent[:5]
+    dev = u.device
+    outs = sums = norms = None
+    if want_out:
+        o3 = torch.empty((3, *shape), dtype=torch.float32, device=dev)      # one allocation, three views
+        outs = list(o3.unbind(0))
+    if want_sums:
+        sums = torch.empty(3, dtype=torch.float64, device=dev)
+    if want_norms:
+        norms = torch.empty(3, dtype=torch.float32, device=dev)
+    with op.launch_lock:               # pointer patch + launch of the (possibly shared, cached) argument struct as one step
+        if want_out:
+            p0, step = o3.data_ptr(), 4 * o3[0].numel()
+            args.out[0], args.out[1], args.out[2] = p0, p0 + step, p0 + 2 * step
+        else:
+            args.out[0] = args.out[1] = args.out[2] = None
+        args.sumsq = sums.data_ptr() if want_sums else None
+        args.norms = norms.data_ptr() if want_norms else None
+        rc = getattr(_lib.lib(), op.fn)(mref, aref, _stream(u))
+    if rc:
+        _lib.check(rc, op.fn)
+    return (outs, sums, norms) if want_norms else (outs, sums)
+
+
+def _prepare_stokes(geom, u, v, p, bc3, vals, f2, consts, in_num, in_den, want_red):
+    """Validation + argument struct of a dn_stokes_apply call, outputs left unset: (mesh, args, tensors to keep alive, field shape)."""
+    ent = _prepare_flow2d(_STOKES, geom, (("u", u), ("v", v), ("p", p)), bc3, vals, f2, in_num, in_den, want_red)
+    args = ent[1]
+    args.visco, args.pspg, args.wscale, transpose = consts
+    args.transpose = 1 if transpose else 0
+    return ent
 
 
 def stokes_apply(geom, u, v, p, bc=None, bc_values=(0.0, 0.0, 0.0), visco=1.0, pspg=0.0, f_gp=None, wscale=1.0, want_out=True,
@@ -1513,181 +1588,32 @@ def stokes_apply(geom, u, v, p, bc=None, bc_values=(0.0, 0.0, 0.0), visco=1.0, p
     result, the float32 tensor of the three Frobenius norms written by the same launch; `transpose`: the adjoint J_R^T = S J_R S (forcing and
     Dirichlet values ignored).  Returns (outs | None, sums | None[, norms]).  Calls on the same buffers reuse their prepared argument structs
     (small LRU, fresh outputs per call: see poisson_apply)."""
-    _stokes_check_mesh(geom)
+    _flow2d_check_mesh(_STOKES, geom)
     bc3, f2, vals = stokes_bc3(bc), stokes_f2(f_gp), tuple(bc_values)
     if len(vals) != 3:
         raise ValueError("stokes_apply: bc_values must hold three entries")
     consts = (float(visco), float(pspg), float(wscale), bool(transpose))
-    flds = (u, v, p)
     want_red = want_sums or want_norms
-    key = None
-    if all(isinstance(t, torch.Tensor) and t.is_cuda for t in flds) and tuple(u.shape[1:]) == (1, *geom.node_shape) and u.shape == v.shape == p.shape:
-        key = _stokes_key(geom, flds, bc3, vals, f2, consts, in_num, in_den, (want_out, want_sums, want_norms))
-    ent = None
-    if key is not None:
-        with _WS_LOCK:
-            ent = _STOKES_CACHE.get(key)
-            if ent is not None:
-                _STOKES_CACHE.move_to_end(key)
-    if ent is None:
-        _CALL_STATS["miss" if key is not None else "uncached"] += 1
-        mesh, args, keep, shape = _prepare_stokes(geom, u, v, p, bc3, vals, f2, consts, in_num, in_den, want_red)
-        with _WS_LOCK:
-            live_ws = list(_STOKES_WS.values())
-        ent = (mesh, args, C.byref(mesh), C.byref(args), shape, [t for t in keep if any(t is x for x in live_ws)])
-        if key is not None:
-            with _WS_LOCK:
-                _STOKES_CACHE[key] = ent
-                while len(_STOKES_CACHE) > _CALL_CACHE_MAX:
-                    _STOKES_CACHE.popitem(last=False)
-    else:
-        _CALL_STATS["hit"] += 1
-    mesh, args, mref, aref, shape = ent[:5]
-    dev = u.device
-    outs = sums = norms = None
-    if want_out:
-        o3 = torch.empty((3, *shape), dtype=torch.float32, device=dev)      # one allocation, three views
-        outs = list(o3.unbind(0))
-    if want_sums:
-        sums = torch.empty(3, dtype=torch.float64, device=dev)
-    if want_norms:
-        norms = torch.empty(3, dtype=torch.float32, device=dev)
-    with _STOKES_LAUNCH_LOCK:          # pointer patch + launch of the (possibly shared, cached) argument struct as one step
-        if want_out:
-            p0, step = o3.data_ptr(), 4 * o3[0].numel()
-            args.out[0], args.out[1], args.out[2] = p0, p0 + step, p0 + 2 * step
-        args.sumsq = sums.data_ptr() if want_sums else None
-        args.norms = norms.data_ptr() if want_norms else None
-        rc = _lib.lib().dn_stokes_apply(mref, aref, _stream(u))
-    if rc:
-        _lib.check(rc, "dn_stokes_apply")
-    return (outs, sums, norms) if want_norms else (outs, sums)
-
-# ---- fused 2-D Navier-Stokes (VMS) residuals and their VJP: dn_ns_apply ------------------------------------------------------------
-# A reduction workspace of its OWN per (device, stream), for the reason given at _STOKES_WS.
-_NS_WS = {}
-_NS_WS_BYTES = {}
-_NS_CACHE = __import__("collections").OrderedDict()
-_NS_LAUNCH_LOCK = _threading.Lock()
-
-
-def _ns_workspace(dev, nbytes):
-    key = (dev.index, _raw_stream(dev))
-    with _WS_LOCK:
-        ws = _NS_WS.get(key)
-        if ws is None or ws.numel() < nbytes:
-            ws = torch.zeros(max(nbytes, 1 << 16), dtype=torch.uint8, device=dev)   # ABI: zero-filled once
-            _NS_WS[key] = ws
-    return ws
-
-
-def _ns_check_mesh(geom):
-    if geom.nsd != 2 or geom.deg != 1 or not 2 <= geom.ngp_1d <= 4:
-        raise DiffNetHipError(f"ns_apply: 2-D Q1 meshes with 2..4 Gauss points per axis only (nsd {geom.nsd}, degree {geom.deg}, ngp {geom.ngp_1d})")
-
-
-def _ns_key(geom, flds, cot, bc3, vals, f2, consts, in_num, in_den, flags):
-    """Key of a cached prepared dn_ns_apply call: the Stokes key of the shared arguments and the cotangents; None when an argument needs a
-    conversion copy."""
-    base = _stokes_key(geom, flds, bc3, vals, f2, consts, in_num, in_den, flags)
-    if base is None:
-        return None
-    parts = [base]
-    for t in (cot if cot is not None else (None, None, None)):
-        k = _tkey(t)
-        if k is None or (k != 0 and k[1] != torch.float32):
-            return None
-        parts.append(k)
-    return tuple(parts)
+    key = _flow2d_key(geom, (u, v, p), bc3, vals, f2, consts, in_num, in_den, (want_out, want_sums, want_norms))
+    return _flow2d_call(_STOKES, key, lambda: _prepare_stokes(geom, u, v, p, bc3, vals, f2, consts, in_num, in_den, want_red),
+                        u, want_out, want_sums, want_norms)
 
 
 def _prepare_ns(geom, u, v, p, cot, bc3, vals, f2, consts, in_num, in_den, want_red):
     """Validation + argument struct of a dn_ns_apply call, outputs left unset: (mesh, args, tensors to keep alive, field shape)."""
-    _ns_check_mesh(geom)
-    flds = [_require(t, n, 4) for t, n in ((u, "u"), (v, "v"), (p, "p"))]
+    flds = [("u", u), ("v", v), ("p", p)]
     if cot is not None:
-        flds += [_require(t, f"cot[{k}]", 4) for k, t in enumerate(cot)]
-    B = flds[0].shape[0]
-    shape = (B, 1, *geom.node_shape)
-    for t in flds:
-        if tuple(t.shape) != shape:
-            raise ValueError(f"ns_apply: field shape {tuple(t.shape)} != {shape}")
-    keep = list(flds)
-    args = DnNsArgs()
-    args.u, args.v, args.p = (t.data_ptr() for t in flds[:3])
-    if cot is not None:
-        for k in range(3):
-            args.cot[k] = flds[3 + k].data_ptr()
-    nn = geom.nnode_total
-
-    def batched(t, name):
-        if tuple(t.shape[-2:]) != tuple(geom.node_shape) or t.numel() not in (B * nn, nn):
-            raise ValueError(f"ns_apply: {name} shape {tuple(t.shape)} does not match the mesh {shape}")
-        return 1 if (t.numel() == B * nn and B > 1) else 0
-
-    for k, m in enumerate(bc3):
-        if m is None:
-            continue
-        if not isinstance(m, torch.Tensor):
-            raise TypeError(f"ns_apply: bc[{k}] must be a tensor or None")
-        if not m.is_cuda:
-            raise DiffNetHipError(f"ns_apply: bc[{k}] is on {m.device}: the FEM ops run on the GPU only (no CPU fallback)")
-        if m.dtype in (torch.bool, torch.uint8):
-            m = m.contiguous()
-            m = m.view(torch.uint8) if m.dtype == torch.bool else m
-            args.mask_is_u8[k] = 1
-        else:
-            m = _require(m, f"bc[{k}]")
-        args.mask_batched[k] = batched(m, f"bc[{k}]")
-        args.bc_mask[k] = m.data_ptr()
-        keep.append(m)
-    for k, val in enumerate(vals):
-        if isinstance(val, torch.Tensor) and val.numel() > 1:
-            if bc3[k] is None:
-                raise ValueError(f"ns_apply: bc_values[{k}] is a field but field {k} has no Dirichlet mask")
-            val = _require(val, f"bc_values[{k}]")
-            args.bc_field_batched[k] = batched(val, f"bc_values[{k}]")
-            args.bc_field[k] = val.data_ptr()
-            keep.append(val)
-        else:
-            args.bc_value[k] = float(val)
-    G, nel = geom.ngp_total, geom.nelem_total
-    for k, f in enumerate(f2):
-        if isinstance(f, torch.Tensor) and f.numel() > 1:
-            f = _require(f, f"f_gp[{k}]")
-            if tuple(f.shape[-3:]) != (G, *geom.elem_shape) or f.numel() not in (G * nel, B * G * nel):
-                raise ValueError(f"ns_apply: f_gp[{k}] shape {tuple(f.shape)} is not (B | 1, {G}, {geom.elem_shape[0]}, {geom.elem_shape[1]})")
-            args.f_batched[k] = 1 if (f.numel() == B * G * nel and B > 1) else 0
-            args.f_gp[k] = f.data_ptr()
-            keep.append(f)
-        else:
-            args.f_value[k] = float(f)
-    args.visco, args.wscale, args.tau_h[0], args.tau_h[1], args.cinv = consts
-    args.vjp = 1 if cot is not None else 0
-    if (in_num is None) != (in_den is None):
-        raise ValueError("ns_apply: in_num and in_den go together")
+        flds += [(f"cot[{k}]", t) for k, t in enumerate(cot)]
+    ent = _prepare_flow2d(_NS, geom, flds, bc3, vals, f2, in_num, in_den, want_red)
     if in_num is not None and cot is None:
         raise ValueError("ns_apply: in_num / in_den scale the cotangents of a VJP (cot)")
-    for name, t in (("in_num", in_num), ("in_den", in_den)):
-        if t is not None:
-            t = _require(t, name, 1)
-            if t.numel() != 3:
-                raise ValueError(f"{name} must hold 3 floats")
-            setattr(args, name, t.data_ptr())
-            keep.append(t)
-    mesh = geom.mesh_struct(B)
-    if want_red:
-        key = (mesh.nx, mesh.ny, mesh.ngp, B)
-        nbytes = _NS_WS_BYTES.get(key)
-        if nbytes is None:
-            nbytes = _lib.lib().dn_ns_workspace_bytes(C.byref(mesh))
-            if nbytes < 0:
-                _lib.check(int(nbytes), "dn_ns_workspace_bytes")
-            _NS_WS_BYTES[key] = nbytes
-        ws = _ns_workspace(flds[0].device, nbytes)
-        keep.append(ws)
-        args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
-    return mesh, args, keep, shape
+    args, keep = ent[1], ent[2]
+    if cot is not None:
+        for k in range(3):
+            args.cot[k] = keep[3 + k].data_ptr()
+    args.visco, args.wscale, args.tau_h[0], args.tau_h[1], args.cinv = consts
+    args.vjp = 1 if cot is not None else 0
+    return ent
 
 
 def ns_apply(geom, u, v, p, bc=None, bc_values=(0.0, 0.0, 0.0), visco=1.0, f_gp=None, wscale=1.0, tau_h=None, cinv=36.0, cot=None,
@@ -1698,7 +1624,7 @@ def ns_apply(geom, u, v, p, bc=None, bc_values=(0.0, 0.0, 0.0), visco=1.0, f_gp=
     constant.  `cot` (three fields like u): the VJP launch instead -- the gradient of sum_k <cot_k, R_k> with respect to (u, v, p) at the
     point (u, v, p), tau held fixed, with cot_k scaled by in_num[k] / in_den[k] where those are given.  Returns (outs | None, sums | None[,
     norms]).  Calls on the same buffers reuse their prepared argument structs (small LRU, fresh outputs per call: see poisson_apply)."""
-    _ns_check_mesh(geom)
+    _flow2d_check_mesh(_NS, geom)
     bc3, f2, vals = stokes_bc3(bc), stokes_f2(f_gp), tuple(bc_values)
     if len(vals) != 3:
         raise ValueError("ns_apply: bc_values must hold three entries")
@@ -1708,52 +1634,11 @@ def ns_apply(geom, u, v, p, bc=None, bc_values=(0.0, 0.0, 0.0), visco=1.0, f_gp=
             raise ValueError("ns_apply: cot must hold three fields")
     th = geom.hs[:2] if tau_h is None else tuple(tau_h)
     consts = (float(visco), float(wscale), float(th[0]), float(th[1]), float(cinv))
-    flds = (u, v, p)
     want_red = want_sums or want_norms
-    key = None
-    if all(isinstance(t, torch.Tensor) and t.is_cuda for t in flds) and tuple(u.shape[1:]) == (1, *geom.node_shape) and u.shape == v.shape == p.shape:
-        key = _ns_key(geom, flds, cot, bc3, vals, f2, consts, in_num, in_den, (want_out, want_sums, want_norms))
-    ent = None
-    if key is not None:
-        with _WS_LOCK:
-            ent = _NS_CACHE.get(key)
-            if ent is not None:
-                _NS_CACHE.move_to_end(key)
-    if ent is None:
-        _CALL_STATS["miss" if key is not None else "uncached"] += 1
-        mesh, args, keep, shape = _prepare_ns(geom, u, v, p, cot, bc3, vals, f2, consts, in_num, in_den, want_red)
-        with _WS_LOCK:
-            live_ws = list(_NS_WS.values())
-        ent = (mesh, args, C.byref(mesh), C.byref(args), shape, [t for t in keep if any(t is x for x in live_ws)])
-        if key is not None:
-            with _WS_LOCK:
-                _NS_CACHE[key] = ent
-                while len(_NS_CACHE) > _CALL_CACHE_MAX:
-                    _NS_CACHE.popitem(last=False)
-    else:
-        _CALL_STATS["hit"] += 1
-    mesh, args, mref, aref, shape = ent[:5]
-    dev = u.device
-    outs = sums = norms = None
-    if want_out:
-        o3 = torch.empty((3, *shape), dtype=torch.float32, device=dev)      # one allocation, three views
-        outs = list(o3.unbind(0))
-    if want_sums:
-        sums = torch.empty(3, dtype=torch.float64, device=dev)
-    if want_norms:
-        norms = torch.empty(3, dtype=torch.float32, device=dev)
-    with _NS_LAUNCH_LOCK:              # pointer patch + launch of the (possibly shared, cached) argument struct as one step
-        if want_out:
-            p0, step = o3.data_ptr(), 4 * o3[0].numel()
-            args.out[0], args.out[1], args.out[2] = p0, p0 + step, p0 + 2 * step
-        else:
-            args.out[0] = args.out[1] = args.out[2] = None
-        args.sumsq = sums.data_ptr() if want_sums else None
-        args.norms = norms.data_ptr() if want_norms else None
-        rc = _lib.lib().dn_ns_apply(mref, aref, _stream(u))
-    if rc:
-        _lib.check(rc, "dn_ns_apply")
-    return (outs, sums, norms) if want_norms else (outs, sums)
+    key = _flow2d_key(geom, (u, v, p), bc3, vals, f2, consts, in_num, in_den, (want_out, want_sums, want_norms),
+                      cot if cot is not None else (None, None, None))
+    return _flow2d_call(_NS, key, lambda: _prepare_ns(geom, u, v, p, cot, bc3, vals, f2, consts, in_num, in_den, want_red),
+                        u, want_out, want_sums, want_norms)
 
 
 def compute_winding_nodes(points, normals, area, q):

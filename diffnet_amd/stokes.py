@@ -64,59 +64,50 @@ def stokes_residuals(fem, u, v, p, bc, bc_values=(0.0, 0.0, 0.0), visco=1.0, psp
 
 class _StokesLoss(torch.autograd.Function):
     """The three Frobenius norms (one (3,) tensor) written by the launch that computes the residuals (in-kernel fixed-order fp64 sums); the
-    VJP of all three is ONE transpose launch on the saved residuals, which the kernel scales by gout_k / ||R_k|| as it loads them."""
+    VJP of all three is ONE transpose launch on the saved residuals, which the kernel scales by gout_k / ||R_k|| as it loads them.  `total`:
+    their sum as a scalar."""
 
     @staticmethod
-    def forward(ctx, u, v, p, fem, bc, bc_values, visco, pspg, f_gp, wscale):
+    def forward(ctx, u, v, p, fem, bc, bc_values, visco, pspg, f_gp, wscale, total):
         outs, _, norms = ops.stokes_apply(fem.geom, u, v, p, bc, bc_values, visco, pspg, f_gp, wscale, want_sums=False, want_norms=True)
         ctx.save_for_backward(*outs, norms)
-        ctx.fem, ctx.bc, ctx.coef = fem, bc, (visco, pspg, wscale)
-        return norms
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gnorms):
-        *Rs, norms = ctx.saved_tensors
-        visco, pspg, wscale = ctx.coef
-        # d||R_k||/dR_k = R_k / ||R_k||, zero where ||R_k|| == 0 (torch's norm_backward convention); the kernel forms gnorms[k] / norms[k]
-        outs, _ = ops.stokes_apply(ctx.fem.geom, *Rs, ctx.bc, (0.0, 0.0, 0.0), visco, pspg, None, wscale, want_sums=False,
-                                   in_num=gnorms.contiguous(), in_den=norms, transpose=True)
-        return outs[0], outs[1], outs[2], None, None, None, None, None, None, None
-
-
-def stokes_loss(fem, u, v, p, bc, bc_values=(0.0, 0.0, 0.0), visco=1.0, pspg=0.0, f_gp=None, wscale=None):
-    """(||R1||, ||R2||, ||R3||): the three losses of the scripts (one per optimizer, `optimizer_idx`), each differentiable; one launch
-    forward, one launch backward for all three cotangents."""
-    norms = _StokesLoss.apply(u, v, p, fem, bc, _vals(bc_values), visco, pspg, f_gp, _wscale(fem, wscale))
-    return norms.unbind(0)
-
-
-class _StokesTotal(torch.autograd.Function):
-    """sum_k ||R_k|| as one autograd node with a scalar output."""
-
-    @staticmethod
-    def forward(ctx, u, v, p, fem, bc, bc_values, visco, pspg, f_gp, wscale):
-        outs, _, norms = ops.stokes_apply(fem.geom, u, v, p, bc, bc_values, visco, pspg, f_gp, wscale, want_sums=False, want_norms=True)
-        ctx.save_for_backward(*outs, norms)
-        ctx.fem, ctx.bc, ctx.coef = fem, bc, (visco, pspg, wscale)
-        return norms.sum()
+        ctx.fem, ctx.bc, ctx.coef, ctx.total = fem, bc, (visco, pspg, wscale), total
+        return norms.sum() if total else norms
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gout):
         *Rs, norms = ctx.saved_tensors
         visco, pspg, wscale = ctx.coef
+        # d||R_k||/dR_k = R_k / ||R_k||, zero where ||R_k|| == 0 (torch's norm_backward convention); the kernel forms gout[k] / norms[k]
+        g = gout.expand(3).contiguous() if ctx.total else gout.contiguous()
         outs, _ = ops.stokes_apply(ctx.fem.geom, *Rs, ctx.bc, (0.0, 0.0, 0.0), visco, pspg, None, wscale, want_sums=False,
-                                   in_num=gout.expand(3).contiguous(), in_den=norms, transpose=True)
-        return outs[0], outs[1], outs[2], None, None, None, None, None, None, None
+                                   in_num=g, in_den=norms, transpose=True)
+        return outs[0], outs[1], outs[2], None, None, None, None, None, None, None, None
+
+
+def stokes_loss(fem, u, v, p, bc, bc_values=(0.0, 0.0, 0.0), visco=1.0, pspg=0.0, f_gp=None, wscale=None):
+    """(||R1||, ||R2||, ||R3||): the three losses of the scripts (one per optimizer, `optimizer_idx`), each differentiable; one launch
+    forward, one launch backward for all three cotangents."""
+    norms = _StokesLoss.apply(u, v, p, fem, bc, _vals(bc_values), visco, pspg, f_gp, _wscale(fem, wscale), False)
+    return norms.unbind(0)
 
 
 def stokes_total_loss(fem, u, v, p, bc, bc_values=(0.0, 0.0, 0.0), visco=1.0, pspg=0.0, f_gp=None, wscale=None):
     """||R1|| + ||R2|| + ||R3|| as one differentiable scalar (the loss of e1_stokes_mms_resmin.py:214-217)."""
-    return _StokesTotal.apply(u, v, p, fem, bc, _vals(bc_values), visco, pspg, f_gp, _wscale(fem, wscale))
+    return _StokesLoss.apply(u, v, p, fem, bc, _vals(bc_values), visco, pspg, f_gp, _wscale(fem, wscale), True)
 
 
 _ONES = {}
+
+
+def _ones3(dev):
+    """The default weights of *_loss_and_grad: one cached (3,) vector of ones per device."""
+    key = (dev.type, dev.index)
+    ones = _ONES.get(key)
+    if ones is None:
+        ones = _ONES[key] = torch.ones(3, dtype=torch.float32, device=dev)
+    return ones
 
 
 def stokes_loss_and_grad(fem, u, v, p, bc, bc_values=(0.0, 0.0, 0.0), visco=1.0, pspg=0.0, f_gp=None, wscale=None, weights=None):
@@ -127,10 +118,7 @@ def stokes_loss_and_grad(fem, u, v, p, bc, bc_values=(0.0, 0.0, 0.0), visco=1.0,
     with torch.no_grad():
         Rs, _, norms = ops.stokes_apply(fem.geom, u, v, p, bc, _vals(bc_values), visco, pspg, f_gp, wscale, want_sums=False, want_norms=True)
         if weights is None:
-            key = (u.device.type, u.device.index)
-            weights = _ONES.get(key)
-            if weights is None:
-                weights = _ONES[key] = torch.ones(3, dtype=torch.float32, device=u.device)
+            weights = _ones3(u.device)
         grads, _ = ops.stokes_apply(fem.geom, *Rs, bc, (0.0, 0.0, 0.0), visco, pspg, None, wscale, want_sums=False, in_num=weights,
                                     in_den=norms, transpose=True)
     return norms, grads
@@ -144,36 +132,44 @@ def _condition(m):
     return m >= 0.5
 
 
+# ---- the composed route (shared with navier_stokes.ns_residuals_composed) ----
+
+def _fix(t, m, val):
+    """where(m, val, t): the Dirichlet substitution of a field / the Dirichlet rows of a residual"""
+    if m is None:
+        return t
+    return torch.where(_condition(m), val if isinstance(val, torch.Tensor) else torch.full_like(t, float(val)), t)
+
+
+def _forcing(f, pg, geom):
+    """A forcing term (constant or Gauss-point tensor) at the Gauss points, shaped like the Gauss-point field pg (B | 1 samples)"""
+    if isinstance(f, torch.Tensor) and f.numel() > 1:
+        return f.to(pg.device).reshape(-1, geom.ngp_total, *geom.elem_shape)
+    return torch.full_like(pg, float(f))
+
+
+def _weak_form(fem, dev, wscale):
+    """weak(a_x, a_y, a_0) = sum_g JxW ( dN_x a_x + dN_y a_y + N a_0 ), per local basis function -> (B, nbf, nelY, nelX)"""
+    N, Nx, Ny = (t.to(dev) for t in (fem.Nvalues, fem.dN_x_values, fem.dN_y_values))       # (1, nbf, ngp, 1, 1)
+    jxw = (fem.gpw.to(dev) * wscale).reshape(1, 1, -1, 1, 1)
+
+    def weak(a_x, a_y, a_0):
+        t = Nx * a_x.unsqueeze(1) + Ny * a_y.unsqueeze(1) + N * a_0.unsqueeze(1)
+        return torch.sum(t * jxw, 2)
+
+    return weak
+
+
 def stokes_residuals_composed(fem, u, v, p, bc, bc_values=(0.0, 0.0, 0.0), visco=1.0, pspg=0.0, f_gp=None, wscale=None):
     """Same residuals from the single-launch HIP operators (9 gauss_pt_eval launches + torch elementwise + 3 assemblies), batched."""
     wscale = _wscale(fem, wscale)
     bc3, vals, f2 = ops.stokes_bc3(bc), _vals(bc_values), ops.stokes_f2(f_gp)
-
-    def fix(t, m, val):
-        if m is None:
-            return t
-        return torch.where(_condition(m), val if isinstance(val, torch.Tensor) else torch.full_like(t, float(val)), t)
-
-    u, v, p = (fix(t, m, val) for t, m, val in zip((u, v, p), bc3, vals))
+    u, v, p = (_fix(t, m, val) for t, m, val in zip((u, v, p), bc3, vals))
     ev, dx, dy = fem.gauss_pt_evaluation, fem.gauss_pt_evaluation_der_x, fem.gauss_pt_evaluation_der_y
     ux, uy, vx, vy = dx(u), dy(u), dx(v), dy(v)
     pg, px, py = ev(p), dx(p), dy(p)
-    dev = u.device
-    N, Nx, Ny = (t.to(dev) for t in (fem.Nvalues, fem.dN_x_values, fem.dN_y_values))       # (1, nbf, ngp, 1, 1)
-    jxw = (fem.gpw.to(dev) * wscale).reshape(1, 1, -1, 1, 1)
-    G, eshape = fem.geom.ngp_total, fem.geom.elem_shape
-
-    def forcing(f):
-        if isinstance(f, torch.Tensor) and f.numel() > 1:
-            return f.to(dev).reshape(-1, G, *eshape)
-        return torch.full_like(pg, float(f))
-
-    def weak(a_x, a_y, a_0):
-        """sum_g JxW ( dN_x a_x + dN_y a_y + N a_0 ), per local basis function -> (B, nbf, nelY, nelX)"""
-        t = Nx * a_x.unsqueeze(1) + Ny * a_y.unsqueeze(1) + N * a_0.unsqueeze(1)
-        return torch.sum(t * jxw, 2)
-
-    R1 = fem.assemble(weak(visco * ux - pg, visco * uy, -forcing(f2[0]).expand_as(pg)))
-    R2 = fem.assemble(weak(visco * vx, visco * vy - pg, -forcing(f2[1]).expand_as(pg)))
+    weak = _weak_form(fem, u.device, wscale)
+    R1 = fem.assemble(weak(visco * ux - pg, visco * uy, -_forcing(f2[0], pg, fem.geom).expand_as(pg)))
+    R2 = fem.assemble(weak(visco * vx, visco * vy - pg, -_forcing(f2[1], pg, fem.geom).expand_as(pg)))
     R3 = fem.assemble(weak(pspg * px, pspg * py, ux + vy))
-    return tuple(fix(R, m, val) for R, m, val in zip((R1, R2, R3), bc3, vals))
+    return tuple(_fix(R, m, val) for R, m, val in zip((R1, R2, R3), bc3, vals))
