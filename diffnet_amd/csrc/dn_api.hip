@@ -2,7 +2,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "dn_common.h"
+#include "dn_reduce.h"
 
 #define DN_STR2(x) #x
 #define DN_STR(x) DN_STR2(x)
@@ -57,11 +57,11 @@ extern "C" const char* dn_config_get(const char* key) {
     return k < 0 ? nullptr : g_cfg[k];
 }
 
-// ---- sticky error word of a launch workspace (poisson_common.h: DN_WS_ERRWORD) ------------------------------------------------
+// ---- sticky error word of a launch workspace (dn_reduce.h: DN_WS_ERRWORD) ------------------------------------------------------
 extern "C" int dn_workspace_status(void* workspace, void* stream) {
     if (!workspace) return DN_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    unsigned* word = reinterpret_cast<unsigned*>(workspace) + 8;          // DN_WS_ERRWORD
+    unsigned* word = reinterpret_cast<unsigned*>(workspace) + dn::DN_WS_ERRWORD;
     unsigned v = 0u;
     hipError_t e = hipMemcpyAsync(&v, word, sizeof(v), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);

@@ -6,11 +6,11 @@
 #pragma once
 #include <algorithm>
 
-#include "fsdt_common.h"
+#include "dn_reduce.h"
 
 namespace dn {
 
-// StokesParams and NsParams derive from this (finish_sums3 reads part, counter, sumsq, norms)
+// StokesParams and NsParams derive from this
 struct Flow2dParams {
     float fconst[2];                       // constant forcing (where fgp[k] is NULL)
     const float* fld[3];                   // u, v, p
@@ -25,7 +25,7 @@ struct Flow2dParams {
     const float* in_num;                   // optional 3 + 3 device floats: the scale in_num[k] / in_den[k] (flow2d_in_scale)
     const float* in_den;
     float* out[3];
-    double* part;                          // [3][nblocks] partial sums of squares (finish_sums3)
+    double* part;                          // [3][nblocks] partial sums of squares (finish_sums3 in dn_reduce.h)
     unsigned* counter;
     double* sumsq;
     float* norms;
@@ -153,8 +153,6 @@ __device__ __forceinline__ bool flow2d_fixed(const Flow2dParams& p, const Raw& w
 
 // ---- host ----
 
-static constexpr int64_t FLOW2D_WS_HEADER = 64 * (1 + 64);     // top counter + DN_NSHARD shard counters (finish_sums3)
-
 struct Flow2dGeom { int chunks, strips, R, wpb, gx; };
 
 static inline int flow2d_validate(const dn_mesh* m) {
@@ -183,7 +181,7 @@ static inline Flow2dGeom flow2d_plan(const dn_mesh* m, int min_rows) {
 }
 
 static inline int64_t flow2d_workspace_bytes(const Flow2dGeom& g, int batch) {
-    return FLOW2D_WS_HEADER + (int64_t)(3 * sizeof(double)) * g.gx * batch;
+    return DN_WS_HEADER + (int64_t)(3 * sizeof(double)) * g.gx * batch;
 }
 
 // the DN_E_BADARG checks common to dn_stokes_args and dn_ns_args
@@ -229,7 +227,7 @@ static void flow2d_fill(Flow2dParams& pp, const dn_mesh* m, const Args* a, const
     pp.in_num = a->in_num;
     pp.in_den = a->in_den;
     pp.counter = reinterpret_cast<unsigned*>(a->workspace);
-    pp.part = a->workspace ? reinterpret_cast<double*>(reinterpret_cast<char*>(a->workspace) + FLOW2D_WS_HEADER) : nullptr;
+    pp.part = a->workspace ? reinterpret_cast<double*>(reinterpret_cast<char*>(a->workspace) + DN_WS_HEADER) : nullptr;
     pp.sumsq = a->sumsq;
     pp.norms = a->norms;
     pp.nx = m->nx; pp.ny = m->ny;

@@ -471,16 +471,15 @@ __global__ void __launch_bounds__(CH ? 64 * FS_CH_MAXW : 256) fsdt2d_kernel(cons
     if constexpr (CH) {               // a hand-over poll ran into its bound: NaN sums + the sticky error word of the workspace (never silent)
 #pragma unroll
         for (int k = 0; k < 3; ++k) sq[k] += spin_poison;
-        if (spin_poison != spin_poison && p.counter != nullptr && (threadIdx.x & 63u) == 0u) atomicOr(p.counter + 8, 1u);      // DN_WS_ERRWORD
+        if (spin_poison != spin_poison && p.counter != nullptr && (threadIdx.x & 63u) == 0u) atomicOr(p.counter + DN_WS_ERRWORD, 1u);
     }
     if (p.want_sums) {
         if (p.defer_sums) store_partials3(p, sq, (int)threadIdx.x, (int)blockDim.x, red);
-        else finish_sums3(p, sq, (int)threadIdx.x, (int)blockDim.x, red, &last_flag);
+        else finish_sums3(p.part, p.counter, p.sumsq, p.norms, sq, (int)threadIdx.x, (int)blockDim.x, red, &last_flag);
     }
 }
 
 static inline int fs_ceil_div(int a, int b) { return (a + b - 1) / b; }
-static constexpr int64_t FSDT_WS_HEADER = 64 * (1 + 64);
 
 struct FsdtGeom { int T, chunks, R, strips, W; };     // W > 1: chained launch, W one-wave sub-strips per workgroup (T == 64); strips = workgroups per column of chunks
 
@@ -596,7 +595,7 @@ extern "C" int64_t dn_fsdt_workspace_bytes(const dn_mesh* m) {
     if (fsdt_validate(m) != 0) return DN_E_BADARG;
     const FsdtGeom g = fsdt_plan(m, false), gc = fsdt_plan(m, true);         // either plan fits (un-chained has the most workgroups per strip)
     const int64_t n1 = (int64_t)g.chunks * g.strips * m->batch, n2 = (int64_t)gc.chunks * gc.strips * m->batch;
-    return FSDT_WS_HEADER + (int64_t)(3 * sizeof(double)) * std::max(std::max(n1, n2), fsdt_st_workgroups(m));
+    return DN_WS_HEADER + (int64_t)(3 * sizeof(double)) * std::max(std::max(n1, n2), fsdt_st_workgroups(m));
 }
 
 extern "C" int dn_fsdt_apply(const dn_mesh* m, const dn_fsdt_args* a, void* stream) {
@@ -621,7 +620,7 @@ extern "C" int dn_fsdt_apply(const dn_mesh* m, const dn_fsdt_args* a, void* stre
     const bool ask_st = form && form[0] == 's';
     const bool stencil = !(form && form[0] == 'e') && config(CFG_FSDT_GENERIC) == nullptr && g.W == 1 && (m->degree <= 2 || (ask_st && !any_bcf));
     const int64_t nwg = stencil ? fsdt_st_workgroups(m) : (int64_t)g.chunks * g.strips * m->batch;
-    if (want_red && (!a->workspace || a->workspace_bytes < FSDT_WS_HEADER + (int64_t)(3 * sizeof(double)) * nwg)) return DN_E_WORKSPACE;
+    if (want_red && (!a->workspace || a->workspace_bytes < DN_WS_HEADER + (int64_t)(3 * sizeof(double)) * nwg)) return DN_E_WORKSPACE;
 
     FsdtParams pp;
     for (int i = 0; i < 4; ++i)
@@ -641,7 +640,7 @@ extern "C" int dn_fsdt_apply(const dn_mesh* m, const dn_fsdt_args* a, void* stre
         pp.out[k] = a->out[k];
     }
     pp.counter = reinterpret_cast<unsigned*>(a->workspace);
-    pp.part = a->workspace ? reinterpret_cast<double*>(reinterpret_cast<char*>(a->workspace) + FSDT_WS_HEADER) : nullptr;
+    pp.part = a->workspace ? reinterpret_cast<double*>(reinterpret_cast<char*>(a->workspace) + DN_WS_HEADER) : nullptr;
     pp.sumsq = a->sumsq;
     pp.nx = m->nx; pp.ny = m->ny;
     pp.nelx = (m->nx - 1) / m->degree; pp.nely = (m->ny - 1) / m->degree;
@@ -650,7 +649,7 @@ extern "C" int dn_fsdt_apply(const dn_mesh* m, const dn_fsdt_args* a, void* stre
     pp.defer_sums = a->defer_sums;
     pp.den_ticket = a->den_ticket;
     pp.den_counter = reinterpret_cast<const unsigned*>(a->den_workspace);
-    pp.den_part = a->den_workspace ? reinterpret_cast<const double*>(reinterpret_cast<const char*>(a->den_workspace) + FSDT_WS_HEADER) : nullptr;
+    pp.den_part = a->den_workspace ? reinterpret_cast<const double*>(reinterpret_cast<const char*>(a->den_workspace) + DN_WS_HEADER) : nullptr;
     pp.spin_limit = config(CFG_HANDOVER_SPIN_LIMIT) ? std::atoi(config(CFG_HANDOVER_SPIN_LIMIT)) : 0;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (stencil) {

@@ -471,7 +471,7 @@ __global__ void __launch_bounds__(256) fsdt2d_st_kernel(const FsdtParams p, cons
     }
     if (p.want_sums) {
         if (p.defer_sums) store_partials3(p, sq, (int)threadIdx.x, (int)blockDim.x, red);
-        else finish_sums3(p, sq, (int)threadIdx.x, (int)blockDim.x, red, &last_flag);
+        else finish_sums3(p.part, p.counter, p.sumsq, p.norms, sq, (int)threadIdx.x, (int)blockDim.x, red, &last_flag);
     }
 }
 

@@ -251,7 +251,7 @@ __global__ void __launch_bounds__(256) ns2d_kernel(const NsParams p) {
             if (e + 1 < j1) step(e + 1, W1);
         }
     }
-    if (p.want_sums) finish_sums3(p, sq, (int)threadIdx.x, (int)blockDim.x, red, &last_flag);
+    if (p.want_sums) finish_sums3(p.part, p.counter, p.sumsq, p.norms, sq, (int)threadIdx.x, (int)blockDim.x, red, &last_flag);
 }
 
 template <int NGP, bool VJP>

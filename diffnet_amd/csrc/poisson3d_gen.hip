@@ -271,24 +271,13 @@ __global__ void __launch_bounds__(256) poisson3d_gen_node_kernel(const PoissonPa
 
 __global__ void __launch_bounds__(256) poisson3d_gen_finish_kernel(const PoissonParams p, const Gen3DParams q) {
     __shared__ double re[256], rs[256];
-    // the partials are requested eight at a time before any is added (a load-add loop is one memory round trip per partial: 14.3 us of the 129^3 Q2
-    // call); same per-thread order of additions
-    double e = 0.0, s = 0.0;
-    auto strided_sum = [&](const double* part, int n, double& acc) {
-        for (int i0 = threadIdx.x; i0 < n; i0 += 256 * 8) {
-            double v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int i = i0 + j * 256;
-                v[j] = part[i < n ? i : 0];
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc += (i0 + j * 256 < n) ? v[j] : 0.0;
-        }
-    };
-    strided_sum(q.part_e, q.n1, e);
-    strided_sum(q.part_s, q.n2, s);
-    re[threadIdx.x] = e; rs[threadIdx.x] = s;
+    // eight partials ahead (a load-add loop is one memory round trip per partial: 14.3 us of the 129^3 Q2 call); the two arrays differ in length
+    const double* const pe[1] = {q.part_e};
+    const double* const ps[1] = {q.part_s};
+    double e[1], s[1];
+    sum_partials<1, 8, false, true>(pe, q.n1, (int)threadIdx.x, 256, e);
+    sum_partials<1, 8, false, true>(ps, q.n2, (int)threadIdx.x, 256, s);
+    re[threadIdx.x] = e[0]; rs[threadIdx.x] = s[0];
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
         if ((int)threadIdx.x < o) { re[threadIdx.x] += re[threadIdx.x + o]; rs[threadIdx.x] += rs[threadIdx.x + o]; }

@@ -1,7 +1,7 @@
 // Shared device-side pieces of the fused Poisson kernels: kernel parameter block, per-sample base pointers,
-// Dirichlet handling and the in-kernel deterministic final reduction.
+// Dirichlet handling and what Poisson does with the sums of the final reduction (dn_reduce.h).
 #pragma once
-#include "dn_common.h"
+#include "dn_reduce.h"
 #include "poisson_elem.h"
 
 namespace dn {
@@ -52,6 +52,15 @@ struct PoissonParams {
     int fold_n, fold_acc;
     int spin_limit;        // bound of the chained strips' LDS hand-over polls (0: the kernels' default; "HANDOVER_SPIN_LIMIT": test hook for the error path)
 };
+
+// The totals of a launch (thread 0 of the workgroup that formed them).  acc: they are added to what energy / sumsq hold -- the second
+// launch of a split evaluation (the host checks that both double slots exist): fixed order, first + second
+__device__ __forceinline__ void write_sums(double e, double s, int acc, double* energy, double* sumsq, float* energy_f32, double energy_scale) {
+    if (acc) { e += *energy; s += *sumsq; }
+    if (energy) *energy = e;
+    if (sumsq) *sumsq = s;
+    if (energy_f32) *energy_f32 = (float)(e * energy_scale);
+}
 
 // strip index of the idx-th launched strip (split evaluations launch a subset of the strips: PoissonParams::strip_sel)
 __device__ __forceinline__ int selected_strip(const PoissonParams& p, int idx) {
@@ -130,122 +139,33 @@ __device__ __forceinline__ unsigned load_apply_bc(const PoissonParams& p, const 
     return bits;
 }
 
-// Block-level reduction of the two scalars + arrival of this workgroup at the in-kernel final reduction.
-// Two-level arrival (DN_NSHARD shard counters on separate 64-B lines, then one top counter) keeps the
-// same-address atomic fan-in at ~nblocks/64 + 64 instead of nblocks (one address retires only ~88 atomics/us:
-// MI355X_MICROARCH.md "fanin").  The workgroup that arrives last sums all per-workgroup partials in index
-// order (=> deterministic whatever the arrival order); counters are reset by their last arriver, so the
-// workspace is ready for the next launch.  Protocol (cdna_hip_programming.md, Guideline 16): partials are
-// stored write-through (sc1) and drained before the arrival atomic; the last arriver does an agent-scope
-// acquire and reads the partials with sc1 loads.
-#define DN_NSHARD 64
+// Block sums of the workgroup's two scalars, then the in-kernel final reduction (dn_reduce.h) and what Poisson does with the totals.
 __device__ __forceinline__ void finish_sums(const PoissonParams& p, float e1, float e2, float sq, int tid, int nthreads,
                                             double* red, int* flag, double escale = 1.0) {
-    const int nblocks = gridDim.x * gridDim.y * gridDim.z;
-    const int blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    double es = escale * ((double)p.T.c * (double)e1 - (double)e2), ss = (double)sq;
-    block_sum2(es, ss, red, tid, nthreads);
-    if (p.defer_sums) {                          // no arrival protocol, no tail: the kernel boundary publishes the partials
-        if (tid == 0) { p.part_energy[blk] = es; p.part_sumsq[blk] = ss; }
+    double mine[2] = {escale * ((double)p.T.c * (double)e1 - (double)e2), (double)sq}, tot[2];
+    block_sum2(mine[0], mine[1], red, tid, nthreads);
+    double* const part[2] = {p.part_energy, p.part_sumsq};
+    if (p.defer_sums) {                          // no arrival, no tail: the kernel boundary publishes the partials
+        if (tid == 0) store_partials<2, false>(part, workgroup_index(), mine);
         return;
     }
+    if (!last_arriver_sums<2, 16, true, false>(part, p.counter, mine, tid, nthreads, flag, tot)) return;
+    block_sum2(tot[0], tot[1], red, tid, nthreads);
     if (tid == 0) {
-        // write-through (sc1) 8-byte stores + drain instead of an agent-scope release fence: a release is a
-        // `buffer_wbl2` of the whole XCD L2, i.e. every workgroup would wait for everybody's freshly written
-        // output lines to be flushed (measured: +5..30 us per workgroup at 8k workgroups).
-        __hip_atomic_store(&p.part_energy[blk], es, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&p.part_sumsq[blk], ss, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        int last = 0;
-        if (nblocks <= DN_NSHARD) {              // few workgroups: one counter, one atomic round trip on the launch's critical path
-            const unsigned prev = __hip_atomic_fetch_add(p.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            last = (prev == (unsigned)(nblocks - 1)) ? 1 : 0;
-        } else {
-            const int nshard = DN_NSHARD;
-            const int shard = blk % nshard;
-            const unsigned in_shard = (unsigned)((nblocks - shard + nshard - 1) / nshard);
-            unsigned* sc = p.counter + 16 * (1 + shard);              // shard counters: one per 64-B line
-            const unsigned prev = __hip_atomic_fetch_add(sc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (prev == in_shard - 1) {
-                __hip_atomic_store(sc, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned prev2 = __hip_atomic_fetch_add(p.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                last = (prev2 == (unsigned)(nshard - 1)) ? 1 : 0;
-            }
-        }
-        *flag = last;
-    }
-    __syncthreads();
-    if (*flag) {
-        if (tid == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __syncthreads();
-        // the last arriver's loop sits on the critical path of the whole launch (every other workgroup has finished): sixteen partials of
-        // each sum are requested before the first is added (one L2 round trip per 16 partials instead of per 1; 2048 workgroups x 128
-        // threads: 1 trip instead of 16).  Same per-thread order of additions as the plain loop: bitwise the same sums.
-        double e = 0.0, s = 0.0;
-        constexpr int NB_ = 16;                       // partials of each sum in flight per thread
-        for (int i0 = tid; i0 < nblocks; i0 += nthreads * NB_) {
-            double ve[NB_], vs[NB_];
-#pragma unroll
-            for (int k = 0; k < NB_; ++k) {
-                const int i = i0 + k * nthreads;
-                const int ic = i < nblocks ? i : 0;
-                ve[k] = __hip_atomic_load(&p.part_energy[ic], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                vs[k] = __hip_atomic_load(&p.part_sumsq[ic], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-#pragma unroll
-            for (int k = 0; k < NB_; ++k) {
-                const bool ok = i0 + k * nthreads < nblocks;
-                e += ok ? ve[k] : 0.0;
-                s += ok ? vs[k] : 0.0;
-            }
-        }
-        block_sum2(e, s, red, tid, nthreads);
-        if (tid == 0) {
-            if (p.acc_sums) {         // second launch of a split evaluation (host checks that both double slots exist): fixed order, first + second
-                e += *p.energy;
-                s += *p.sumsq;
-            }
-            if (p.energy) *p.energy = e;
-            if (p.sumsq) *p.sumsq = s;
-            if (p.energy_f32) *p.energy_f32 = (float)(e * p.energy_scale);
-            __hip_atomic_store(p.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        write_sums(tot[0], tot[1], p.acc_sums, p.energy, p.sumsq, p.energy_f32, p.energy_scale);
+        arrival_reset(p.counter);
     }
 }
 
-// dn_poisson_args.fold_prev: the final reduction of an EARLIER launch, done by the first workgroup of this one before its march (same
-// arithmetic as poisson_finish_sums_kernel: each thread adds its partials in index order, fixed-order block sum -> bitwise reproducible).
-// Sixteen partials of each sum are requested before the first addition (one memory round trip per 16).  `red`: >= 2 * waves doubles.
+// dn_poisson_args.fold_prev: the final reduction of an EARLIER launch, done by the first workgroup of this one before its march.
+// `red`: >= 2 * waves doubles.
 __device__ __forceinline__ void fold_prev_sums(const PoissonParams& p, int tid, int nthreads, double* red) {
     if (p.fold_n <= 0) return;                    // (wave-uniform)
-    double e = 0.0, s = 0.0;
-    constexpr int NB_ = 16;
-    for (int i0 = tid; i0 < p.fold_n; i0 += nthreads * NB_) {
-        double ve[NB_], vs[NB_];
-#pragma unroll
-        for (int k = 0; k < NB_; ++k) {
-            const int i = i0 + k * nthreads;
-            const int ic = i < p.fold_n ? i : 0;
-            ve[k] = p.fold_pe[ic];
-            vs[k] = p.fold_ps[ic];
-        }
-#pragma unroll
-        for (int k = 0; k < NB_; ++k) {
-            const bool ok = i0 + k * nthreads < p.fold_n;
-            e += ok ? ve[k] : 0.0;
-            s += ok ? vs[k] : 0.0;
-        }
-    }
-    block_sum2(e, s, red, tid, nthreads);
-    if (tid == 0) {
-        if (p.fold_acc) { e += *p.fold_energy; s += *p.fold_sumsq; }
-        if (p.fold_energy) *p.fold_energy = e;
-        if (p.fold_sumsq) *p.fold_sumsq = s;
-        if (p.fold_energy_f32) *p.fold_energy_f32 = (float)(e * p.fold_scale);
-    }
+    const double* const part[2] = {p.fold_pe, p.fold_ps};
+    double tot[2];
+    sum_partials<2, 16, false, false>(part, p.fold_n, tid, nthreads, tot);
+    block_sum2(tot[0], tot[1], red, tid, nthreads);
+    if (tid == 0) write_sums(tot[0], tot[1], p.fold_acc, p.fold_energy, p.fold_sumsq, p.fold_energy_f32, p.fold_scale);
 }
 
 // Raw (not yet interpreted) Dirichlet data of one row segment: issued early, applied later, so that the
@@ -365,11 +285,7 @@ int launch_poisson3d_q1_g4(const PoissonParams& pp, const Geom3D& g, int batch, 
 bool poisson3d_q1_cf_ok(const PoissonParams& pp);
 int launch_poisson3d_q1_cf(const PoissonParams& pp, const Geom3D& g, int batch, hipStream_t s);
 
-// 3-D Q2 / Q3 (poisson3d_gen.hip): element vectors + fixed-order gather assembly; its workspace lies behind the common header
-static constexpr int64_t DN_WS_HEADER = 64 * (1 + 64);   // top counter + DN_NSHARD shard counters, one 64-B line each
-static constexpr int DN_WS_ERRWORD = 8;                    // word 8 of the top counter's line: sticky error bits of the launches that used this workspace
-                                                          // (bit 0: a bounded LDS hand-over poll of a chained-strip kernel ran out -- its results are NaN); read and
-                                                          // cleared by dn_workspace_status
+// 3-D Q2 / Q3 (poisson3d_gen.hip): element vectors + fixed-order gather assembly; its workspace lies behind the common header (DN_WS_HEADER)
 void gen3d_layout(const dn_mesh* m, long long& n1, long long& n2, long long& elem_floats);
 int launch_poisson3d_gen(const PoissonParams& pp, const dn_mesh* m, void* workspace, int64_t workspace_bytes, hipStream_t s);
 

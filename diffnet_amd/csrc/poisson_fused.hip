@@ -445,21 +445,16 @@ static bool q1n2_needed(const dn_poisson_args* a) {
 }
 
 namespace dn {
-// Final reduction of a launch's per-workgroup partial sums as its own (one-workgroup) kernel: fixed order -- thread t adds partials
-// t, t + 256, ... in turn, then the fixed-order block sum -- so the scalars are bitwise repeatable.  Same output semantics as the in-kernel
-// reduction (finish_sums in poisson_common.h).
+// Final reduction of a launch's per-workgroup partial sums as its own (one-workgroup) kernel: sum_partials and write_sums, like the
+// in-kernel reduction (finish_sums in poisson_common.h).
 __global__ void __launch_bounds__(256) poisson_finish_sums_kernel(const double* __restrict__ part_energy, const double* __restrict__ part_sumsq, int n,
                                                                   double* energy, double* sumsq, float* energy_f32, double energy_scale, int acc) {
     __shared__ double red[2 * 4];
-    double e = 0.0, s = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) { e += part_energy[i]; s += part_sumsq[i]; }
-    block_sum2(e, s, red, (int)threadIdx.x, 256);
-    if (threadIdx.x == 0) {
-        if (acc) { e += *energy; s += *sumsq; }
-        if (energy) *energy = e;
-        if (sumsq) *sumsq = s;
-        if (energy_f32) *energy_f32 = (float)(e * energy_scale);
-    }
+    const double* const part[2] = {part_energy, part_sumsq};
+    double tot[2];
+    sum_partials<2, 16, false, false>(part, n, (int)threadIdx.x, 256, tot);
+    block_sum2(tot[0], tot[1], red, (int)threadIdx.x, 256);
+    if (threadIdx.x == 0) write_sums(tot[0], tot[1], acc, energy, sumsq, energy_f32, energy_scale);
 }
 }  // namespace dn
 

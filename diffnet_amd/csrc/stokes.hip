@@ -194,7 +194,7 @@ __global__ void __launch_bounds__(256) stokes2d_kernel(const StokesParams p) {
         }
         (void)fix_unused;
     }
-    if (p.want_sums) finish_sums3(p, sq, (int)threadIdx.x, (int)blockDim.x, red, &last_flag);
+    if (p.want_sums) finish_sums3(p.part, p.counter, p.sumsq, p.norms, sq, (int)threadIdx.x, (int)blockDim.x, red, &last_flag);
 }
 
 // The kernels of one rule.  Without Gauss-point forcing the rule only enters the matrices: one instantiation serves every rule
