@@ -75,6 +75,17 @@ class DnNsArgs(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class DnTransportArgs(C.Structure):
+    _fields_ = [("u", C.c_void_p), ("nu", C.c_void_p), ("nu_batched", C.c_int32), ("r_first_wins", C.c_int32),
+                ("bc_mask", C.c_void_p * 2), ("mask_is_u8", C.c_int32 * 2), ("mask_batched", C.c_int32 * 2),
+                ("bc_field", C.c_void_p * 2), ("bc_field_batched", C.c_int32 * 2), ("bc_value", C.c_float * 2),
+                ("f_gp", C.c_void_p), ("f_batched", C.c_int32), ("f_value", C.c_float),
+                ("adv", C.c_float * 2), ("kappa", C.c_float * 2), ("tau", C.c_float), ("react", C.c_float * 4), ("wscale", C.c_float),
+                ("vjp", C.c_int32),
+                ("cot", C.c_void_p), ("out", C.c_void_p), ("sumsq", C.c_void_p), ("norm", C.c_void_p),
+                ("in_num", C.c_void_p), ("in_den", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 I32x3 = C.c_int32 * 3
 
 # name -> (restype, argtypes); must list every symbol of include/diffnet_hip.h
@@ -112,6 +123,8 @@ SYMBOLS = {
     "dn_stokes_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnStokesArgs), C.c_void_p]),
     "dn_ns_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
     "dn_ns_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnNsArgs), C.c_void_p]),
+    "dn_transport_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
+    "dn_transport_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnTransportArgs), C.c_void_p]),
     "dn_upconv_out_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "dn_upconv_out_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                     C.c_void_p, C.c_int64, C.c_void_p]),

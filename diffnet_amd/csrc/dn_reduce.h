@@ -115,19 +115,22 @@ __device__ __forceinline__ bool last_arriver_sums(double* const (&part)[N], unsi
     return true;
 }
 
-// The tail of the operators that reduce three sums of squares (FSDT, Stokes, Navier-Stokes; part: [3][nblocks]): block sums, the
-// in-launch reduction, sumsq and norms = sqrt where asked, and the ticket of an earlier deferring launch in this workspace is cleared (its
-// partials are gone).  red: >= nthreads / 64 doubles.
-__device__ __forceinline__ void finish_sums3(double* part, unsigned* counter, double* sumsq, float* norms, const float (&sq)[3], int tid,
-                                             int nthreads, double* red, int* flag) {
+// The tail of the operators that reduce N sums of squares (part: [N][nblocks]): block sums, the in-launch reduction, sumsq and
+// norms = sqrt where asked, and the ticket of an earlier deferring launch in this workspace is cleared (its partials are gone).
+// red: >= nthreads / 64 doubles.
+template <int N>
+__device__ __forceinline__ void finish_sums(double* part, unsigned* counter, double* sumsq, float* norms, const float (&sq)[N], int tid,
+                                            int nthreads, double* red, int* flag) {
     const int nblocks = launch_workgroups();
-    double* const parts[3] = {part, part + nblocks, part + 2 * (size_t)nblocks};
-    double mine[3], tot[3];
+    double* parts[N];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) mine[k] = block_sum((double)sq[k], red, tid, nthreads);
-    if (!last_arriver_sums<3, 8, false, true>(parts, counter, mine, tid, nthreads, flag, tot)) return;
+    for (int k = 0; k < N; ++k) parts[k] = part + k * (size_t)nblocks;
+    double mine[N], tot[N];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < N; ++k) mine[k] = block_sum((double)sq[k], red, tid, nthreads);
+    if (!last_arriver_sums<N, 8, false, true>(parts, counter, mine, tid, nthreads, flag, tot)) return;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
         const double e = block_sum(tot[k], red, tid, nthreads);
         if (tid == 0) {
             if (sumsq) sumsq[k] = e;
@@ -138,6 +141,12 @@ __device__ __forceinline__ void finish_sums3(double* part, unsigned* counter, do
         arrival_reset(counter);
         counter[DN_WS_TICKET_WORD] = 0u;
     }
+}
+
+// ... three of them (FSDT, Stokes, Navier-Stokes)
+__device__ __forceinline__ void finish_sums3(double* part, unsigned* counter, double* sumsq, float* norms, const float (&sq)[3], int tid,
+                                             int nthreads, double* red, int* flag) {
+    finish_sums<3>(part, counter, sumsq, norms, sq, tid, nthreads, red, flag);
 }
 
 }  // namespace dn

@@ -35,8 +35,9 @@ struct Flow2dParams {
 constexpr int FLOW2D_OWNERS = 62;          // owner lanes per wave (lanes 1 .. 62); lanes 0 and 63 are ghosts that only supply the x halo
 
 // One wave per (62-column chunk, strip of node rows, sample): the wave's chunk and strip (strip >= p.strips: a wave of the last
-// workgroup with nothing to do) and the lane
-__device__ __forceinline__ void flow2d_wave(const Flow2dParams& p, int& lane, int& chunk, int& strip) {
+// workgroup with nothing to do) and the lane.  Params: anything with `chunks` (transport.hip places its waves the same way)
+template <class Params>
+__device__ __forceinline__ void flow2d_wave(const Params& p, int& lane, int& chunk, int& strip) {
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     lane = (int)threadIdx.x & 63;
     const int wid = (int)blockIdx.x * ((int)blockDim.x >> 6) + wave;

@@ -11,7 +11,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import DnDirichlet, DnFsdtArgs, DnMesh, DnNsArgs, DnPoissonArgs, DnStokesArgs, I32x3, DiffNetHipError
+from ._lib import DnDirichlet, DnFsdtArgs, DnMesh, DnNsArgs, DnPoissonArgs, DnStokesArgs, DnTransportArgs, I32x3, DiffNetHipError
 
 
 def _require(t, name, ndim=None, strict=False):
@@ -600,11 +600,13 @@ def call_cache_clear():
         _FSDT_CACHE.clear()
         _STOKES.cache.clear()
         _NS.cache.clear()
+        _TRANSPORT.cache.clear()
         _PACK_CACHE.clear()
     _POISSON_WS_BYTES.clear()
     _FSDT_WS_BYTES.clear()
     _STOKES.ws_bytes.clear()
     _NS.ws_bytes.clear()
+    _TRANSPORT.ws_bytes.clear()
 
 
 class PoissonPlan:
@@ -1639,6 +1641,204 @@ def ns_apply(geom, u, v, p, bc=None, bc_values=(0.0, 0.0, 0.0), visco=1.0, f_gp=
                       cot if cot is not None else (None, None, None))
     return _flow2d_call(_NS, key, lambda: _prepare_ns(geom, u, v, p, cot, bc3, vals, f2, consts, in_num, in_den, want_red),
                         u, want_out, want_sums, want_norms)
+
+
+# ---- the one-field 2-D transport operator: dn_transport_apply (SUPG residual and its VJP) ------------------------------------------
+# Its own reduction workspace per (device, stream), prepared-call cache and launch lock, like _STOKES / _NS and for the same reason: an
+# FSDT deferring pair or a flow launch in between must not disturb its partial sums, nor it theirs.
+_TRANSPORT = _Flow2dOp("transport_apply", DnTransportArgs)
+
+
+def transport_bc2(bc):
+    """The two Dirichlet masks of a transport call: None, one mask (condition 1) or a pair (either may be None)."""
+    if bc is None or isinstance(bc, torch.Tensor):
+        return (bc, None)
+    bc = tuple(bc)
+    if len(bc) != 2:
+        raise ValueError(f"transport: bc must be one mask or a pair (got {len(bc)})")
+    return bc
+
+
+def _transport_key(geom, u, nu, bc2, vals, f, consts, in_num, in_den, flags, cot):
+    """Key of a cached prepared call (see _call_key); None when an argument needs a conversion copy."""
+    if not (isinstance(u, torch.Tensor) and u.is_cuda and tuple(u.shape[1:]) == (1, *geom.node_shape)):
+        return None
+    parts = [geom.key, u.device.index, _raw_stream(u.device), consts, flags]
+    k = _tkey(u)
+    if k is None or k == 0 or k[1] != torch.float32:
+        return None
+    parts.append(k)
+    for m in bc2:
+        k = _tkey(m)
+        if k is None or (k != 0 and k[1] not in (torch.float32, torch.uint8, torch.bool)):
+            return None
+        parts.append(k)
+    for v in tuple(vals) + (f,):
+        if isinstance(v, torch.Tensor) and v.numel() > 1:
+            k = _tkey(v)
+            if k is None or k[1] != torch.float32:
+                return None
+            parts.append(k)
+        else:
+            parts.append(float(v))
+    for t in (nu, cot, in_num, in_den):
+        k = _tkey(t)
+        if k is None or (k != 0 and k[1] != torch.float32):
+            return None
+        parts.append(k)
+    return tuple(parts)
+
+
+def _prepare_transport(geom, u, nu, cot, bc2, vals, f, consts, in_num, in_den, want_red):
+    """Validation + argument struct of a dn_transport_apply call, outputs left unset: (mesh, args, tensors to keep alive, field shape)."""
+    name = _TRANSPORT.name
+    _flow2d_check_mesh(_TRANSPORT, geom)
+    u = _require(u, "u", 4)
+    B = u.shape[0]
+    shape = (B, 1, *geom.node_shape)
+    if tuple(u.shape) != shape:
+        raise ValueError(f"{name}: field shape {tuple(u.shape)} != {shape}")
+    keep = [u]
+    args = DnTransportArgs()
+    args.u = u.data_ptr()
+    nn = geom.nnode_total
+
+    def batched(t, what):
+        if tuple(t.shape[-2:]) != tuple(geom.node_shape) or t.numel() not in (B * nn, nn):
+            raise ValueError(f"{name}: {what} shape {tuple(t.shape)} does not match the mesh {shape}")
+        return 1 if (t.numel() == B * nn and B > 1) else 0
+
+    if nu is not None:
+        nu = _require(nu, "nu")
+        args.nu_batched = batched(nu, "nu")
+        args.nu = nu.data_ptr()
+        keep.append(nu)
+    if cot is not None:
+        cot = _require(cot, "cot", 4)
+        if tuple(cot.shape) != shape:
+            raise ValueError(f"{name}: cot shape {tuple(cot.shape)} != {shape}")
+        args.cot = cot.data_ptr()
+        keep.append(cot)
+    elif in_num is not None:
+        raise ValueError(f"{name}: in_num / in_den scale the cotangent of a VJP (cot)")
+    args.vjp = 1 if cot is not None else 0
+    for k, m in enumerate(bc2):
+        if m is None:
+            continue
+        if not isinstance(m, torch.Tensor):
+            raise TypeError(f"{name}: bc[{k}] must be a tensor or None")
+        if not m.is_cuda:
+            raise DiffNetHipError(f"{name}: bc[{k}] is on {m.device}: the FEM ops run on the GPU only (no CPU fallback)")
+        if m.dtype in (torch.bool, torch.uint8):
+            m = m.contiguous()
+            m = m.view(torch.uint8) if m.dtype == torch.bool else m
+            args.mask_is_u8[k] = 1
+        else:
+            m = _require(m, f"bc[{k}]")
+        args.mask_batched[k] = batched(m, f"bc[{k}]")
+        args.bc_mask[k] = m.data_ptr()
+        keep.append(m)
+    for k, val in enumerate(vals):
+        if isinstance(val, torch.Tensor) and val.numel() > 1:
+            if bc2[k] is None:
+                raise ValueError(f"{name}: bc_values[{k}] is a field but condition {k} has no mask")
+            val = _require(val, f"bc_values[{k}]")
+            args.bc_field_batched[k] = batched(val, f"bc_values[{k}]")
+            args.bc_field[k] = val.data_ptr()
+            keep.append(val)
+        else:
+            args.bc_value[k] = float(val)
+    G, nel = geom.ngp_total, geom.nelem_total
+    if isinstance(f, torch.Tensor) and f.numel() > 1:
+        f = _require(f, "f_gp")
+        if tuple(f.shape[-3:]) != (G, *geom.elem_shape) or f.numel() not in (G * nel, B * G * nel):
+            raise ValueError(f"{name}: f_gp shape {tuple(f.shape)} is not (B | 1, {G}, {geom.elem_shape[0]}, {geom.elem_shape[1]})")
+        args.f_batched = 1 if (f.numel() == B * G * nel and B > 1) else 0
+        args.f_gp = f.data_ptr()
+        keep.append(f)
+    else:
+        args.f_value = float(f)
+    if in_den is not None and in_num is None:
+        raise ValueError(f"{name}: in_den needs in_num")
+    for what, t in (("in_num", in_num), ("in_den", in_den)):
+        if t is not None:
+            t = _require(t, what)
+            if t.numel() != 1:
+                raise ValueError(f"{what} must hold one float")
+            setattr(args, what, t.data_ptr())
+            keep.append(t)
+    (args.adv[0], args.adv[1], args.kappa[0], args.kappa[1], args.tau, args.react[0], args.react[1], args.react[2], args.react[3],
+     args.wscale, first) = consts
+    args.r_first_wins = 1 if first else 0
+    mesh = geom.mesh_struct(B)
+    if want_red:
+        ws = _flow2d_workspace(_TRANSPORT, mesh, B, u.device)
+        keep.append(ws)
+        args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    return mesh, args, keep, shape
+
+
+def transport_apply(geom, u, nu=None, bc=None, bc_values=(0.0, 0.0), r_first_wins=False, f_gp=None, adv=(0.0, 0.0), kappa=(1.0, 1.0),
+                    tau=0.0, react=(0.0, 0.0, 0.0, 0.0), wscale=1.0, cot=None, want_out=True, want_sums=True, want_norm=False, in_num=None,
+                    in_den=None):
+    """One launch of dn_transport_apply (include/diffnet_hip.h): the assembled scalar transport (SUPG) residual of the field u
+    (B,1,ny,nx) and / or the float64 device tensor (1,) of its sum of squares.  `nu`: None or a nodal coefficient field (B | 1,1,ny,nx);
+    `bc`: None, one mask or a pair (either None), fp32 (`>= 0.5`) or bool / uint8, per sample or shared; `bc_values[k]`: float or tensor u
+    and the residual take under condition k (where both hold, condition 2 wins on u; on the residual condition 1 if `r_first_wins`);
+    `f_gp`: None, a float or a Gauss-point tensor (B | 1, G, nely, nelx); `adv`, `kappa`, `tau`, `react`: the coefficients.  `cot` (a field
+    like u): the VJP launch instead -- the gradient of <cot, R> with respect to u at the point u, with cot scaled by in_num[0] (/ in_den[0])
+    where those (float32 device tensors of 1) are given.  `want_norm`: a third result, the float32 tensor (1,) of the Frobenius norm written
+    by the same launch.  Returns (out | None, sums | None[, norm]).  Calls on the same buffers reuse their prepared argument structs (small
+    LRU, fresh outputs per call: see poisson_apply)."""
+    _flow2d_check_mesh(_TRANSPORT, geom)
+    bc2, vals = transport_bc2(bc), tuple(bc_values)
+    if len(vals) != 2:
+        raise ValueError("transport_apply: bc_values must hold two entries")
+    adv, kappa, react = tuple(adv), tuple(kappa), tuple(react)
+    if len(adv) != 2 or len(kappa) != 2 or len(react) != 4:
+        raise ValueError("transport_apply: adv and kappa hold two entries, react four")
+    f = 0.0 if f_gp is None else f_gp
+    consts = (*(float(x) for x in adv), *(float(x) for x in kappa), float(tau), *(float(x) for x in react), float(wscale), bool(r_first_wins))
+    want_red = want_sums or want_norm
+    op = _TRANSPORT
+    key = _transport_key(geom, u, nu, bc2, vals, f, consts, in_num, in_den, (want_out, want_sums, want_norm), cot)
+    ent = None
+    if key is not None:
+        with _WS_LOCK:
+            ent = op.cache.get(key)
+            if ent is not None:
+                op.cache.move_to_end(key)
+    if ent is None:
+        _CALL_STATS["miss" if key is not None else "uncached"] += 1
+        mesh, args, keep, shape = _prepare_transport(geom, u, nu, cot, bc2, vals, f, consts, in_num, in_den, want_red)
+        with _WS_LOCK:
+            live_ws = list(op.ws.values())
+        # an uncached call keeps its (possibly converted) tensors alive until it has been issued; a cached one only the workspace
+        ent = (mesh, args, C.byref(mesh), C.byref(args), shape, keep if key is None else [t for t in keep if any(t is x for x in live_ws)])
+        if key is not None:
+            with _WS_LOCK:
+                op.cache[key] = ent
+                while len(op.cache) > _CALL_CACHE_MAX:
+                    op.cache.popitem(last=False)
+    else:
+        _CALL_STATS["hit"] += 1
+    mesh, args, mref, aref, shape = ent[:5]
+    dev = u.device
+    out = sums = norm = None
+    if want_out:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    if want_sums:
+        sums = torch.empty(1, dtype=torch.float64, device=dev)
+    if want_norm:
+        norm = torch.empty(1, dtype=torch.float32, device=dev)
+    with op.launch_lock:               # pointer patch + launch of the (possibly shared, cached) argument struct as one step
+        args.out = out.data_ptr() if want_out else None
+        args.sumsq = sums.data_ptr() if want_sums else None
+        args.norm = norm.data_ptr() if want_norm else None
+        rc = _lib.lib().dn_transport_apply(mref, aref, _stream(u))
+    if rc:
+        _lib.check(rc, op.fn)
+    return (out, sums, norm) if want_norm else (out, sums)
 
 
 def compute_winding_nodes(points, normals, area, q):

@@ -404,6 +404,68 @@ typedef struct dn_ns_args {
 int64_t dn_ns_workspace_bytes(const dn_mesh *mesh);
 int dn_ns_apply(const dn_mesh *mesh, const dn_ns_args *args, void *stream);
 
+/* ---- fused 2-D scalar transport (SUPG) residual and its VJP ------------------------------------------------------------
+ * Replaces the residual body of the scalar transport scripts of the reference under examples/poisson/single_instance/:
+ * e17_adv_diff_2d_resmin.py:99-171 (AdvDiff2d.loss), e3_st_mms_resmin.py:97-173 (SpaceTimeHeat.loss_resmin) and
+ * e18_allen_cahn_ice_melt.py:77-151 (AllenCahnIceMelt.loss): the two Dirichlet substitutions, the Gauss-point evaluations, the
+ * stabilised weak form, the assembly, the Dirichlet rows and the sum of squares, in ONE launch.  Mesh: nsd = 2, degree 1, ngp 2..4.
+ *   u~ = where(bc2, value2, where(bc1, value1, u))      (mask: fp32 >= 0.5, u8 != 0; where both hold condition 2 wins on u)
+ *   at every Gauss point, from u~ and the nodal coefficient nu (NULL: 1) evaluated there:
+ *     adv = adv[0] u_x + adv[1] u_y,   r(u) = react[0] + react[1] u + react[2] u^2 + react[3] u^3,   f = f_gp or f_value
+ *     A = adv + r(u) - f,   B = kappa[0] nu u_x + tau adv[0] (adv - f),   C = kappa[1] nu u_y + tau adv[1] (adv - f)
+ *   R = assemble(sum_g wscale w_g (N_a A + Nx_a B + Ny_a C))
+ *   R = where(bc, value, R)   (Dirichlet rows take the VALUE, as in the scripts; where both conditions hold: value1 if
+ *                              r_first_wins (e3), else value2 (e17, e18))
+ * u (B,1,ny,nx) fp32.  nu (1 | B,1,ny,nx).  Per condition k: bc_mask[k] NULL (no condition) or an fp32 / u8 image, shared
+ * (1,1,ny,nx) or per sample; the value is bc_field[k] (shared or per sample) or the constant bc_value[k].  Forcing: f_gp at the Gauss
+ * points (Bf,G,nely,nelx) with Bf = 1 (f_batched 0) or B, else the constant f_value.  out may be NULL; sumsq (1 double) / norm
+ * (1 float, sqrt of sumsq): fixed-order fp64 reduction in the kernel, needs `workspace` (zero-filled once before first use,
+ * dn_transport_workspace_bytes; one per stream, not shared with other operators).  out is bitwise independent of the batch it is
+ * computed in and of the launch plan; sumsq / norm are reproducible for a given mesh and batch size.
+ * vjp != 0: the vector-Jacobian product at the linearisation point u -- with the same masks, values and coefficients -- of the
+ * cotangent cot of R: out = d/du <cot, R>, zero on the Dirichlet nodes (the cotangent of a Dirichlet row of R is dropped):
+ *     q = L + tau (adv[0] L_x + adv[1] L_y),  A' = L r'(u),  B' = adv[0] q + kappa[0] nu L_x,  C' = adv[1] q + kappa[1] nu L_y
+ * with (L, L_x, L_y) the cotangent evaluated like a field; the forcing is not read, and u only where react[1..3] != 0.
+ * in_num (VJP only): cot is scaled by in_num[0] as it is loaded -- the VJP of the loss sum R^2 is this launch on the saved R with
+ * in_num = 2 gout; with in_den also: by in_num[0] / in_den[0] (0 where in_den[0] <= 0) -- the VJP of the norm, in_den = the norm.
+ * Coefficients of the scripts (h: element size), wscale = (h/2)^2:
+ *   e17: adv = (cos pi/6, sin pi/6), kappa = (D, D), tau = 1 / (2 |adv| / h + 4 D / h^2), react = 0, value1 = 1, value2 = 0;
+ *   e3:  adv = (0, 1), kappa = (D, 0), tau = h / 2, react = 0, value1 = the field u0, r_first_wins;
+ *   e18: adv = (0, 1), kappa = (D Cn^2, D Cn^2), tau = 0, react = (-D^2 k, 2 D^2 A, -6 D^2 A, 4 D^2 A), value1 = the field u0.
+ * DN_E_UNSUPPORTED for nsd != 2, degree != 1, ngp outside 2..4; DN_E_BADARG for a NULL u, no output at all, in_den without in_num,
+ * in_num outside the VJP mode, a VJP without its cotangent, flags outside {0, 1} or a bc_field without its mask; DN_E_WORKSPACE
+ * for a reduction without a large enough workspace; nothing is launched then. */
+typedef struct dn_transport_args {
+    const float *u;
+    const float *nu;
+    int32_t nu_batched;
+    int32_t r_first_wins;
+    const void *bc_mask[2];
+    int32_t mask_is_u8[2];
+    int32_t mask_batched[2];
+    const float *bc_field[2];
+    int32_t bc_field_batched[2];
+    float bc_value[2];
+    const float *f_gp;
+    int32_t f_batched;
+    float f_value;
+    float adv[2];
+    float kappa[2];
+    float tau;
+    float react[4];
+    float wscale;
+    int32_t vjp;
+    const float *cot;
+    float *out;
+    double *sumsq;
+    float *norm;
+    const float *in_num, *in_den;
+    void *workspace;
+    int64_t workspace_bytes;
+} dn_transport_args;
+int64_t dn_transport_workspace_bytes(const dn_mesh *mesh);
+int dn_transport_apply(const dn_mesh *mesh, const dn_transport_args *args, void *stream);
+
 /* ---- fused output block of the 2-D U-Net generator ----------------------------------------------------------
  * Upsample(x2, nearest) -> ZeroPad2d((1,0,1,0)) -> Conv2d(C -> 1, 4x4, padding 1, bias) -> Sigmoid
  * (DiffNet/networks/unets.py:68-74, `self.final`) without materialising the upsampled tensor.
