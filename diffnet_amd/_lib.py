@@ -86,6 +86,12 @@ class DnTransportArgs(C.Structure):
                 ("in_num", C.c_void_p), ("in_den", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class DnCoefGradArgs(C.Structure):
+    _fields_ = [("u", C.c_void_p), ("v", C.c_void_p), ("bc", DnDirichlet * 2),
+                ("a_nu", C.c_float), ("a_f", C.c_float), ("wscale", C.c_float),
+                ("in_scale", C.c_void_p), ("g_nu", C.c_void_p), ("g_f", C.c_void_p)]
+
+
 I32x3 = C.c_int32 * 3
 
 # name -> (restype, argtypes); must list every symbol of include/diffnet_hip.h
@@ -125,6 +131,7 @@ SYMBOLS = {
     "dn_ns_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnNsArgs), C.c_void_p]),
     "dn_transport_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
     "dn_transport_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnTransportArgs), C.c_void_p]),
+    "dn_poisson_coef_grad": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnCoefGradArgs), C.c_void_p]),
     "dn_upconv_out_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "dn_upconv_out_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                     C.c_void_p, C.c_int64, C.c_void_p]),

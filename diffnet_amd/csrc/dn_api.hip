@@ -17,20 +17,27 @@ extern "C" const char* dn_build_info(void) {
 // ---- tuning switches: one table, filled from DN_<KEY> when the library is loaded, changed only through dn_config_set ----
 namespace {
 const char* const kKeys[dn::CFG_COUNT] = {"PLAN2D", "PLAN3D", "PLAN_FSDT", "Q1_RULE_KERNEL", "GPE_GATHER", "GPE_TILED", "Q1_3D_T16", "Q1_3D_E1SUM", "FSDT_GENERIC", "Q1_3D_E1", "HANDOVER_SPIN_LIMIT", "CONV2D_V1", "CONV_WRW_WGS", "Q1_3D_N2", "FSDT_FORM"};
-char g_cfg[dn::CFG_COUNT][64];
+// Switches of the host layer (diffnet_amd/ops.py), kept in the same table so that one call and one DN_<KEY> convention serve both: no
+// kernel and no entry point reads them, so they choose between routes of the caller, never between forms of a launch.
+constexpr int kHostCount = 1;
+const char* const kHostKeys[kHostCount] = {"COEF_GRAD"};
+constexpr int kAllCount = dn::CFG_COUNT + kHostCount;
+char g_cfg[kAllCount][64];
+
+const char* key_name(int k) { return k < dn::CFG_COUNT ? kKeys[k] : kHostKeys[k - dn::CFG_COUNT]; }
 
 int key_index(const char* key) {
     if (!key) return -1;
-    for (int k = 0; k < dn::CFG_COUNT; ++k)
-        if (std::strcmp(key, kKeys[k]) == 0) return k;
+    for (int k = 0; k < kAllCount; ++k)
+        if (std::strcmp(key, key_name(k)) == 0) return k;
     return -1;
 }
 
 struct ConfigInit {
     ConfigInit() {
-        for (int k = 0; k < dn::CFG_COUNT; ++k) {
+        for (int k = 0; k < kAllCount; ++k) {
             char name[80] = "DN_";
-            std::strncat(name, kKeys[k], sizeof(name) - 4);
+            std::strncat(name, key_name(k), sizeof(name) - 4);
             const char* e = std::getenv(name);                   // the ONLY getenv of the library: once, at load
             g_cfg[k][0] = 0;
             if (e && std::strlen(e) < sizeof(g_cfg[k])) std::strcpy(g_cfg[k], e);

@@ -186,6 +186,11 @@ class DiffNetFEM(PDE):
     def energy_loss_and_grad(self, u, nu=None, f=None, f_gp=None, dirichlet=(), c=1.0, jac=1.0, out=None):
         return ops.energy_loss_and_grad(self.geom, u, nu, f, f_gp, dirichlet, c, jac, out=out)
 
+    def energy_loss_and_grads(self, u, nu=None, f=None, dirichlet=(), c=1.0, jac=1.0, wrt=("u", "nu", "f")):
+        """(loss, {"u": ..., "nu": ..., "f": ...}) of the energy loss outside autograd, from two launches (ops.energy_loss_and_grads): the
+        coefficient gradient of a topology optimisation (reference: examples/poisson/single_instance/16_topopt.py) without a graph."""
+        return ops.energy_loss_and_grads(self.geom, u, nu, f, dirichlet, c, jac, wrt)
+
     def residual(self, u, nu=None, f=None, f_gp=None, dirichlet=(), jac=1.0):
         """Assembled, Dirichlet-masked weak-form residual (12_klsum.py:80-126, e8_3d_poisson_mms.py:89-136)."""
         return ops.residual(self.geom, u, nu, f, f_gp, dirichlet, jac)

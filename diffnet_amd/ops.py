@@ -11,7 +11,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import DnDirichlet, DnFsdtArgs, DnMesh, DnNsArgs, DnPoissonArgs, DnStokesArgs, DnTransportArgs, I32x3, DiffNetHipError
+from ._lib import DnCoefGradArgs, DnDirichlet, DnFsdtArgs, DnMesh, DnNsArgs, DnPoissonArgs, DnStokesArgs, DnTransportArgs, I32x3, DiffNetHipError
 
 
 def _require(t, name, ndim=None, strict=False):
@@ -988,36 +988,57 @@ def composed_residual(geom, u, nu=None, f=None, f_gp=None, dirichlet=(), jac=1.0
 class _PoissonFn(torch.autograd.Function):
     """(out, sums, loss) of one dn_poisson_apply launch, differentiable wrt u -- the eager counterpart of the registered operator
     diffnet_mi::poisson_apply (torch_ops.py), whose dispatch costs ~100 us per call (204 -> ~60 us for an energy_loss + backward at
-    64^2, tools/host_profile.py); same formulas as torch_ops._pa_backward, and differentiable again (its backward calls `_fused`)."""
+    64^2, tools/host_profile.py); same formulas as torch_ops._pa_backward, and differentiable again (its backward calls `_fused`).
+    Also differentiable wrt nu and the nodal f: the operator is bilinear in ((nu, f), u~), and the transpose of u~ -> out with respect to
+    (nu, f) is one dn_poisson_coef_grad launch (`_coef`) per cotangent that arrives."""
 
     @staticmethod
     def forward(ctx, u, nu, f, f_gp, geom, dl, alpha, beta, c, wscale, out_scale, loss_scale):
         out, sums, loss = poisson_apply(geom, u, nu, f, f_gp, dl, alpha=alpha, beta=beta, c=c, wscale=wscale, out_scale=out_scale,
                                         want_out=True, want_sums=True, loss_scale=loss_scale)
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(out, nu)
+        ctx.save_for_backward(out, nu, u)
         ctx.meta = (geom, dl, alpha, beta, c, wscale, out_scale, loss_scale)
+        ctx.f_shape = tuple(f.shape) if isinstance(f, torch.Tensor) else None
         return out, sums, loss
 
     @staticmethod
     def backward(ctx, g_out, g_sums, g_loss):
-        out, nu = ctx.saved_tensors
+        out, nu, u = ctx.saved_tensors
         geom, dl, alpha, beta, c, wscale, out_scale, loss_scale = ctx.meta
+        need_u, need_nu, need_f = ctx.needs_input_grad[:3]
+        gnu = gf = None
+
+        def coef_add(v, a_nu, a_f, in_scale=None):
+            nonlocal gnu, gf
+            tn, tf = _coef(geom, u, v, dl, a_nu, a_f, wscale, need_nu, need_f, in_scale)
+            if tn is not None:
+                gnu = tn if gnu is None else gnu + tn
+            if tf is not None:
+                gf = tf if gf is None else gf + tf
+
+        if need_nu or need_f:
+            # out = out_scale Z (alpha K_nu u~ - beta F f);  sumsq = sum (out / out_scale)^2;  energy = sum W (c nu |grad u~|^2 - u~ f)
+            if g_out is not None:
+                coef_add(g_out.contiguous(), out_scale * alpha, -out_scale * beta)
+            if g_sums is not None:
+                coef_add(out * (2.0 / out_scale), alpha, -beta, g_sums[1:2].to(torch.float32))
         hom = tuple(Dirichlet(d.mask, 0.0) for d in dl)       # J = s alpha M K M is symmetric: J^T v is the same launch, homogeneous conditions, no forcing
 
         def K(v, scale):
             return _fused(geom, v, nu, None, None, hom, alpha, 0.0, 0.0, wscale, scale, 0.0)[0]
 
         gu = None
-        if g_out is not None:
+        if g_out is not None and need_u:
             gu = K(g_out.contiguous(), out_scale)
         coef = None
         if g_loss is not None:
             coef = g_loss * loss_scale
         if g_sums is not None:
             coef = g_sums[0].to(torch.float32) if coef is None else coef + g_sums[0].to(torch.float32)
-            t = K(out * (2.0 / out_scale), 1.0) * g_sums[1].to(torch.float32)
-            gu = t if gu is None else gu + t
+            if need_u:
+                t = K(out * (2.0 / out_scale), 1.0) * g_sums[1].to(torch.float32)
+                gu = t if gu is None else gu + t
         if coef is not None:
             if alpha != 2.0 * c or beta != 1.0:
                 if g_loss is not None or c != 0.0:
@@ -1025,7 +1046,13 @@ class _PoissonFn(torch.autograd.Function):
             else:
                 t = out * (coef / out_scale)
                 gu = t if gu is None else gu + t
-        return (gu,) + (None,) * 11
+                if need_nu or need_f:
+                    coef_add(None, c, -1.0, coef.reshape(1))
+        if gnu is not None and nu.shape[0] != gnu.shape[0]:
+            gnu = gnu.sum(0, keepdim=True)               # one coefficient shared by the batch
+        if gf is not None and ctx.f_shape[0] != gf.shape[0]:
+            gf = gf.sum(0, keepdim=True)
+        return (gu if need_u else None, gnu, gf) + (None,) * 9
 
 
 def _fused(geom, u, nu, f, f_gp, dirichlet, alpha, beta, c, wscale, out_scale, loss_scale):
@@ -1043,7 +1070,7 @@ def _fused(geom, u, nu, f, f_gp, dirichlet, alpha, beta, c, wscale, out_scale, l
     for d in dirichlet:
         if isinstance(d.mask, torch.Tensor) and d.mask.dtype == torch.int32:
             raise TypeError("Dirichlet mask images are float32, uint8 or bool; int32 tensors are reserved for bit-packed masks (wrap them in ops.PackedMask)")
-    if torch.is_grad_enabled() and isinstance(u, torch.Tensor) and u.requires_grad:
+    if _wants_grad(u, nu, None if isinstance(f, LoadVector) else f):
         return _PoissonFn.apply(u, nu, f, f_gp, geom, tuple(dirichlet), float(alpha), float(beta), float(c), float(wscale), float(out_scale),
                                 float(loss_scale))
     return poisson_apply(geom, u, nu, f, f_gp, dirichlet, alpha=alpha, beta=beta, c=c, wscale=wscale, out_scale=out_scale, want_out=True,
@@ -1051,10 +1078,11 @@ def _fused(geom, u, nu, f, f_gp, dirichlet, alpha, beta, c, wscale, out_scale, l
 
 
 def energy_loss(geom, u, nu=None, f=None, f_gp=None, dirichlet=(), c=1.0, jac=1.0):
-    """mean_{b,e} sum_g gpw_g*jac*(c*nu_g*|grad u|_g^2 - u_g*f_g).  One fused launch, differentiable wrt u; when nu / f /
-    f_gp / a Dirichlet value field requires a gradient the composed operator form runs instead (see composed_energy)."""
+    """mean_{b,e} sum_g gpw_g*jac*(c*nu_g*|grad u|_g^2 - u_g*f_g).  One fused launch, differentiable wrt u, and on Q1 meshes wrt nu and
+    the nodal f (one dn_poisson_coef_grad launch in the backward pass); when f_gp or a Dirichlet value field requires a gradient, or on
+    Q2 / Q3 meshes, the composed operator form runs instead (see composed_energy)."""
     dirichlet = tuple(_norm_dirichlet(dirichlet))
-    if _extra_grad_inputs(nu, f, f_gp, dirichlet):
+    if _extra_grad_inputs(nu, f, f_gp, dirichlet) and not _coef_route(geom, u, f_gp, dirichlet):
         return composed_energy(geom, u, nu, f, f_gp, dirichlet, float(c), float(jac))
     scale = 1.0 / (u.shape[0] * geom.nelem_total)
     return _fused(geom, u, nu, f, f_gp, dirichlet, 2.0 * c, 1.0, c, jac, scale, scale)[2]
@@ -1073,16 +1101,189 @@ def energy_loss_and_grad(geom, u, nu=None, f=None, f_gp=None, dirichlet=(), c=1.
 
 def residual(geom, u, nu=None, f=None, f_gp=None, dirichlet=(), jac=1.0):
     dirichlet = tuple(_norm_dirichlet(dirichlet))
-    if _extra_grad_inputs(nu, f, f_gp, dirichlet):
+    if _extra_grad_inputs(nu, f, f_gp, dirichlet) and not _coef_route(geom, u, f_gp, dirichlet):
         return composed_residual(geom, u, nu, f, f_gp, dirichlet, float(jac))
     return _fused(geom, u, nu, f, f_gp, dirichlet, 1.0, 1.0, 0.0, jac, 1.0, 0.0)[0]
 
 
 def residual_loss(geom, u, nu=None, f=None, f_gp=None, dirichlet=(), jac=1.0):
     dirichlet = tuple(_norm_dirichlet(dirichlet))
-    if _extra_grad_inputs(nu, f, f_gp, dirichlet):
+    if _extra_grad_inputs(nu, f, f_gp, dirichlet) and not _coef_route(geom, u, f_gp, dirichlet):
         return torch.sum(composed_residual(geom, u, nu, f, f_gp, dirichlet, float(jac)) ** 2)
     return _fused(geom, u, nu, f, f_gp, dirichlet, 1.0, 1.0, 0.0, jac, 1.0, 0.0)[1][1].to(torch.float32)
+
+
+# ---- gradient wrt the coefficient and the forcing (dn_poisson_coef_grad) --------------------------------------------------------------
+# The fused operator is bilinear in ((nu, f), u~).  Its transpose with respect to (nu, f) is again a per-element quadrature followed by
+# element -> node assembly: one launch (csrc/poisson_coef_grad.hip), no workspace, no reduction -- it touches no operator's workspace and
+# no deferred partial sums, so it may stand between any two launches of a chained pair.
+_COEF_STATS = {"launch": 0}
+
+
+def _coef_route(geom, u, f_gp, dirichlet):
+    """Does the fused route differentiate this call wrt nu / f?  Q1 meshes with rules of 2 to 4 points, eager mode, no gradient asked for
+    f_gp or a Dirichlet value field, and dn_config_set("COEF_GRAD", "composed") not set (the route of before, for A/B runs)."""
+    if torch.compiler.is_compiling() or _lib.CONFIG_MIRROR.get("COEF_GRAD") == "composed":
+        return False
+    if geom.deg != 1 or not 2 <= geom.ngp_1d <= 4 or not (isinstance(u, torch.Tensor) and u.is_cuda):
+        return False
+    return not _wants_grad(f_gp, *[d.value for d in dirichlet])
+
+
+def poisson_coef_grad(geom, u, v=None, dirichlet=(), a_nu=1.0, a_f=1.0, wscale=1.0, want=("nu", "f"), in_scale=None):
+    """One launch of dn_poisson_coef_grad (include/diffnet_hip.h): (g_nu | None, g_f | None), fresh (B,1,*N) tensors,
+        g_nu[a] = a_nu s sum_e sum_g W_g N_a grad v_g . grad u~_g,    g_f[a] = a_f s sum_e sum_g W_g N_a v_g,    W_g = gpw_g wscale
+    with u~ = u after the Dirichlet conditions, v read as zero on every Dirichlet node (v=None: v = u~) and s = in_scale[0] (a one-element
+    float32 device tensor) or 1.  Outside autograd; Q1 meshes only.  PackedMask / BoxFaces conditions are expanded to their images."""
+    nsd = geom.nsd
+    u = _require(u, "u", nsd + 2)
+    B = u.shape[0]
+    node_shape = tuple(geom.node_shape)
+    if tuple(u.shape[1:]) != (1, *node_shape):
+        raise ValueError(f"u has shape {tuple(u.shape)}, expected (B,1,{','.join(map(str, node_shape))})")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("nu", "f") for w in want):
+        raise ValueError('want must name "nu" and / or "f"')
+    keep = [u]
+    args = DnCoefGradArgs()
+    args.u = u.data_ptr()
+    if v is not None:
+        v = _require(v, "v", nsd + 2)
+        if v.shape != u.shape or v.device != u.device:
+            raise ValueError("v must have u's shape and device")
+        keep.append(v)
+        args.v = v.data_ptr()
+    dl = _norm_dirichlet(dirichlet)
+    imgs = []
+    for d in dl:
+        m = _mask_image(d.mask, u)
+        if not isinstance(m, torch.Tensor) or not m.is_cuda:
+            raise DiffNetHipError("Dirichlet mask must be a CUDA tensor")
+        if m.dtype == torch.bool:
+            m = m.to(torch.uint8)
+        if m.dtype not in (torch.float32, torch.uint8):
+            raise TypeError("Dirichlet mask must be float32, uint8 or bool")
+        m = m.contiguous()
+        if m.dim() != nsd + 2 or tuple(m.shape[1:]) != (1, *node_shape) or m.shape[0] not in (1, B):
+            raise ValueError(f"Dirichlet mask shape {tuple(m.shape)} does not match u")
+        imgs.append(m)
+    if len(imgs) == 2 and imgs[0].dtype != imgs[1].dtype:       # the kernels read both images in one format
+        imgs = [(m > 0.5).to(torch.uint8) if m.dtype == torch.float32 else m for m in imgs]
+    for k, (d, m) in enumerate(zip(dl, imgs)):
+        keep.append(m)
+        bc = args.bc[k]
+        bc.mask = m.data_ptr()
+        bc.mask_kind = _lib.MASK_U8 if m.dtype == torch.uint8 else _lib.MASK_F32
+        bc.mask_batched = int(m.shape[0] == B)
+        if isinstance(d.value, torch.Tensor):
+            val = d.value
+            if val.dim() == nsd:
+                val = val[(None,) * 2]
+            val = _require(val.detach().to(u.device), "Dirichlet value", nsd + 2)
+            if tuple(val.shape[1:]) != (1, *node_shape) or val.shape[0] not in (1, B):
+                raise ValueError("Dirichlet value field shape does not match u")
+            keep.append(val)
+            bc.field = val.data_ptr()
+            bc.field_batched = int(val.shape[0] == B)
+        else:
+            bc.value = float(d.value)
+    args.a_nu, args.a_f, args.wscale = float(a_nu), float(a_f), float(wscale)
+    if in_scale is not None:
+        in_scale = _require(in_scale, "in_scale")
+        if in_scale.numel() != 1 or in_scale.device != u.device:
+            raise ValueError("in_scale must hold one float on u's device")
+        keep.append(in_scale)
+        args.in_scale = in_scale.data_ptr()
+    g_nu = torch.empty_like(u) if "nu" in want else None
+    g_f = torch.empty_like(u) if "f" in want else None
+    args.g_nu = g_nu.data_ptr() if g_nu is not None else None
+    args.g_f = g_f.data_ptr() if g_f is not None else None
+    mesh = geom.mesh_struct(B)
+    rc = _lib.lib().dn_poisson_coef_grad(C.byref(mesh), C.byref(args), _stream(u))
+    if rc:
+        _lib.check(rc, "dn_poisson_coef_grad")
+    _COEF_STATS["launch"] += 1
+    return g_nu, g_f
+
+
+class _CoefFn(torch.autograd.Function):
+    """(g_nu, g_f) of one dn_poisson_coef_grad launch, differentiable wrt u and v -- the composed route it replaces can be differentiated
+    twice, so this one can.  For cotangents (mu, mu_f):  <mu, g_nu> = a_nu <v, K_mu u~>  and  <mu_f, g_f> = a_f <v, M mu_f>  (K_mu the
+    stiffness operator with coefficient mu, M the load operator), so the pullbacks are launches of the fused Poisson operator itself
+    (`_fused`: they nest like _PoissonFn): to v, Z (a_nu K_mu u~ + a_f M mu_f); to u, a_nu Z K_mu v; with v absent the two collapse into
+    the energy-gradient operator with (nu, f) := (a_nu mu, -a_f mu_f) and alpha = 2."""
+
+    @staticmethod
+    def forward(ctx, u, v, geom, dl, a_nu, a_f, wscale, want_nu, want_f):
+        want = (("nu",) if want_nu else ()) + (("f",) if want_f else ())
+        g_nu, g_f = poisson_coef_grad(geom, u, v, dl, a_nu, a_f, wscale, want)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(u, v)
+        ctx.meta = (geom, dl, a_nu, a_f, wscale)
+        return g_nu, g_f
+
+    @staticmethod
+    def backward(ctx, mu, mu_f):
+        u, v = ctx.saved_tensors
+        geom, dl, a_nu, a_f, wscale = ctx.meta
+        gu = gv = None
+        if mu is None and mu_f is None:
+            return (None,) * 9
+        mu = None if mu is None else mu.contiguous()
+        mu_f = None if mu_f is None else mu_f.contiguous()
+        if v is None:
+            if ctx.needs_input_grad[0]:
+                gu = _fused(geom, u, None if mu is None else a_nu * mu, None if mu_f is None else -a_f * mu_f, None, dl,
+                            2.0 if mu is not None else 0.0, 1.0, 0.0, wscale, 1.0, 0.0)[0]
+        else:
+            if ctx.needs_input_grad[0] and mu is not None:
+                hom = tuple(Dirichlet(d.mask, 0.0) for d in dl)
+                gu = _fused(geom, v, mu, None, None, hom, a_nu, 0.0, 0.0, wscale, 1.0, 0.0)[0]
+            if ctx.needs_input_grad[1]:
+                gv = _fused(geom, u, mu, mu_f, None, dl, a_nu if mu is not None else 0.0, -a_f, 0.0, wscale, 1.0, 0.0)[0]
+        return (gu, gv) + (None,) * 7
+
+
+def _coef(geom, u, v, dl, a_nu, a_f, wscale, want_nu, want_f, in_scale=None):
+    """poisson_coef_grad as a differentiable function of u, v and in_scale (autograd.Function where one of them requires a gradient -- a
+    backward pass under create_graph --, the bare launch with the scale applied by the kernel otherwise)."""
+    if _wants_grad(u, v, in_scale):
+        g_nu, g_f = _CoefFn.apply(u, v, geom, tuple(dl), float(a_nu), float(a_f), float(wscale), bool(want_nu), bool(want_f))
+        if in_scale is not None:
+            g_nu = None if g_nu is None else g_nu * in_scale
+            g_f = None if g_f is None else g_f * in_scale
+        return g_nu, g_f
+    want = (("nu",) if want_nu else ()) + (("f",) if want_f else ())
+    return poisson_coef_grad(geom, u, v, dl, a_nu, a_f, wscale, want, in_scale)
+
+
+def energy_loss_and_grads(geom, u, nu=None, f=None, dirichlet=(), c=1.0, jac=1.0, wrt=("u", "nu", "f")):
+    """(loss, {"u": dloss/du, "nu": dloss/dnu, "f": dloss/df} restricted to `wrt`) of the energy loss from TWO launches, outside autograd:
+    the fused operator (loss and u gradient) and dn_poisson_coef_grad (nu and f gradients) -- the optimiser-loop form, the sibling of
+    energy_loss_and_grad.  A nu / f shared by the batch, shape (1,1,*N), receives the sum over the samples.  Q1 meshes."""
+    wrt = (wrt,) if isinstance(wrt, str) else tuple(wrt)
+    if any(w not in ("u", "nu", "f") for w in wrt):
+        raise ValueError('wrt must name "u", "nu" and / or "f"')
+    dl = tuple(_norm_dirichlet(dirichlet))
+    B = u.shape[0]
+    scale = 1.0 / (B * geom.nelem_total)
+    ud = u.detach()
+    nud = nu.detach() if isinstance(nu, torch.Tensor) else nu
+    fd = f.detach() if isinstance(f, torch.Tensor) else f
+    grad, _, loss = poisson_apply(geom, ud, nud, fd, None, dl, alpha=2.0 * c, beta=1.0, c=c, wscale=jac, out_scale=scale,
+                                  want_out="u" in wrt, want_sums=True, loss_scale=scale)
+    grads = {}
+    if "u" in wrt:
+        grads["u"] = grad
+    want = tuple(w for w in ("nu", "f") if w in wrt)
+    if want:
+        g_nu, g_f = poisson_coef_grad(geom, ud, None, dl, scale * c, -scale, jac, want)
+        for name, g, src in (("nu", g_nu, nud), ("f", g_f, fd)):
+            if g is not None:
+                if isinstance(src, torch.Tensor) and src.shape[0] != B:
+                    g = g.sum(0, keepdim=True)
+                grads[name] = g
+    return loss, grads
 
 
 _FSDT_WS_BYTES = {}

@@ -52,7 +52,11 @@ extern "C" {
  *   dn_conv2d_k4s2_wrw launch aims at when it splits K; default 1024), "Q1_3D_N2" (non-empty: the round-3 per-Gauss-point form of the 3-D Q1
  *   two-element kernel also where the closed-form-in-z kernel of round 4, csrc/poisson3d_q1_cf.hip, applies),
  *   "FSDT_FORM" ("elem": dn_fsdt_apply runs the element form of rounds 1-3, csrc/fsdt.hip, instead of the assembled-stencil form of round 4,
- *   csrc/fsdt_st.hip, which is the default for Q1 and Q2 meshes; "stencil": the stencil form also for Q3 meshes, where the element form is the default).  value NULL or "" clears the switch.
+ *   csrc/fsdt_st.hip, which is the default for Q1 and Q2 meshes; "stencil": the stencil form also for Q3 meshes, where the element form is the default).
+ *   dn_poisson_coef_grad takes the node rows per strip of its 2-D launch from the R of "PLAN2D" (its results do not depend on it).
+ *   Beside these, the table keeps the switches of the HOST layer (kHostKeys in csrc/dn_api.hip), which no kernel or entry point reads:
+ *   "COEF_GRAD" ("composed": diffnet_amd.ops differentiates the Poisson losses with respect to nu / f on the composed operators, as
+ *   before dn_poisson_coef_grad existed, instead of with that launch).  value NULL or "" clears the switch.
  * Returns 0, or DN_E_BADARG for an unknown key / over-long value.  Not thread-safe against concurrent launches.
  * No reference counterpart (the reference has no tuning surface). */
 int dn_config_set(const char *key, const char *value);
@@ -465,6 +469,38 @@ typedef struct dn_transport_args {
 } dn_transport_args;
 int64_t dn_transport_workspace_bytes(const dn_mesh *mesh);
 int dn_transport_apply(const dn_mesh *mesh, const dn_transport_args *args, void *stream);
+
+/* ---- gradient of the Poisson losses with respect to the nodal coefficient and forcing ------------------------------------
+ * Replaces what autograd does for the coefficient in the topology optimisation of the reference,
+ * examples/poisson/single_instance/16_topopt.py:119-195 (loss = 0.5 nu grad u . grad v - v f with nu from the network, compliance
+ * = -u f): backward through the Gauss-point evaluations of nu, u and f and the elementwise integrand, in ONE launch.
+ * The gradient of the energy with respect to u is linear in (nu, f); this operator is the transpose of that map:
+ *     g_nu[a] = a_nu * s * sum_{e contains a} sum_g W_g N_a(g) grad v_g . grad u~_g
+ *     g_f [a] = a_f  * s * sum_{e contains a} sum_g W_g N_a(g) v_g                      W_g = gpw_g * wscale,  s = in_scale[0] or 1
+ * u~ is u after bc[0], bc[1] (applied in order, as in dn_poisson_args); v (B,1,*N) is read as ZERO on every Dirichlet node; v NULL:
+ * v = u~ (Dirichlet values included).  g_nu, g_f: (B,1,*N), one value per node and sample, either may be NULL (not both).
+ *   energy loss  s_l sum W (c nu |grad u~|^2 - u~ f):   d/dnu = g_nu (v NULL, a_nu = s_l c),  d/df = g_f (v NULL, a_f = -s_l)
+ *   residual R = Z (K_nu u~ - F f), cotangent lambda:   d<lambda,R>/dnu = g_nu (v = lambda, a_nu = 1),  d/df = g_f (v = lambda, a_f = -1)
+ *   compliance-style functionals: g_f alone.
+ * in_scale: optional device float multiplied into both outputs (the upstream grad_output without a host synchronisation).
+ * Mesh: degree 1, ngp 2..4; nsd = 2 (the marching kernel of dn_transport_apply) or nsd = 3 (a plain one-thread-per-node form:
+ * correct and deterministic, not optimised).  Conditions: DN_MASK_F32 / DN_MASK_U8 images (both of the same format when there are
+ * two), shared or per sample, constant value or value field.  No workspace, no reduction, no atomics: every node is written once with
+ * the same additions in the same order under any launch plan and batch size -- the outputs are bitwise reproducible and bitwise
+ * independent of the batch they are computed in.
+ * DN_E_UNSUPPORTED for degree > 1, ngp outside 2..4, DN_MASK_BITS / DN_MASK_BOX conditions (expand them: dn_unpack_mask_bits) or two
+ * images of different formats; Gauss-point forcing has no nodal gradient and is not an argument.  DN_E_BADARG for a NULL u, no output
+ * at all, flags outside {0, 1} or a value field without its mask; nothing is launched then. */
+typedef struct dn_coef_grad_args {
+    const float *u;        /* (B,1,*N) nodal field                                      */
+    const float *v;        /* (B,1,*N) second field or NULL (v = u~)                    */
+    dn_dirichlet bc[2];    /* applied in order                                          */
+    float a_nu, a_f, wscale;
+    const float *in_scale; /* optional: one device float                                */
+    float *g_nu;           /* (B,1,*N) or NULL                                          */
+    float *g_f;            /* (B,1,*N) or NULL                                          */
+} dn_coef_grad_args;
+int dn_poisson_coef_grad(const dn_mesh *mesh, const dn_coef_grad_args *args, void *stream);
 
 /* ---- fused output block of the 2-D U-Net generator ----------------------------------------------------------
  * Upsample(x2, nearest) -> ZeroPad2d((1,0,1,0)) -> Conv2d(C -> 1, 4x4, padding 1, bias) -> Sigmoid
