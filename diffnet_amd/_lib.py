@@ -86,6 +86,14 @@ class DnTransportArgs(C.Structure):
                 ("in_num", C.c_void_p), ("in_den", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class DnStrongformArgs(C.Structure):
+    _fields_ = [("u", C.c_void_p), ("f", C.c_void_p), ("f_gp", C.c_void_p), ("f_batched", C.c_int32), ("f_value", C.c_float),
+                ("bc", DnDirichlet * 2),
+                ("ax", C.c_float), ("ay", C.c_float), ("b", C.c_float), ("dxx", C.c_float), ("dyy", C.c_float), ("fs", C.c_float),
+                ("wscale", C.c_float), ("out_scale", C.c_float), ("d2basis", (C.c_float * 4) * 4),
+                ("in_scale", C.c_void_p), ("grad", C.c_void_p), ("sum", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class DnCoefGradArgs(C.Structure):
     _fields_ = [("u", C.c_void_p), ("v", C.c_void_p), ("bc", DnDirichlet * 2),
                 ("a_nu", C.c_float), ("a_f", C.c_float), ("wscale", C.c_float),
@@ -131,6 +139,8 @@ SYMBOLS = {
     "dn_ns_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnNsArgs), C.c_void_p]),
     "dn_transport_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
     "dn_transport_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnTransportArgs), C.c_void_p]),
+    "dn_strongform_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
+    "dn_strongform_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnStrongformArgs), C.c_void_p]),
     "dn_poisson_coef_grad": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnCoefGradArgs), C.c_void_p]),
     "dn_upconv_out_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "dn_upconv_out_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,

@@ -35,8 +35,8 @@ class FemGeometry:
         self.nelem_total = int(np.prod(self.nel))
         self.nnode_total = int(np.prod(self.sizes))
         self.gpx_1d, self.gpw_1d = np.asarray(gpx_1d, float), np.asarray(gpw_1d, float)
-        B, D, _ = Basis1D(deg).at_gauss(self.gpx_1d)
-        self.basis, self.dbasis = B, D
+        B, D, D2 = Basis1D(deg).at_gauss(self.gpx_1d)
+        self.basis, self.dbasis, self.d2basis = B, D, D2
         self._mesh = {}
         # everything a launch takes from the geometry, as a hashable value (ops.poisson_apply keys its cached prepared calls on it)
         self.key = (nsd, deg, ngp_1d, self.sizes, self.hs, tuple(float(x) for x in self.gpx_1d), tuple(float(x) for x in self.gpw_1d))

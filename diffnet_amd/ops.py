@@ -11,7 +11,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import DnCoefGradArgs, DnDirichlet, DnFsdtArgs, DnMesh, DnNsArgs, DnPoissonArgs, DnStokesArgs, DnTransportArgs, I32x3, DiffNetHipError
+from ._lib import DnCoefGradArgs, DnDirichlet, DnFsdtArgs, DnMesh, DnNsArgs, DnPoissonArgs, DnStokesArgs, DnStrongformArgs, DnTransportArgs, I32x3, DiffNetHipError
 
 
 def _require(t, name, ndim=None, strict=False):
@@ -601,12 +601,14 @@ def call_cache_clear():
         _STOKES.cache.clear()
         _NS.cache.clear()
         _TRANSPORT.cache.clear()
+        _STRONGFORM.cache.clear()
         _PACK_CACHE.clear()
     _POISSON_WS_BYTES.clear()
     _FSDT_WS_BYTES.clear()
     _STOKES.ws_bytes.clear()
     _NS.ws_bytes.clear()
     _TRANSPORT.ws_bytes.clear()
+    _STRONGFORM.ws_bytes.clear()
 
 
 class PoissonPlan:
@@ -1571,7 +1573,7 @@ _NS = _Flow2dOp("ns_apply", DnNsArgs)
 
 def _flow2d_workspace(op, mesh, B, dev):
     """The operator's reduction workspace on the current stream of `dev`, large enough for `mesh`."""
-    key = (mesh.nx, mesh.ny, mesh.ngp, B)
+    key = (mesh.nx, mesh.ny, mesh.degree, mesh.ngp, B)
     nbytes = op.ws_bytes.get(key)
     if nbytes is None:
         nbytes = getattr(_lib.lib(), op.ws_fn)(C.byref(mesh))
@@ -2040,6 +2042,184 @@ def transport_apply(geom, u, nu=None, bc=None, bc_values=(0.0, 0.0), r_first_win
     if rc:
         _lib.check(rc, op.fn)
     return (out, sums, norm) if want_norm else (out, sums)
+
+
+# ---- the fused 2-D strong-form least-squares loss and its gradient: dn_strongform_apply ----------------------------------------
+# Its own reduction workspace per (device, stream), prepared-call cache and launch lock, like _TRANSPORT and for the same reason.
+_STRONGFORM = _Flow2dOp("strongform_apply", DnStrongformArgs)
+
+
+def _strongform_check_mesh(geom):
+    if geom.nsd != 2 or geom.deg not in (1, 2, 3) or not 2 <= geom.ngp_1d <= 4 or (geom.deg > 1 and geom.ngp_1d < 3):
+        raise DiffNetHipError(f"strongform_apply: 2-D meshes of degree 1..3 with 2..4 Gauss points per axis (3 or 4 above degree 1) only "
+                              f"(nsd {geom.nsd}, degree {geom.deg}, ngp {geom.ngp_1d})")
+    if any((n - 1) % geom.deg for n in geom.sizes):
+        raise ValueError(f"strongform_apply: a degree-{geom.deg} mesh needs (n - 1) % {geom.deg} == 0 nodes per axis, got {geom.sizes}")
+
+
+def _strongform_key(geom, u, bc2, vals, f, f_gp, consts, in_scale, flags):
+    """Key of a cached prepared call (see _call_key); None when an argument needs a conversion copy."""
+    if not (isinstance(u, torch.Tensor) and u.is_cuda and tuple(u.shape[1:]) == (1, *geom.node_shape)):
+        return None
+    parts = [geom.key, u.device.index, _raw_stream(u.device), consts, flags]
+    k = _tkey(u)
+    if k is None or k == 0 or k[1] != torch.float32:
+        return None
+    parts.append(k)
+    for m in bc2:
+        k = _tkey(m)
+        if k is None or (k != 0 and k[1] not in (torch.float32, torch.uint8, torch.bool)):
+            return None
+        parts.append(k)
+    for v in tuple(vals) + (f_gp,):
+        if isinstance(v, torch.Tensor) and v.numel() > 1:
+            k = _tkey(v)
+            if k is None or k[1] != torch.float32:
+                return None
+            parts.append(k)
+        else:
+            parts.append(float(v))
+    for t in (f, in_scale):
+        k = _tkey(t)
+        if k is None or (k != 0 and k[1] != torch.float32):
+            return None
+        parts.append(k)
+    return tuple(parts)
+
+
+def _prepare_strongform(geom, u, bc2, vals, f, f_gp, consts, in_scale, want_sum):
+    """Validation + argument struct of a dn_strongform_apply call, outputs left unset: (mesh, args, tensors to keep alive, field shape)."""
+    name = _STRONGFORM.name
+    _strongform_check_mesh(geom)
+    u = _require(u, "u", 4)
+    B = u.shape[0]
+    shape = (B, 1, *geom.node_shape)
+    if tuple(u.shape) != shape:
+        raise ValueError(f"{name}: field shape {tuple(u.shape)} != {shape}")
+    keep = [u]
+    args = DnStrongformArgs()
+    args.u = u.data_ptr()
+    nn = geom.nnode_total
+
+    def batched(t, what):
+        if tuple(t.shape[-2:]) != tuple(geom.node_shape) or t.numel() not in (B * nn, nn):
+            raise ValueError(f"{name}: {what} shape {tuple(t.shape)} does not match the mesh {shape}")
+        return 1 if (t.numel() == B * nn and B > 1) else 0
+
+    for k, m in enumerate(bc2):
+        if m is None:
+            continue
+        if not isinstance(m, torch.Tensor):
+            raise TypeError(f"{name}: bc[{k}] must be a tensor or None (expand a PackedMask / BoxFaces to its image)")
+        if not m.is_cuda:
+            raise DiffNetHipError(f"{name}: bc[{k}] is on {m.device}: the FEM ops run on the GPU only (no CPU fallback)")
+        if m.dtype in (torch.bool, torch.uint8):
+            m = m.contiguous()
+            m = m.view(torch.uint8) if m.dtype == torch.bool else m
+            args.bc[k].mask_kind = _lib.MASK_U8
+        else:
+            m = _require(m, f"bc[{k}]")
+            args.bc[k].mask_kind = _lib.MASK_F32
+        args.bc[k].mask_batched = batched(m, f"bc[{k}]")
+        args.bc[k].mask = m.data_ptr()
+        keep.append(m)
+    for k, val in enumerate(vals):
+        if isinstance(val, torch.Tensor) and val.numel() > 1:
+            if bc2[k] is None:
+                raise ValueError(f"{name}: bc_values[{k}] is a field but condition {k} has no mask")
+            val = _require(val, f"bc_values[{k}]")
+            args.bc[k].field_batched = batched(val, f"bc_values[{k}]")
+            args.bc[k].field = val.data_ptr()
+            keep.append(val)
+        else:
+            args.bc[k].value = float(val)
+    G, nel = geom.ngp_total, geom.nelem_total
+    if f is not None:
+        if isinstance(f_gp, torch.Tensor) and f_gp.numel() > 1:
+            raise ValueError(f"{name}: nodal forcing f and Gauss-point forcing f_gp exclude each other")
+        f = _require(f, "f")
+        args.f_batched = batched(f, "f")
+        args.f = f.data_ptr()
+        keep.append(f)
+    elif isinstance(f_gp, torch.Tensor) and f_gp.numel() > 1:
+        f_gp = _require(f_gp, "f_gp")
+        if tuple(f_gp.shape[-3:]) != (G, *geom.elem_shape) or f_gp.numel() not in (G * nel, B * G * nel):
+            raise ValueError(f"{name}: f_gp shape {tuple(f_gp.shape)} is not (B | 1, {G}, {geom.elem_shape[0]}, {geom.elem_shape[1]})")
+        args.f_batched = 1 if (f_gp.numel() == B * G * nel and B > 1) else 0
+        args.f_gp = f_gp.data_ptr()
+        keep.append(f_gp)
+    else:
+        args.f_value = float(f_gp)
+    if in_scale is not None:
+        in_scale = _require(in_scale, "in_scale")
+        if in_scale.numel() != 1 or in_scale.device != u.device:
+            raise ValueError(f"{name}: in_scale must hold one float on u's device")
+        args.in_scale = in_scale.data_ptr()
+        keep.append(in_scale)
+    args.ax, args.ay, args.b, args.dxx, args.dyy, args.fs, args.wscale, args.out_scale = consts
+    for i in range(geom.ngp_1d):             # phi''(xi_ig) from the rule's own (truncated) abscissae, as the reference's tables
+        for j in range(geom.deg + 1):
+            args.d2basis[i][j] = geom.d2basis[i, j]
+    mesh = geom.mesh_struct(B)
+    if want_sum:
+        ws = _flow2d_workspace(_STRONGFORM, mesh, B, u.device)
+        keep.append(ws)
+        args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    return mesh, args, keep, shape
+
+
+def strongform_apply(geom, u, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=None, coef=(0.0, 0.0, 0.0, 0.0, 0.0, 0.0), wscale=1.0,
+                     out_scale=1.0, in_scale=None, want_grad=True, want_sum=True):
+    """One launch of dn_strongform_apply (include/diffnet_hip.h): sum_{b,e,g} W_g r_g^2 of the strong-form residual
+    r = ax u_x + ay u_y + b u u_x + dxx u_xx + dyy u_yy + fs f of the field u (B,1,ny,nx) as a float64 device tensor (1,) and / or
+    its gradient with respect to u times `out_scale` (times in_scale[0], a float32 device tensor of 1, where given).  `coef`:
+    (ax, ay, b, dxx, dyy, fs); `bc`: None, one mask or a pair (either None), fp32 (`> 0.5`) or bool / uint8, per sample or shared;
+    `bc_values[k]`: float or tensor u takes under condition k (where both hold, condition 2's); the forcing: a nodal field `f`
+    (B | 1,1,ny,nx), or `f_gp`, a float or a Gauss-point tensor (B | 1, G, nely, nelx).  Degree 1..3.  Returns (grad | None, sum | None).
+    Calls on the same buffers reuse their prepared argument structs (small LRU, fresh outputs per call: see poisson_apply)."""
+    _strongform_check_mesh(geom)
+    bc2, vals, coef = transport_bc2(bc), tuple(bc_values), tuple(float(x) for x in coef)
+    if len(vals) != 2:
+        raise ValueError("strongform_apply: bc_values must hold two entries")
+    if len(coef) != 6:
+        raise ValueError("strongform_apply: coef holds (ax, ay, b, dxx, dyy, fs)")
+    if not (want_grad or want_sum):
+        raise ValueError("strongform_apply: nothing to compute (want_grad and want_sum are both off)")
+    fg = 0.0 if f_gp is None else f_gp
+    consts = (*coef, float(wscale), float(out_scale))
+    op = _STRONGFORM
+    key = _strongform_key(geom, u, bc2, vals, f, fg, consts, in_scale, (want_grad, want_sum))
+    ent = None
+    if key is not None:
+        with _WS_LOCK:
+            ent = op.cache.get(key)
+            if ent is not None:
+                op.cache.move_to_end(key)
+    if ent is None:
+        _CALL_STATS["miss" if key is not None else "uncached"] += 1
+        mesh, args, keep, shape = _prepare_strongform(geom, u, bc2, vals, f, fg, consts, in_scale, want_sum)
+        with _WS_LOCK:
+            live_ws = list(op.ws.values())
+        # an uncached call keeps its (possibly converted) tensors alive until it has been issued; a cached one only the workspace
+        ent = (mesh, args, C.byref(mesh), C.byref(args), shape, keep if key is None else [t for t in keep if any(t is x for x in live_ws)])
+        if key is not None:
+            with _WS_LOCK:
+                op.cache[key] = ent
+                while len(op.cache) > _CALL_CACHE_MAX:
+                    op.cache.popitem(last=False)
+    else:
+        _CALL_STATS["hit"] += 1
+    mesh, args, mref, aref, shape = ent[:5]
+    dev = u.device
+    grad = torch.empty(shape, dtype=torch.float32, device=dev) if want_grad else None
+    sums = torch.empty(1, dtype=torch.float64, device=dev) if want_sum else None
+    with op.launch_lock:               # pointer patch + launch of the (possibly shared, cached) argument struct as one step
+        args.grad = grad.data_ptr() if want_grad else None
+        args.sum = sums.data_ptr() if want_sum else None
+        rc = _lib.lib().dn_strongform_apply(mref, aref, _stream(u))
+    if rc:
+        _lib.check(rc, op.fn)
+    return grad, sums
 
 
 def compute_winding_nodes(points, normals, area, q):

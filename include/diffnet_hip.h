@@ -470,6 +470,52 @@ typedef struct dn_transport_args {
 int64_t dn_transport_workspace_bytes(const dn_mesh *mesh);
 int dn_transport_apply(const dn_mesh *mesh, const dn_transport_args *args, void *stream);
 
+/* ---- fused 2-D strong-form least-squares loss and its gradient ------------------------------------------------------------
+ * Replaces the loss bodies of the strong-form scripts of the reference, the only callers of its second-derivative Gauss-point
+ * evaluations: examples/burgers/single_instance/01_2d_space_time.py:73-96 (Burgers.loss: space-time Burgers on Q2, y is time) and
+ * examples/poisson/single_instance/10_manufactured_strong_form_higher_order.py:69-96 (Poisson.loss: strong-form Poisson on Q3) -- the
+ * two Dirichlet substitutions, 4-5 Gauss-point evaluations, the weighted sum of squares and the autograd backward through all of it,
+ * in ONE launch that reads u once.  Mesh: nsd = 2, degree 1..3, ngp 2..4 (>= 3 for degree > 1), (n - 1) % degree == 0.
+ *   u~ = u after bc[0] then bc[1] (applied in order, as in dn_poisson_args: where both hold, condition 2's value is used)
+ *   at every Gauss point, from u~:   r_g = ax u_x + ay u_y + b u u_x + dxx u_xx + dyy u_yy + fs f_g        (x is the fastest axis)
+ *   sum    = sum_{b,e,g} W_g r_g^2,   W_g = gpw_g * wscale        (one double, unscaled; fixed-order fp64 reduction in the kernel)
+ *   grad_a = out_scale * s * sum_{e contains a} sum_g 2 W_g r_g ( ax Nx_a + ay Ny_a + b (N_a u_x + u Nx_a) + dxx Nxx_a + dyy Nyy_a )
+ *   grad is zero on the Dirichlet nodes;  s = in_scale[0] when that device float is given, else 1.
+ * u, grad (B,1,ny,nx) fp32.  The forcing f_g is the nodal field f (1 | B,1,ny,nx) interpolated with the basis, or f_gp at the Gauss
+ * points (Bf,G,nely,nelx) with Bf = 1 (f_batched 0) or B, or the constant f_value; f and f_gp exclude each other.  Conditions:
+ * DN_MASK_F32 / DN_MASK_U8 images, shared or per sample, constant value or value field.  d2basis[ig][ib] = phi''_ib(xi_ig) in
+ * reference coordinates (dn_mesh carries no second-derivative table); the kernel scales it by scale[d]^2.  For degree 1 the
+ * second-derivative terms vanish identically and no work is spent on them.
+ * Either grad or sum may be NULL (not both).  sum needs `workspace` (zero-filled once before first use, dn_strongform_workspace_bytes;
+ * every call leaves it ready for the next; one per stream, not shared with other operators).  No atomics on the data path: grad is
+ * bitwise independent of the batch it is computed in and of the launch plan ("PLAN_FSDT" "T,R" overrides the plan, as for the FSDT
+ * element form); sum is reproducible for a given mesh, batch size and plan.
+ * Coefficients of the scripts, both with wscale = 1 and out_scale = 1 / (B nel) (torch.mean of the gpw-weighted sums, no Jacobian):
+ *   01_2d_space_time: (ax, ay, b, dxx, dyy, fs) = (0, 1, 1, 0, 0, 0) -- its loss evaluates u_xx but never uses it; the viscous form
+ *   is dxx = -nu with nu = 0.01 / pi;  10_manufactured_strong_form_higher_order: (0, 0, 0, 1, 1, 1) with the nodal forcing.
+ * DN_E_UNSUPPORTED for degree outside 1..3, ngp outside 2..4 (or 2 with degree > 1), DN_MASK_BITS / DN_MASK_BOX conditions (expand
+ * them: dn_unpack_mask_bits); DN_E_BADARG for nsd != 2, (n - 1) % degree != 0, a NULL u, no output at all, f together with f_gp,
+ * flags outside {0, 1} or a value field without its mask; DN_E_WORKSPACE for sum without a large enough workspace; nothing is
+ * launched then. */
+typedef struct dn_strongform_args {
+    const float *u;        /* (B,1,ny,nx) nodal field                                   */
+    const float *f;        /* (B | 1,1,ny,nx) nodal forcing or NULL                     */
+    const float *f_gp;     /* (Bf,G,nely,nelx) forcing at Gauss points or NULL          */
+    int32_t f_batched;     /* 0: one forcing for the whole batch                        */
+    float f_value;         /* the forcing when f and f_gp are NULL                      */
+    dn_dirichlet bc[2];    /* applied in order                                          */
+    float ax, ay, b, dxx, dyy, fs;
+    float wscale, out_scale;
+    float d2basis[4][4];
+    const float *in_scale; /* optional: one device float                                */
+    float *grad;           /* (B,1,ny,nx) or NULL                                       */
+    double *sum;           /* device scalar or NULL                                     */
+    void *workspace;
+    int64_t workspace_bytes;
+} dn_strongform_args;
+int64_t dn_strongform_workspace_bytes(const dn_mesh *mesh);
+int dn_strongform_apply(const dn_mesh *mesh, const dn_strongform_args *args, void *stream);
+
 /* ---- gradient of the Poisson losses with respect to the nodal coefficient and forcing ------------------------------------
  * Replaces what autograd does for the coefficient in the topology optimisation of the reference,
  * examples/poisson/single_instance/16_topopt.py:119-195 (loss = 0.5 nu grad u . grad v - v f with nu from the network, compliance
