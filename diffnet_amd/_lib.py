@@ -94,6 +94,16 @@ class DnStrongformArgs(C.Structure):
                 ("in_scale", C.c_void_p), ("grad", C.c_void_p), ("sum", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class DnFoslsArgs(C.Structure):
+    _fields_ = [("u", C.c_void_p), ("mx", C.c_void_p), ("my", C.c_void_p), ("field_stride", C.c_int64),
+                ("nu", C.c_void_p), ("nu_batched", C.c_int32), ("nu_value", C.c_float),
+                ("f", C.c_void_p), ("f_gp", C.c_void_p), ("f_batched", C.c_int32), ("f_value", C.c_float),
+                ("bc", DnDirichlet * 2),
+                ("wq", C.c_float), ("wd", C.c_float), ("fs", C.c_float), ("wscale", C.c_float), ("out_scale", C.c_float),
+                ("in_scale", C.c_void_p), ("grad_u", C.c_void_p), ("grad_mx", C.c_void_p), ("grad_my", C.c_void_p), ("grad_stride", C.c_int64),
+                ("sum", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class DnCoefGradArgs(C.Structure):
     _fields_ = [("u", C.c_void_p), ("v", C.c_void_p), ("bc", DnDirichlet * 2),
                 ("a_nu", C.c_float), ("a_f", C.c_float), ("wscale", C.c_float),
@@ -141,6 +151,8 @@ SYMBOLS = {
     "dn_transport_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnTransportArgs), C.c_void_p]),
     "dn_strongform_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
     "dn_strongform_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnStrongformArgs), C.c_void_p]),
+    "dn_fosls_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
+    "dn_fosls_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnFoslsArgs), C.c_void_p]),
     "dn_poisson_coef_grad": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnCoefGradArgs), C.c_void_p]),
     "dn_upconv_out_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "dn_upconv_out_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,

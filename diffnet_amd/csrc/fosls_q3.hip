@@ -1,0 +1,3 @@
+// Q3 instantiations of the fused first-order-system least-squares kernel (see fosls.hip).
+#define FO_DEGREE 3
+#include "fosls.hip"

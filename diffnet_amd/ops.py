@@ -11,7 +11,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import DnCoefGradArgs, DnDirichlet, DnFsdtArgs, DnMesh, DnNsArgs, DnPoissonArgs, DnStokesArgs, DnStrongformArgs, DnTransportArgs, I32x3, DiffNetHipError
+from ._lib import DnCoefGradArgs, DnDirichlet, DnFoslsArgs, DnFsdtArgs, DnMesh, DnNsArgs, DnPoissonArgs, DnStokesArgs, DnStrongformArgs, DnTransportArgs, I32x3, DiffNetHipError
 
 
 def _require(t, name, ndim=None, strict=False):
@@ -602,6 +602,7 @@ def call_cache_clear():
         _NS.cache.clear()
         _TRANSPORT.cache.clear()
         _STRONGFORM.cache.clear()
+        _FOSLS.cache.clear()
         _PACK_CACHE.clear()
     _POISSON_WS_BYTES.clear()
     _FSDT_WS_BYTES.clear()
@@ -609,6 +610,7 @@ def call_cache_clear():
     _NS.ws_bytes.clear()
     _TRANSPORT.ws_bytes.clear()
     _STRONGFORM.ws_bytes.clear()
+    _FOSLS.ws_bytes.clear()
 
 
 class PoissonPlan:
@@ -2220,6 +2222,233 @@ def strongform_apply(geom, u, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=None, 
     if rc:
         _lib.check(rc, op.fn)
     return grad, sums
+
+
+# ---- the fused 2-D first-order-system least-squares loss (u, mx, my) and its gradients: dn_fosls_apply --------------------------
+# Its own reduction workspace per (device, stream), prepared-call cache and launch lock, like _STRONGFORM and for the same reason.
+_FOSLS = _Flow2dOp("fosls_apply", DnFoslsArgs)
+
+
+def _fosls_check_mesh(geom):
+    if geom.nsd != 2 or geom.deg not in (1, 2, 3) or not 2 <= geom.ngp_1d <= 4 or (geom.deg > 1 and geom.ngp_1d < 3):
+        raise DiffNetHipError(f"fosls_apply: 2-D meshes of degree 1..3 with 2..4 Gauss points per axis (3 or 4 above degree 1) only "
+                              f"(nsd {geom.nsd}, degree {geom.deg}, ngp {geom.ngp_1d})")
+    if any((n - 1) % geom.deg for n in geom.sizes):
+        raise ValueError(f"fosls_apply: a degree-{geom.deg} mesh needs (n - 1) % {geom.deg} == 0 nodes per axis, got {geom.sizes}")
+
+
+def _fosls_key(geom, flds, packed, nu, bc2, vals, f, f_gp, consts, in_scale, flags):
+    """Key of a cached prepared call (see _call_key); None when an argument needs a conversion copy."""
+    first = flds[0]
+    if not (isinstance(first, torch.Tensor) and first.is_cuda):
+        return None
+    parts = [geom.key, first.device.index, _raw_stream(first.device), consts, flags, packed]
+    for t in flds:
+        k = _tkey(t)
+        if k is None or k == 0 or k[1] != torch.float32 or tuple(k[2][1:]) != ((3 if packed else 1), *geom.node_shape):
+            return None
+        parts.append(k)
+    for m in bc2:
+        k = _tkey(m)
+        if k is None or (k != 0 and k[1] not in (torch.float32, torch.uint8, torch.bool)):
+            return None
+        parts.append(k)
+    for v in tuple(vals) + (f_gp, nu):
+        if isinstance(v, torch.Tensor) and v.numel() > 1:
+            k = _tkey(v)
+            if k is None or k[1] != torch.float32:
+                return None
+            parts.append(k)
+        else:
+            parts.append(float(v))
+    for t in (f, in_scale):
+        k = _tkey(t)
+        if k is None or (k != 0 and k[1] != torch.float32):
+            return None
+        parts.append(k)
+    return tuple(parts)
+
+
+def _prepare_fosls(geom, flds, packed, nu, bc2, vals, f, f_gp, consts, in_scale, want_sum):
+    """Validation + argument struct of a dn_fosls_apply call, outputs left unset: (mesh, args, tensors to keep alive, batch size)."""
+    name = _FOSLS.name
+    _fosls_check_mesh(geom)
+    nn = geom.nnode_total
+    args = DnFoslsArgs()
+    if packed:
+        t = _require(flds[0], "fields", 4)
+        B = t.shape[0]
+        if tuple(t.shape) != (B, 3, *geom.node_shape):
+            raise ValueError(f"{name}: fields shape {tuple(t.shape)} != {(B, 3, *geom.node_shape)} (channels u, mx, my)")
+        keep = [t]
+        args.u, args.mx, args.my = t.data_ptr(), t.data_ptr() + 4 * nn, t.data_ptr() + 8 * nn
+        args.field_stride = 3 * nn
+        u = t
+    else:
+        keep = []
+        B = flds[0].shape[0] if isinstance(flds[0], torch.Tensor) and flds[0].dim() == 4 else 0
+        shape = (B, 1, *geom.node_shape)
+        for what, t in zip(("u", "mx", "my"), flds):
+            t = _require(t, what, 4)
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name}: field {what} shape {tuple(t.shape)} != {shape}")
+            if t.device != flds[0].device:
+                raise ValueError(f"{name}: the three fields must be on one device")
+            setattr(args, what, t.data_ptr())
+            keep.append(t)
+        args.field_stride = nn
+        u = keep[0]
+    shape = (B, 1, *geom.node_shape)
+
+    def batched(t, what):
+        if tuple(t.shape[-2:]) != tuple(geom.node_shape) or t.numel() not in (B * nn, nn):
+            raise ValueError(f"{name}: {what} shape {tuple(t.shape)} does not match the mesh {shape}")
+        return 1 if (t.numel() == B * nn and B > 1) else 0
+
+    if isinstance(nu, torch.Tensor) and nu.numel() > 1:
+        nu = _require(nu, "nu")
+        args.nu_batched = batched(nu, "nu")
+        args.nu = nu.data_ptr()
+        keep.append(nu)
+    else:
+        args.nu_value = float(nu)
+    for k, m in enumerate(bc2):
+        if m is None:
+            continue
+        if not isinstance(m, torch.Tensor):
+            raise TypeError(f"{name}: bc[{k}] must be a tensor or None (expand a PackedMask / BoxFaces to its image)")
+        if not m.is_cuda:
+            raise DiffNetHipError(f"{name}: bc[{k}] is on {m.device}: the FEM ops run on the GPU only (no CPU fallback)")
+        if m.dtype in (torch.bool, torch.uint8):
+            m = m.contiguous()
+            m = m.view(torch.uint8) if m.dtype == torch.bool else m
+            args.bc[k].mask_kind = _lib.MASK_U8
+        else:
+            m = _require(m, f"bc[{k}]")
+            args.bc[k].mask_kind = _lib.MASK_F32
+        args.bc[k].mask_batched = batched(m, f"bc[{k}]")
+        args.bc[k].mask = m.data_ptr()
+        keep.append(m)
+    for k, val in enumerate(vals):
+        if isinstance(val, torch.Tensor) and val.numel() > 1:
+            if bc2[k] is None:
+                raise ValueError(f"{name}: bc_values[{k}] is a field but condition {k} has no mask")
+            val = _require(val, f"bc_values[{k}]")
+            args.bc[k].field_batched = batched(val, f"bc_values[{k}]")
+            args.bc[k].field = val.data_ptr()
+            keep.append(val)
+        else:
+            args.bc[k].value = float(val)
+    G, nel = geom.ngp_total, geom.nelem_total
+    if f is not None:
+        if isinstance(f_gp, torch.Tensor) and f_gp.numel() > 1:
+            raise ValueError(f"{name}: nodal forcing f and Gauss-point forcing f_gp exclude each other")
+        f = _require(f, "f")
+        args.f_batched = batched(f, "f")
+        args.f = f.data_ptr()
+        keep.append(f)
+    elif isinstance(f_gp, torch.Tensor) and f_gp.numel() > 1:
+        f_gp = _require(f_gp, "f_gp")
+        if tuple(f_gp.shape[-3:]) != (G, *geom.elem_shape) or f_gp.numel() not in (G * nel, B * G * nel):
+            raise ValueError(f"{name}: f_gp shape {tuple(f_gp.shape)} is not (B | 1, {G}, {geom.elem_shape[0]}, {geom.elem_shape[1]})")
+        args.f_batched = 1 if (f_gp.numel() == B * G * nel and B > 1) else 0
+        args.f_gp = f_gp.data_ptr()
+        keep.append(f_gp)
+    else:
+        args.f_value = float(f_gp)
+    if in_scale is not None:
+        in_scale = _require(in_scale, "in_scale")
+        if in_scale.numel() != 1 or in_scale.device != u.device:
+            raise ValueError(f"{name}: in_scale must hold one float on the fields' device")
+        args.in_scale = in_scale.data_ptr()
+        keep.append(in_scale)
+    args.wq, args.wd, args.fs, args.wscale, args.out_scale = consts
+    mesh = geom.mesh_struct(B)
+    if want_sum:
+        ws = _flow2d_workspace(_FOSLS, mesh, B, u.device)
+        keep.append(ws)
+        args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    return mesh, args, keep, B
+
+
+def fosls_apply(geom, u=None, mx=None, my=None, nu=None, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=None, weights=(1.0, 1.0), fs=1.0,
+                wscale=1.0, out_scale=1.0, in_scale=None, want_grad=True, want_sum=True, fields=None):
+    """One launch of dn_fosls_apply (include/diffnet_hip.h): sum_{b,e,g} W_g (wq (qx^2 + qy^2) + wd d^2) of the first-order system
+    qx = mx - nu u_x, qy = my - nu u_y, d = mx_x + my_y + fs f of the fields u, mx, my (B,1,ny,nx each) as a float64 device tensor (1,)
+    and / or its gradients with respect to u, mx and my times `out_scale` (times in_scale[0], a float32 device tensor of 1, where
+    given).  `fields`: instead of u, mx, my, one packed (B,3,ny,nx) tensor (channels u, mx, my), read in place; the gradient then is one
+    packed (B,3,ny,nx) tensor.  `weights`: (wq, wd); `nu`: None (1), a float or a nodal field (B | 1,1,ny,nx); `bc`: None, one mask or a
+    pair (either None) for u, fp32 (`> 0.5`) or bool / uint8, per sample or shared; `bc_values[k]`: float or tensor u takes under
+    condition k (where both hold, condition 2's); the forcing: a nodal field `f` (B | 1,1,ny,nx), or `f_gp`, a float or a Gauss-point
+    tensor (B | 1, G, nely, nelx).  `want_grad`: a bool, or with separate fields three bools (u, mx, my).  Degree 1..3.
+    Returns ((gu, gmx, gmy) | packed gradient | None, sum | None); a gradient that was not asked for is None.
+    Calls on the same buffers reuse their prepared argument structs (small LRU, fresh outputs per call: see poisson_apply)."""
+    _fosls_check_mesh(geom)
+    packed = fields is not None
+    if packed and not (u is None and mx is None and my is None):
+        raise ValueError("fosls_apply: pass either the packed `fields` or u, mx, my")
+    if not packed and (u is None or mx is None or my is None):
+        raise ValueError("fosls_apply: u, mx and my (or the packed `fields`) are required")
+    bc2, vals, weights = transport_bc2(bc), tuple(bc_values), tuple(float(x) for x in weights)
+    if len(vals) != 2:
+        raise ValueError("fosls_apply: bc_values must hold two entries")
+    if len(weights) != 2:
+        raise ValueError("fosls_apply: weights holds (wq, wd)")
+    want3 = (bool(want_grad),) * 3 if isinstance(want_grad, (bool, int)) else tuple(bool(x) for x in want_grad)
+    if len(want3) != 3:
+        raise ValueError("fosls_apply: want_grad is a bool or three of them (u, mx, my)")
+    if packed and any(want3) != all(want3):
+        raise ValueError("fosls_apply: a packed gradient holds all three channels; pass u, mx, my separately for a subset")
+    if not (any(want3) or want_sum):
+        raise ValueError("fosls_apply: nothing to compute (want_grad and want_sum are both off)")
+    fg = 0.0 if f_gp is None else f_gp
+    nuv = 1.0 if nu is None else nu
+    consts = (*weights, float(fs), float(wscale), float(out_scale))
+    flds = (fields,) if packed else (u, mx, my)
+    op = _FOSLS
+    key = _fosls_key(geom, flds, packed, nuv, bc2, vals, f, fg, consts, in_scale, (want3, want_sum))
+    ent = None
+    if key is not None:
+        with _WS_LOCK:
+            ent = op.cache.get(key)
+            if ent is not None:
+                op.cache.move_to_end(key)
+    if ent is None:
+        _CALL_STATS["miss" if key is not None else "uncached"] += 1
+        mesh, args, keep, B = _prepare_fosls(geom, flds, packed, nuv, bc2, vals, f, fg, consts, in_scale, want_sum)
+        with _WS_LOCK:
+            live_ws = list(op.ws.values())
+        # an uncached call keeps its (possibly converted) tensors alive until it has been issued; a cached one only the workspace
+        ent = (mesh, args, C.byref(mesh), C.byref(args), B, keep if key is None else [t for t in keep if any(t is x for x in live_ws)])
+        if key is not None:
+            with _WS_LOCK:
+                op.cache[key] = ent
+                while len(op.cache) > _CALL_CACHE_MAX:
+                    op.cache.popitem(last=False)
+    else:
+        _CALL_STATS["hit"] += 1
+    mesh, args, mref, aref, B = ent[:5]
+    dev = flds[0].device
+    nn = geom.nnode_total
+    if packed:
+        grads = torch.empty((B, 3, *geom.node_shape), dtype=torch.float32, device=dev) if want3[0] else None
+        ptrs = [grads.data_ptr() + 4 * nn * k if grads is not None else None for k in range(3)]
+        gstride = 3 * nn
+    else:
+        grads = tuple(torch.empty((B, 1, *geom.node_shape), dtype=torch.float32, device=dev) if w else None for w in want3)
+        ptrs = [g.data_ptr() if g is not None else None for g in grads]
+        gstride = nn
+        if not any(want3):
+            grads = None
+    sums = torch.empty(1, dtype=torch.float64, device=dev) if want_sum else None
+    with op.launch_lock:               # pointer patch + launch of the (possibly shared, cached) argument struct as one step
+        args.grad_u, args.grad_mx, args.grad_my = ptrs
+        args.grad_stride = gstride
+        args.sum = sums.data_ptr() if want_sum else None
+        rc = _lib.lib().dn_fosls_apply(mref, aref, _stream(flds[0]))
+    if rc:
+        _lib.check(rc, op.fn)
+    return grads, sums
 
 
 def compute_winding_nodes(points, normals, area, q):

@@ -516,6 +516,61 @@ typedef struct dn_strongform_args {
 int64_t dn_strongform_workspace_bytes(const dn_mesh *mesh);
 int dn_strongform_apply(const dn_mesh *mesh, const dn_strongform_args *args, void *stream);
 
+/* ---- fused 2-D first-order-system least-squares loss (u, mx, my) and its three gradients ------------------------------------
+ * Replaces the loss body of the three-field strong-form script of the reference,
+ * examples/poisson/single_instance/11_manufactured_strong_form_two_dofs.py:37-71 (Poisson.loss on u and the flux (mx, my)) -- the two
+ * Dirichlet substitutions of u, eleven Gauss-point evaluations, the weighted sums of squares and the autograd backward through all
+ * of it, in ONE launch that reads every field once.  Mesh: nsd = 2, degree 1..3, ngp 2..4 (>= 3 for degree > 1), (n - 1) % degree == 0.
+ *   u~ = u after bc[0] then bc[1] (applied in order, as in dn_strongform_args: where both hold, condition 2's value is used);
+ *   the conditions act on u only, mx and my are free.  At every Gauss point (x is the fastest axis):
+ *   qx = mx - nu u~_x,   qy = my - nu u~_y,   d = mx_x + my_y + fs f_g
+ *   sum       = sum_{b,e,g} W_g ( wq (qx^2 + qy^2) + wd d^2 ),   W_g = gpw_g * wscale   (one double, unscaled; fixed-order fp64 reduction)
+ *   grad_u_a  = out_scale * s * sum -2 W_g wq nu (qx Nx_a + qy Ny_a)                    (zero on the Dirichlet nodes)
+ *   grad_mx_a = out_scale * s * sum  2 W_g (wq qx N_a + wd d Nx_a)
+ *   grad_my_a = out_scale * s * sum  2 W_g (wq qy N_a + wd d Ny_a)                      s = in_scale[0] when that device float is given, else 1
+ * u, mx, my are fp32 node images (ny,nx) per sample, sample b of each at its pointer + b * field_stride elements: field_stride is
+ * ny*nx for three separate (B,1,ny,nx) tensors and 3*ny*nx for channels of one packed (B,3,ny,nx) tensor, which is then read without
+ * a copy.  grad_u, grad_mx, grad_my likewise with grad_stride; any of them may be NULL.  nu is the constant nu_value or a nodal field
+ * (1 | B,1,ny,nx) interpolated with the basis.  The forcing f_g is the nodal field f (1 | B,1,ny,nx) interpolated with the basis,
+ * or f_gp at the Gauss points (Bf,G,nely,nelx) with Bf = 1 (f_batched 0) or B, or the constant f_value; f and f_gp exclude each
+ * other.  Conditions: DN_MASK_F32 / DN_MASK_U8 images, shared or per sample, constant value or value field.
+ * Any subset of the three gradients and sum may be requested (not none).  sum needs `workspace` (zero-filled once before first use,
+ * dn_fosls_workspace_bytes; every call leaves it ready for the next; one per stream, not shared with other operators).  No atomics on
+ * the data path: the gradients are bitwise independent of the batch they are computed in and of the launch plan ("PLAN_FSDT" "T,R"
+ * overrides the plan, as for dn_strongform_apply); sum is reproducible for a given mesh, batch size and plan.
+ * The script: degree 1, ngp 2, wq = wd = fs = 1, wscale = 1, out_scale = 1 / (B nel) (torch.mean of the gpw-weighted sums, no
+ * Jacobian), nu and f nodal fields, conditions `> 0.5` with values 1 and 0.
+ * DN_E_UNSUPPORTED for degree outside 1..3, ngp outside 2..4 (or 2 with degree > 1), DN_MASK_BITS / DN_MASK_BOX conditions (expand
+ * them: dn_unpack_mask_bits); DN_E_BADARG for nsd != 2, (n - 1) % degree != 0, a NULL u, mx or my, no output at all, f together with
+ * f_gp, flags outside {0, 1}, a value field without its mask, or field_stride (grad_stride, when a gradient is requested) smaller
+ * than ny*nx; DN_E_WORKSPACE for sum without a large enough workspace; nothing is launched then. */
+typedef struct dn_fosls_args {
+    const float *u;        /* sample b at u + b * field_stride, (ny,nx)                 */
+    const float *mx;
+    const float *my;
+    int64_t field_stride;  /* elements between samples of u, mx, my                     */
+    const float *nu;       /* (B | 1,1,ny,nx) nodal coefficient or NULL                 */
+    int32_t nu_batched;    /* 0: one coefficient field for the whole batch              */
+    float nu_value;        /* the coefficient when nu is NULL                           */
+    const float *f;        /* (B | 1,1,ny,nx) nodal forcing or NULL                     */
+    const float *f_gp;     /* (Bf,G,nely,nelx) forcing at Gauss points or NULL          */
+    int32_t f_batched;     /* 0: one forcing for the whole batch                        */
+    float f_value;         /* the forcing when f and f_gp are NULL                      */
+    dn_dirichlet bc[2];    /* applied to u in order                                     */
+    float wq, wd, fs;
+    float wscale, out_scale;
+    const float *in_scale; /* optional: one device float                                */
+    float *grad_u;         /* sample b at grad_u + b * grad_stride, or NULL             */
+    float *grad_mx;
+    float *grad_my;
+    int64_t grad_stride;   /* elements between samples of the gradients                 */
+    double *sum;           /* device scalar or NULL                                     */
+    void *workspace;
+    int64_t workspace_bytes;
+} dn_fosls_args;
+int64_t dn_fosls_workspace_bytes(const dn_mesh *mesh);
+int dn_fosls_apply(const dn_mesh *mesh, const dn_fosls_args *args, void *stream);
+
 /* ---- gradient of the Poisson losses with respect to the nodal coefficient and forcing ------------------------------------
  * Replaces what autograd does for the coefficient in the topology optimisation of the reference,
  * examples/poisson/single_instance/16_topopt.py:119-195 (loss = 0.5 nu grad u . grad v - v f with nu from the network, compliance
