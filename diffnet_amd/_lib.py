@@ -104,6 +104,16 @@ class DnFoslsArgs(C.Structure):
                 ("sum", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class DnHelmholtzArgs(C.Structure):
+    _fields_ = [("u", C.c_void_p), ("nu", C.c_void_p), ("sigma", C.c_void_p), ("f", C.c_void_p), ("f_gp", C.c_void_p),
+                ("nu_batched", C.c_int32), ("sigma_batched", C.c_int32), ("f_batched", C.c_int32),
+                ("sigma_value", C.c_float), ("f_value", C.c_float),
+                ("bc", DnDirichlet * 2),
+                ("c", C.c_float), ("cr", C.c_float), ("fs", C.c_float), ("alpha", C.c_float), ("gamma", C.c_float), ("beta", C.c_float),
+                ("wscale", C.c_float), ("out_scale", C.c_float),
+                ("out", C.c_void_p), ("energy", C.c_void_p), ("sumsq", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class DnCoefGradArgs(C.Structure):
     _fields_ = [("u", C.c_void_p), ("v", C.c_void_p), ("bc", DnDirichlet * 2),
                 ("a_nu", C.c_float), ("a_f", C.c_float), ("wscale", C.c_float),
@@ -153,6 +163,8 @@ SYMBOLS = {
     "dn_strongform_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnStrongformArgs), C.c_void_p]),
     "dn_fosls_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
     "dn_fosls_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnFoslsArgs), C.c_void_p]),
+    "dn_helmholtz_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
+    "dn_helmholtz_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnHelmholtzArgs), C.c_void_p]),
     "dn_poisson_coef_grad": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnCoefGradArgs), C.c_void_p]),
     "dn_upconv_out_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "dn_upconv_out_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,

@@ -11,7 +11,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import DnCoefGradArgs, DnDirichlet, DnFoslsArgs, DnFsdtArgs, DnMesh, DnNsArgs, DnPoissonArgs, DnStokesArgs, DnStrongformArgs, DnTransportArgs, I32x3, DiffNetHipError
+from ._lib import DnCoefGradArgs, DnDirichlet, DnFoslsArgs, DnFsdtArgs, DnHelmholtzArgs, DnMesh, DnNsArgs, DnPoissonArgs, DnStokesArgs, DnStrongformArgs, DnTransportArgs, I32x3, DiffNetHipError
 
 
 def _require(t, name, ndim=None, strict=False):
@@ -603,6 +603,7 @@ def call_cache_clear():
         _TRANSPORT.cache.clear()
         _STRONGFORM.cache.clear()
         _FOSLS.cache.clear()
+        _HELMHOLTZ.cache.clear()
         _PACK_CACHE.clear()
     _POISSON_WS_BYTES.clear()
     _FSDT_WS_BYTES.clear()
@@ -611,6 +612,7 @@ def call_cache_clear():
     _TRANSPORT.ws_bytes.clear()
     _STRONGFORM.ws_bytes.clear()
     _FOSLS.ws_bytes.clear()
+    _HELMHOLTZ.ws_bytes.clear()
 
 
 class PoissonPlan:
@@ -2449,6 +2451,193 @@ def fosls_apply(geom, u=None, mx=None, my=None, nu=None, bc=None, bc_values=(0.0
     if rc:
         _lib.check(rc, op.fn)
     return grads, sums
+
+
+# ---- the fused 2-D Helmholtz energy and weak-form residual: dn_helmholtz_apply ---------------------------------------------------
+# Its own reduction workspace per (device, stream), prepared-call cache and launch lock, like _STRONGFORM and for the same reason.
+_HELMHOLTZ = _Flow2dOp("helmholtz_apply", DnHelmholtzArgs)
+
+
+def _helmholtz_check_mesh(geom):
+    if geom.nsd != 2 or geom.deg not in (1, 2, 3) or not 2 <= geom.ngp_1d <= 4 or (geom.deg > 1 and geom.ngp_1d < 3):
+        raise DiffNetHipError(f"helmholtz_apply: 2-D meshes of degree 1..3 with 2..4 Gauss points per axis (3 or 4 above degree 1) only "
+                              f"(nsd {geom.nsd}, degree {geom.deg}, ngp {geom.ngp_1d})")
+    if any((n - 1) % geom.deg for n in geom.sizes):
+        raise ValueError(f"helmholtz_apply: a degree-{geom.deg} mesh needs (n - 1) % {geom.deg} == 0 nodes per axis, got {geom.sizes}")
+
+
+def _helmholtz_key(geom, u, nu, sigma, bc2, vals, f, f_gp, consts, flags):
+    """Key of a cached prepared call (see _call_key); None when an argument needs a conversion copy."""
+    if not (isinstance(u, torch.Tensor) and u.is_cuda and tuple(u.shape[1:]) == (1, *geom.node_shape)):
+        return None
+    parts = [geom.key, u.device.index, _raw_stream(u.device), consts, flags]
+    k = _tkey(u)
+    if k is None or k == 0 or k[1] != torch.float32:
+        return None
+    parts.append(k)
+    for m in bc2:
+        k = _tkey(m)
+        if k is None or (k != 0 and k[1] not in (torch.float32, torch.uint8, torch.bool)):
+            return None
+        parts.append(k)
+    for v in tuple(vals) + (f_gp, sigma):
+        if isinstance(v, torch.Tensor) and v.numel() > 1:
+            k = _tkey(v)
+            if k is None or k[1] != torch.float32:
+                return None
+            parts.append(k)
+        else:
+            parts.append(float(v))
+    for t in (nu, f):
+        k = _tkey(t)
+        if k is None or (k != 0 and k[1] != torch.float32):
+            return None
+        parts.append(k)
+    return tuple(parts)
+
+
+def _prepare_helmholtz(geom, u, nu, sigma, bc2, vals, f, f_gp, consts, want_sums):
+    """Validation + argument struct of a dn_helmholtz_apply call, outputs left unset: (mesh, args, tensors to keep alive, field shape)."""
+    name = _HELMHOLTZ.name
+    _helmholtz_check_mesh(geom)
+    u = _require(u, "u", 4)
+    B = u.shape[0]
+    shape = (B, 1, *geom.node_shape)
+    if tuple(u.shape) != shape:
+        raise ValueError(f"{name}: field shape {tuple(u.shape)} != {shape}")
+    keep = [u]
+    args = DnHelmholtzArgs()
+    args.u = u.data_ptr()
+    nn = geom.nnode_total
+
+    def batched(t, what):
+        if tuple(t.shape[-2:]) != tuple(geom.node_shape) or t.numel() not in (B * nn, nn):
+            raise ValueError(f"{name}: {what} shape {tuple(t.shape)} does not match the mesh {shape}")
+        return 1 if (t.numel() == B * nn and B > 1) else 0
+
+    if nu is not None:
+        nu = _require(nu, "nu")
+        args.nu_batched = batched(nu, "nu")
+        args.nu = nu.data_ptr()
+        keep.append(nu)
+    if isinstance(sigma, torch.Tensor) and sigma.numel() > 1:
+        sigma = _require(sigma, "sigma")
+        args.sigma_batched = batched(sigma, "sigma")
+        args.sigma = sigma.data_ptr()
+        keep.append(sigma)
+    else:
+        args.sigma_value = float(sigma)
+    for k, m in enumerate(bc2):
+        if m is None:
+            continue
+        if not isinstance(m, torch.Tensor):
+            raise TypeError(f"{name}: bc[{k}] must be a tensor or None (expand a PackedMask / BoxFaces to its image)")
+        if not m.is_cuda:
+            raise DiffNetHipError(f"{name}: bc[{k}] is on {m.device}: the FEM ops run on the GPU only (no CPU fallback)")
+        if m.dtype in (torch.bool, torch.uint8):
+            m = m.contiguous()
+            m = m.view(torch.uint8) if m.dtype == torch.bool else m
+            args.bc[k].mask_kind = _lib.MASK_U8
+        else:
+            m = _require(m, f"bc[{k}]")
+            args.bc[k].mask_kind = _lib.MASK_F32
+        args.bc[k].mask_batched = batched(m, f"bc[{k}]")
+        args.bc[k].mask = m.data_ptr()
+        keep.append(m)
+    for k, val in enumerate(vals):
+        if isinstance(val, torch.Tensor) and val.numel() > 1:
+            if bc2[k] is None:
+                raise ValueError(f"{name}: bc_values[{k}] is a field but condition {k} has no mask")
+            val = _require(val, f"bc_values[{k}]")
+            args.bc[k].field_batched = batched(val, f"bc_values[{k}]")
+            args.bc[k].field = val.data_ptr()
+            keep.append(val)
+        else:
+            args.bc[k].value = float(val)
+    G, nel = geom.ngp_total, geom.nelem_total
+    if f is not None:
+        if isinstance(f_gp, torch.Tensor) and f_gp.numel() > 1:
+            raise ValueError(f"{name}: nodal forcing f and Gauss-point forcing f_gp exclude each other")
+        f = _require(f, "f")
+        args.f_batched = batched(f, "f")
+        args.f = f.data_ptr()
+        keep.append(f)
+    elif isinstance(f_gp, torch.Tensor) and f_gp.numel() > 1:
+        f_gp = _require(f_gp, "f_gp")
+        if tuple(f_gp.shape[-3:]) != (G, *geom.elem_shape) or f_gp.numel() not in (G * nel, B * G * nel):
+            raise ValueError(f"{name}: f_gp shape {tuple(f_gp.shape)} is not (B | 1, {G}, {geom.elem_shape[0]}, {geom.elem_shape[1]})")
+        args.f_batched = 1 if (f_gp.numel() == B * G * nel and B > 1) else 0
+        args.f_gp = f_gp.data_ptr()
+        keep.append(f_gp)
+    else:
+        args.f_value = float(f_gp)
+    args.c, args.cr, args.fs, args.alpha, args.gamma, args.beta, args.wscale, args.out_scale = consts
+    mesh = geom.mesh_struct(B)
+    if want_sums:
+        ws = _flow2d_workspace(_HELMHOLTZ, mesh, B, u.device)
+        keep.append(ws)
+        args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    return mesh, args, keep, shape
+
+
+def helmholtz_apply(geom, u, nu=None, sigma=0.0, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=None, energy_coef=(0.5, 0.5, 1.0),
+                    out_coef=(1.0, 1.0, 1.0), wscale=1.0, out_scale=1.0, want_out=True, want_energy=True, want_sumsq=False):
+    """One launch of dn_helmholtz_apply (include/diffnet_hip.h) on the field u (B,1,ny,nx):
+    energy = sum W (c nu |grad u~|^2 - cr sg u~^2 - fs u~ f), `energy_coef` = (c, cr, fs);
+    out = out_scale * zero_on_dirichlet(assembled W (alpha nu gradN . grad u~ - gamma sg N u~ - beta N f)), `out_coef` = (alpha, gamma,
+    beta); sumsq = sum (out / out_scale)^2.  `nu`: None (1) or a nodal field (B | 1,1,ny,nx); `sigma`: a float or a nodal field likewise;
+    `bc`: None, one mask or a pair (either None), fp32 (`> 0.5`) or bool / uint8, per sample or shared; `bc_values[k]`: float or tensor u
+    takes under condition k (where both hold, condition 2's); the forcing: a nodal field `f` (B | 1,1,ny,nx), or `f_gp`, a float or a
+    Gauss-point tensor (B | 1, G, nely, nelx).  Degree 1..3.  Returns (out | None, energy | None, sumsq | None), the two sums as float64
+    device tensors (1,), unscaled.  Calls on the same buffers reuse their prepared argument structs (small LRU, fresh outputs per call:
+    see poisson_apply)."""
+    _helmholtz_check_mesh(geom)
+    bc2, vals = transport_bc2(bc), tuple(bc_values)
+    energy_coef, out_coef = tuple(float(x) for x in energy_coef), tuple(float(x) for x in out_coef)
+    if len(vals) != 2:
+        raise ValueError("helmholtz_apply: bc_values must hold two entries")
+    if len(energy_coef) != 3 or len(out_coef) != 3:
+        raise ValueError("helmholtz_apply: energy_coef holds (c, cr, fs), out_coef (alpha, gamma, beta)")
+    if not (want_out or want_energy or want_sumsq):
+        raise ValueError("helmholtz_apply: nothing to compute (want_out, want_energy and want_sumsq are all off)")
+    fg = 0.0 if f_gp is None else f_gp
+    sigma = 0.0 if sigma is None else sigma
+    consts = (*energy_coef, *out_coef, float(wscale), float(out_scale))
+    want_sums = want_energy or want_sumsq
+    op = _HELMHOLTZ
+    key = _helmholtz_key(geom, u, nu, sigma, bc2, vals, f, fg, consts, (want_out, want_sums))
+    ent = None
+    if key is not None:
+        with _WS_LOCK:
+            ent = op.cache.get(key)
+            if ent is not None:
+                op.cache.move_to_end(key)
+    if ent is None:
+        _CALL_STATS["miss" if key is not None else "uncached"] += 1
+        mesh, args, keep, shape = _prepare_helmholtz(geom, u, nu, sigma, bc2, vals, f, fg, consts, want_sums)
+        with _WS_LOCK:
+            live_ws = list(op.ws.values())
+        # an uncached call keeps its (possibly converted) tensors alive until it has been issued; a cached one only the workspace
+        ent = (mesh, args, C.byref(mesh), C.byref(args), shape, keep if key is None else [t for t in keep if any(t is x for x in live_ws)])
+        if key is not None:
+            with _WS_LOCK:
+                op.cache[key] = ent
+                while len(op.cache) > _CALL_CACHE_MAX:
+                    op.cache.popitem(last=False)
+    else:
+        _CALL_STATS["hit"] += 1
+    mesh, args, mref, aref, shape = ent[:5]
+    dev = u.device
+    out = torch.empty(shape, dtype=torch.float32, device=dev) if want_out else None
+    sums = torch.empty(2, dtype=torch.float64, device=dev) if want_sums else None
+    with op.launch_lock:               # pointer patch + launch of the (possibly shared, cached) argument struct as one step
+        args.out = out.data_ptr() if want_out else None
+        args.energy = sums.data_ptr() if want_energy else None
+        args.sumsq = sums.data_ptr() + 8 if want_sumsq else None
+        rc = _lib.lib().dn_helmholtz_apply(mref, aref, _stream(u))
+    if rc:
+        _lib.check(rc, op.fn)
+    return out, (sums[0:1] if want_energy else None), (sums[1:2] if want_sumsq else None)
 
 
 def compute_winding_nodes(points, normals, area, q):

@@ -571,6 +571,62 @@ typedef struct dn_fosls_args {
 int64_t dn_fosls_workspace_bytes(const dn_mesh *mesh);
 int dn_fosls_apply(const dn_mesh *mesh, const dn_fosls_args *args, void *stream);
 
+/* ---- fused 2-D Helmholtz energy and weak-form residual -------------------------------------------------------------------
+ * Replaces the loss body the two Helmholtz scripts of the reference share, examples/poisson/single_instance/14_helmholtz_mms.py:37-63
+ * and 14_helmholtz_ddelta.py:37-63 (Poisson.loss: gpw (0.5 (nu |grad u|^2 - khh^2 u^2) - u f), the Poisson energy plus a reaction
+ * term) -- the two Dirichlet substitutions, five Gauss-point evaluations, the weighted sum and the autograd backward through all of
+ * it -- in ONE launch that reads u once.  Mesh: nsd = 2, degree 1..3, ngp 2..4 (>= 3 for degree > 1), (n - 1) % degree == 0.
+ *   u~ = u after bc[0] then bc[1] (applied in order, as in dn_poisson_args: where both hold, condition 2's value is used)
+ *   energy = sum_{b,e,g} W_g ( c nu_g |grad u~_g|^2  -  cr sg_g u~_g^2  -  fs u~_g f_g ),            W_g = gpw_g * wscale
+ *   out_a  = out_scale * zero_on_dirichlet( sum_{e contains a} sum_g W_g ( alpha nu_g gradN_a . grad u~_g
+ *                                                                          - gamma sg_g N_a u~_g  -  beta N_a f_g ) )
+ *   sumsq  = sum over (b, nodes) of (out / out_scale)^2
+ * u, out (B,1,ny,nx) fp32.  nu is NULL (nu == 1) or a nodal field (1 | B,1,ny,nx) interpolated with the basis; sg is the constant
+ * sigma_value, or the nodal field sigma (1 | B,1,ny,nx) interpolated the same way (sigma_value is ignored then).  The forcing f_g is
+ * the nodal field f (1 | B,1,ny,nx) interpolated with the basis, or f_gp at the Gauss points (Bf,G,nely,nelx) with Bf = 1 (f_batched
+ * 0) or B, or the constant f_value; f and f_gp exclude each other.  Conditions: DN_MASK_F32 / DN_MASK_U8 images, shared or per sample,
+ * constant value or value field.  energy, sumsq: device doubles, unscaled (fixed-order fp64 reduction in the kernel); each may be
+ * NULL, but at least one of out, energy, sumsq must be given.
+ * It replaces, per call:
+ *   - the energy and its gradient (alpha = 2c, gamma = 2cr, beta = fs).  The scripts: c = cr = 0.5, sigma_value = khh^2, fs = 1,
+ *     wscale = 1, out_scale = 1 / (B nel) (torch.mean of the gpw-weighted sums, no Jacobian), nu and f nodal fields;
+ *   - the weak-form residual R with sumsq = sum R^2 (alpha = gamma = beta = 1), the well-posed loss once sigma exceeds the lowest
+ *     eigenvalue and the energy is indefinite (what the *_resmin scripts do for Poisson, e8_2d_poisson_mms.py:92-150);
+ *   - the backward of the residual loss: the operator is symmetric, so the gradient of sum R^2 is a second launch on u := 2R with
+ *     no forcing (beta = 0, f = f_gp = NULL, f_value = 0) and the same masks with value 0 (no value field).
+ * Energy or sumsq needs `workspace` (zero-filled once before first use, dn_helmholtz_workspace_bytes =
+ * 4160 + 16 * chunks * nely * B bytes with nely = (ny - 1) / degree, Q = (nx - 1) / degree + 1 and chunks = 1 for Q <= 64, else
+ * ceil((Q - 1) / 63); every call leaves it ready for the next; one per stream, not shared with other operators).  No atomics on the
+ * data path: out is bitwise independent of the batch it is computed in and of the launch plan ("PLAN_FSDT" "T,R" overrides the plan,
+ * as for dn_strongform_apply); energy and sumsq are reproducible for a given mesh, batch size and plan.
+ * DN_E_UNSUPPORTED for degree outside 1..3, ngp outside 2..4 (or 2 with degree > 1), DN_MASK_BITS / DN_MASK_BOX conditions (expand
+ * them: dn_unpack_mask_bits); DN_E_BADARG for nsd != 2, (n - 1) % degree != 0, a NULL u, no output at all, f together with f_gp,
+ * flags outside {0, 1} or a value field without its mask; DN_E_WORKSPACE for energy or sumsq without a large enough workspace;
+ * nothing is launched then. */
+typedef struct dn_helmholtz_args {
+    const float *u;        /* (B,1,ny,nx) nodal field                                   */
+    const float *nu;       /* (B | 1,1,ny,nx) nodal coefficient or NULL (nu == 1)       */
+    const float *sigma;    /* (B | 1,1,ny,nx) nodal reaction coefficient or NULL        */
+    const float *f;        /* (B | 1,1,ny,nx) nodal forcing or NULL                     */
+    const float *f_gp;     /* (Bf,G,nely,nelx) forcing at Gauss points or NULL          */
+    int32_t nu_batched;    /* 0: one coefficient field for the whole batch              */
+    int32_t sigma_batched; /* same for sigma                                            */
+    int32_t f_batched;     /* same for f / f_gp                                         */
+    float sigma_value;     /* the reaction coefficient when sigma is NULL               */
+    float f_value;         /* the forcing when f and f_gp are NULL                      */
+    dn_dirichlet bc[2];    /* applied in order                                          */
+    float c, cr, fs;       /* the energy's coefficients                                 */
+    float alpha, gamma, beta; /* out's coefficients                                     */
+    float wscale, out_scale;
+    float *out;            /* (B,1,ny,nx) or NULL                                       */
+    double *energy;        /* device scalar: sum (unscaled) or NULL                     */
+    double *sumsq;         /* device scalar: sum over nodes of (out/out_scale)^2 or NULL */
+    void *workspace;
+    int64_t workspace_bytes;
+} dn_helmholtz_args;
+int64_t dn_helmholtz_workspace_bytes(const dn_mesh *mesh);
+int dn_helmholtz_apply(const dn_mesh *mesh, const dn_helmholtz_args *args, void *stream);
+
 /* ---- gradient of the Poisson losses with respect to the nodal coefficient and forcing ------------------------------------
  * Replaces what autograd does for the coefficient in the topology optimisation of the reference,
  * examples/poisson/single_instance/16_topopt.py:119-195 (loss = 0.5 nu grad u . grad v - v f with nu from the network, compliance
