@@ -25,36 +25,19 @@
 //
 // Optional inputs are compile-time forms: MASK (any condition), BCF (any value field), FK (forcing: constant / nodal / at the Gauss
 // points), NUF (nu: constant / nodal field).
-#include <algorithm>
-#include <cstdio>
-
-#include "dn_reduce.h"
+#include "elem2d_common.h"      // everything the kernel shares with strongform.hip and helmholtz.hip: parameters, the march, plan, checks, launch switch
 
 namespace dn {
 
-struct FoParams {
-    float b[4][4], dx[4][4], dy[4][4];     // 1-D tables at the Gauss points (derivatives scaled by 2/h)
-    float w2[4][4];                        // w[jg] * w[ig] * wscale
+struct FoParams : Elem2dParams {
     float wq, wd, fs, fconst, nuconst, out_scale;
     const float* fld[3];                   // u, mx, my
     int64_t fld_stride, grad_stride;       // elements between samples
     const float* nu;                       // NUF: nodal coefficient
     int nu_batched;
-    const float* f;                        // FK == 1: nodal forcing
-    const float* fgp;                      // FK == 2: (B | 1, G, nely, nelx)
-    int f_batched;
-    const void* mask[2];
-    int mask_kind[2];                      // 0: none, 1: uint8 (!= 0), 2: fp32 (> 0.5)
-    int mask_batched[2];
-    const float* bcf[2];
-    int bcf_batched[2];
-    float bcv[2];
     const float* in_scale;
     float* grad[3];
-    double* part;                          // [nblocks] partial sums
-    unsigned* counter;
     double* sum;
-    int nx, ny, nelx, nely, rows_per_strip, want_sums;
 };
 
 // One element: nodal values F[k][jb][ib] of u~, mx, my (Cn: the nodal coefficient, Fn: the nodal forcing); its contributions to the
@@ -136,323 +119,92 @@ __device__ __forceinline__ float fo_elem(const FoParams& p, const float (&F)[3][
     return esum;
 }
 
-// grid = (chunks_x, strips_y, B), block = T threads; one element column per thread (chunks overlap by one thread column).  The P new node
-// rows of layer k + 1 (and its Gauss-point forcing) are requested before the arithmetic of layer k; the finished rows of layer k are
-// stored after that request (fsdt.hip has the reasons).
+// What the march (elem2d_march.inl) asks of the operator: three fields (one barrier per node row for the three), one sum
+template <int P_, int NGP_, int FK_, bool NUF>
+struct FoOp {
+    static constexpr int P = P_, NGP = NGP_, FK = FK_, NF = 3, NS = 1, NB = P + 1;
+    static constexpr bool FOLDS_OK = true;      // fo_elem folds `ok` into the weights
+    struct Raw { float v[3][NB], c[NUF ? NB : 1]; };
+    const float* ub;
+    const float* fldb[3];
+    const float* nub;
+    float gscale;
+    float cu[3][NB][NB], cn[NB][NB];
+
+    __device__ __forceinline__ void init(const FoParams& p, int b, int64_t nps) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) fldb[k] = p.fld[k] + (int64_t)b * p.fld_stride;
+        ub = fldb[0];
+        nub = NUF ? p.nu + (p.nu_batched ? (int64_t)b * nps : 0) : ub;
+    }
+    __device__ __forceinline__ void start(const FoParams& p) {
+        gscale = p.out_scale;
+        if (p.in_scale) gscale *= p.in_scale[0];
+#pragma unroll
+        for (int r = 0; r < NB; ++r)
+#pragma unroll
+            for (int n = 0; n < NB; ++n) cn[r][n] = 0.f;
+    }
+    __device__ __forceinline__ float* out_base(const FoParams& p, int k, int b, int64_t) const {
+        return p.grad[k] ? p.grad[k] + (int64_t)b * p.grad_stride : nullptr;
+    }
+    template <class F>
+    __device__ __forceinline__ void issue(const FoParams& p, unsigned rowoff, int x0, Raw& w, F issue_f) const {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) load_seg<P, false>(fldb[k], rowoff, x0, p.nx, w.v[k]);
+        if constexpr (NUF) load_seg<P, false>(nub, rowoff, x0, p.nx, w.c);
+        issue_f();
+    }
+    __device__ __forceinline__ float raw_u(const Raw& w, int n) const { return w.v[0][n]; }
+    // mx and my are free
+    __device__ __forceinline__ void put(const FoParams&, const Raw& w, int r, int n, float v) {
+        cu[0][r][n] = v;
+        cu[1][r][n] = w.v[1][n];
+        cu[2][r][n] = w.v[2][n];
+        if constexpr (NUF) cn[r][n] = w.c[n];
+    }
+    __device__ __forceinline__ void shift(int n) {
+        cn[0][n] = cn[P][n];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) cu[k][0][n] = cu[k][P][n];
+    }
+    __device__ __forceinline__ float element(const FoParams& p, const float (&fn)[NB][NB], const float (&fg)[NGP * NGP], float okf,
+                                             float (&acc)[3][NB][NB]) const {
+        return fo_elem<P, NGP, FK, NUF>(p, cu, cn, fn, fg, okf, acc);
+    }
+    // no gradient of u reaches a Dirichlet node
+    __device__ __forceinline__ float finish_row(const FoParams&, int k, float (&row)[P], unsigned fixed, int) const {
+#pragma unroll
+        for (int n = 0; n < P; ++n) {
+            float v = row[n] * gscale;
+            if (k == 0) v = (fixed & (1u << n)) ? 0.f : v;
+            row[n] = v;
+        }
+        return 0.f;
+    }
+    __device__ __forceinline__ void write_sums(const FoParams& p, const double (&tot)[1]) const { p.sum[0] = tot[0]; }
+};
+
 template <int P, int NGP, bool MASK, bool BCF, int FK, bool NUF>
 __global__ void __launch_bounds__(256) fosls2d_kernel(const FoParams p) {
-    constexpr int NB = P + 1;
-    constexpr int NW = P;                  // nodes owned per thread per node row
-    constexpr int G = NGP * NGP;
-    static_assert(MASK || !BCF, "a value field belongs to a condition");
-    const int T = (int)blockDim.x, tid = (int)threadIdx.x;
-    const int chunk = blockIdx.x, b = blockIdx.z;
-    const int R = p.rows_per_strip;
-    const int ey_own = (int)blockIdx.y * R;
-    const int q = chunk * (T - 1) + tid;
-    const int ex0 = q, x0 = ex0 * P;
-    const bool col_owner = !(chunk > 0 && tid == 0);
-    const int64_t nps = (int64_t)p.nx * p.ny;
-    const int nel = p.nelx * p.nely;
-    const int ey_begin = ey_own > 0 ? ey_own - 1 : ey_own;        // the layer under the strip's first node row is recomputed
-    const int ey_end = min(ey_own + R, p.nely);
-    const int ymax = p.ny - 1;
-    const bool has_elem = ex0 < p.nelx;
-    const float okf = has_elem ? 1.f : 0.f;      // threads right of the mesh compute on clamped data, weighted by 0
-    const unsigned exc = (unsigned)min(ex0, p.nelx - 1);
-
-    const float* fldb[3];
-    float* ob[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        fldb[k] = p.fld[k] + (int64_t)b * p.fld_stride;
-        ob[k] = p.grad[k] ? p.grad[k] + (int64_t)b * p.grad_stride : nullptr;
-    }
-    const float* ub = fldb[0];
-    const float* nub = NUF ? p.nu + (p.nu_batched ? (int64_t)b * nps : 0) : ub;
-    const float* fb = FK == 1 ? p.f + (p.f_batched ? (int64_t)b * nps : 0) : ub;
-    const float* fgb = FK == 2 ? p.fgp + (p.f_batched ? (int64_t)b * G * nel : 0) : ub;
-    const float* bcfb[2];
-    const float* mfp[2];
-    const uint8_t* mbp[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        bcfb[k] = p.bcf[k] ? p.bcf[k] + (p.bcf_batched[k] ? (int64_t)b * nps : 0) : ub;
-        const int64_t mo = p.mask_batched[k] ? (int64_t)b * nps : 0;
-        mfp[k] = p.mask_kind[k] == 2 ? reinterpret_cast<const float*>(p.mask[k]) + mo : ub;
-        mbp[k] = p.mask_kind[k] == 1 ? reinterpret_cast<const uint8_t*>(p.mask[k]) + mo : reinterpret_cast<const uint8_t*>(ub);
-    }
-    float gscale = p.out_scale;
-    if (p.in_scale) gscale *= p.in_scale[0];
-
-    __shared__ float xch[2][P][3][256];
-    __shared__ double red[16];
-    __shared__ int last_flag;
-
-    float cu[3][NB][NB], cn[NB][NB], fn[NB][NB], acc[3][NB][NB];
-    unsigned fixed[NB];
-#pragma unroll
-    for (int r = 0; r < NB; ++r) {
-        fixed[r] = 0u;
-#pragma unroll
-        for (int n = 0; n < NB; ++n) {
-            cn[r][n] = 0.f; fn[r][n] = 0.f;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) acc[k][r][n] = 0.f;
-        }
-    }
-
-    struct RawRow {
-        float v[3][NW + 1], c[NUF ? NW + 1 : 1], f[FK == 1 ? NW + 1 : 1];
-        float mf[MASK ? 2 : 1][NW + 1], bf[BCF ? 2 : 1][NW + 1];
-        uint8_t mb[MASK ? 2 : 1][NW + 1];
-    };
-    auto row_issue = [&](int yr, RawRow& w) {
-        const unsigned rowoff = (unsigned)min(yr, ymax) * (unsigned)p.nx;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) load_seg<NW, false>(fldb[k], rowoff, x0, p.nx, w.v[k]);
-        if constexpr (NUF) load_seg<NW, false>(nub, rowoff, x0, p.nx, w.c);
-        if constexpr (FK == 1) load_seg<NW, false>(fb, rowoff, x0, p.nx, w.f);
-        if constexpr (MASK) {
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                if (p.mask_kind[k] == 2) load_seg<NW, false>(mfp[k], rowoff, x0, p.nx, w.mf[k]);
-                else if (p.mask_kind[k] == 1) load_seg<NW, false>(mbp[k], rowoff, x0, p.nx, w.mb[k]);
-            }
-        }
-        if constexpr (BCF) {
-#pragma unroll
-            for (int k = 0; k < 2; ++k)
-                if (p.bcf[k]) load_seg<NW, false>(bcfb[k], rowoff, x0, p.nx, w.bf[k]);
-        }
-    };
-    // landed row -> slot r: the two Dirichlet substitutions of u in order (condition 2 wins where both hold); mx and my are free
-    auto row_consume = [&](const RawRow& w, int r) {
-        unsigned bits = 0u;
-#pragma unroll
-        for (int n = 0; n <= NW; ++n) {
-            float v = w.v[0][n];
-            if constexpr (MASK) {
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const bool fx = p.mask_kind[k] == 2 ? (w.mf[k][n] > 0.5f) : (p.mask_kind[k] == 1 ? (w.mb[k][n] != 0) : false);
-                    float bv = p.bcv[k];
-                    if constexpr (BCF) bv = p.bcf[k] ? w.bf[k][n] : bv;
-                    v = fx ? bv : v;
-                    bits |= fx ? (1u << n) : 0u;
-                }
-            }
-            cu[0][r][n] = v;
-            cu[1][r][n] = w.v[1][n];
-            cu[2][r][n] = w.v[2][n];
-            if constexpr (NUF) cn[r][n] = w.c[n];
-            if constexpr (FK == 1) fn[r][n] = w.f[n];
-        }
-        fixed[r] = bits;
-    };
-    auto fg_issue = [&](int ey, float (&w)[G]) {
-        if constexpr (FK == 2) {
-            const unsigned eoff = (unsigned)min(ey, p.nely - 1) * (unsigned)p.nelx + exc;
-#pragma unroll
-            for (int gq = 0; gq < G; ++gq) w[gq] = ld_at<float>(fgb, eoff + (unsigned)(gq * nel));
-        }
-    };
-
-    double sq = 0.0;
-    int par = 0;
-
-    // finished node rows wait here until flush_rows() stores them
-    float pend[P][3][NW];
-    unsigned pend_off[P];
-    bool pend_st[P];
-#pragma unroll
-    for (int r = 0; r < P; ++r) pend_st[r] = false;
-    auto flush_rows = [&]() {
-#pragma unroll
-        for (int r = 0; r < P; ++r) {
-            if (pend_st[r]) {
-#pragma unroll
-                for (int k = 0; k < 3; ++k)
-                    if (ob[k]) store_seg<NW, false>(ob[k], pend_off[r], x0, p.nx, pend[r][k]);
-            }
-            pend_st[r] = false;
-        }
-    };
-    // Emit node row yr from acc[.][r] (+ the left neighbour's hand-over for n == 0); no gradient of u reaches a Dirichlet node
-    auto emit_row = [&](int r, int slot, int yr, bool owned_row) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) xch[par][r % P][k][tid] = acc[k][r][NW];
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS-only barrier (loads stay in flight)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float left = (tid > 0) ? xch[par][r % P][k][tid - 1] : 0.f;
-#pragma unroll
-            for (int n = 0; n < NW; ++n) {
-                float v = (acc[k][r][n] + (n == 0 ? left : 0.f)) * gscale;
-                if (k == 0) v = (fixed[r] & (1u << n)) ? 0.f : v;
-                pend[slot][k][n] = v;
-            }
-        }
-        pend_off[slot] = (unsigned)yr * (unsigned)p.nx;
-        pend_st[slot] = owned_row && col_owner;
-    };
-
-    {
-        RawRow W[P];
-        float fgw[FK == 2 ? G : 1], fgc[G];
-#pragma unroll
-        for (int gq = 0; gq < G; ++gq) fgc[gq] = 0.f;
-        {
-            RawRow w0;
-            row_issue(ey_begin * P, w0);
-#pragma unroll
-            for (int r = 1; r <= P; ++r) row_issue(ey_begin * P + r, W[r - 1]);       // all P + 1 rows of the first layer in flight together
-            if constexpr (FK == 2) fg_issue(ey_begin, fgw);
-            row_consume(w0, 0);
-        }
-        for (int ey = ey_begin; ey < ey_end; ++ey) {
-#pragma unroll
-            for (int r = 1; r <= P; ++r) row_consume(W[r - 1], r);
-            if constexpr (FK == 2) {
-#pragma unroll
-                for (int gq = 0; gq < G; ++gq) fgc[gq] = fgw[gq];
-            }
-#pragma unroll
-            for (int r = 1; r <= P; ++r) row_issue((ey + 1) * P + r, W[r - 1]);      // rows beyond the mesh re-read the last one (unused)
-            if constexpr (FK == 2) fg_issue(ey + 1, fgw);
-            flush_rows();
-            const bool own_layer = ey >= ey_own;
-            const float es = fo_elem<P, NGP, FK, NUF>(p, cu, cn, fn, fgc, okf, acc);
-            sq += (own_layer && col_owner && has_elem) ? (double)es : 0.0;
-#pragma unroll
-            for (int r = 0; r < P; ++r) emit_row(r, r, ey * P + r, own_layer);
-            par ^= 1;
-#pragma unroll
-            for (int n = 0; n <= NW; ++n) {
-                cn[0][n] = cn[P][n];
-                fn[0][n] = fn[P][n];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    cu[k][0][n] = cu[k][P][n];
-                    acc[k][0][n] = acc[k][P][n];
-#pragma unroll
-                    for (int r = 1; r <= P; ++r) acc[k][r][n] = 0.f;
-                }
-            }
-            fixed[0] = fixed[P];
-        }
-        flush_rows();
-        if (ey_end == p.nely) {
-            emit_row(0, 0, p.ny - 1, true);
-            flush_rows();
-        }
-    }
-
-    if (p.want_sums) {
-        const int nthreads = (int)blockDim.x;
-        double* const parts[1] = {p.part};
-        const double mine[1] = {block_sum(sq, red, tid, nthreads)};
-        double tot[1];
-        if (last_arriver_sums<1, 8, false, true>(parts, p.counter, mine, tid, nthreads, &last_flag, tot)) {
-            const double e = block_sum(tot[0], red, tid, nthreads);
-            if (tid == 0) {
-                p.sum[0] = e;
-                arrival_reset(p.counter);
-                p.counter[DN_WS_TICKET_WORD] = 0u;
-            }
-        }
-    }
+    using Op = FoOp<P, NGP, FK, NUF>;
+#include "elem2d_march.inl"
 }
 
-#ifndef FO_DEGREE      // the host side of the entry points: fosls.hip alone
-static inline int fo_ceil_div(int a, int b) { return (a + b - 1) / b; }
-
-struct FoGeom { int T, chunks, R, strips; };
-
-constexpr int FO_MIN_ROWS = 4;             // shortest strip the library chooses (element rows): a strip recomputes one layer
-
-// The plan of the strong-form kernel (strongform.hip: threads per workgroup by utilisation of the last chunk, then the strip height for
-// ~4 waves per SIMD at the price of one recomputed layer per strip).  "PLAN_FSDT" ("T,R") overrides both, as it does there; the
-// results do not depend on the plan.
-static FoGeom fo_plan(const dn_mesh* m) {
-    FoGeom g;
-    const int P = m->degree;
-    const int Q = (m->nx - 1) / P + 1;          // logical thread columns (one per element + the closing column)
-    const int nely = (m->ny - 1) / P;
-    double best = -1.0;
-    g.T = 64; g.chunks = 1;
-    for (int T = 64; T <= 256; T += 64) {
-        const int chunks = Q <= T ? 1 : fo_ceil_div(Q - 1, T - 1);
-        const double score = (double)Q / ((double)chunks * T) + 0.0003 * T;
-        if (score > best) { best = score; g.T = T; g.chunks = chunks; }
+struct FoFamily {
+    using Params = FoParams;
+    template <int P, int NGP, bool MASK, bool BCF, int FK>
+    static void launch(dim3 grid, dim3 block, hipStream_t s, const FoParams& pp) {
+        if (pp.nu) hipLaunchKernelGGL((fosls2d_kernel<P, NGP, MASK, BCF, FK, true>), grid, block, 0, s, pp);
+        else hipLaunchKernelGGL((fosls2d_kernel<P, NGP, MASK, BCF, FK, false>), grid, block, 0, s, pp);
     }
-    const long long per_strip = (long long)g.chunks * m->batch * (g.T / 64);
-    int R = 32;
-    while (R > FO_MIN_ROWS && per_strip * fo_ceil_div(nely, R) < 4096) R /= 2;
-    const char* e = config(CFG_PLAN_FSDT);
-    int T, RR;
-    if (e && sscanf(e, "%d,%d", &T, &RR) == 2 && T >= 64 && T <= 256 && T % 64 == 0 && RR >= 1) {
-        g.T = T; R = RR;
-        g.chunks = Q <= T ? 1 : fo_ceil_div(Q - 1, T - 1);
-    }
-    g.R = std::max(1, std::min(R, nely));
-    g.strips = fo_ceil_div(nely, g.R);
-    return g;
-}
+};
 
-static int fo_validate(const dn_mesh* m) {
-    if (!m || m->nsd != 2) return DN_E_BADARG;
-    if (m->degree < 1 || m->degree > 3 || m->ngp < 2 || m->ngp > 4 || (m->degree > 1 && m->ngp < 3)) return DN_E_UNSUPPORTED;
-    if (m->batch < 1 || m->batch > 65535 || m->nx < 2 || m->ny < 2) return DN_E_BADARG;
-    if ((m->nx - 1) % m->degree || (m->ny - 1) % m->degree) return DN_E_BADARG;
-    if ((int64_t)m->nx * m->ny >= (1ll << 30)) return DN_E_UNSUPPORTED;
-    const int64_t nel = (int64_t)((m->nx - 1) / m->degree) * ((m->ny - 1) / m->degree);
-    if (nel * m->ngp * m->ngp >= (1ll << 30) || (m->ny - 1) / m->degree > 65535) return DN_E_UNSUPPORTED;     // 32-bit offsets; grid.y
-    return 0;
-}
-
-// An upper bound over every launch plan (one-wave chunks, one-row strips): the size does not change with "PLAN_FSDT"
-static inline int64_t fo_workspace_bytes(const dn_mesh* m) {
-    const int P = m->degree;
-    const int Q = (m->nx - 1) / P + 1, nely = (m->ny - 1) / P;
-    const int64_t chunks = Q <= 64 ? 1 : fo_ceil_div(Q - 1, 63);
-    return DN_WS_HEADER + (int64_t)sizeof(double) * chunks * nely * m->batch;
-}
-
-#endif
-
-#define FO_LAUNCH(...) hipLaunchKernelGGL((fosls2d_kernel<__VA_ARGS__>), grid, block, 0, s, pp)
-
-// sel: 0 no condition, 1 conditions with constants, 2 with a value field
-template <int P, int NGP, int FK, bool NUF>
-static void fo_launch_mask(const FoParams& pp, int sel, dim3 grid, dim3 block, hipStream_t s) {
-    if (sel == 2) FO_LAUNCH(P, NGP, true, true, FK, NUF);
-    else if (sel == 1) FO_LAUNCH(P, NGP, true, false, FK, NUF);
-    else FO_LAUNCH(P, NGP, false, false, FK, NUF);
-}
-
-template <int P, int NGP, bool NUF>
-static void fo_launch_fk(const FoParams& pp, int sel, dim3 grid, dim3 block, hipStream_t s) {
-    if (pp.fgp) fo_launch_mask<P, NGP, 2, NUF>(pp, sel, grid, block, s);
-    else if (pp.f) fo_launch_mask<P, NGP, 1, NUF>(pp, sel, grid, block, s);
-    else fo_launch_mask<P, NGP, 0, NUF>(pp, sel, grid, block, s);
-}
-
-template <int P, int NGP>
-void fo_launch_forms(const FoParams& pp, int sel, dim3 grid, dim3 block, hipStream_t s) {
-    if (pp.nu) fo_launch_fk<P, NGP, true>(pp, sel, grid, block, s);
-    else fo_launch_fk<P, NGP, false>(pp, sel, grid, block, s);
-}
-
-#ifndef FO_DEGREE
-// The Q2 and Q3 instantiations compile in translation units of their own (fosls_q2.hip, fosls_q3.hip)
-extern template void fo_launch_forms<2, 3>(const FoParams&, int, dim3, dim3, hipStream_t);
-extern template void fo_launch_forms<2, 4>(const FoParams&, int, dim3, dim3, hipStream_t);
-extern template void fo_launch_forms<3, 3>(const FoParams&, int, dim3, dim3, hipStream_t);
-extern template void fo_launch_forms<3, 4>(const FoParams&, int, dim3, dim3, hipStream_t);
+#ifndef FO_DEGREE      // fosls.hip itself; fosls_q2.hip and fosls_q3.hip compile the higher degrees
+ELEM2D_DEGREE(extern, FoFamily, 2);
+ELEM2D_DEGREE(extern, FoFamily, 3);
 #else
-template void fo_launch_forms<FO_DEGREE, 3>(const FoParams&, int, dim3, dim3, hipStream_t);
-template void fo_launch_forms<FO_DEGREE, 4>(const FoParams&, int, dim3, dim3, hipStream_t);
+ELEM2D_DEGREE(, FoFamily, FO_DEGREE);
 #endif
 
 }  // namespace dn
@@ -461,40 +213,24 @@ template void fo_launch_forms<FO_DEGREE, 4>(const FoParams&, int, dim3, dim3, hi
 using namespace dn;
 
 extern "C" int64_t dn_fosls_workspace_bytes(const dn_mesh* m) {
-    if (fo_validate(m) != 0) return DN_E_BADARG;
-    return fo_workspace_bytes(m);
+    if (elem2d_validate(m) != 0) return DN_E_BADARG;
+    return elem2d_workspace_bytes(m, 1);
 }
 
 extern "C" int dn_fosls_apply(const dn_mesh* m, const dn_fosls_args* a, void* stream) {
-    int rc = fo_validate(m);
+    int rc = elem2d_validate(m);
     if (rc) return rc;
     if (!a || !a->u || !a->mx || !a->my) return DN_E_BADARG;
     const bool any_grad = a->grad_u || a->grad_mx || a->grad_my;
     if (!any_grad && !a->sum) return DN_E_BADARG;
     const int64_t nps = (int64_t)m->nx * m->ny;
     if (a->field_stride < nps || (any_grad && a->grad_stride < nps)) return DN_E_BADARG;
-    if (a->f && a->f_gp) return DN_E_BADARG;
-    if ((a->f_batched | a->nu_batched) & ~1) return DN_E_BADARG;
-    for (int k = 0; k < 2; ++k) {
-        const dn_dirichlet& d = a->bc[k];
-        if (d.mask_kind == DN_MASK_BITS || d.mask_kind == DN_MASK_BOX) return DN_E_UNSUPPORTED;     // expand them: dn_unpack_mask_bits
-        if (d.mask_kind != DN_MASK_F32 && d.mask_kind != DN_MASK_U8) return DN_E_BADARG;
-        if ((d.mask_batched | d.field_batched) & ~1) return DN_E_BADARG;
-        if (d.field && !d.mask) return DN_E_BADARG;                           // a value field without its mask
-    }
-    if (a->sum && (!a->workspace || a->workspace_bytes < fo_workspace_bytes(m))) return DN_E_WORKSPACE;
-    const FoGeom g = fo_plan(m);
+    if (a->nu_batched & ~1) return DN_E_BADARG;
+    if ((rc = elem2d_check_args(m, a, a->sum ? 1 : 0))) return rc;
+    const Elem2dGeom g = elem2d_plan(m);
 
     FoParams pp;
-    const double sx = m->scale[0], sy = m->scale[1];
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            const bool in = i < m->ngp && j <= m->degree;
-            pp.b[i][j] = in ? m->basis[i][j] : 0.f;
-            pp.dx[i][j] = in ? (float)(m->dbasis[i][j] * sx) : 0.f;
-            pp.dy[i][j] = in ? (float)(m->dbasis[i][j] * sy) : 0.f;
-            pp.w2[i][j] = (i < m->ngp && j < m->ngp) ? m->gpw[i] * (m->gpw[j] * a->wscale) : 0.f;
-        }
+    elem2d_fill(pp, m, a, g, a->sum != nullptr);
     pp.wq = a->wq; pp.wd = a->wd; pp.fs = a->fs;
     pp.fconst = (a->f || a->f_gp) ? 0.f : a->f_value;
     pp.nuconst = a->nu ? 0.f : a->nu_value;
@@ -502,41 +238,10 @@ extern "C" int dn_fosls_apply(const dn_mesh* m, const dn_fosls_args* a, void* st
     pp.fld[0] = a->u; pp.fld[1] = a->mx; pp.fld[2] = a->my;
     pp.fld_stride = a->field_stride; pp.grad_stride = any_grad ? a->grad_stride : 0;
     pp.nu = a->nu; pp.nu_batched = a->nu_batched;
-    pp.f = a->f; pp.fgp = a->f_gp; pp.f_batched = a->f_batched;
-    bool mask = false, bcf = false;
-    for (int k = 0; k < 2; ++k) {
-        const dn_dirichlet& d = a->bc[k];
-        pp.mask[k] = d.mask;
-        pp.mask_kind[k] = !d.mask ? 0 : (d.mask_kind == DN_MASK_U8 ? 1 : 2);
-        pp.mask_batched[k] = d.mask_batched;
-        pp.bcf[k] = d.field;
-        pp.bcf_batched[k] = d.field_batched;
-        pp.bcv[k] = d.value;
-        mask = mask || d.mask;
-        bcf = bcf || d.field;
-    }
     pp.in_scale = a->in_scale;
     pp.grad[0] = a->grad_u; pp.grad[1] = a->grad_mx; pp.grad[2] = a->grad_my;
-    pp.counter = reinterpret_cast<unsigned*>(a->workspace);
-    pp.part = a->workspace ? reinterpret_cast<double*>(reinterpret_cast<char*>(a->workspace) + DN_WS_HEADER) : nullptr;
     pp.sum = a->sum;
-    pp.nx = m->nx; pp.ny = m->ny;
-    pp.nelx = (m->nx - 1) / m->degree; pp.nely = (m->ny - 1) / m->degree;
-    pp.rows_per_strip = g.R;
-    pp.want_sums = a->sum ? 1 : 0;
-
-    const dim3 grid(g.chunks, g.strips, m->batch), block(g.T);
-    const int sel = mask ? (bcf ? 2 : 1) : 0;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (m->degree * 10 + m->ngp) {
-        case 12: fo_launch_forms<1, 2>(pp, sel, grid, block, s); break;
-        case 13: fo_launch_forms<1, 3>(pp, sel, grid, block, s); break;
-        case 14: fo_launch_forms<1, 4>(pp, sel, grid, block, s); break;
-        case 23: fo_launch_forms<2, 3>(pp, sel, grid, block, s); break;
-        case 24: fo_launch_forms<2, 4>(pp, sel, grid, block, s); break;
-        case 33: fo_launch_forms<3, 3>(pp, sel, grid, block, s); break;
-        default: fo_launch_forms<3, 4>(pp, sel, grid, block, s); break;
-    }
+    elem2d_launch<FoFamily>(m, pp, g, reinterpret_cast<hipStream_t>(stream));
     DN_LAUNCH_CHECK();
     return 0;
 }

@@ -20,34 +20,17 @@
 //
 // Optional inputs are compile-time forms: MASK (any condition), BCF (any value field), FK (forcing: constant / nodal / at the Gauss
 // points), NL (b != 0), D2 (second-order terms present; never for P = 1, where they vanish identically).
-#include <algorithm>
-#include <cstdio>
-
-#include "dn_reduce.h"
+#include "elem2d_common.h"      // everything the kernel shares with fosls.hip and helmholtz.hip: parameters, the march, plan, checks, launch switch
 
 namespace dn {
 
-struct SfParams {
-    float b[4][4], dx[4][4], dy[4][4];     // 1-D tables at the Gauss points (derivatives scaled by 2/h)
+struct SfParams : Elem2dParams {
     float dxx[4][4], dyy[4][4];            // second derivatives (scaled by (2/h)^2)
-    float w2[4][4];                        // w[jg] * w[ig] * wscale
     float ax, ay, bb, cxx, cyy, fs, fconst, out_scale;
     const float* u;
-    const float* f;                        // FK == 1: nodal forcing
-    const float* fgp;                      // FK == 2: (B | 1, G, nely, nelx)
-    int f_batched;
-    const void* mask[2];
-    int mask_kind[2];                      // 0: none, 1: uint8 (!= 0), 2: fp32 (> 0.5)
-    int mask_batched[2];
-    const float* bcf[2];
-    int bcf_batched[2];
-    float bcv[2];
     const float* in_scale;
     float* grad;
-    double* part;                          // [nblocks] partial sums
-    unsigned* counter;
     double* sum;
-    int nx, ny, nelx, nely, rows_per_strip, want_sums;
 };
 
 // One element: nodal values F[jb][ib] (Fn: the nodal forcing); its contributions to the gradient are ADDED to g[jb][ib]; returns the
@@ -127,314 +110,78 @@ __device__ __forceinline__ float sf_elem(const SfParams& p, const float (&F)[P +
     return esum;
 }
 
-// grid = (chunks_x, strips_y, B), block = T threads; one element column per thread (chunks overlap by one thread column).  The P new node
-// rows of layer k + 1 (and its Gauss-point forcing) are requested before the arithmetic of layer k; the finished rows of layer k are
-// stored after that request (fsdt.hip has the reasons).
+// What the march (elem2d_march.inl) asks of the operator: one field, one sum
+template <int P_, int NGP_, int FK_, bool NL, bool D2>
+struct SfOp {
+    static constexpr int P = P_, NGP = NGP_, FK = FK_, NF = 1, NS = 1, NB = P + 1;
+    static constexpr bool FOLDS_OK = false;
+    struct Raw { float v[NB]; };
+    const float* ub;
+    float gscale;
+    float cu[NB][NB];
+
+    __device__ __forceinline__ void init(const SfParams& p, int b, int64_t nps) {
+        ub = p.u + (int64_t)b * nps;
+    }
+    __device__ __forceinline__ void start(const SfParams& p) {
+        gscale = p.out_scale;
+        if (p.in_scale) gscale *= p.in_scale[0];
+    }
+    __device__ __forceinline__ float* out_base(const SfParams& p, int, int b, int64_t nps) const { return p.grad ? p.grad + (int64_t)b * nps : nullptr; }
+    template <class F>
+    __device__ __forceinline__ void issue(const SfParams& p, unsigned rowoff, int x0, Raw& w, F issue_f) const {
+        load_seg<P, false>(ub, rowoff, x0, p.nx, w.v);
+        issue_f();
+    }
+    __device__ __forceinline__ float raw_u(const Raw& w, int n) const { return w.v[n]; }
+    __device__ __forceinline__ void put(const SfParams&, const Raw&, int r, int n, float v) { cu[r][n] = v; }
+    __device__ __forceinline__ void shift(int n) { cu[0][n] = cu[P][n]; }
+    __device__ __forceinline__ float element(const SfParams& p, const float (&fn)[NB][NB], const float (&fg)[NGP * NGP], float,
+                                             float (&g)[1][NB][NB]) const {
+        return sf_elem<P, NGP, FK, NL, D2>(p, cu, fn, fg, g[0]);
+    }
+    // no gradient reaches a Dirichlet node
+    __device__ __forceinline__ float finish_row(const SfParams&, int, float (&row)[P], unsigned fixed, int) const {
+#pragma unroll
+        for (int n = 0; n < P; ++n) {
+            const float v = row[n] * gscale;
+            row[n] = (fixed & (1u << n)) ? 0.f : v;
+        }
+        return 0.f;
+    }
+    __device__ __forceinline__ void write_sums(const SfParams& p, const double (&tot)[1]) const { p.sum[0] = tot[0]; }
+};
+
 template <int P, int NGP, bool MASK, bool BCF, int FK, bool NL, bool D2>
 __global__ void __launch_bounds__(256) strongform2d_kernel(const SfParams p) {
-    constexpr int NB = P + 1;
-    constexpr int NW = P;                  // nodes owned per thread per node row
-    constexpr int G = NGP * NGP;
     static_assert(!(D2 && P == 1), "the second derivatives of a Q1 field vanish");
-    static_assert(MASK || !BCF, "a value field belongs to a condition");
-    const int T = (int)blockDim.x, tid = (int)threadIdx.x;
-    const int chunk = blockIdx.x, b = blockIdx.z;
-    const int R = p.rows_per_strip;
-    const int ey_own = (int)blockIdx.y * R;
-    const int q = chunk * (T - 1) + tid;
-    const int ex0 = q, x0 = ex0 * P;
-    const bool col_owner = !(chunk > 0 && tid == 0);
-    const int64_t nps = (int64_t)p.nx * p.ny;
-    const int nel = p.nelx * p.nely;
-    const int ey_begin = ey_own > 0 ? ey_own - 1 : ey_own;        // the layer under the strip's first node row is recomputed
-    const int ey_end = min(ey_own + R, p.nely);
-    const int ymax = p.ny - 1;
-    const bool has_elem = ex0 < p.nelx;
-    const float okf = has_elem ? 1.f : 0.f;      // threads right of the mesh compute on clamped data, scaled by 0
-    const unsigned exc = (unsigned)min(ex0, p.nelx - 1);
+    using Op = SfOp<P, NGP, FK, NL, D2>;
+#include "elem2d_march.inl"
+}
 
-    const float* ub = p.u + (int64_t)b * nps;
-    const float* fb = FK == 1 ? p.f + (p.f_batched ? (int64_t)b * nps : 0) : ub;
-    const float* fgb = FK == 2 ? p.fgp + (p.f_batched ? (int64_t)b * G * nel : 0) : ub;
-    float* ob = p.grad ? p.grad + (int64_t)b * nps : nullptr;
-    const float* bcfb[2];
-    const float* mfp[2];
-    const uint8_t* mbp[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        bcfb[k] = p.bcf[k] ? p.bcf[k] + (p.bcf_batched[k] ? (int64_t)b * nps : 0) : ub;
-        const int64_t mo = p.mask_batched[k] ? (int64_t)b * nps : 0;
-        mfp[k] = p.mask_kind[k] == 2 ? reinterpret_cast<const float*>(p.mask[k]) + mo : ub;
-        mbp[k] = p.mask_kind[k] == 1 ? reinterpret_cast<const uint8_t*>(p.mask[k]) + mo : reinterpret_cast<const uint8_t*>(ub);
-    }
-    float gscale = p.out_scale;
-    if (p.in_scale) gscale *= p.in_scale[0];
-
-    __shared__ float xch[2][P][256];
-    __shared__ double red[16];
-    __shared__ int last_flag;
-
-    float cu[NB][NB], fn[NB][NB], acc[NB][NB];
-    unsigned fixed[NB];
-#pragma unroll
-    for (int r = 0; r < NB; ++r) {
-        fixed[r] = 0u;
-#pragma unroll
-        for (int n = 0; n < NB; ++n) { acc[r][n] = 0.f; fn[r][n] = 0.f; }
-    }
-
-    struct RawRow {
-        float v[NW + 1], f[FK == 1 ? NW + 1 : 1];
-        float mf[MASK ? 2 : 1][NW + 1], bf[BCF ? 2 : 1][NW + 1];
-        uint8_t mb[MASK ? 2 : 1][NW + 1];
-    };
-    auto row_issue = [&](int yr, RawRow& w) {
-        const unsigned rowoff = (unsigned)min(yr, ymax) * (unsigned)p.nx;
-        load_seg<NW, false>(ub, rowoff, x0, p.nx, w.v);
-        if constexpr (FK == 1) load_seg<NW, false>(fb, rowoff, x0, p.nx, w.f);
-        if constexpr (MASK) {
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                if (p.mask_kind[k] == 2) load_seg<NW, false>(mfp[k], rowoff, x0, p.nx, w.mf[k]);
-                else if (p.mask_kind[k] == 1) load_seg<NW, false>(mbp[k], rowoff, x0, p.nx, w.mb[k]);
+// NL: b != 0; D2: a second-order term present (Q1: identically zero, no work spent on them)
+struct SfFamily {
+    using Params = SfParams;
+    template <int P, int NGP, bool MASK, bool BCF, int FK>
+    static void launch(dim3 grid, dim3 block, hipStream_t s, const SfParams& pp) {
+        const bool nl = pp.bb != 0.f;
+        if constexpr (P > 1) {
+            if (pp.cxx != 0.f || pp.cyy != 0.f) {
+                if (nl) hipLaunchKernelGGL((strongform2d_kernel<P, NGP, MASK, BCF, FK, true, true>), grid, block, 0, s, pp);
+                else hipLaunchKernelGGL((strongform2d_kernel<P, NGP, MASK, BCF, FK, false, true>), grid, block, 0, s, pp);
+                return;
             }
         }
-        if constexpr (BCF) {
-#pragma unroll
-            for (int k = 0; k < 2; ++k)
-                if (p.bcf[k]) load_seg<NW, false>(bcfb[k], rowoff, x0, p.nx, w.bf[k]);
-        }
-    };
-    // landed row -> slot r: the two Dirichlet substitutions in order (condition 2 wins where both hold)
-    auto row_consume = [&](const RawRow& w, int r) {
-        unsigned bits = 0u;
-#pragma unroll
-        for (int n = 0; n <= NW; ++n) {
-            float v = w.v[n];
-            if constexpr (MASK) {
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const bool fx = p.mask_kind[k] == 2 ? (w.mf[k][n] > 0.5f) : (p.mask_kind[k] == 1 ? (w.mb[k][n] != 0) : false);
-                    float bv = p.bcv[k];
-                    if constexpr (BCF) bv = p.bcf[k] ? w.bf[k][n] : bv;
-                    v = fx ? bv : v;
-                    bits |= fx ? (1u << n) : 0u;
-                }
-            }
-            cu[r][n] = v;
-            if constexpr (FK == 1) fn[r][n] = w.f[n];
-        }
-        fixed[r] = bits;
-    };
-    auto fg_issue = [&](int ey, float (&w)[G]) {
-        if constexpr (FK == 2) {
-            const unsigned eoff = (unsigned)min(ey, p.nely - 1) * (unsigned)p.nelx + exc;
-#pragma unroll
-            for (int gq = 0; gq < G; ++gq) w[gq] = ld_at<float>(fgb, eoff + (unsigned)(gq * nel));
-        }
-    };
-
-    double sq = 0.0;
-    int par = 0;
-
-    // finished node rows wait here until flush_rows() stores them
-    float pend[P][NW];
-    unsigned pend_off[P];
-    bool pend_st[P];
-#pragma unroll
-    for (int r = 0; r < P; ++r) pend_st[r] = false;
-    auto flush_rows = [&]() {
-#pragma unroll
-        for (int r = 0; r < P; ++r) {
-            if (pend_st[r]) store_seg<NW, false>(ob, pend_off[r], x0, p.nx, pend[r]);
-            pend_st[r] = false;
-        }
-    };
-    // Emit node row yr from acc[r] (+ the left neighbour's hand-over for n == 0); no gradient reaches a Dirichlet node
-    auto emit_row = [&](int r, int slot, int yr, bool owned_row) {
-        xch[par][r % P][tid] = acc[r][NW];
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS-only barrier (loads stay in flight)
-        const float left = (tid > 0) ? xch[par][r % P][tid - 1] : 0.f;
-#pragma unroll
-        for (int n = 0; n < NW; ++n) {
-            float v = (acc[r][n] + (n == 0 ? left : 0.f)) * gscale;
-            v = (fixed[r] & (1u << n)) ? 0.f : v;
-            pend[slot][n] = v;
-        }
-        pend_off[slot] = (unsigned)yr * (unsigned)p.nx;
-        pend_st[slot] = owned_row && col_owner && ob != nullptr;
-    };
-
-    {
-        RawRow W[P];
-        float fgw[FK == 2 ? G : 1], fgc[G];
-#pragma unroll
-        for (int gq = 0; gq < G; ++gq) fgc[gq] = 0.f;
-        {
-            RawRow w0;
-            row_issue(ey_begin * P, w0);
-#pragma unroll
-            for (int r = 1; r <= P; ++r) row_issue(ey_begin * P + r, W[r - 1]);       // all P + 1 rows of the first layer in flight together
-            if constexpr (FK == 2) fg_issue(ey_begin, fgw);
-            row_consume(w0, 0);
-        }
-        for (int ey = ey_begin; ey < ey_end; ++ey) {
-#pragma unroll
-            for (int r = 1; r <= P; ++r) row_consume(W[r - 1], r);
-            if constexpr (FK == 2) {
-#pragma unroll
-                for (int gq = 0; gq < G; ++gq) fgc[gq] = fgw[gq];
-            }
-#pragma unroll
-            for (int r = 1; r <= P; ++r) row_issue((ey + 1) * P + r, W[r - 1]);      // rows beyond the mesh re-read the last one (unused)
-            if constexpr (FK == 2) fg_issue(ey + 1, fgw);
-            flush_rows();
-            const bool own_layer = ey >= ey_own;
-            {
-                float g[NB][NB];
-#pragma unroll
-                for (int jb = 0; jb < NB; ++jb)
-#pragma unroll
-                    for (int ib = 0; ib < NB; ++ib) g[jb][ib] = 0.f;
-                const float es = sf_elem<P, NGP, FK, NL, D2>(p, cu, fn, fgc, g);
-                sq += (own_layer && col_owner && has_elem) ? (double)es : 0.0;
-#pragma unroll
-                for (int jb = 0; jb < NB; ++jb)
-#pragma unroll
-                    for (int ib = 0; ib < NB; ++ib) acc[jb][ib] = fmaf(okf, g[jb][ib], acc[jb][ib]);
-            }
-#pragma unroll
-            for (int r = 0; r < P; ++r) emit_row(r, r, ey * P + r, own_layer);
-            par ^= 1;
-#pragma unroll
-            for (int n = 0; n <= NW; ++n) {
-                cu[0][n] = cu[P][n];
-                fn[0][n] = fn[P][n];
-                acc[0][n] = acc[P][n];
-#pragma unroll
-                for (int r = 1; r <= P; ++r) acc[r][n] = 0.f;
-            }
-            fixed[0] = fixed[P];
-        }
-        flush_rows();
-        if (ey_end == p.nely) {
-            emit_row(0, 0, p.ny - 1, true);
-            flush_rows();
-        }
+        if (nl) hipLaunchKernelGGL((strongform2d_kernel<P, NGP, MASK, BCF, FK, true, false>), grid, block, 0, s, pp);
+        else hipLaunchKernelGGL((strongform2d_kernel<P, NGP, MASK, BCF, FK, false, false>), grid, block, 0, s, pp);
     }
+};
 
-    if (p.want_sums) {
-        const int nthreads = (int)blockDim.x;
-        double* const parts[1] = {p.part};
-        const double mine[1] = {block_sum(sq, red, tid, nthreads)};
-        double tot[1];
-        if (last_arriver_sums<1, 8, false, true>(parts, p.counter, mine, tid, nthreads, &last_flag, tot)) {
-            const double e = block_sum(tot[0], red, tid, nthreads);
-            if (tid == 0) {
-                p.sum[0] = e;
-                arrival_reset(p.counter);
-                p.counter[DN_WS_TICKET_WORD] = 0u;
-            }
-        }
-    }
-}
-
-#ifndef SF_DEGREE      // the host side of the entry points: strongform.hip alone
-static inline int sf_ceil_div(int a, int b) { return (a + b - 1) / b; }
-
-struct SfGeom { int T, chunks, R, strips; };
-
-constexpr int SF_MIN_ROWS = 4;             // shortest strip the library chooses (element rows): a strip recomputes one layer
-
-// Threads per workgroup by utilisation of the last chunk (wider wins at equal utilisation), then the strip height: enough waves for ~4
-// per SIMD at the price of one recomputed layer per strip -- the rule of the FSDT element form, whose element this one resembles.
-// "PLAN_FSDT" ("T,R") overrides both, as it does there; the results do not depend on the plan.
-static SfGeom sf_plan(const dn_mesh* m) {
-    SfGeom g;
-    const int P = m->degree;
-    const int Q = (m->nx - 1) / P + 1;          // logical thread columns (one per element + the closing column)
-    const int nely = (m->ny - 1) / P;
-    double best = -1.0;
-    g.T = 64; g.chunks = 1;
-    for (int T = 64; T <= 256; T += 64) {
-        const int chunks = Q <= T ? 1 : sf_ceil_div(Q - 1, T - 1);
-        const double score = (double)Q / ((double)chunks * T) + 0.0003 * T;
-        if (score > best) { best = score; g.T = T; g.chunks = chunks; }
-    }
-    const long long per_strip = (long long)g.chunks * m->batch * (g.T / 64);
-    int R = 32;
-    while (R > SF_MIN_ROWS && per_strip * sf_ceil_div(nely, R) < 4096) R /= 2;
-    const char* e = config(CFG_PLAN_FSDT);
-    int T, RR;
-    if (e && sscanf(e, "%d,%d", &T, &RR) == 2 && T >= 64 && T <= 256 && T % 64 == 0 && RR >= 1) {
-        g.T = T; R = RR;
-        g.chunks = Q <= T ? 1 : sf_ceil_div(Q - 1, T - 1);
-    }
-    g.R = std::max(1, std::min(R, nely));
-    g.strips = sf_ceil_div(nely, g.R);
-    return g;
-}
-
-static int sf_validate(const dn_mesh* m) {
-    if (!m || m->nsd != 2) return DN_E_BADARG;
-    if (m->degree < 1 || m->degree > 3 || m->ngp < 2 || m->ngp > 4 || (m->degree > 1 && m->ngp < 3)) return DN_E_UNSUPPORTED;
-    if (m->batch < 1 || m->batch > 65535 || m->nx < 2 || m->ny < 2) return DN_E_BADARG;
-    if ((m->nx - 1) % m->degree || (m->ny - 1) % m->degree) return DN_E_BADARG;
-    if ((int64_t)m->nx * m->ny >= (1ll << 30)) return DN_E_UNSUPPORTED;
-    const int64_t nel = (int64_t)((m->nx - 1) / m->degree) * ((m->ny - 1) / m->degree);
-    if (nel * m->ngp * m->ngp >= (1ll << 30) || (m->ny - 1) / m->degree > 65535) return DN_E_UNSUPPORTED;     // 32-bit offsets; grid.y
-    return 0;
-}
-
-// An upper bound over every launch plan (one-wave chunks, one-row strips): the size does not change with "PLAN_FSDT"
-static inline int64_t sf_workspace_bytes(const dn_mesh* m) {
-    const int P = m->degree;
-    const int Q = (m->nx - 1) / P + 1, nely = (m->ny - 1) / P;
-    const int64_t chunks = Q <= 64 ? 1 : sf_ceil_div(Q - 1, 63);
-    return DN_WS_HEADER + (int64_t)sizeof(double) * chunks * nely * m->batch;
-}
-
-#endif
-
-#define SF_LAUNCH(...) hipLaunchKernelGGL((strongform2d_kernel<__VA_ARGS__>), grid, block, 0, s, pp)
-
-// sel: 0 no condition, 1 conditions with constants, 2 with a value field
-template <int P, int NGP, int FK, bool NL, bool D2>
-static void sf_launch_mask(const SfParams& pp, int sel, dim3 grid, dim3 block, hipStream_t s) {
-    if (sel == 2) SF_LAUNCH(P, NGP, true, true, FK, NL, D2);
-    else if (sel == 1) SF_LAUNCH(P, NGP, true, false, FK, NL, D2);
-    else SF_LAUNCH(P, NGP, false, false, FK, NL, D2);
-}
-
-template <int P, int NGP, bool NL, bool D2>
-static void sf_launch_fk(const SfParams& pp, int sel, dim3 grid, dim3 block, hipStream_t s) {
-    if (pp.fgp) sf_launch_mask<P, NGP, 2, NL, D2>(pp, sel, grid, block, s);
-    else if (pp.f) sf_launch_mask<P, NGP, 1, NL, D2>(pp, sel, grid, block, s);
-    else sf_launch_mask<P, NGP, 0, NL, D2>(pp, sel, grid, block, s);
-}
-
-template <int P, int NGP>
-void sf_launch_terms(const SfParams& pp, int sel, bool nl, bool d2, dim3 grid, dim3 block, hipStream_t s) {
-    if constexpr (P > 1) {
-        if (d2) {
-            if (nl) sf_launch_fk<P, NGP, true, true>(pp, sel, grid, block, s);
-            else sf_launch_fk<P, NGP, false, true>(pp, sel, grid, block, s);
-            return;
-        }
-    }
-    if (nl) sf_launch_fk<P, NGP, true, false>(pp, sel, grid, block, s);
-    else sf_launch_fk<P, NGP, false, false>(pp, sel, grid, block, s);
-}
-
-#ifndef SF_DEGREE
-// The Q2 and Q3 instantiations compile in translation units of their own (strongform_q2.hip, strongform_q3.hip)
-extern template void sf_launch_terms<2, 3>(const SfParams&, int, bool, bool, dim3, dim3, hipStream_t);
-extern template void sf_launch_terms<2, 4>(const SfParams&, int, bool, bool, dim3, dim3, hipStream_t);
-extern template void sf_launch_terms<3, 3>(const SfParams&, int, bool, bool, dim3, dim3, hipStream_t);
-extern template void sf_launch_terms<3, 4>(const SfParams&, int, bool, bool, dim3, dim3, hipStream_t);
+#ifndef SF_DEGREE      // strongform.hip itself; strongform_q2.hip and strongform_q3.hip compile the higher degrees
+ELEM2D_DEGREE(extern, SfFamily, 2);
+ELEM2D_DEGREE(extern, SfFamily, 3);
 #else
-template void sf_launch_terms<SF_DEGREE, 3>(const SfParams&, int, bool, bool, dim3, dim3, hipStream_t);
-template void sf_launch_terms<SF_DEGREE, 4>(const SfParams&, int, bool, bool, dim3, dim3, hipStream_t);
+ELEM2D_DEGREE(, SfFamily, SF_DEGREE);
 #endif
 
 }  // namespace dn
@@ -443,79 +190,35 @@ template void sf_launch_terms<SF_DEGREE, 4>(const SfParams&, int, bool, bool, di
 using namespace dn;
 
 extern "C" int64_t dn_strongform_workspace_bytes(const dn_mesh* m) {
-    if (sf_validate(m) != 0) return DN_E_BADARG;
-    return sf_workspace_bytes(m);
+    if (elem2d_validate(m) != 0) return DN_E_BADARG;
+    return elem2d_workspace_bytes(m, 1);
 }
 
 extern "C" int dn_strongform_apply(const dn_mesh* m, const dn_strongform_args* a, void* stream) {
-    int rc = sf_validate(m);
+    int rc = elem2d_validate(m);
     if (rc) return rc;
     if (!a || !a->u) return DN_E_BADARG;
     if (!a->grad && !a->sum) return DN_E_BADARG;
-    if (a->f && a->f_gp) return DN_E_BADARG;
-    if (a->f_batched & ~1) return DN_E_BADARG;
-    for (int k = 0; k < 2; ++k) {
-        const dn_dirichlet& d = a->bc[k];
-        if (d.mask_kind == DN_MASK_BITS || d.mask_kind == DN_MASK_BOX) return DN_E_UNSUPPORTED;     // expand them: dn_unpack_mask_bits
-        if (d.mask_kind != DN_MASK_F32 && d.mask_kind != DN_MASK_U8) return DN_E_BADARG;
-        if ((d.mask_batched | d.field_batched) & ~1) return DN_E_BADARG;
-        if (d.field && !d.mask) return DN_E_BADARG;                           // a value field without its mask
-    }
-    if (a->sum && (!a->workspace || a->workspace_bytes < sf_workspace_bytes(m))) return DN_E_WORKSPACE;
-    const SfGeom g = sf_plan(m);
+    if ((rc = elem2d_check_args(m, a, a->sum ? 1 : 0))) return rc;
+    const Elem2dGeom g = elem2d_plan(m);
 
     SfParams pp;
+    elem2d_fill(pp, m, a, g, a->sum != nullptr);
     const double sx = m->scale[0], sy = m->scale[1];
     for (int i = 0; i < 4; ++i)
         for (int j = 0; j < 4; ++j) {
             const bool in = i < m->ngp && j <= m->degree;
-            pp.b[i][j] = in ? m->basis[i][j] : 0.f;
-            pp.dx[i][j] = in ? (float)(m->dbasis[i][j] * sx) : 0.f;
-            pp.dy[i][j] = in ? (float)(m->dbasis[i][j] * sy) : 0.f;
             pp.dxx[i][j] = in ? (float)(a->d2basis[i][j] * sx * sx) : 0.f;
             pp.dyy[i][j] = in ? (float)(a->d2basis[i][j] * sy * sy) : 0.f;
-            pp.w2[i][j] = (i < m->ngp && j < m->ngp) ? m->gpw[i] * (m->gpw[j] * a->wscale) : 0.f;
         }
     pp.ax = a->ax; pp.ay = a->ay; pp.bb = a->b; pp.cxx = a->dxx; pp.cyy = a->dyy; pp.fs = a->fs;
     pp.fconst = (a->f || a->f_gp) ? 0.f : a->f_value;
     pp.out_scale = a->out_scale;
-    pp.u = a->u; pp.f = a->f; pp.fgp = a->f_gp; pp.f_batched = a->f_batched;
-    bool mask = false, bcf = false;
-    for (int k = 0; k < 2; ++k) {
-        const dn_dirichlet& d = a->bc[k];
-        pp.mask[k] = d.mask;
-        pp.mask_kind[k] = !d.mask ? 0 : (d.mask_kind == DN_MASK_U8 ? 1 : 2);
-        pp.mask_batched[k] = d.mask_batched;
-        pp.bcf[k] = d.field;
-        pp.bcf_batched[k] = d.field_batched;
-        pp.bcv[k] = d.value;
-        mask = mask || d.mask;
-        bcf = bcf || d.field;
-    }
+    pp.u = a->u;
     pp.in_scale = a->in_scale;
     pp.grad = a->grad;
-    pp.counter = reinterpret_cast<unsigned*>(a->workspace);
-    pp.part = a->workspace ? reinterpret_cast<double*>(reinterpret_cast<char*>(a->workspace) + DN_WS_HEADER) : nullptr;
     pp.sum = a->sum;
-    pp.nx = m->nx; pp.ny = m->ny;
-    pp.nelx = (m->nx - 1) / m->degree; pp.nely = (m->ny - 1) / m->degree;
-    pp.rows_per_strip = g.R;
-    pp.want_sums = a->sum ? 1 : 0;
-
-    const dim3 grid(g.chunks, g.strips, m->batch), block(g.T);
-    const int sel = mask ? (bcf ? 2 : 1) : 0;
-    const bool nl = a->b != 0.f;
-    const bool d2 = m->degree > 1 && (a->dxx != 0.f || a->dyy != 0.f);       // Q1: identically zero, no work spent on them
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (m->degree * 10 + m->ngp) {
-        case 12: sf_launch_terms<1, 2>(pp, sel, nl, d2, grid, block, s); break;
-        case 13: sf_launch_terms<1, 3>(pp, sel, nl, d2, grid, block, s); break;
-        case 14: sf_launch_terms<1, 4>(pp, sel, nl, d2, grid, block, s); break;
-        case 23: sf_launch_terms<2, 3>(pp, sel, nl, d2, grid, block, s); break;
-        case 24: sf_launch_terms<2, 4>(pp, sel, nl, d2, grid, block, s); break;
-        case 33: sf_launch_terms<3, 3>(pp, sel, nl, d2, grid, block, s); break;
-        default: sf_launch_terms<3, 4>(pp, sel, nl, d2, grid, block, s); break;
-    }
+    elem2d_launch<SfFamily>(m, pp, g, reinterpret_cast<hipStream_t>(stream));
     DN_LAUNCH_CHECK();
     return 0;
 }

@@ -1569,6 +1569,7 @@ class _Flow2dOp:
         self.ws_bytes = {}
         self.cache = __import__("collections").OrderedDict()
         self.launch_lock = _threading.Lock()
+        self.entry = None                  # the bound C entry point, where a caller keeps it (_elem2d_launch)
 
 
 _STOKES = _Flow2dOp("stokes_apply", DnStokesArgs)
@@ -2048,34 +2049,33 @@ def transport_apply(geom, u, nu=None, bc=None, bc_values=(0.0, 0.0), r_first_win
     return (out, sums, norm) if want_norm else (out, sums)
 
 
-# ---- the fused 2-D strong-form least-squares loss and its gradient: dn_strongform_apply ----------------------------------------
-# Its own reduction workspace per (device, stream), prepared-call cache and launch lock, like _TRANSPORT and for the same reason.
+# ---- the three element-march operators on 2-D Q_P meshes: dn_strongform_apply, dn_fosls_apply, dn_helmholtz_apply ----------------
+# Each has its own reduction workspace per (device, stream), prepared-call cache and launch lock, like _TRANSPORT and for the same
+# reason.  What their calls share -- the mesh check, the key of a prepared call, the two conditions, the forcing, in_scale, the
+# workspace, the look-up / prepare / cache step and the patch-under-lock / launch step -- is written once (_elem2d_*); an operator's own
+# functions name its own arguments and allocate its outputs.
 _STRONGFORM = _Flow2dOp("strongform_apply", DnStrongformArgs)
+_FOSLS = _Flow2dOp("fosls_apply", DnFoslsArgs)
+_HELMHOLTZ = _Flow2dOp("helmholtz_apply", DnHelmholtzArgs)
 
 
-def _strongform_check_mesh(geom):
+def _elem2d_check_mesh(op, geom):
     if geom.nsd != 2 or geom.deg not in (1, 2, 3) or not 2 <= geom.ngp_1d <= 4 or (geom.deg > 1 and geom.ngp_1d < 3):
-        raise DiffNetHipError(f"strongform_apply: 2-D meshes of degree 1..3 with 2..4 Gauss points per axis (3 or 4 above degree 1) only "
+        raise DiffNetHipError(f"{op.name}: 2-D meshes of degree 1..3 with 2..4 Gauss points per axis (3 or 4 above degree 1) only "
                               f"(nsd {geom.nsd}, degree {geom.deg}, ngp {geom.ngp_1d})")
     if any((n - 1) % geom.deg for n in geom.sizes):
-        raise ValueError(f"strongform_apply: a degree-{geom.deg} mesh needs (n - 1) % {geom.deg} == 0 nodes per axis, got {geom.sizes}")
+        raise ValueError(f"{op.name}: a degree-{geom.deg} mesh needs (n - 1) % {geom.deg} == 0 nodes per axis, got {geom.sizes}")
 
 
-def _strongform_key(geom, u, bc2, vals, f, f_gp, consts, in_scale, flags):
-    """Key of a cached prepared call (see _call_key); None when an argument needs a conversion copy."""
-    if not (isinstance(u, torch.Tensor) and u.is_cuda and tuple(u.shape[1:]) == (1, *geom.node_shape)):
-        return None
-    parts = [geom.key, u.device.index, _raw_stream(u.device), consts, flags]
-    k = _tkey(u)
-    if k is None or k == 0 or k[1] != torch.float32:
-        return None
-    parts.append(k)
-    for m in bc2:
+def _elem2d_key(parts, masks, scalars, optional):
+    """Completes the key of a cached prepared call (see _call_key) that starts with `parts`: the masks (fp32 / uint8 / bool or None),
+    the float-or-fp32-tensor arguments `scalars` and the optional fp32 tensors; None when an argument needs a conversion copy."""
+    for m in masks:
         k = _tkey(m)
         if k is None or (k != 0 and k[1] not in (torch.float32, torch.uint8, torch.bool)):
             return None
         parts.append(k)
-    for v in tuple(vals) + (f_gp,):
+    for v in scalars:
         if isinstance(v, torch.Tensor) and v.numel() > 1:
             k = _tkey(v)
             if k is None or k[1] != torch.float32:
@@ -2083,7 +2083,7 @@ def _strongform_key(geom, u, bc2, vals, f, f_gp, consts, in_scale, flags):
             parts.append(k)
         else:
             parts.append(float(v))
-    for t in (f, in_scale):
+    for t in optional:
         k = _tkey(t)
         if k is None or (k != 0 and k[1] != torch.float32):
             return None
@@ -2091,25 +2091,32 @@ def _strongform_key(geom, u, bc2, vals, f, f_gp, consts, in_scale, flags):
     return tuple(parts)
 
 
-def _prepare_strongform(geom, u, bc2, vals, f, f_gp, consts, in_scale, want_sum):
-    """Validation + argument struct of a dn_strongform_apply call, outputs left unset: (mesh, args, tensors to keep alive, field shape)."""
-    name = _STRONGFORM.name
-    _strongform_check_mesh(geom)
-    u = _require(u, "u", 4)
-    B = u.shape[0]
-    shape = (B, 1, *geom.node_shape)
-    if tuple(u.shape) != shape:
-        raise ValueError(f"{name}: field shape {tuple(u.shape)} != {shape}")
-    keep = [u]
-    args = DnStrongformArgs()
-    args.u = u.data_ptr()
+def _elem2d_u_key(geom, u, consts, flags):
+    """The head of the key of a call on one field u (B,1,ny,nx), or None."""
+    if not (isinstance(u, torch.Tensor) and u.is_cuda and tuple(u.shape[1:]) == (1, *geom.node_shape)):
+        return None
+    k = _tkey(u)
+    if k is None or k == 0 or k[1] != torch.float32:
+        return None
+    return [geom.key, u.device.index, _raw_stream(u.device), consts, flags, k]
+
+
+def _elem2d_field(op, geom, args, keep, B, t, what, member, fp32=True):
+    """A nodal field (B | 1, ., ny, nx) into args.<member> and args.<member>_batched."""
     nn = geom.nnode_total
+    if fp32:
+        t = _require(t, what)
+    if tuple(t.shape[-2:]) != tuple(geom.node_shape) or t.numel() not in (B * nn, nn):
+        raise ValueError(f"{op.name}: {what} shape {tuple(t.shape)} does not match the mesh {(B, 1, *geom.node_shape)}")
+    setattr(args, member + "_batched", 1 if (t.numel() == B * nn and B > 1) else 0)
+    setattr(args, member, t.data_ptr())
+    keep.append(t)
 
-    def batched(t, what):
-        if tuple(t.shape[-2:]) != tuple(geom.node_shape) or t.numel() not in (B * nn, nn):
-            raise ValueError(f"{name}: {what} shape {tuple(t.shape)} does not match the mesh {shape}")
-        return 1 if (t.numel() == B * nn and B > 1) else 0
 
+def _prepare_elem2d(op, geom, args, keep, B, dev, bc2, vals, f, f_gp, want_sums, in_scale=None, in_scale_on=None):
+    """The members the three argument structs have in common, after the operator's own: the two conditions, the forcing, in_scale (where
+    the struct has one) and the workspace of a reducing call.  Returns the mesh struct."""
+    name = op.name
     for k, m in enumerate(bc2):
         if m is None:
             continue
@@ -2117,34 +2124,24 @@ def _prepare_strongform(geom, u, bc2, vals, f, f_gp, consts, in_scale, want_sum)
             raise TypeError(f"{name}: bc[{k}] must be a tensor or None (expand a PackedMask / BoxFaces to its image)")
         if not m.is_cuda:
             raise DiffNetHipError(f"{name}: bc[{k}] is on {m.device}: the FEM ops run on the GPU only (no CPU fallback)")
-        if m.dtype in (torch.bool, torch.uint8):
+        byte = m.dtype in (torch.bool, torch.uint8)
+        if byte:
             m = m.contiguous()
             m = m.view(torch.uint8) if m.dtype == torch.bool else m
-            args.bc[k].mask_kind = _lib.MASK_U8
-        else:
-            m = _require(m, f"bc[{k}]")
-            args.bc[k].mask_kind = _lib.MASK_F32
-        args.bc[k].mask_batched = batched(m, f"bc[{k}]")
-        args.bc[k].mask = m.data_ptr()
-        keep.append(m)
+        args.bc[k].mask_kind = _lib.MASK_U8 if byte else _lib.MASK_F32
+        _elem2d_field(op, geom, args.bc[k], keep, B, m, f"bc[{k}]", "mask", fp32=not byte)
     for k, val in enumerate(vals):
         if isinstance(val, torch.Tensor) and val.numel() > 1:
             if bc2[k] is None:
                 raise ValueError(f"{name}: bc_values[{k}] is a field but condition {k} has no mask")
-            val = _require(val, f"bc_values[{k}]")
-            args.bc[k].field_batched = batched(val, f"bc_values[{k}]")
-            args.bc[k].field = val.data_ptr()
-            keep.append(val)
+            _elem2d_field(op, geom, args.bc[k], keep, B, val, f"bc_values[{k}]", "field")
         else:
             args.bc[k].value = float(val)
     G, nel = geom.ngp_total, geom.nelem_total
     if f is not None:
         if isinstance(f_gp, torch.Tensor) and f_gp.numel() > 1:
             raise ValueError(f"{name}: nodal forcing f and Gauss-point forcing f_gp exclude each other")
-        f = _require(f, "f")
-        args.f_batched = batched(f, "f")
-        args.f = f.data_ptr()
-        keep.append(f)
+        _elem2d_field(op, geom, args, keep, B, f, "f", "f")
     elif isinstance(f_gp, torch.Tensor) and f_gp.numel() > 1:
         f_gp = _require(f_gp, "f_gp")
         if tuple(f_gp.shape[-3:]) != (G, *geom.elem_shape) or f_gp.numel() not in (G * nel, B * G * nel):
@@ -2156,20 +2153,91 @@ def _prepare_strongform(geom, u, bc2, vals, f, f_gp, consts, in_scale, want_sum)
         args.f_value = float(f_gp)
     if in_scale is not None:
         in_scale = _require(in_scale, "in_scale")
-        if in_scale.numel() != 1 or in_scale.device != u.device:
-            raise ValueError(f"{name}: in_scale must hold one float on u's device")
+        if in_scale.numel() != 1 or in_scale.device != dev:
+            raise ValueError(f"{name}: in_scale must hold one float on {in_scale_on} device")
         args.in_scale = in_scale.data_ptr()
         keep.append(in_scale)
+    mesh = geom.mesh_struct(B)
+    if want_sums:
+        ws = _flow2d_workspace(op, mesh, B, dev)
+        keep.append(ws)
+        args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    return mesh
+
+
+def _elem2d_entry(op, key, prepare, pargs):
+    """The prepared call `key` (None: not cacheable) from the operator's cache, or prepare(*pargs) -- (mesh, args, tensors to keep alive,
+    the field shape or the batch size) -- inserted into it: (mesh, args, their two references, shape | B, tensors kept alive)."""
+    ent = None
+    if key is not None:
+        with _WS_LOCK:
+            ent = op.cache.get(key)
+            if ent is not None:
+                op.cache.move_to_end(key)
+    if ent is not None:
+        _CALL_STATS["hit"] += 1
+        return ent
+    _CALL_STATS["miss" if key is not None else "uncached"] += 1
+    mesh, args, keep, shape = prepare(*pargs)
+    with _WS_LOCK:
+        live_ws = list(op.ws.values())
+    # an uncached call keeps its (possibly converted) tensors alive until it has been issued; a cached one only the workspace
+    ent = (mesh, args, C.byref(mesh), C.byref(args), shape, keep if key is None else [t for t in keep if any(t is x for x in live_ws)])
+    if key is not None:
+        with _WS_LOCK:
+            op.cache[key] = ent
+            while len(op.cache) > _CALL_CACHE_MAX:
+                op.cache.popitem(last=False)
+    return ent
+
+
+def _elem2d_launch(op, ent, u, patch, ptrs):
+    """patch(args, ptrs) sets the pointers of the call's fresh outputs in the (possibly shared, cached) argument struct; that and the
+    launch are one step under the operator's lock.  The hit path of a call is host time: no closure, the entry point bound once."""
+    fn = op.entry
+    if fn is None:
+        fn = op.entry = getattr(_lib.lib(), op.fn)
+    with op.launch_lock:
+        patch(ent[1], ptrs)
+        rc = fn(ent[2], ent[3], _stream(u))
+    if rc:
+        _lib.check(rc, op.fn)
+
+
+def _elem2d_u(op, geom, u, args, keep):
+    """The field u (B,1,ny,nx) of a one-field operator into args.u; returns (u, B, its shape)."""
+    u = _require(u, "u", 4)
+    B = u.shape[0]
+    shape = (B, 1, *geom.node_shape)
+    if tuple(u.shape) != shape:
+        raise ValueError(f"{op.name}: field shape {tuple(u.shape)} != {shape}")
+    keep.append(u)
+    args.u = u.data_ptr()
+    return u, B, shape
+
+
+# ---- the fused 2-D strong-form least-squares loss and its gradient: dn_strongform_apply ----------------------------------------
+def _strongform_key(geom, u, bc2, vals, f, f_gp, consts, in_scale, flags):
+    parts = _elem2d_u_key(geom, u, consts, flags)
+    return parts and _elem2d_key(parts, bc2, (*vals, f_gp), (f, in_scale))
+
+
+def _prepare_strongform(geom, u, bc2, vals, f, f_gp, consts, in_scale, want_sum):
+    """Validation + argument struct of a dn_strongform_apply call, outputs left unset: (mesh, args, tensors to keep alive, field shape)."""
+    op = _STRONGFORM
+    _elem2d_check_mesh(op, geom)
+    args, keep = DnStrongformArgs(), []
+    u, B, shape = _elem2d_u(op, geom, u, args, keep)
     args.ax, args.ay, args.b, args.dxx, args.dyy, args.fs, args.wscale, args.out_scale = consts
     for i in range(geom.ngp_1d):             # phi''(xi_ig) from the rule's own (truncated) abscissae, as the reference's tables
         for j in range(geom.deg + 1):
             args.d2basis[i][j] = geom.d2basis[i, j]
-    mesh = geom.mesh_struct(B)
-    if want_sum:
-        ws = _flow2d_workspace(_STRONGFORM, mesh, B, u.device)
-        keep.append(ws)
-        args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    mesh = _prepare_elem2d(op, geom, args, keep, B, u.device, bc2, vals, f, f_gp, want_sum, in_scale, "u's")
     return mesh, args, keep, shape
+
+
+def _strongform_patch(args, ptrs):
+    args.grad, args.sum = ptrs
 
 
 def strongform_apply(geom, u, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=None, coef=(0.0, 0.0, 0.0, 0.0, 0.0, 0.0), wscale=1.0,
@@ -2181,7 +2249,7 @@ def strongform_apply(geom, u, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=None, 
     `bc_values[k]`: float or tensor u takes under condition k (where both hold, condition 2's); the forcing: a nodal field `f`
     (B | 1,1,ny,nx), or `f_gp`, a float or a Gauss-point tensor (B | 1, G, nely, nelx).  Degree 1..3.  Returns (grad | None, sum | None).
     Calls on the same buffers reuse their prepared argument structs (small LRU, fresh outputs per call: see poisson_apply)."""
-    _strongform_check_mesh(geom)
+    _elem2d_check_mesh(_STRONGFORM, geom)
     bc2, vals, coef = transport_bc2(bc), tuple(bc_values), tuple(float(x) for x in coef)
     if len(vals) != 2:
         raise ValueError("strongform_apply: bc_values must hold two entries")
@@ -2191,56 +2259,16 @@ def strongform_apply(geom, u, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=None, 
         raise ValueError("strongform_apply: nothing to compute (want_grad and want_sum are both off)")
     fg = 0.0 if f_gp is None else f_gp
     consts = (*coef, float(wscale), float(out_scale))
-    op = _STRONGFORM
     key = _strongform_key(geom, u, bc2, vals, f, fg, consts, in_scale, (want_grad, want_sum))
-    ent = None
-    if key is not None:
-        with _WS_LOCK:
-            ent = op.cache.get(key)
-            if ent is not None:
-                op.cache.move_to_end(key)
-    if ent is None:
-        _CALL_STATS["miss" if key is not None else "uncached"] += 1
-        mesh, args, keep, shape = _prepare_strongform(geom, u, bc2, vals, f, fg, consts, in_scale, want_sum)
-        with _WS_LOCK:
-            live_ws = list(op.ws.values())
-        # an uncached call keeps its (possibly converted) tensors alive until it has been issued; a cached one only the workspace
-        ent = (mesh, args, C.byref(mesh), C.byref(args), shape, keep if key is None else [t for t in keep if any(t is x for x in live_ws)])
-        if key is not None:
-            with _WS_LOCK:
-                op.cache[key] = ent
-                while len(op.cache) > _CALL_CACHE_MAX:
-                    op.cache.popitem(last=False)
-    else:
-        _CALL_STATS["hit"] += 1
-    mesh, args, mref, aref, shape = ent[:5]
-    dev = u.device
-    grad = torch.empty(shape, dtype=torch.float32, device=dev) if want_grad else None
-    sums = torch.empty(1, dtype=torch.float64, device=dev) if want_sum else None
-    with op.launch_lock:               # pointer patch + launch of the (possibly shared, cached) argument struct as one step
-        args.grad = grad.data_ptr() if want_grad else None
-        args.sum = sums.data_ptr() if want_sum else None
-        rc = _lib.lib().dn_strongform_apply(mref, aref, _stream(u))
-    if rc:
-        _lib.check(rc, op.fn)
+    ent = _elem2d_entry(_STRONGFORM, key, _prepare_strongform, (geom, u, bc2, vals, f, fg, consts, in_scale, want_sum))
+    grad = torch.empty(ent[4], dtype=torch.float32, device=u.device) if want_grad else None
+    sums = torch.empty(1, dtype=torch.float64, device=u.device) if want_sum else None
+    _elem2d_launch(_STRONGFORM, ent, u, _strongform_patch, (grad.data_ptr() if want_grad else None, sums.data_ptr() if want_sum else None))
     return grad, sums
 
 
 # ---- the fused 2-D first-order-system least-squares loss (u, mx, my) and its gradients: dn_fosls_apply --------------------------
-# Its own reduction workspace per (device, stream), prepared-call cache and launch lock, like _STRONGFORM and for the same reason.
-_FOSLS = _Flow2dOp("fosls_apply", DnFoslsArgs)
-
-
-def _fosls_check_mesh(geom):
-    if geom.nsd != 2 or geom.deg not in (1, 2, 3) or not 2 <= geom.ngp_1d <= 4 or (geom.deg > 1 and geom.ngp_1d < 3):
-        raise DiffNetHipError(f"fosls_apply: 2-D meshes of degree 1..3 with 2..4 Gauss points per axis (3 or 4 above degree 1) only "
-                              f"(nsd {geom.nsd}, degree {geom.deg}, ngp {geom.ngp_1d})")
-    if any((n - 1) % geom.deg for n in geom.sizes):
-        raise ValueError(f"fosls_apply: a degree-{geom.deg} mesh needs (n - 1) % {geom.deg} == 0 nodes per axis, got {geom.sizes}")
-
-
 def _fosls_key(geom, flds, packed, nu, bc2, vals, f, f_gp, consts, in_scale, flags):
-    """Key of a cached prepared call (see _call_key); None when an argument needs a conversion copy."""
     first = flds[0]
     if not (isinstance(first, torch.Tensor) and first.is_cuda):
         return None
@@ -2250,31 +2278,14 @@ def _fosls_key(geom, flds, packed, nu, bc2, vals, f, f_gp, consts, in_scale, fla
         if k is None or k == 0 or k[1] != torch.float32 or tuple(k[2][1:]) != ((3 if packed else 1), *geom.node_shape):
             return None
         parts.append(k)
-    for m in bc2:
-        k = _tkey(m)
-        if k is None or (k != 0 and k[1] not in (torch.float32, torch.uint8, torch.bool)):
-            return None
-        parts.append(k)
-    for v in tuple(vals) + (f_gp, nu):
-        if isinstance(v, torch.Tensor) and v.numel() > 1:
-            k = _tkey(v)
-            if k is None or k[1] != torch.float32:
-                return None
-            parts.append(k)
-        else:
-            parts.append(float(v))
-    for t in (f, in_scale):
-        k = _tkey(t)
-        if k is None or (k != 0 and k[1] != torch.float32):
-            return None
-        parts.append(k)
-    return tuple(parts)
+    return _elem2d_key(parts, bc2, (*vals, f_gp, nu), (f, in_scale))
 
 
 def _prepare_fosls(geom, flds, packed, nu, bc2, vals, f, f_gp, consts, in_scale, want_sum):
     """Validation + argument struct of a dn_fosls_apply call, outputs left unset: (mesh, args, tensors to keep alive, batch size)."""
-    name = _FOSLS.name
-    _fosls_check_mesh(geom)
+    op = _FOSLS
+    name = op.name
+    _elem2d_check_mesh(op, geom)
     nn = geom.nnode_total
     args = DnFoslsArgs()
     if packed:
@@ -2285,7 +2296,6 @@ def _prepare_fosls(geom, flds, packed, nu, bc2, vals, f, f_gp, consts, in_scale,
         keep = [t]
         args.u, args.mx, args.my = t.data_ptr(), t.data_ptr() + 4 * nn, t.data_ptr() + 8 * nn
         args.field_stride = 3 * nn
-        u = t
     else:
         keep = []
         B = flds[0].shape[0] if isinstance(flds[0], torch.Tensor) and flds[0].dim() == 4 else 0
@@ -2299,78 +2309,18 @@ def _prepare_fosls(geom, flds, packed, nu, bc2, vals, f, f_gp, consts, in_scale,
             setattr(args, what, t.data_ptr())
             keep.append(t)
         args.field_stride = nn
-        u = keep[0]
-    shape = (B, 1, *geom.node_shape)
-
-    def batched(t, what):
-        if tuple(t.shape[-2:]) != tuple(geom.node_shape) or t.numel() not in (B * nn, nn):
-            raise ValueError(f"{name}: {what} shape {tuple(t.shape)} does not match the mesh {shape}")
-        return 1 if (t.numel() == B * nn and B > 1) else 0
-
+    dev = keep[0].device
     if isinstance(nu, torch.Tensor) and nu.numel() > 1:
-        nu = _require(nu, "nu")
-        args.nu_batched = batched(nu, "nu")
-        args.nu = nu.data_ptr()
-        keep.append(nu)
+        _elem2d_field(op, geom, args, keep, B, nu, "nu", "nu")
     else:
         args.nu_value = float(nu)
-    for k, m in enumerate(bc2):
-        if m is None:
-            continue
-        if not isinstance(m, torch.Tensor):
-            raise TypeError(f"{name}: bc[{k}] must be a tensor or None (expand a PackedMask / BoxFaces to its image)")
-        if not m.is_cuda:
-            raise DiffNetHipError(f"{name}: bc[{k}] is on {m.device}: the FEM ops run on the GPU only (no CPU fallback)")
-        if m.dtype in (torch.bool, torch.uint8):
-            m = m.contiguous()
-            m = m.view(torch.uint8) if m.dtype == torch.bool else m
-            args.bc[k].mask_kind = _lib.MASK_U8
-        else:
-            m = _require(m, f"bc[{k}]")
-            args.bc[k].mask_kind = _lib.MASK_F32
-        args.bc[k].mask_batched = batched(m, f"bc[{k}]")
-        args.bc[k].mask = m.data_ptr()
-        keep.append(m)
-    for k, val in enumerate(vals):
-        if isinstance(val, torch.Tensor) and val.numel() > 1:
-            if bc2[k] is None:
-                raise ValueError(f"{name}: bc_values[{k}] is a field but condition {k} has no mask")
-            val = _require(val, f"bc_values[{k}]")
-            args.bc[k].field_batched = batched(val, f"bc_values[{k}]")
-            args.bc[k].field = val.data_ptr()
-            keep.append(val)
-        else:
-            args.bc[k].value = float(val)
-    G, nel = geom.ngp_total, geom.nelem_total
-    if f is not None:
-        if isinstance(f_gp, torch.Tensor) and f_gp.numel() > 1:
-            raise ValueError(f"{name}: nodal forcing f and Gauss-point forcing f_gp exclude each other")
-        f = _require(f, "f")
-        args.f_batched = batched(f, "f")
-        args.f = f.data_ptr()
-        keep.append(f)
-    elif isinstance(f_gp, torch.Tensor) and f_gp.numel() > 1:
-        f_gp = _require(f_gp, "f_gp")
-        if tuple(f_gp.shape[-3:]) != (G, *geom.elem_shape) or f_gp.numel() not in (G * nel, B * G * nel):
-            raise ValueError(f"{name}: f_gp shape {tuple(f_gp.shape)} is not (B | 1, {G}, {geom.elem_shape[0]}, {geom.elem_shape[1]})")
-        args.f_batched = 1 if (f_gp.numel() == B * G * nel and B > 1) else 0
-        args.f_gp = f_gp.data_ptr()
-        keep.append(f_gp)
-    else:
-        args.f_value = float(f_gp)
-    if in_scale is not None:
-        in_scale = _require(in_scale, "in_scale")
-        if in_scale.numel() != 1 or in_scale.device != u.device:
-            raise ValueError(f"{name}: in_scale must hold one float on the fields' device")
-        args.in_scale = in_scale.data_ptr()
-        keep.append(in_scale)
     args.wq, args.wd, args.fs, args.wscale, args.out_scale = consts
-    mesh = geom.mesh_struct(B)
-    if want_sum:
-        ws = _flow2d_workspace(_FOSLS, mesh, B, u.device)
-        keep.append(ws)
-        args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    mesh = _prepare_elem2d(op, geom, args, keep, B, dev, bc2, vals, f, f_gp, want_sum, in_scale, "the fields'")
     return mesh, args, keep, B
+
+
+def _fosls_patch(args, ptrs):
+    (args.grad_u, args.grad_mx, args.grad_my), args.grad_stride, args.sum = ptrs
 
 
 def fosls_apply(geom, u=None, mx=None, my=None, nu=None, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=None, weights=(1.0, 1.0), fs=1.0,
@@ -2385,7 +2335,7 @@ def fosls_apply(geom, u=None, mx=None, my=None, nu=None, bc=None, bc_values=(0.0
     tensor (B | 1, G, nely, nelx).  `want_grad`: a bool, or with separate fields three bools (u, mx, my).  Degree 1..3.
     Returns ((gu, gmx, gmy) | packed gradient | None, sum | None); a gradient that was not asked for is None.
     Calls on the same buffers reuse their prepared argument structs (small LRU, fresh outputs per call: see poisson_apply)."""
-    _fosls_check_mesh(geom)
+    _elem2d_check_mesh(_FOSLS, geom)
     packed = fields is not None
     if packed and not (u is None and mx is None and my is None):
         raise ValueError("fosls_apply: pass either the packed `fields` or u, mx, my")
@@ -2407,29 +2357,9 @@ def fosls_apply(geom, u=None, mx=None, my=None, nu=None, bc=None, bc_values=(0.0
     nuv = 1.0 if nu is None else nu
     consts = (*weights, float(fs), float(wscale), float(out_scale))
     flds = (fields,) if packed else (u, mx, my)
-    op = _FOSLS
     key = _fosls_key(geom, flds, packed, nuv, bc2, vals, f, fg, consts, in_scale, (want3, want_sum))
-    ent = None
-    if key is not None:
-        with _WS_LOCK:
-            ent = op.cache.get(key)
-            if ent is not None:
-                op.cache.move_to_end(key)
-    if ent is None:
-        _CALL_STATS["miss" if key is not None else "uncached"] += 1
-        mesh, args, keep, B = _prepare_fosls(geom, flds, packed, nuv, bc2, vals, f, fg, consts, in_scale, want_sum)
-        with _WS_LOCK:
-            live_ws = list(op.ws.values())
-        # an uncached call keeps its (possibly converted) tensors alive until it has been issued; a cached one only the workspace
-        ent = (mesh, args, C.byref(mesh), C.byref(args), B, keep if key is None else [t for t in keep if any(t is x for x in live_ws)])
-        if key is not None:
-            with _WS_LOCK:
-                op.cache[key] = ent
-                while len(op.cache) > _CALL_CACHE_MAX:
-                    op.cache.popitem(last=False)
-    else:
-        _CALL_STATS["hit"] += 1
-    mesh, args, mref, aref, B = ent[:5]
+    ent = _elem2d_entry(_FOSLS, key, _prepare_fosls, (geom, flds, packed, nuv, bc2, vals, f, fg, consts, in_scale, want_sum))
+    B = ent[4]
     dev = flds[0].device
     nn = geom.nnode_total
     if packed:
@@ -2443,141 +2373,35 @@ def fosls_apply(geom, u=None, mx=None, my=None, nu=None, bc=None, bc_values=(0.0
         if not any(want3):
             grads = None
     sums = torch.empty(1, dtype=torch.float64, device=dev) if want_sum else None
-    with op.launch_lock:               # pointer patch + launch of the (possibly shared, cached) argument struct as one step
-        args.grad_u, args.grad_mx, args.grad_my = ptrs
-        args.grad_stride = gstride
-        args.sum = sums.data_ptr() if want_sum else None
-        rc = _lib.lib().dn_fosls_apply(mref, aref, _stream(flds[0]))
-    if rc:
-        _lib.check(rc, op.fn)
+    _elem2d_launch(_FOSLS, ent, flds[0], _fosls_patch, (ptrs, gstride, sums.data_ptr() if want_sum else None))
     return grads, sums
 
 
 # ---- the fused 2-D Helmholtz energy and weak-form residual: dn_helmholtz_apply ---------------------------------------------------
-# Its own reduction workspace per (device, stream), prepared-call cache and launch lock, like _STRONGFORM and for the same reason.
-_HELMHOLTZ = _Flow2dOp("helmholtz_apply", DnHelmholtzArgs)
-
-
-def _helmholtz_check_mesh(geom):
-    if geom.nsd != 2 or geom.deg not in (1, 2, 3) or not 2 <= geom.ngp_1d <= 4 or (geom.deg > 1 and geom.ngp_1d < 3):
-        raise DiffNetHipError(f"helmholtz_apply: 2-D meshes of degree 1..3 with 2..4 Gauss points per axis (3 or 4 above degree 1) only "
-                              f"(nsd {geom.nsd}, degree {geom.deg}, ngp {geom.ngp_1d})")
-    if any((n - 1) % geom.deg for n in geom.sizes):
-        raise ValueError(f"helmholtz_apply: a degree-{geom.deg} mesh needs (n - 1) % {geom.deg} == 0 nodes per axis, got {geom.sizes}")
-
-
 def _helmholtz_key(geom, u, nu, sigma, bc2, vals, f, f_gp, consts, flags):
-    """Key of a cached prepared call (see _call_key); None when an argument needs a conversion copy."""
-    if not (isinstance(u, torch.Tensor) and u.is_cuda and tuple(u.shape[1:]) == (1, *geom.node_shape)):
-        return None
-    parts = [geom.key, u.device.index, _raw_stream(u.device), consts, flags]
-    k = _tkey(u)
-    if k is None or k == 0 or k[1] != torch.float32:
-        return None
-    parts.append(k)
-    for m in bc2:
-        k = _tkey(m)
-        if k is None or (k != 0 and k[1] not in (torch.float32, torch.uint8, torch.bool)):
-            return None
-        parts.append(k)
-    for v in tuple(vals) + (f_gp, sigma):
-        if isinstance(v, torch.Tensor) and v.numel() > 1:
-            k = _tkey(v)
-            if k is None or k[1] != torch.float32:
-                return None
-            parts.append(k)
-        else:
-            parts.append(float(v))
-    for t in (nu, f):
-        k = _tkey(t)
-        if k is None or (k != 0 and k[1] != torch.float32):
-            return None
-        parts.append(k)
-    return tuple(parts)
+    parts = _elem2d_u_key(geom, u, consts, flags)
+    return parts and _elem2d_key(parts, bc2, (*vals, f_gp, sigma), (nu, f))
 
 
 def _prepare_helmholtz(geom, u, nu, sigma, bc2, vals, f, f_gp, consts, want_sums):
     """Validation + argument struct of a dn_helmholtz_apply call, outputs left unset: (mesh, args, tensors to keep alive, field shape)."""
-    name = _HELMHOLTZ.name
-    _helmholtz_check_mesh(geom)
-    u = _require(u, "u", 4)
-    B = u.shape[0]
-    shape = (B, 1, *geom.node_shape)
-    if tuple(u.shape) != shape:
-        raise ValueError(f"{name}: field shape {tuple(u.shape)} != {shape}")
-    keep = [u]
-    args = DnHelmholtzArgs()
-    args.u = u.data_ptr()
-    nn = geom.nnode_total
-
-    def batched(t, what):
-        if tuple(t.shape[-2:]) != tuple(geom.node_shape) or t.numel() not in (B * nn, nn):
-            raise ValueError(f"{name}: {what} shape {tuple(t.shape)} does not match the mesh {shape}")
-        return 1 if (t.numel() == B * nn and B > 1) else 0
-
+    op = _HELMHOLTZ
+    _elem2d_check_mesh(op, geom)
+    args, keep = DnHelmholtzArgs(), []
+    u, B, shape = _elem2d_u(op, geom, u, args, keep)
     if nu is not None:
-        nu = _require(nu, "nu")
-        args.nu_batched = batched(nu, "nu")
-        args.nu = nu.data_ptr()
-        keep.append(nu)
+        _elem2d_field(op, geom, args, keep, B, nu, "nu", "nu")
     if isinstance(sigma, torch.Tensor) and sigma.numel() > 1:
-        sigma = _require(sigma, "sigma")
-        args.sigma_batched = batched(sigma, "sigma")
-        args.sigma = sigma.data_ptr()
-        keep.append(sigma)
+        _elem2d_field(op, geom, args, keep, B, sigma, "sigma", "sigma")
     else:
         args.sigma_value = float(sigma)
-    for k, m in enumerate(bc2):
-        if m is None:
-            continue
-        if not isinstance(m, torch.Tensor):
-            raise TypeError(f"{name}: bc[{k}] must be a tensor or None (expand a PackedMask / BoxFaces to its image)")
-        if not m.is_cuda:
-            raise DiffNetHipError(f"{name}: bc[{k}] is on {m.device}: the FEM ops run on the GPU only (no CPU fallback)")
-        if m.dtype in (torch.bool, torch.uint8):
-            m = m.contiguous()
-            m = m.view(torch.uint8) if m.dtype == torch.bool else m
-            args.bc[k].mask_kind = _lib.MASK_U8
-        else:
-            m = _require(m, f"bc[{k}]")
-            args.bc[k].mask_kind = _lib.MASK_F32
-        args.bc[k].mask_batched = batched(m, f"bc[{k}]")
-        args.bc[k].mask = m.data_ptr()
-        keep.append(m)
-    for k, val in enumerate(vals):
-        if isinstance(val, torch.Tensor) and val.numel() > 1:
-            if bc2[k] is None:
-                raise ValueError(f"{name}: bc_values[{k}] is a field but condition {k} has no mask")
-            val = _require(val, f"bc_values[{k}]")
-            args.bc[k].field_batched = batched(val, f"bc_values[{k}]")
-            args.bc[k].field = val.data_ptr()
-            keep.append(val)
-        else:
-            args.bc[k].value = float(val)
-    G, nel = geom.ngp_total, geom.nelem_total
-    if f is not None:
-        if isinstance(f_gp, torch.Tensor) and f_gp.numel() > 1:
-            raise ValueError(f"{name}: nodal forcing f and Gauss-point forcing f_gp exclude each other")
-        f = _require(f, "f")
-        args.f_batched = batched(f, "f")
-        args.f = f.data_ptr()
-        keep.append(f)
-    elif isinstance(f_gp, torch.Tensor) and f_gp.numel() > 1:
-        f_gp = _require(f_gp, "f_gp")
-        if tuple(f_gp.shape[-3:]) != (G, *geom.elem_shape) or f_gp.numel() not in (G * nel, B * G * nel):
-            raise ValueError(f"{name}: f_gp shape {tuple(f_gp.shape)} is not (B | 1, {G}, {geom.elem_shape[0]}, {geom.elem_shape[1]})")
-        args.f_batched = 1 if (f_gp.numel() == B * G * nel and B > 1) else 0
-        args.f_gp = f_gp.data_ptr()
-        keep.append(f_gp)
-    else:
-        args.f_value = float(f_gp)
     args.c, args.cr, args.fs, args.alpha, args.gamma, args.beta, args.wscale, args.out_scale = consts
-    mesh = geom.mesh_struct(B)
-    if want_sums:
-        ws = _flow2d_workspace(_HELMHOLTZ, mesh, B, u.device)
-        keep.append(ws)
-        args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    mesh = _prepare_elem2d(op, geom, args, keep, B, u.device, bc2, vals, f, f_gp, want_sums)
     return mesh, args, keep, shape
+
+
+def _helmholtz_patch(args, ptrs):
+    args.out, args.energy, args.sumsq = ptrs
 
 
 def helmholtz_apply(geom, u, nu=None, sigma=0.0, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=None, energy_coef=(0.5, 0.5, 1.0),
@@ -2591,7 +2415,7 @@ def helmholtz_apply(geom, u, nu=None, sigma=0.0, bc=None, bc_values=(0.0, 0.0), 
     Gauss-point tensor (B | 1, G, nely, nelx).  Degree 1..3.  Returns (out | None, energy | None, sumsq | None), the two sums as float64
     device tensors (1,), unscaled.  Calls on the same buffers reuse their prepared argument structs (small LRU, fresh outputs per call:
     see poisson_apply)."""
-    _helmholtz_check_mesh(geom)
+    _elem2d_check_mesh(_HELMHOLTZ, geom)
     bc2, vals = transport_bc2(bc), tuple(bc_values)
     energy_coef, out_coef = tuple(float(x) for x in energy_coef), tuple(float(x) for x in out_coef)
     if len(vals) != 2:
@@ -2604,39 +2428,12 @@ def helmholtz_apply(geom, u, nu=None, sigma=0.0, bc=None, bc_values=(0.0, 0.0), 
     sigma = 0.0 if sigma is None else sigma
     consts = (*energy_coef, *out_coef, float(wscale), float(out_scale))
     want_sums = want_energy or want_sumsq
-    op = _HELMHOLTZ
     key = _helmholtz_key(geom, u, nu, sigma, bc2, vals, f, fg, consts, (want_out, want_sums))
-    ent = None
-    if key is not None:
-        with _WS_LOCK:
-            ent = op.cache.get(key)
-            if ent is not None:
-                op.cache.move_to_end(key)
-    if ent is None:
-        _CALL_STATS["miss" if key is not None else "uncached"] += 1
-        mesh, args, keep, shape = _prepare_helmholtz(geom, u, nu, sigma, bc2, vals, f, fg, consts, want_sums)
-        with _WS_LOCK:
-            live_ws = list(op.ws.values())
-        # an uncached call keeps its (possibly converted) tensors alive until it has been issued; a cached one only the workspace
-        ent = (mesh, args, C.byref(mesh), C.byref(args), shape, keep if key is None else [t for t in keep if any(t is x for x in live_ws)])
-        if key is not None:
-            with _WS_LOCK:
-                op.cache[key] = ent
-                while len(op.cache) > _CALL_CACHE_MAX:
-                    op.cache.popitem(last=False)
-    else:
-        _CALL_STATS["hit"] += 1
-    mesh, args, mref, aref, shape = ent[:5]
-    dev = u.device
-    out = torch.empty(shape, dtype=torch.float32, device=dev) if want_out else None
-    sums = torch.empty(2, dtype=torch.float64, device=dev) if want_sums else None
-    with op.launch_lock:               # pointer patch + launch of the (possibly shared, cached) argument struct as one step
-        args.out = out.data_ptr() if want_out else None
-        args.energy = sums.data_ptr() if want_energy else None
-        args.sumsq = sums.data_ptr() + 8 if want_sumsq else None
-        rc = _lib.lib().dn_helmholtz_apply(mref, aref, _stream(u))
-    if rc:
-        _lib.check(rc, op.fn)
+    ent = _elem2d_entry(_HELMHOLTZ, key, _prepare_helmholtz, (geom, u, nu, sigma, bc2, vals, f, fg, consts, want_sums))
+    out = torch.empty(ent[4], dtype=torch.float32, device=u.device) if want_out else None
+    sums = torch.empty(2, dtype=torch.float64, device=u.device) if want_sums else None
+    _elem2d_launch(_HELMHOLTZ, ent, u, _helmholtz_patch, (out.data_ptr() if want_out else None, sums.data_ptr() if want_energy else None,
+                                                          sums.data_ptr() + 8 if want_sumsq else None))
     return out, (sums[0:1] if want_energy else None), (sums[1:2] if want_sumsq else None)
 
 
