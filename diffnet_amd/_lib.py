@@ -114,6 +114,14 @@ class DnHelmholtzArgs(C.Structure):
                 ("out", C.c_void_p), ("energy", C.c_void_p), ("sumsq", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class DnEikonalArgs(C.Structure):
+    _fields_ = [("u", C.c_void_p), ("bc", DnDirichlet * 2),
+                ("f", C.c_void_p), ("f_gp", C.c_void_p), ("f_batched", C.c_int32), ("f_value", C.c_float),
+                ("tau", C.c_float), ("sq", C.c_float), ("wscale", C.c_float), ("vjp", C.c_int32),
+                ("cot", C.c_void_p), ("in_num", C.c_void_p), ("in_den", C.c_void_p),
+                ("out", C.c_void_p), ("sumsq", C.c_void_p), ("norm", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class DnCoefGradArgs(C.Structure):
     _fields_ = [("u", C.c_void_p), ("v", C.c_void_p), ("bc", DnDirichlet * 2),
                 ("a_nu", C.c_float), ("a_f", C.c_float), ("wscale", C.c_float),
@@ -165,6 +173,8 @@ SYMBOLS = {
     "dn_fosls_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnFoslsArgs), C.c_void_p]),
     "dn_helmholtz_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
     "dn_helmholtz_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnHelmholtzArgs), C.c_void_p]),
+    "dn_eikonal_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
+    "dn_eikonal_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnEikonalArgs), C.c_void_p]),
     "dn_poisson_coef_grad": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnCoefGradArgs), C.c_void_p]),
     "dn_upconv_out_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "dn_upconv_out_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,

@@ -1,5 +1,5 @@
-// Shared by the three element-march operators on structured 2-D Q_P meshes (strongform.hip, fosls.hip, helmholtz.hip): everything
-// that is not their mathematics.  The kernel parameters all three use and the block sums of the reduction tail (the march itself is the
+// Shared by the element-march operators on structured 2-D Q_P meshes (strongform.hip, fosls.hip, helmholtz.hip, eikonal.hip): everything
+// that is not their mathematics.  The kernel parameters they all use and the block sums of the reduction tail (the march itself is the
 // kernel body of elem2d_march.inl); on the host the mesh check, the launch plan, the reduction workspace, the argument checks their
 // argument structs have in common (same member names), the fill of the shared parameters and the (degree, rule) x FK x (MASK, BCF)
 // launch switch.  Nothing here asks which operator it serves: what differs comes in through the operator's `Op` (device) and `Family`
@@ -12,12 +12,13 @@
 #pragma once
 #include <algorithm>
 #include <cstdio>
+#include <type_traits>
 
 #include "dn_reduce.h"
 
 namespace dn {
 
-// SfParams, FoParams and HhParams derive from this
+// SfParams, FoParams, HhParams and EkParams derive from this
 struct Elem2dParams {
     float b[4][4], dx[4][4], dy[4][4];     // 1-D tables at the Gauss points (derivatives scaled by 2/h)
     float w2[4][4];                        // w[jg] * w[ig] * wscale
@@ -34,6 +35,13 @@ struct Elem2dParams {
     unsigned* counter;
     int nx, ny, nelx, nely, rows_per_strip, want_sums;
 };
+
+// An operator that wants the Dirichlet nodes of a landed row (eikonal.hip: the cotangent is zero there) has fixed_row(r, bits); for the
+// others the march's call compiles to nothing
+template <class Op, class = void>
+struct elem2d_has_fixed_row : std::false_type {};
+template <class Op>
+struct elem2d_has_fixed_row<Op, std::void_t<decltype(&Op::fixed_row)>> : std::true_type {};
 
 // block_sum of one value, block_sum2 of two (the same additions in the same order as before the kernels shared their tail); results in thread 0
 __device__ __forceinline__ void elem2d_block_sums(double (&v)[1], double* scratch, int tid, int nthreads) { v[0] = block_sum(v[0], scratch, tid, nthreads); }
@@ -96,7 +104,7 @@ static inline int64_t elem2d_workspace_bytes(const dn_mesh* m, int nsums) {
     return DN_WS_HEADER + nsums * (int64_t)sizeof(double) * chunks * nely * m->batch;
 }
 
-// The checks dn_strongform_args, dn_fosls_args and dn_helmholtz_args have in common, after the operator's own DN_E_BADARG checks: the
+// The checks dn_strongform_args, dn_fosls_args, dn_helmholtz_args and dn_eikonal_args have in common, after the operator's own DN_E_BADARG checks: the
 // forcing, the two conditions and the workspace of a call that reduces nsums sums (0: none)
 template <class Args>
 static int elem2d_check_args(const dn_mesh* m, const Args* a, int nsums) {

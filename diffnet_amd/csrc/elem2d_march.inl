@@ -1,4 +1,4 @@
-// The march of one thread of the three element-march kernels (strongform.hip, fosls.hip, helmholtz.hip), written once: the BODY of a
+// The march of one thread of the element-march kernels (strongform.hip, fosls.hip, helmholtz.hip, eikonal.hip), written once: the BODY of a
 // kernel, included between its braces with the template parameters P, NGP, FK (forcing: constant / nodal / at the Gauss points), MASK
 // and BCF (any condition / any value field), the type `Op` and the parameters `p` in scope.  It is text and not a function on purpose:
 // with the body in an inlined function that receives p, the compiler splits the kernel's copy of the parameters into registers at entry
@@ -16,6 +16,7 @@
 //   out_base(p, k, b, nps)       sample b of output field k, or nullptr
 //   issue(p, rowoff, x0, w, issue_f)   requests its raw row, and the nodal forcing (issue_f()) at its place in the order
 //   raw_u(w, n), put(p, w, r, n, v)   a landed row into slot r: v is u after the two conditions
+//   fixed_row(r, bits)           optional (elem2d_has_fixed_row): after put() of a whole row into slot r, its Dirichlet nodes as bits
 //   shift(n)                     slot P becomes slot 0
 //   element(p, fn, fg, okf, g)   adds the element's contributions to g; returns its share of sum 0.  FOLDS_OK: it weighs them with okf
 //                                itself (g is acc); otherwise the march adds okf * g to acc afterwards.  The two round differently
@@ -124,6 +125,7 @@ auto row_consume = [&](const RawRow& w, int r) {
         if constexpr (FK == 1) fn[r][n] = w.f[n];
     }
     fixed[r] = bits;
+    if constexpr (elem2d_has_fixed_row<Op>::value) op.fixed_row(r, bits);
 };
 auto fg_issue = [&](int ey, float (&w)[G]) {
     if constexpr (FK == 2) {

@@ -11,7 +11,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import DnCoefGradArgs, DnDirichlet, DnFoslsArgs, DnFsdtArgs, DnHelmholtzArgs, DnMesh, DnNsArgs, DnPoissonArgs, DnStokesArgs, DnStrongformArgs, DnTransportArgs, I32x3, DiffNetHipError
+from ._lib import DnCoefGradArgs, DnDirichlet, DnEikonalArgs, DnFoslsArgs, DnFsdtArgs, DnHelmholtzArgs, DnMesh, DnNsArgs, DnPoissonArgs, DnStokesArgs, DnStrongformArgs, DnTransportArgs, I32x3, DiffNetHipError
 
 
 def _require(t, name, ndim=None, strict=False):
@@ -604,6 +604,7 @@ def call_cache_clear():
         _STRONGFORM.cache.clear()
         _FOSLS.cache.clear()
         _HELMHOLTZ.cache.clear()
+        _EIKONAL.cache.clear()
         _PACK_CACHE.clear()
     _POISSON_WS_BYTES.clear()
     _FSDT_WS_BYTES.clear()
@@ -613,6 +614,7 @@ def call_cache_clear():
     _STRONGFORM.ws_bytes.clear()
     _FOSLS.ws_bytes.clear()
     _HELMHOLTZ.ws_bytes.clear()
+    _EIKONAL.ws_bytes.clear()
 
 
 class PoissonPlan:
@@ -2049,7 +2051,7 @@ def transport_apply(geom, u, nu=None, bc=None, bc_values=(0.0, 0.0), r_first_win
     return (out, sums, norm) if want_norm else (out, sums)
 
 
-# ---- the three element-march operators on 2-D Q_P meshes: dn_strongform_apply, dn_fosls_apply, dn_helmholtz_apply ----------------
+# ---- the element-march operators on 2-D Q_P meshes: dn_strongform_apply, dn_fosls_apply, dn_helmholtz_apply, dn_eikonal_apply ----
 # Each has its own reduction workspace per (device, stream), prepared-call cache and launch lock, like _TRANSPORT and for the same
 # reason.  What their calls share -- the mesh check, the key of a prepared call, the two conditions, the forcing, in_scale, the
 # workspace, the look-up / prepare / cache step and the patch-under-lock / launch step -- is written once (_elem2d_*); an operator's own
@@ -2057,6 +2059,7 @@ def transport_apply(geom, u, nu=None, bc=None, bc_values=(0.0, 0.0), r_first_win
 _STRONGFORM = _Flow2dOp("strongform_apply", DnStrongformArgs)
 _FOSLS = _Flow2dOp("fosls_apply", DnFoslsArgs)
 _HELMHOLTZ = _Flow2dOp("helmholtz_apply", DnHelmholtzArgs)
+_EIKONAL = _Flow2dOp("eikonal_apply", DnEikonalArgs)
 
 
 def _elem2d_check_mesh(op, geom):
@@ -2435,6 +2438,83 @@ def helmholtz_apply(geom, u, nu=None, sigma=0.0, bc=None, bc_values=(0.0, 0.0), 
     _elem2d_launch(_HELMHOLTZ, ent, u, _helmholtz_patch, (out.data_ptr() if want_out else None, sums.data_ptr() if want_energy else None,
                                                           sums.data_ptr() + 8 if want_sumsq else None))
     return out, (sums[0:1] if want_energy else None), (sums[1:2] if want_sumsq else None)
+
+
+# ---- the fused 2-D eikonal weak-form residual and its VJP: dn_eikonal_apply --------------------------------------------------------
+
+def _eikonal_key(geom, u, bc2, vals, f, f_gp, consts, cot, in_num, in_den, flags):
+    parts = _elem2d_u_key(geom, u, consts, flags)
+    if not parts:
+        return None
+    for t in (in_num, in_den):
+        k = _tkey(t)
+        if k is None or (k != 0 and k[2] != (1,)):
+            return None
+    return _elem2d_key(parts, bc2, (*vals, f_gp), (f, cot, in_num, in_den))
+
+
+def _prepare_eikonal(geom, u, bc2, vals, f, f_gp, consts, cot, in_num, in_den, want_sums):
+    """Validation + argument struct of a dn_eikonal_apply call, outputs left unset: (mesh, args, tensors to keep alive, field shape)."""
+    op = _EIKONAL
+    _elem2d_check_mesh(op, geom)
+    args, keep = DnEikonalArgs(), []
+    u, B, shape = _elem2d_u(op, geom, u, args, keep)
+    args.tau, args.sq, args.wscale = consts
+    if cot is not None:
+        cot = _require(cot, "cot", 4)
+        if tuple(cot.shape) != shape or cot.device != u.device:
+            raise ValueError(f"{op.name}: cotangent shape {tuple(cot.shape)} != {shape} (on u's device)")
+        args.vjp, args.cot = 1, cot.data_ptr()
+        keep.append(cot)
+    for what, t in (("in_num", in_num), ("in_den", in_den)):
+        if t is None:
+            continue
+        t = _require(t, what)
+        if t.numel() != 1 or t.device != u.device:
+            raise ValueError(f"{op.name}: {what} must hold one float on u's device")
+        setattr(args, what, t.data_ptr())
+        keep.append(t)
+    mesh = _prepare_elem2d(op, geom, args, keep, B, u.device, bc2, vals, f, f_gp, want_sums)
+    return mesh, args, keep, shape
+
+
+def _eikonal_patch(args, ptrs):
+    args.out, args.sumsq, args.norm = ptrs
+
+
+def eikonal_apply(geom, u, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=1.0, tau=0.0, sq=None, wscale=1.0, cot=None, in_num=None, in_den=None,
+                  want_out=True, want_sumsq=False, want_norm=False):
+    """One launch of dn_eikonal_apply (include/diffnet_hip.h) on the field u (B,1,ny,nx):
+    R = zero_on_dirichlet(assembled W (tau u~ gradN . grad u~ + sq N |grad u~|^2 - N f)), `sq` None: 1 + tau; with `cot` (B,1,ny,nx) the
+    launch is the VJP instead: the pullback of cot -- times in_num[0], divided by in_den[0] (float32 device tensors of 1) where given,
+    zero on the Dirichlet nodes -- through R at u; it does not read the forcing.  `bc`: None, one mask or a pair (either None), fp32
+    (`> 0.5`) or bool / uint8, per sample or shared; `bc_values[k]`: float or tensor u takes under condition k (where both hold,
+    condition 2's); the forcing: a nodal field `f` (B | 1,1,ny,nx), or `f_gp`, a float (default 1) or a Gauss-point tensor
+    (B | 1, G, nely, nelx).  Degree 1..3.  Returns (out | None, sumsq | None, norm | None): the sum of out^2 as a float64 device tensor
+    (1,), its square root as a float32 one.  Calls on the same buffers reuse their prepared argument structs (small LRU, fresh outputs
+    per call: see poisson_apply)."""
+    _elem2d_check_mesh(_EIKONAL, geom)
+    bc2, vals = transport_bc2(bc), tuple(bc_values)
+    if len(vals) != 2:
+        raise ValueError("eikonal_apply: bc_values must hold two entries")
+    if not (want_out or want_sumsq or want_norm):
+        raise ValueError("eikonal_apply: nothing to compute (want_out, want_sumsq and want_norm are all off)")
+    if cot is None and (in_num is not None or in_den is not None):
+        raise ValueError("eikonal_apply: in_num / in_den scale the cotangent of a VJP launch (cot is None)")
+    if in_den is not None and in_num is None:
+        raise ValueError("eikonal_apply: in_den needs in_num")
+    fg = 1.0 if f_gp is None else f_gp
+    tau = float(tau)
+    consts = (tau, 1.0 + tau if sq is None else float(sq), float(wscale))
+    want_sums = want_sumsq or want_norm
+    key = _eikonal_key(geom, u, bc2, vals, f, fg, consts, cot, in_num, in_den, (want_out, want_sums))
+    ent = _elem2d_entry(_EIKONAL, key, _prepare_eikonal, (geom, u, bc2, vals, f, fg, consts, cot, in_num, in_den, want_sums))
+    out = torch.empty(ent[4], dtype=torch.float32, device=u.device) if want_out else None
+    ss = torch.empty(1, dtype=torch.float64, device=u.device) if want_sumsq else None
+    nrm = torch.empty(1, dtype=torch.float32, device=u.device) if want_norm else None
+    _elem2d_launch(_EIKONAL, ent, u, _eikonal_patch, (out.data_ptr() if want_out else None, ss.data_ptr() if want_sumsq else None,
+                                                      nrm.data_ptr() if want_norm else None))
+    return out, ss, nrm
 
 
 def compute_winding_nodes(points, normals, area, q):

@@ -627,6 +627,55 @@ typedef struct dn_helmholtz_args {
 int64_t dn_helmholtz_workspace_bytes(const dn_mesh *mesh);
 int dn_helmholtz_apply(const dn_mesh *mesh, const dn_helmholtz_args *args, void *stream);
 
+/* ---- fused 2-D stabilised eikonal weak-form residual and its VJP ----------------------------------------------------------
+ * Replaces the domain term of the eikonal scripts of the reference, examples/eiqonal/parametric/10_fixed_bc.py:127-216
+ * (loss_eikonal) and examples/eiqonal/single_instance/e01_curve_reconstruction.py:452-558 (loss4) -- the two Dirichlet substitutions,
+ * three Gauss-point evaluations, the stabilised weak form, its assembly, the zeroed Dirichlet rows and the Frobenius norm -- in one
+ * launch.  Mesh: nsd = 2, degree 1..3, ngp 2..4 (>= 3 for degree > 1), (n - 1) % degree == 0.
+ *   u~ = u after bc[0] then bc[1] (applied in order, as in dn_poisson_args: where both hold, condition 2's value is used)
+ *   R_a = zero_on_dirichlet( sum_{e contains a} sum_g W_g ( tau u~_g gradN_a . grad u~_g + sq N_a |grad u~_g|^2 - N_a f_g ) )
+ *   W_g = gpw_g * wscale;   sumsq = sum over (b, nodes) of R^2;   norm = sqrt(sumsq)
+ * The scripts: sq = 1 + tau, f = 1, wscale = (hx/2)(hy/2); tau = 0, sq = 1 is the unstabilised N (|grad u|^2 - 1).
+ * vjp = 0: out = R.  The forcing f_g is the nodal field f (1 | B,1,ny,nx) interpolated with the basis, or f_gp at the Gauss points
+ * (Bf,G,nely,nelx) with Bf = 1 (f_batched 0) or B, or the constant f_value; f and f_gp exclude each other.
+ * vjp = 1: out = J(u~)^T cot', the pullback of cot (B,1,ny,nx) through R at u, zero on the Dirichlet nodes; cot' is cot times
+ * in_num[0] (divided by in_den[0] where given; 0 where in_den[0] == 0), read as zero on the Dirichlet nodes.  The forcing is not read.
+ * With cot = R, in_num -> 2 this is the gradient of sumsq; with in_num -> 1 and in_den -> the norm of the forward launch, of the norm:
+ * loss plus gradient are two launches with nothing in between.  in_num, in_den: device floats.
+ * u, out (B,1,ny,nx) fp32.  Conditions: DN_MASK_F32 / DN_MASK_U8 images, shared or per sample, constant value or value field.
+ * sumsq: device double; norm: device float (fixed-order fp64 reduction in the kernel); each may be NULL, but at least one of out,
+ * sumsq, norm must be given.  sumsq or norm needs `workspace` (zero-filled once before first use, dn_eikonal_workspace_bytes =
+ * 4160 + 16 * chunks * nely * B bytes with nely = (ny - 1) / degree, Q = (nx - 1) / degree + 1 and chunks = 1 for Q <= 64, else
+ * ceil((Q - 1) / 63); every call leaves it ready for the next; one per stream, not shared with other operators).  No atomics on the
+ * data path: out is bitwise independent of the batch it is computed in and of the launch plan ("PLAN_FSDT" "T,R" overrides the plan,
+ * as for dn_strongform_apply); sumsq and norm are reproducible for a given mesh, batch size and plan.
+ * DN_E_UNSUPPORTED for degree outside 1..3, ngp outside 2..4 (or 2 with degree > 1), DN_MASK_BITS / DN_MASK_BOX conditions (expand
+ * them: dn_unpack_mask_bits); DN_E_BADARG for nsd != 2, (n - 1) % degree != 0, a NULL u, no output at all, f together with f_gp,
+ * vjp without cot, in_den without in_num, in_num with vjp = 0, flags outside {0, 1} or a value field without its mask;
+ * DN_E_WORKSPACE for sumsq or norm without a large enough workspace; nothing is launched then. */
+typedef struct dn_eikonal_args {
+    const float *u;        /* (B,1,ny,nx) nodal field (vjp: the linearisation point)    */
+    dn_dirichlet bc[2];    /* applied in order                                          */
+    const float *f;        /* (B | 1,1,ny,nx) nodal forcing or NULL                     */
+    const float *f_gp;     /* (Bf,G,nely,nelx) forcing at Gauss points or NULL          */
+    int32_t f_batched;     /* 0: one forcing field for the whole batch                  */
+    float f_value;         /* the forcing when f and f_gp are NULL (the scripts: 1)     */
+    float tau;             /* stabilisation: tau u grad N . grad u                      */
+    float sq;              /* weight of N |grad u|^2 (the scripts: 1 + tau)             */
+    float wscale;
+    int32_t vjp;           /* 0: residual, 1: its VJP                                   */
+    const float *cot;      /* vjp: (B,1,ny,nx) cotangent of R                           */
+    const float *in_num;   /* vjp: device float, cot is scaled by in_num[0]; or NULL    */
+    const float *in_den;   /* vjp: device float, ... and divided by in_den[0]; or NULL  */
+    float *out;            /* (B,1,ny,nx) or NULL                                       */
+    double *sumsq;         /* device scalar: sum of out^2 or NULL                       */
+    float *norm;           /* device scalar: its square root or NULL                    */
+    void *workspace;
+    int64_t workspace_bytes;
+} dn_eikonal_args;
+int64_t dn_eikonal_workspace_bytes(const dn_mesh *mesh);
+int dn_eikonal_apply(const dn_mesh *mesh, const dn_eikonal_args *args, void *stream);
+
 /* ---- gradient of the Poisson losses with respect to the nodal coefficient and forcing ------------------------------------
  * Replaces what autograd does for the coefficient in the topology optimisation of the reference,
  * examples/poisson/single_instance/16_topopt.py:119-195 (loss = 0.5 nu grad u . grad v - v f with nu from the network, compliance
