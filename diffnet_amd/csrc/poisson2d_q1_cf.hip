@@ -1,15 +1,20 @@
 // 2-D Q1 fused Poisson kernel, closed-form element (the default for nodal / absent forcing).
 //
-// With u, nu, f bilinear on the element,
-//     u(a, c) = U0 + a UX + c UY + a c UXY,   a, c in [0, 1] the lerp coordinates of the 1-D Gauss points,
-// every quadrature sum of the reference's loss bodies is a polynomial in (a_i, c_j) summed against the rule, i.e. a
-// combination of the rule's moments  M_r = sum_g w_g b_g^r  (r = 0..3; the x moments carry the Jacobian / user scale):
-//     sum_ij W_ij nu_ij (u_x)^2_j = hs0^2 (UX^2 A0 + 2 UX UXY A1 + UXY^2 A2),  A_k = P My_k + Q My_{k+1},
-//                                   P = Mx0 N0 + Mx1 NX,  Q = Mx0 NY + Mx1 NXY          (and likewise in y with B_k),
-//     sum_ij W_ij f_ij u_ij       = L0 U0 + LX UX + LY UY + LXY UXY                     (L.: moment combinations of f).
-// This is algebra, not a change of rule: the moments are computed from the rule's own points and weights (including the
-// reference's truncated 3- and 4-point literals), so the value equals the Gauss sum over any ngp x ngp points to rounding,
-// while the element costs ~75 VALU instructions whatever ngp is (115 for the per-point form at 3 x 3).
+// With u, nu, f bilinear on the element, every quadrature sum of the reference's loss bodies is a polynomial in the lerp coordinates
+// b_g in [0, 1] of the 1-D Gauss points summed against the rule, i.e. a combination of the rule's moments  sum_g w_g (1 - b_g)^r b_g^s.
+// Stiffness term, symmetric in the layer's lower (L) and upper (U) node row (q1cf_stage / q1cf_elem in poisson_elem.h): per node row and
+// element the kernel stages  du[e] = u[e + 1] - u[e]  and the x-moment of nu  pn[e] = sum_i wx_i nu(x_i)  ONCE, when the row lands (each
+// row is the upper row of one layer and the lower row of the next); a layer then needs, with a = du_L, b = du_U, p = pn_L, q = pn_U,
+//     sum_g W nu u_x^2 = hs0^2 ( a^2 (p r30 + q r21) + 2 a b (p r21 + q r12) + b^2 (p r12 + q r03) ),   r_rs = sum_g w_g (1 - b_g)^r b_g^s,
+// and the same cubic in the per-node vertical differences V[n] = u_U[n] - u_L[n] and y-moments S[n] of nu for the y-derivative.  hs^2
+// and the user scale are folded into the r_rs on the host (ElemTab::q1xm / q1ym, in double); alpha enters where the cotangents are added to
+// the nodes (an FMA in place of an add), so the energy sums need no division and alpha = 0 is as good as any.  Forcing term:  sum_g W f N_a = (mass_x (x) mass_y) f, applied axis by axis (fstage / layer).
+// This is algebra, not a change of rule: the moments are computed from the rule's own points and weights (including the reference's
+// truncated 3- and 4-point literals), so the value equals the Gauss sum over any ngp x ngp points to rounding
+// (tests/test_q1cf_rowstaged.py: 1e-12 in float64).  Main loop of the bench instantiation <4, true, nu | f | one bit-packed condition, 1>,
+// two node rows = eight elements per thread: 552 VALU instructions, 16 loads, 2 stores, 2 barriers, 98 VGPRs (the element on raw nodal
+// values it replaced: 724 and 105; tools/q1cf_loop_count.py, profiles/q1cf_rowstaged.txt).  The generic mask / value-field form (CF_BC)
+// keeps the element on raw nodal values (ROWSTAGED below).
 //
 // Mapping as the other 2-D kernels: a thread owns E consecutive elements of a strip and marches over element rows; it
 // carries the lower node row (raw nodal values) and the layer-below contributions to that row's nodes; two rows per loop
@@ -24,7 +29,8 @@ namespace dn {
 
 // CF_BC_PACKED: bit-packed masks / box faces with constant values; CF_PK_NB1 / CF_PK_NB2: one / two of the conditions are bit arrays
 // (compile-time: a load inside a wave-uniform branch costs an s_waitcnt vmcnt(0) where the branch joins)
-enum : int { CF_NU = 1, CF_F = 2, CF_BC = 8, CF_BC_U8C = 16, CF_BC_PACKED = 32, CF_PK_NB1 = 64, CF_PK_NB2 = 128, CF_UA = 256 };
+// CF_ONE (packed and uint8-constant masks): exactly one condition is present -- the absent one costs no bit test, compare or select
+enum : int { CF_NU = 1, CF_F = 2, CF_BC = 8, CF_BC_U8C = 16, CF_BC_PACKED = 32, CF_PK_NB1 = 64, CF_PK_NB2 = 128, CF_UA = 256, CF_ONE = 512 };
 // CF_UA (E = 4, vector accesses, one strip per workgroup): rows of 4 k + 1 nodes -- the 2^n + 1 meshes.  The 16-byte row accesses are then aligned to 4 bytes
 // only (the hardware takes that), and the mesh's LAST node column belongs to the last full thread column (its node x0 + 4) instead of to a thread column of
 // its own: the launch has the geometry of the 4 k mesh (513^2 x 64: 112.9 -> the time of 512^2, tools/time_2d_sizes.py).
@@ -33,6 +39,7 @@ template <int E>
 struct CfRow {
     float u[E + 1], n[E + 1], f[E + 1];
     float g[E + 1];          // x-stage of the forcing term: (1-D element mass matrix in x) applied to f over the thread's own elements
+    float du[E], pn[E];      // x-stage of the stiffness term (q1cf_stage): u[e + 1] - u[e] and the x-moment of nu over element e
     float keep[E];
     float keepx;             // CF_UA: keep of the node x0 + E (the mesh's last node column in the last thread column)
     BcRaw<E> bc;
@@ -90,7 +97,8 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : 2) poisso
     constexpr int NW = E;
     constexpr bool HAS_NU = (FL & CF_NU) != 0, HAS_F = (FL & CF_F) != 0;
     constexpr bool BC_ANY = (FL & (CF_BC | CF_BC_U8C | CF_BC_PACKED)) != 0, BC_U8C = (FL & CF_BC_U8C) != 0, BC_PACKED = (FL & CF_BC_PACKED) != 0;
-    constexpr bool UA = (FL & CF_UA) != 0;
+    constexpr bool UA = (FL & CF_UA) != 0, ONE = (FL & CF_ONE) != 0;
+    static_assert(!ONE || ((BC_PACKED || BC_U8C) && (FL & CF_PK_NB2) == 0), "CF_ONE: one packed or uint8-constant condition");
     static_assert(!UA || (E == 4 && VEC && W == 1), "CF_UA: four elements per thread, vector accesses, one strip per workgroup");
     // W > 1: the workgroup holds W sub-strips of CF_TS threads each; sub (wave-uniform) is this thread's sub-strip
     const int T = W > 1 ? CF_TS : (int)blockDim.x;
@@ -167,6 +175,7 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : 2) poisso
     const unsigned bsel[2] = {isbits[0] ? NBITS : 0u, isbits[1] ? NBITS : 0u};
     // load slot j reads the bit array of condition src[j]; with one array it is whichever condition has it
     const int src0 = (NB == 2 || isbits[0]) ? 0 : 1;
+    const int kone = p.bc[0].kind >= 0 ? 0 : 1;                // CF_ONE: the condition that is present
     const uint32_t* bptr[2] = {reinterpret_cast<const uint32_t*>(sb.mask[src0]), reinterpret_cast<const uint32_t*>(sb.mask[1])};
     // two ALIGNED dwords per bit array and row (the word that holds node x0 and the next one; 8 lanes share an address) and one
     // v_alignbit: an unaligned 2-byte window costs the address path 16 cycles per wave-instruction, an aligned dword 4.5
@@ -200,8 +209,12 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : 2) poisso
             const uint32_t w0 = ld_at<uint32_t>(bptr[j], ro + bw0[j]), w1 = ld_at<uint32_t>(bptr[j], ro + bw1[j]);
             r.mb[j] = __builtin_amdgcn_alignbit(w1, w0, bsh);          // bit n = node x0 + n
         }
+        if constexpr (ONE) {
+            if constexpr (NB == 0) r.bx[0] = (yc == (kone ? ylo[1] : ylo[0]) || yc == (kone ? yhi[1] : yhi[0])) ? NBITS : (kone ? boxx[1] : boxx[0]);
+        } else {
 #pragma unroll
-        for (int k = 0; k < 2; ++k) r.bx[k] = (yc == ylo[k] || yc == yhi[k]) ? NBITS : boxx[k];
+            for (int k = 0; k < 2; ++k) r.bx[k] = (yc == ylo[k] || yc == yhi[k]) ? NBITS : boxx[k];
+        }
     };
 
     auto row_issue = [&](int yr, CfRow<E>& r) {
@@ -215,6 +228,14 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : 2) poisso
         if constexpr (HAS_F) load_seg_stream<NW, VEC>(sb.f, rowoff, x0, p.nx, r.f);
         if constexpr (BC_PACKED) {
             packed_issue(yp, r);
+        } else if constexpr (BC_U8C && ONE) {
+            uint8_t t[NW + 1];
+            load_seg_stream<NW, VEC>(mask8[0], rowoff, x0, p.nx, t);          // mask8[0]: the image of the condition that is present
+            uint32_t w = 0u;
+#pragma unroll
+            for (int n = 0; n < NW; ++n) w |= (uint32_t)t[n] << (8 * n);
+            r.m8[0][0] = w;
+            r.m8[0][1] = t[NW];
         } else if constexpr (BC_U8C) {
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
@@ -237,7 +258,20 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : 2) poisso
 #pragma unroll
         for (int n = 0; n < NW; ++n) r.keep[n] = 1.f;
         if constexpr (UA) r.keepx = 1.f;
-        if constexpr (BC_PACKED) {
+        if constexpr ((BC_PACKED || BC_U8C) && ONE) {
+            const float v = kone ? p.bc[1].value : p.bc[0].value;
+            unsigned b = 0u;
+            if constexpr (BC_PACKED) b = NB == 1 ? r.mb[0] : r.bx[0];      // (one condition: a bit array or box faces)
+#pragma unroll
+            for (int n = 0; n <= NW; ++n) {
+                bool set;
+                if constexpr (BC_PACKED) set = (b & (1u << n)) != 0u;
+                else set = n < NW ? ((r.m8[0][0] >> (8 * n)) & 0xffu) != 0u : r.m8[0][1] != 0u;
+                r.u[n] = set ? v : r.u[n];
+                if (n < NW) r.keep[n] = set ? 0.f : 1.f;
+                else if constexpr (UA) r.keepx = set ? 0.f : 1.f;
+            }
+        } else if constexpr (BC_PACKED) {
             unsigned b0 = r.bx[0], b1 = r.bx[1];
             if constexpr (NB == 2) { b0 |= r.mb[0] & bsel[0]; b1 |= r.mb[1] & bsel[1]; }
             if constexpr (NB == 1) { b0 |= r.mb[0] & bsel[0]; b1 |= r.mb[0] & bsel[1]; }
@@ -336,12 +370,20 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : 2) poisso
     const float mx0 = p.T.mxs[0], mx1 = p.T.mxs[1], mx2 = p.T.mxs[2], mx3 = p.T.mxs[3];
     const float my0 = p.T.m[0], my1 = p.T.m[1], my2 = p.T.m[2], my3 = p.T.m[3];
     const float k0 = p.T.q1c[0], k1 = p.T.q1c[1], h0 = p.T.q1c[2], h1 = p.T.q1c[3], nb = -p.T.beta;
+    // ROWSTAGED: the stiffness term from quantities staged once per node row (q1cf_stage / q1cf_elem, poisson_elem.h), hs^2 folded into the
+    // moment constants on the host (ElemTab); alpha enters where the cotangents are added to the nodes.  Every form but the generic mask / value-field one (CF_BC),
+    // which keeps the element on raw nodal values: its register budget is at the edge of 4 waves per SIMD as it is.
+    // STAGE_DU: du[] kept per row; the chained strips (W > 1, 13 more VGPRs for the hand-overs) keep pn[] only and recompute the differences
+    constexpr bool ROWSTAGED = (FL & CF_BC) == 0, STAGE_DU = W == 1;
+    const float xm[4] = {p.T.q1xm[0], p.T.q1xm[1], p.T.q1xm[2], p.T.q1xm[3]}, ym[4] = {p.T.q1ym[0], p.T.q1ym[1], p.T.q1ym[2], p.T.q1ym[3]};
+    const float px0 = p.T.q1px[0], px1 = p.T.q1px[1], sy0 = p.T.q1sy[0], sy1 = p.T.q1sy[1];
 
     // forcing term as a tensor-product mass matrix applied row by row (14 instead of 28 instructions per element: -11 % VALU instructions,
-    // time unchanged -- the kernel moves its ~312 MB at 5.45 TB/s whatever the arithmetic costs, profiles/r2_ab2d_fmass.txt); not in the
+    // 1.7-1.8 us per launch on the masked forms: box 56.6 -> 54.9, bits + box 57.7 -> 55.9 us, profiles/r2_ab2d_fmass.txt); not in the
     // generic mask / value-field form, whose register budget it would push from 4 to 3 waves per SIMD
-    constexpr bool FMASS = HAS_F && (FL & CF_BC) == 0;
+    constexpr bool FMASS = HAS_F && ROWSTAGED;
     const float cx00 = p.T.q1mx[0], cx01 = p.T.q1mx[1], cx11 = p.T.q1mx[2], cy00 = p.T.q1my[0], cy01 = p.T.q1my[1], cy11 = p.T.q1my[2];
+    const float alpha = p.T.alpha;
     // sum_g W_g f_g N_a(g) with f bilinear is (mass_x (x) mass_y) f.  x-stage, once per node row: g[n] = the row's forcing seen through
     // the thread's own elements (elements beyond the mesh excluded; the node shared with the right neighbour gets the rest over the
     // hand-over that o[] takes anyway, by linearity)
@@ -359,6 +401,21 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : 2) poisso
         }
     };
 
+    // x-stage of the stiffness term, once per node row (after its Dirichlet select): du[], pn[] (q1cf_stage)
+    auto sstage = [&](CfRow<E>& r) {
+        if constexpr (ROWSTAGED) {
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                if constexpr (HAS_NU) {
+                    q1cf_stage(px0, px1, r.u[e], r.u[e + 1], r.n[e], r.n[e + 1], r.du[e], r.pn[e]);
+                } else {              // nu == 1: its x-moment is the rule's
+                    r.du[e] = r.u[e + 1] - r.u[e];
+                    r.pn[e] = mx0;
+                }
+            }
+        }
+    };
+
     // one element layer between the lower row L (Dirichlet applied) and the freshly landed upper row U; cin holds the
     // contributions of the layer below to L's nodes, cout receives this layer's contributions to U's nodes
     // fresh: U has just landed from HBM (Dirichlet select and forcing x-stage still to do); not fresh: U came finished from the strip above
@@ -366,6 +423,7 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : 2) poisso
         const bool own_layer = ey >= e_from && ey <= e_until;
         const float cnt = (own_layer && col_owner) ? 1.f : 0.f;
         if constexpr (decltype(fresh)::value) { row_bc(U); fstage(U); }
+        sstage(U);                        // (a row that came from the strip above through LDS restages here as well: nothing more is published)
         float o[NW + 1], le1 = 0.f, le2 = 0.f;
 #pragma unroll
         for (int n = 0; n <= NW; ++n) { o[n] = cin[n]; cout[n] = 0.f; }
@@ -378,41 +436,58 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : 2) poisso
                 le2 = fmaf(U.u[n], tup, fmaf(L.u[n], tlo, le2));
             }
         }
+        if constexpr (ROWSTAGED) {
+            // per node: vertical difference of u and y-moment of nu (q1cf_elem)
+            float V[NW + 1], S[NW + 1];
 #pragma unroll
-        for (int e = 0; e < E; ++e) {
-            if (ex0 + e < p.nelx) {       // elements beyond the domain are skipped (and: scheduling fence between elements)
-                const float U0 = L.u[e], UX = L.u[e + 1] - L.u[e], UY = U.u[e] - L.u[e], UXY = (U.u[e + 1] - U.u[e]) - UX;
-                float P = mx0, Q = 0.f, Pp = my0, Qp = 0.f;
-                if constexpr (HAS_NU) {
-                    const float N0 = L.n[e], NX = L.n[e + 1] - N0, NY = U.n[e] - N0, NXY = (U.n[e + 1] - U.n[e]) - NX;
-                    P = fmaf(mx1, NX, mx0 * N0);
-                    Q = fmaf(mx1, NXY, mx0 * NY);
-                    Pp = fmaf(my1, NY, my0 * N0);
-                    Qp = fmaf(my1, NXY, my0 * NX);
+            for (int n = 0; n <= NW; ++n) {
+                V[n] = U.u[n] - L.u[n];
+                S[n] = HAS_NU ? fmaf(sy1, U.n[n], sy0 * L.n[n]) : my0;
+            }
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                if (ex0 + e < p.nelx) {       // elements beyond the domain are skipped (and: scheduling fence between elements)
+                    const float a = STAGE_DU ? L.du[e] : L.u[e + 1] - L.u[e], b = STAGE_DU ? U.du[e] : U.u[e + 1] - U.u[e];
+                    q1cf_elem(xm, ym, a, b, L.pn[e], U.pn[e], V[e], V[e + 1], S[e], S[e + 1], alpha, o[e], o[e + 1], cout[e], cout[e + 1], le1);
                 }
-                const float A0 = fmaf(Q, my1, P * my0), A1 = fmaf(Q, my2, P * my1), A2 = fmaf(Q, my3, P * my2);
-                const float B0 = fmaf(Qp, mx1, Pp * mx0), B1 = fmaf(Qp, mx2, Pp * mx1), B2 = fmaf(Qp, mx3, Pp * mx2);
-                const float tX0 = fmaf(UXY, A1, UX * A0), tX1 = fmaf(UXY, A2, UX * A1);
-                const float tY0 = fmaf(UXY, B1, UY * B0), tY1 = fmaf(UXY, B2, UY * B1);
-                le1 += fmaf(h1, fmaf(UXY, tY1, UY * tY0), h0 * fmaf(UXY, tX1, UX * tX0));
-                float cU0 = 0.f, cUX = k0 * tX0, cUY = k1 * tY0, cUXY = fmaf(k0, tX1, k1 * tY1);
-                if constexpr (HAS_F && !FMASS) {
-                    const float F0 = L.f[e], FX = L.f[e + 1] - F0, FY = U.f[e] - F0, FXY = (U.f[e + 1] - U.f[e]) - FX;
-                    const float S0 = fmaf(mx1, FX, mx0 * F0), S1 = fmaf(mx1, FXY, mx0 * FY);
-                    const float T0 = fmaf(mx2, FX, mx1 * F0), T1 = fmaf(mx2, FXY, mx1 * FY);
-                    const float L0 = fmaf(my1, S1, my0 * S0), LX = fmaf(my1, T1, my0 * T0);
-                    const float LY = fmaf(my2, S1, my1 * S0), LXY = fmaf(my2, T1, my1 * T0);
-                    le2 += fmaf(LXY, UXY, fmaf(LY, UY, fmaf(LX, UX, L0 * U0)));
-                    cU0 = nb * L0;
-                    cUX = fmaf(nb, LX, cUX);
-                    cUY = fmaf(nb, LY, cUY);
-                    cUXY = fmaf(nb, LXY, cUXY);
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                if (ex0 + e < p.nelx) {
+                    const float U0 = L.u[e], UX = L.u[e + 1] - L.u[e], UY = U.u[e] - L.u[e], UXY = (U.u[e + 1] - U.u[e]) - UX;
+                    float P = mx0, Q = 0.f, Pp = my0, Qp = 0.f;
+                    if constexpr (HAS_NU) {
+                        const float N0 = L.n[e], NX = L.n[e + 1] - N0, NY = U.n[e] - N0, NXY = (U.n[e + 1] - U.n[e]) - NX;
+                        P = fmaf(mx1, NX, mx0 * N0);
+                        Q = fmaf(mx1, NXY, mx0 * NY);
+                        Pp = fmaf(my1, NY, my0 * N0);
+                        Qp = fmaf(my1, NXY, my0 * NX);
+                    }
+                    const float A0 = fmaf(Q, my1, P * my0), A1 = fmaf(Q, my2, P * my1), A2 = fmaf(Q, my3, P * my2);
+                    const float B0 = fmaf(Qp, mx1, Pp * mx0), B1 = fmaf(Qp, mx2, Pp * mx1), B2 = fmaf(Qp, mx3, Pp * mx2);
+                    const float tX0 = fmaf(UXY, A1, UX * A0), tX1 = fmaf(UXY, A2, UX * A1);
+                    const float tY0 = fmaf(UXY, B1, UY * B0), tY1 = fmaf(UXY, B2, UY * B1);
+                    le1 += fmaf(h1, fmaf(UXY, tY1, UY * tY0), h0 * fmaf(UXY, tX1, UX * tX0));
+                    float cU0 = 0.f, cUX = k0 * tX0, cUY = k1 * tY0, cUXY = fmaf(k0, tX1, k1 * tY1);
+                    if constexpr (HAS_F) {
+                        const float F0 = L.f[e], FX = L.f[e + 1] - F0, FY = U.f[e] - F0, FXY = (U.f[e + 1] - U.f[e]) - FX;
+                        const float S0 = fmaf(mx1, FX, mx0 * F0), S1 = fmaf(mx1, FXY, mx0 * FY);
+                        const float T0 = fmaf(mx2, FX, mx1 * F0), T1 = fmaf(mx2, FXY, mx1 * FY);
+                        const float L0 = fmaf(my1, S1, my0 * S0), LX = fmaf(my1, T1, my0 * T0);
+                        const float LY = fmaf(my2, S1, my1 * S0), LXY = fmaf(my2, T1, my1 * T0);
+                        le2 += fmaf(LXY, UXY, fmaf(LY, UY, fmaf(LX, UX, L0 * U0)));
+                        cU0 = nb * L0;
+                        cUX = fmaf(nb, LX, cUX);
+                        cUY = fmaf(nb, LY, cUY);
+                        cUXY = fmaf(nb, LXY, cUXY);
+                    }
+                    const float g01 = cUX - cUXY, g10 = cUY - cUXY;
+                    o[e] += (cU0 - cUX) - g10;
+                    o[e + 1] += g01;
+                    cout[e] += g10;
+                    cout[e + 1] += cUXY;
                 }
-                const float g01 = cUX - cUXY, g10 = cUY - cUXY;
-                o[e] += (cU0 - cUX) - g10;
-                o[e + 1] += g01;
-                cout[e] += g10;
-                cout[e + 1] += cUXY;
             }
         }
         e1_acc = fmaf(cnt, le1, e1_acc);
@@ -489,6 +564,7 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : 2) poisso
     row_issue(ey_begin, RA);
     row_bc(RA);
     fstage(RA);
+    sstage(RA);
     if constexpr (W > 1) {
         if (chain_dn) publish_row(RA);
     }
@@ -576,13 +652,17 @@ static void cf_launch_flags(const PoissonParams& pp, const Geom2D& g, int batch,
         if (pp.bc[k].kind == DN_MASK_BITS || pp.bc[k].kind == DN_MASK_BOX) packed = true;     // dn_poisson_apply admits no mix with mask images
     }
     const int nbits = (pp.bc[0].kind == DN_MASK_BITS) + (pp.bc[1].kind == DN_MASK_BITS);
+    const bool one = (pp.bc[0].kind >= 0) != (pp.bc[1].kind >= 0);        // one condition: the instantiations without the absent one's selects
     const int nf = (pp.nu ? CF_NU : 0) | (pp.f ? CF_F : 0);
 #define DN_CF(FLAGS)                                                                         \
     (!any ? cf_launch_one<E, VEC, (FLAGS) | UAF>(pp, g, batch, s)                                  \
           : packed ? (nbits == 2 ? cf_launch_one<E, VEC, (FLAGS) | UAF | CF_BC_PACKED | CF_PK_NB2>(pp, g, batch, s)          \
-                     : nbits == 1 ? cf_launch_one<E, VEC, (FLAGS) | UAF | CF_BC_PACKED | CF_PK_NB1>(pp, g, batch, s)        \
-                                  : cf_launch_one<E, VEC, (FLAGS) | UAF | CF_BC_PACKED>(pp, g, batch, s))                   \
-          : u8c ? cf_launch_one<E, VEC, (FLAGS) | UAF | CF_BC_U8C>(pp, g, batch, s)                \
+                     : nbits == 1 ? (one ? cf_launch_one<E, VEC, (FLAGS) | UAF | CF_BC_PACKED | CF_PK_NB1 | CF_ONE>(pp, g, batch, s)        \
+                                         : cf_launch_one<E, VEC, (FLAGS) | UAF | CF_BC_PACKED | CF_PK_NB1>(pp, g, batch, s))        \
+                     : one ? cf_launch_one<E, VEC, (FLAGS) | UAF | CF_BC_PACKED | CF_ONE>(pp, g, batch, s)                   \
+                           : cf_launch_one<E, VEC, (FLAGS) | UAF | CF_BC_PACKED>(pp, g, batch, s))                   \
+          : u8c ? (one ? cf_launch_one<E, VEC, (FLAGS) | UAF | CF_BC_U8C | CF_ONE>(pp, g, batch, s)                \
+                       : cf_launch_one<E, VEC, (FLAGS) | UAF | CF_BC_U8C>(pp, g, batch, s))                \
                 : cf_launch_one<E, VEC, (FLAGS) | UAF | CF_BC>(pp, g, batch, s))
     switch (nf) {
         case 0: DN_CF(0); break;

@@ -60,6 +60,11 @@ struct ElemTab {
     // closed-form 2-D Q1 kernel: the 1-D element mass matrix [[c00, c01], [c01, c11]] = sum_g w_g [(1-b)^2, b(1-b); b(1-b), b^2] of the
     // rule (from its moments, in double): the forcing term is (mass_x (x) mass_y) f, applied axis by axis (x carries wscale)
     float q1mx[3], q1my[3];   // c00, c01, c11
+    // closed-form 2-D Q1 kernel, row-staged stiffness element (q1cf_elem below).  With r_rs = sum_g w_g (1 - b_g)^r b_g^s (r + s = 3) of the 1-D rule, in double:
+    float q1xm[4];       // hs0^2 (r30, r21, r12, r03): x-derivative term (its nu x-moments pn carry wscale)
+    float q1ym[4];       // hs1^2 wscale (r30, r21, r12, r03): y-derivative term
+    float q1px[2];       // wscale (m0 - m1, m1): pn[e] = q1px[0] n[e] + q1px[1] n[e + 1]
+    float q1sy[2];       // (m0 - m1, m1): y-moment of nu per node, S[n] = q1sy[0] n_L[n] + q1sy[1] n_U[n]
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -198,6 +203,36 @@ __device__ __forceinline__ void q1_layer_2d(const ElemTab& T, const float (&TU0)
     }
     e1 = fmaf(T.q1c[2], a1x, T.q1c[3] * a1y);                    // hs0^2 * a1x + hs1^2 * a1y
     e2 = a2;
+}
+
+// ---------------------------------------------------------------------------------------------
+// 2-D Q1, closed form, symmetric in the lower (L) and upper (U) node row of the layer (poisson2d_q1_cf.hip).  Staged once per node
+// row and element:  du[e] = u[e + 1] - u[e]  and the x-moment of nu  pn[e] = sum_i wx_i nu(x_i) = q1px[0] n[e] + q1px[1] n[e + 1].
+// With a = du_L, b = du_U, p = pn_L, q = pn_U the x-derivative at height c is (1 - c) a + c b and the x-summed nu (1 - c) p + c q, so
+//     sum_g W nu u_x^2 = hs0^2 ( a^2 (p r30 + q r21) + 2 a b (p r21 + q r12) + b^2 (p r12 + q r03) ),
+// and the y-derivative term is the same cubic in the per-node differences V[n] = u_U[n] - u_L[n] and the per-node y-moments S[n] of nu
+// with the x-moments of the rule.  xm / ym carry hs^2 (ElemTab::q1xm / q1ym): e accumulates the element's  sum_g W nu |grad u|^2  as it
+// is, and alpha enters where the cotangents are added to the nodes (an FMA in place of an add: alpha = 0, the energy of c = 0, costs nothing).
+// ---------------------------------------------------------------------------------------------
+__host__ __device__ __forceinline__ void q1cf_stage(const float px0, const float px1, const float u0, const float u1, const float n0, const float n1,
+                                                    float& du, float& pn) {
+    du = u1 - u0;
+    pn = fmaf(px1, n1, px0 * n0);
+}
+
+__host__ __device__ __forceinline__ void q1cf_elem(const float (&xm)[4], const float (&ym)[4], const float a, const float b, const float p,
+                                                   const float q, const float V0, const float V1, const float S0, const float S1,
+                                                   const float alpha, float& gL0, float& gL1, float& gU0, float& gU1, float& e) {
+    const float X0 = fmaf(q, xm[1], p * xm[0]), X1 = fmaf(q, xm[2], p * xm[1]), X2 = fmaf(q, xm[3], p * xm[2]);
+    const float ta = fmaf(b, X1, a * X0), tb = fmaf(b, X2, a * X1);               // cotangents of du_L, du_U
+    const float Y0 = fmaf(S1, ym[1], S0 * ym[0]), Y1 = fmaf(S1, ym[2], S0 * ym[1]), Y2 = fmaf(S1, ym[3], S0 * ym[2]);
+    const float t0 = fmaf(V1, Y1, V0 * Y0), t1 = fmaf(V1, Y2, V0 * Y1);           // cotangents of V[e], V[e + 1]
+    e = fmaf(b, tb, fmaf(a, ta, e));
+    e = fmaf(V1, t1, fmaf(V0, t0, e));
+    gL0 = fmaf(-alpha, ta + t0, gL0);
+    gL1 = fmaf(alpha, ta - t1, gL1);
+    gU0 = fmaf(alpha, t0 - tb, gU0);
+    gU1 = fmaf(alpha, tb + t1, gU1);
 }
 
 // ---------------------------------------------------------------------------------------------

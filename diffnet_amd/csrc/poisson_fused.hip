@@ -553,6 +553,16 @@ extern "C" int dn_poisson_apply(const dn_mesh* m, const dn_poisson_args* a, void
         }
         pp.T.q1my[0] = (float)(mm[0] - 2.0 * mm[1] + mm[2]); pp.T.q1my[1] = (float)(mm[1] - mm[2]); pp.T.q1my[2] = (float)mm[2];
         for (int r = 0; r < 3; ++r) pp.T.q1mx[r] = (float)((double)(r == 0 ? mm[0] - 2.0 * mm[1] + mm[2] : (r == 1 ? mm[1] - mm[2] : mm[2])) * (double)a->wscale);
+        {   // row-staged closed-form element (q1cf_elem): r_rs = sum_g w_g (1 - b_g)^r b_g^s from the moments, scales folded in
+            const double rr[4] = {mm[0] - 3.0 * mm[1] + 3.0 * mm[2] - mm[3], mm[1] - 2.0 * mm[2] + mm[3], mm[2] - mm[3], mm[3]};
+            const double hx = 0.5 * (double)m->scale[0], hy = 0.5 * (double)m->scale[1], ws = a->wscale;
+            for (int r = 0; r < 4; ++r) {
+                pp.T.q1xm[r] = (float)(hx * hx * rr[r]);
+                pp.T.q1ym[r] = (float)(hy * hy * ws * rr[r]);
+            }
+            pp.T.q1px[0] = (float)((mm[0] - mm[1]) * ws); pp.T.q1px[1] = (float)(mm[1] * ws);
+            pp.T.q1sy[0] = (float)(mm[0] - mm[1]);        pp.T.q1sy[1] = (float)mm[1];
+        }
         for (int r = 0; r < 4; ++r) {
             pp.T.m[r] = (float)mm[r];
             pp.T.mxs[r] = (float)(mm[r] * (double)a->wscale);
