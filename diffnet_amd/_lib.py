@@ -175,6 +175,8 @@ SYMBOLS = {
     "dn_helmholtz_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnHelmholtzArgs), C.c_void_p]),
     "dn_eikonal_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
     "dn_eikonal_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnEikonalArgs), C.c_void_p]),
+    "dn_eikonal3d_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
+    "dn_eikonal3d_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnEikonalArgs), C.c_void_p]),
     "dn_poisson_coef_grad": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnCoefGradArgs), C.c_void_p]),
     "dn_upconv_out_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "dn_upconv_out_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,

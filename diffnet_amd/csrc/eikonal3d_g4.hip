@@ -1,0 +1,3 @@
+// 4-point-rule instantiations of the fused 3-D eikonal kernel (see eikonal3d.hip).
+#define EK3_NGP 4
+#include "eikonal3d.hip"

@@ -1,4 +1,4 @@
-"""2-D stabilised eikonal weak-form residual on the HIP operators -- the domain term of the eikonal scripts of the reference under
+"""2-D and 3-D stabilised eikonal weak-form residual on the HIP operators -- the domain term of the eikonal scripts of the reference under
 `examples/eiqonal/`: `parametric/10_fixed_bc.py:127-216` (loss_eikonal) and `single_instance/e01_curve_reconstruction.py:452-558` (loss4).
 
     u~ = where(bc2, value2, where(bc1, value1, u));  at every Gauss point, from u~:
@@ -18,7 +18,12 @@ backward is a hand-derived pullback in the same flux form: with the cotangent (z
 `eikonal_residual_composed` is the same computation spelled with the single-launch HIP operators (`gauss_pt_evaluation*`, `assemble`)
 and torch elementwise ops, differentiable by autograd with respect to every tensor input; the fused functions are differentiable with
 respect to u only, so when `f`, `f_gp` or a value field requires a gradient the public functions take the composed route (no input gets
-a silent zero gradient)."""
+a silent zero gradient).
+
+On a `DiffNet3DFEM` the same functions are the domain term of `single_instance/05_3d_sphere_loss4.py:269-425` (loss4; `04_3d_sphere_recon.py`
+is tau = 0, sq = 1, f_gp = h): fields are (B,1,nz,ny,nx), the flux gains  D = tau u u_z  on Nz_a (VJP:  A' = tau grad L . grad u,
+D' = 2 sq L u_z + tau u L_z),  `wscale` defaults to (hx/2)(hy/2)(hz/2) and the fused launch is dn_eikonal3d_apply
+(csrc/eikonal3d.hip), for Q1 meshes; on a 3-D Q2 or Q3 mesh the fused functions raise and `eikonal_residual_composed` is the route."""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -36,8 +41,23 @@ def eikonal_coefficients(tau):
 
 def _coef(fem, tau, sq, wscale):
     tau = float(tau)
-    ws = (0.5 * fem.hx) * (0.5 * fem.hy) if wscale is None else float(wscale)
+    if wscale is not None:
+        ws = float(wscale)
+    elif fem.nsd == 3:
+        ws = (0.5 * fem.hx) * (0.5 * fem.hy) * (0.5 * fem.hz)
+    else:
+        ws = (0.5 * fem.hx) * (0.5 * fem.hy)
     return dict(tau=tau, sq=1.0 + tau if sq is None else float(sq), wscale=ws)
+
+
+def _apply(fem):
+    """The fused launch of the mesh: dn_eikonal_apply in 2-D, dn_eikonal3d_apply in 3-D (Q1 only there)"""
+    if fem.nsd != 3:
+        return ops.eikonal_apply
+    if fem.geom.deg != 1:
+        raise ops.DiffNetHipError(f"the fused 3-D eikonal residual is compiled for Q1 meshes only (degree {fem.geom.deg}): use "
+                                  "eikonal_residual_composed, which takes any degree")
+    return ops.eikonal3d_apply
 
 
 def _kind(kind):
@@ -53,7 +73,7 @@ def _needs_composed(f, f_gp, vals):
 class _EikonalResidual(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, fem, bc, bc_values, f, f_gp, coef):
-        out, _, _ = ops.eikonal_apply(fem.geom, u, bc, bc_values, f, f_gp, **coef)
+        out, _, _ = _apply(fem)(fem.geom, u, bc, bc_values, f, f_gp, **coef)
         ctx.save_for_backward(u)
         ctx.fem, ctx.args = fem, (bc, bc_values, coef)
         return out
@@ -62,7 +82,7 @@ class _EikonalResidual(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g):
         bc, bc_values, coef = ctx.args
-        out, _, _ = ops.eikonal_apply(ctx.fem.geom, ctx.saved_tensors[0], bc, bc_values, cot=g.contiguous(), **coef)
+        out, _, _ = _apply(ctx.fem)(ctx.fem.geom, ctx.saved_tensors[0], bc, bc_values, cot=g.contiguous(), **coef)
         return out, None, None, None, None, None, None
 
 
@@ -72,7 +92,7 @@ class _EikonalLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, u, fem, bc, bc_values, f, f_gp, coef, norm):
-        out, ss, nrm = ops.eikonal_apply(fem.geom, u, bc, bc_values, f, f_gp, want_sumsq=not norm, want_norm=norm, **coef)
+        out, ss, nrm = _apply(fem)(fem.geom, u, bc, bc_values, f, f_gp, want_sumsq=not norm, want_norm=norm, **coef)
         val = nrm if norm else ss.float()
         ctx.save_for_backward(u, out, val)
         ctx.fem, ctx.args, ctx.norm = fem, (bc, bc_values, coef), norm
@@ -85,7 +105,7 @@ class _EikonalLoss(torch.autograd.Function):
         bc, bc_values, coef = ctx.args
         g = gout.reshape(1).float()
         kw = dict(in_num=g.contiguous(), in_den=val) if ctx.norm else dict(in_num=2.0 * g)
-        out, _, _ = ops.eikonal_apply(ctx.fem.geom, u, bc, bc_values, cot=R, **coef, **kw)
+        out, _, _ = _apply(ctx.fem)(ctx.fem.geom, u, bc, bc_values, cot=R, **coef, **kw)
         return out, None, None, None, None, None, None, None
 
 
@@ -113,12 +133,13 @@ def eikonal_loss_and_grad(fem, u, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=1.
     `eikonal_loss(...).backward()` leaves in u.grad -- from two launches and no autograd graph."""
     norm = _kind(kind)
     coef, vals = _coef(fem, tau, sq, wscale), _vals2(bc_values)
+    apply = _apply(fem)
     with torch.no_grad():
-        R, ss, nrm = ops.eikonal_apply(fem.geom, u, bc, vals, f, f_gp, want_sumsq=not norm, want_norm=norm, **coef)
+        R, ss, nrm = apply(fem.geom, u, bc, vals, f, f_gp, want_sumsq=not norm, want_norm=norm, **coef)
         if norm:
-            grad, _, _ = ops.eikonal_apply(fem.geom, u, bc, vals, cot=R, in_num=_const(u.device, 1.0), in_den=nrm, **coef)
+            grad, _, _ = apply(fem.geom, u, bc, vals, cot=R, in_num=_const(u.device, 1.0), in_den=nrm, **coef)
             return nrm[0], grad
-        grad, _, _ = ops.eikonal_apply(fem.geom, u, bc, vals, cot=R, in_num=_const(u.device, 2.0), **coef)
+        grad, _, _ = apply(fem.geom, u, bc, vals, cot=R, in_num=_const(u.device, 2.0), **coef)
         return ss[0], grad
 
 
@@ -134,9 +155,26 @@ def eikonal_residual_composed(fem, u, bc=None, bc_values=(0.0, 0.0), f=None, f_g
     u = _fix(_fix(u, m1, v1), m2, v2)
     ug, ux, uy = fem.gauss_pt_evaluation(u), fem.gauss_pt_evaluation_der_x(u), fem.gauss_pt_evaluation_der_y(u)
     if f is not None:
-        fg = fem.gauss_pt_evaluation(f if f.dim() == 4 else f.reshape(-1, 1, *fem.geom.node_shape))
+        fg = fem.gauss_pt_evaluation(f if f.dim() == fem.nsd + 2 else f.reshape(-1, 1, *fem.geom.node_shape))
     else:
         fg = _forcing(1.0 if f_gp is None else f_gp, ug, fem.geom)
+    if fem.nsd == 3:
+        uz = fem.gauss_pt_evaluation_der_z(u)
+        A = sq * (ux ** 2 + uy ** 2 + uz ** 2) - fg.expand_as(ux)
+        R = fem.assemble(_weak_form3(fem, u.device, c["wscale"])((tau * ug) * ux, (tau * ug) * uy, (tau * ug) * uz, A))
+        return _fix(_fix(R, m1, 0.0), m2, 0.0)
     A = sq * (ux ** 2 + uy ** 2) - fg.expand_as(ux)
     R = fem.assemble(_weak_form(fem, u.device, c["wscale"])((tau * ug) * ux, (tau * ug) * uy, A))
     return _fix(_fix(R, m1, 0.0), m2, 0.0)
+
+
+def _weak_form3(fem, dev, wscale):
+    """weak(a_x, a_y, a_z, a_0) = sum_g JxW ( dN_x a_x + dN_y a_y + dN_z a_z + N a_0 ), per local basis function -> (B, nbf, nelZ, nelY, nelX)"""
+    N, Nx, Ny, Nz = (t.to(dev) for t in (fem.Nvalues, fem.dN_x_values, fem.dN_y_values, fem.dN_z_values))       # (1, nbf, ngp, 1, 1, 1)
+    jxw = (fem.gpw.to(dev) * wscale).reshape(1, 1, -1, 1, 1, 1)
+
+    def weak(a_x, a_y, a_z, a_0):
+        t = Nx * a_x.unsqueeze(1) + Ny * a_y.unsqueeze(1) + Nz * a_z.unsqueeze(1) + N * a_0.unsqueeze(1)
+        return torch.sum(t * jxw, 2)
+
+    return weak

@@ -605,6 +605,7 @@ def call_cache_clear():
         _FOSLS.cache.clear()
         _HELMHOLTZ.cache.clear()
         _EIKONAL.cache.clear()
+        _EIKONAL3D.cache.clear()
         _PACK_CACHE.clear()
     _POISSON_WS_BYTES.clear()
     _FSDT_WS_BYTES.clear()
@@ -615,6 +616,7 @@ def call_cache_clear():
     _FOSLS.ws_bytes.clear()
     _HELMHOLTZ.ws_bytes.clear()
     _EIKONAL.ws_bytes.clear()
+    _EIKONAL3D.ws_bytes.clear()
 
 
 class PoissonPlan:
@@ -2060,6 +2062,7 @@ _STRONGFORM = _Flow2dOp("strongform_apply", DnStrongformArgs)
 _FOSLS = _Flow2dOp("fosls_apply", DnFoslsArgs)
 _HELMHOLTZ = _Flow2dOp("helmholtz_apply", DnHelmholtzArgs)
 _EIKONAL = _Flow2dOp("eikonal_apply", DnEikonalArgs)
+_EIKONAL3D = _Flow2dOp("eikonal3d_apply", DnEikonalArgs)
 
 
 def _elem2d_check_mesh(op, geom):
@@ -2514,6 +2517,152 @@ def eikonal_apply(geom, u, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=1.0, tau=
     nrm = torch.empty(1, dtype=torch.float32, device=u.device) if want_norm else None
     _elem2d_launch(_EIKONAL, ent, u, _eikonal_patch, (out.data_ptr() if want_out else None, ss.data_ptr() if want_sumsq else None,
                                                       nrm.data_ptr() if want_norm else None))
+    return out, ss, nrm
+
+
+# ---- the fused 3-D eikonal weak-form residual and its VJP: dn_eikonal3d_apply ----------------------------------------------------
+
+def _eikonal3d_check_mesh(geom):
+    if geom.nsd != 3:
+        raise DiffNetHipError(f"eikonal3d_apply: 3-D meshes only (nsd {geom.nsd}); 2-D meshes: eikonal_apply")
+    if geom.deg != 1 or not 2 <= geom.ngp_1d <= 4:
+        raise DiffNetHipError(f"eikonal3d_apply: 3-D Q1 meshes with 2..4 Gauss points per axis only (degree {geom.deg}, ngp {geom.ngp_1d}); "
+                              "any degree: eikonal.eikonal_residual_composed")
+
+
+def _eikonal3d_workspace(mesh, B, dev):
+    """The operator's own reduction workspace on the current stream of `dev`, large enough for `mesh` under the launch plan in force."""
+    op = _EIKONAL3D
+    key = (mesh.nx, mesh.ny, mesh.nz, mesh.ngp, B)
+    nbytes = op.ws_bytes.get(key)
+    if nbytes is None:
+        nbytes = getattr(_lib.lib(), op.ws_fn)(C.byref(mesh))
+        if nbytes < 0:
+            _lib.check(int(nbytes), op.ws_fn)
+        op.ws_bytes[key] = nbytes
+    key = (dev.index, _raw_stream(dev))
+    with _WS_LOCK:
+        ws = op.ws.get(key)
+        if ws is None or ws.numel() < nbytes:
+            ws = torch.zeros(max(nbytes, 1 << 16), dtype=torch.uint8, device=dev)   # ABI: zero-filled once
+            op.ws[key] = ws
+    return ws
+
+
+def _eikonal3d_field(geom, args, keep, B, t, what, member, fp32=True):
+    """A nodal field (B | 1, ., nz, ny, nx) into args.<member> and args.<member>_batched."""
+    nn = geom.nnode_total
+    if fp32:
+        t = _require(t, what)
+    if tuple(t.shape[-3:]) != tuple(geom.node_shape) or t.numel() not in (B * nn, nn):
+        raise ValueError(f"eikonal3d_apply: {what} shape {tuple(t.shape)} does not match the mesh {(B, 1, *geom.node_shape)}")
+    setattr(args, member + "_batched", 1 if (t.numel() == B * nn and B > 1) else 0)
+    setattr(args, member, t.data_ptr())
+    keep.append(t)
+
+
+def _prepare_eikonal3d(geom, u, bc2, vals, f, f_gp, consts, cot, in_num, in_den, want_sums):
+    """Validation + argument struct of a dn_eikonal3d_apply call, outputs left unset: (mesh, args, tensors to keep alive, field shape)."""
+    name = "eikonal3d_apply"
+    _eikonal3d_check_mesh(geom)
+    args, keep = DnEikonalArgs(), []
+    u = _require(u, "u", 5)
+    B = u.shape[0]
+    shape = (B, 1, *geom.node_shape)
+    if tuple(u.shape) != shape:
+        raise ValueError(f"{name}: field shape {tuple(u.shape)} != {shape}")
+    keep.append(u)
+    args.u = u.data_ptr()
+    args.tau, args.sq, args.wscale = consts
+    if cot is not None:
+        cot = _require(cot, "cot", 5)
+        if tuple(cot.shape) != shape or cot.device != u.device:
+            raise ValueError(f"{name}: cotangent shape {tuple(cot.shape)} != {shape} (on u's device)")
+        args.vjp, args.cot = 1, cot.data_ptr()
+        keep.append(cot)
+    for what, t in (("in_num", in_num), ("in_den", in_den)):
+        if t is None:
+            continue
+        t = _require(t, what)
+        if t.numel() != 1 or t.device != u.device:
+            raise ValueError(f"{name}: {what} must hold one float on u's device")
+        setattr(args, what, t.data_ptr())
+        keep.append(t)
+    for k, m in enumerate(bc2):
+        if m is None:
+            continue
+        if not isinstance(m, torch.Tensor):
+            raise TypeError(f"{name}: bc[{k}] must be a tensor or None (expand a PackedMask / BoxFaces to its image)")
+        if not m.is_cuda:
+            raise DiffNetHipError(f"{name}: bc[{k}] is on {m.device}: the FEM ops run on the GPU only (no CPU fallback)")
+        byte = m.dtype in (torch.bool, torch.uint8)
+        if byte:
+            m = m.contiguous()
+            m = m.view(torch.uint8) if m.dtype == torch.bool else m
+        args.bc[k].mask_kind = _lib.MASK_U8 if byte else _lib.MASK_F32
+        _eikonal3d_field(geom, args.bc[k], keep, B, m, f"bc[{k}]", "mask", fp32=not byte)
+    for k, val in enumerate(vals):
+        if isinstance(val, torch.Tensor) and val.numel() > 1:
+            if bc2[k] is None:
+                raise ValueError(f"{name}: bc_values[{k}] is a field but condition {k} has no mask")
+            _eikonal3d_field(geom, args.bc[k], keep, B, val, f"bc_values[{k}]", "field")
+        else:
+            args.bc[k].value = float(val)
+    G, nel = geom.ngp_total, geom.nelem_total
+    if f is not None:
+        if isinstance(f_gp, torch.Tensor) and f_gp.numel() > 1:
+            raise ValueError(f"{name}: nodal forcing f and Gauss-point forcing f_gp exclude each other")
+        _eikonal3d_field(geom, args, keep, B, f, "f", "f")
+    elif isinstance(f_gp, torch.Tensor) and f_gp.numel() > 1:
+        f_gp = _require(f_gp, "f_gp")
+        if tuple(f_gp.shape[-4:]) != (G, *geom.elem_shape) or f_gp.numel() not in (G * nel, B * G * nel):
+            raise ValueError(f"{name}: f_gp shape {tuple(f_gp.shape)} is not (B | 1, {G}, {', '.join(str(n) for n in geom.elem_shape)})")
+        args.f_batched = 1 if (f_gp.numel() == B * G * nel and B > 1) else 0
+        args.f_gp = f_gp.data_ptr()
+        keep.append(f_gp)
+    else:
+        args.f_value = float(f_gp)
+    mesh = geom.mesh_struct(B)
+    if want_sums:
+        ws = _eikonal3d_workspace(mesh, B, u.device)
+        keep.append(ws)
+        args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    return mesh, args, keep, shape
+
+
+def eikonal3d_apply(geom, u, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=1.0, tau=0.0, sq=None, wscale=1.0, cot=None, in_num=None, in_den=None,
+                    want_out=True, want_sumsq=False, want_norm=False):
+    """One launch of dn_eikonal3d_apply (include/diffnet_hip.h) on the field u (B,1,nz,ny,nx) of a 3-D Q1 mesh: the 3-D twin of
+    `eikonal_apply`, with the same arguments and results.
+    R = zero_on_dirichlet(assembled W (N (sq |grad u~|^2 - f) + tau u~ gradN . grad u~)), `sq` None: 1 + tau; with `cot` (B,1,nz,ny,nx)
+    the launch is the VJP instead: the pullback of cot -- times in_num[0], divided by in_den[0] (float32 device tensors of 1) where
+    given, zero on the Dirichlet nodes -- through R at u; it does not read the forcing.  `bc`: None, one mask or a pair (either None),
+    fp32 (`> 0.5`) or bool / uint8, per sample or shared; `bc_values[k]`: float or tensor u takes under condition k (where both hold,
+    condition 2's); the forcing: a nodal field `f` (B | 1,1,nz,ny,nx), or `f_gp`, a float (default 1) or a Gauss-point tensor
+    (B | 1, G, nelz, nely, nelx) in the order of `gauss_pt_evaluation`.  Returns (out | None, sumsq | None, norm | None): the sum of
+    out^2 as a float64 device tensor (1,), its square root as a float32 one.  Calls on the same buffers reuse their prepared argument
+    structs; the reduction workspace is the operator's own, one per stream."""
+    _eikonal3d_check_mesh(geom)
+    bc2, vals = transport_bc2(bc), tuple(bc_values)
+    if len(vals) != 2:
+        raise ValueError("eikonal3d_apply: bc_values must hold two entries")
+    if not (want_out or want_sumsq or want_norm):
+        raise ValueError("eikonal3d_apply: nothing to compute (want_out, want_sumsq and want_norm are all off)")
+    if cot is None and (in_num is not None or in_den is not None):
+        raise ValueError("eikonal3d_apply: in_num / in_den scale the cotangent of a VJP launch (cot is None)")
+    if in_den is not None and in_num is None:
+        raise ValueError("eikonal3d_apply: in_den needs in_num")
+    fg = 1.0 if f_gp is None else f_gp
+    tau = float(tau)
+    consts = (tau, 1.0 + tau if sq is None else float(sq), float(wscale))
+    want_sums = want_sumsq or want_norm
+    key = _eikonal_key(geom, u, bc2, vals, f, fg, consts, cot, in_num, in_den, (want_out, want_sums))
+    ent = _elem2d_entry(_EIKONAL3D, key, _prepare_eikonal3d, (geom, u, bc2, vals, f, fg, consts, cot, in_num, in_den, want_sums))
+    out = torch.empty(ent[4], dtype=torch.float32, device=u.device) if want_out else None
+    ss = torch.empty(1, dtype=torch.float64, device=u.device) if want_sumsq else None
+    nrm = torch.empty(1, dtype=torch.float32, device=u.device) if want_norm else None
+    _elem2d_launch(_EIKONAL3D, ent, u, _eikonal_patch, (out.data_ptr() if want_out else None, ss.data_ptr() if want_sumsq else None,
+                                                        nrm.data_ptr() if want_norm else None))
     return out, ss, nrm
 
 

@@ -676,6 +676,42 @@ typedef struct dn_eikonal_args {
 int64_t dn_eikonal_workspace_bytes(const dn_mesh *mesh);
 int dn_eikonal_apply(const dn_mesh *mesh, const dn_eikonal_args *args, void *stream);
 
+/* ---- fused 3-D stabilised eikonal weak-form residual and its VJP ----------------------------------------------------------
+ * The 3-D twin of dn_eikonal_apply: the domain term of examples/eiqonal/single_instance/05_3d_sphere_loss4.py:269-425 (loss4;
+ * 04_3d_sphere_recon.py::loss is its unstabilised form) -- the two Dirichlet substitutions, four Gauss-point evaluations, the
+ * stabilised weak form, its assembly, the zeroed Dirichlet rows and the Frobenius norm -- in one launch.  It takes the same
+ * dn_eikonal_args.  Mesh: nsd = 3, degree 1, ngp 2..4.
+ *   u~ = u after bc[0] then bc[1] (where both hold, condition 2's value is used)
+ *   at a Gauss point:  A = sq |grad u~|^2 - f,   (B, C, D) = tau u~ grad u~
+ *   R_a = zero_on_dirichlet( sum_{e contains a} sum_g W_g ( N_a A + Nx_a B + Ny_a C + Nz_a D ) ),   W_g = gpw_g * wscale
+ *   sumsq = sum over (b, nodes) of R^2;   norm = sqrt(sumsq)
+ * The scripts: sq = 1 + tau, f = 1, wscale = (hx/2)(hy/2)(hz/2); 04 is tau = 0, sq = 1, f = h.
+ * vjp = 0: out = R.  The forcing f_g is the nodal field f (1 | B,1,nz,ny,nx) interpolated with the basis, or f_gp at the Gauss points
+ * (Bf,G,nelz,nely,nelx) with Bf = 1 (f_batched 0) or B and the Gauss points in the order of gauss_pt_evaluation on a 3-D mesh
+ * (g = (kg * ngp + jg) * ngp + ig, x fastest), or the constant f_value; f and f_gp exclude each other.
+ * vjp = 1: out = J(u~)^T cot', the pullback of cot (B,1,nz,ny,nx) through R at u, zero on the Dirichlet nodes: with cot' evaluated like
+ * a field (L, grad L),  A' = tau grad L . grad u~,  (B', C', D') = 2 sq L grad u~ + tau u~ grad L  in the same flux form.  cot' is cot
+ * times in_num[0] (divided by in_den[0] where given; 0 where in_den[0] == 0, NaN is propagated), read as zero on the Dirichlet nodes.
+ * The forcing is not read.  With cot = R, in_num -> 2 this is the gradient of sumsq; with in_num -> 1 and in_den -> the norm of the
+ * forward launch, of the norm: loss plus gradient are two launches with nothing in between.
+ * u, out (B,1,nz,ny,nx) fp32.  Conditions: DN_MASK_F32 / DN_MASK_U8 images, shared or per sample, constant value or value field.
+ * sumsq: device double; norm: device float (fixed-order fp64 reduction in the kernel); each may be NULL, but at least one of out,
+ * sumsq, norm must be given.  sumsq or norm needs `workspace` (zero-filled once before first use; every call leaves it ready for the
+ * next; one per stream, not shared with other operators) of dn_eikonal3d_workspace_bytes =
+ *   4160 + 8 * chunks * tiles * strips * B bytes,   tiles(n, T) = 1 for n <= T, else ceil((n - 1) / (T - 1)),
+ *   chunks = tiles(nx, TX), tiles = tiles(ny, TY), strips = ceil(nelz / R), nelz = nz - 1, for the launch plan (TX, TY, R):
+ *   TX = 16; TY = the first of 4, 8, 12, 16 with the largest ny / (tiles(ny, TY) * TY) + 0.002 * TY; R = 32, halved while R > 4 and
+ *   chunks * tiles * B * ceil(nelz / R) < 1024, then at most nelz.  "PLAN3D" "TX,TY,E,R" (2 <= TX, TY; TX * TY a multiple of 64, at
+ *   most 256; R >= 1; E is ignored: one element per thread) overrides the plan and with it the size.
+ * No atomics on the data path: out is bitwise independent of the batch it is computed in and of the launch plan; sumsq and norm are
+ * reproducible for a given mesh, batch size and plan.  Samples of 2^30 nodes or more are DN_E_UNSUPPORTED (32-bit in-sample offsets).
+ * DN_E_UNSUPPORTED for degree other than 1, ngp outside 2..4, DN_MASK_BITS / DN_MASK_BOX conditions (expand them:
+ * dn_unpack_mask_bits); DN_E_BADARG for nsd != 3, a NULL u, no output at all, f together with f_gp, vjp without cot, in_den without
+ * in_num, in_num with vjp = 0, flags outside {0, 1}, a value field without its mask or an unknown mask kind; DN_E_WORKSPACE for sumsq
+ * or norm without a large enough workspace; nothing is launched then.  dn_eikonal_apply keeps refusing nsd = 3. */
+int64_t dn_eikonal3d_workspace_bytes(const dn_mesh *mesh);
+int dn_eikonal3d_apply(const dn_mesh *mesh, const dn_eikonal_args *args, void *stream);
+
 /* ---- gradient of the Poisson losses with respect to the nodal coefficient and forcing ------------------------------------
  * Replaces what autograd does for the coefficient in the topology optimisation of the reference,
  * examples/poisson/single_instance/16_topopt.py:119-195 (loss = 0.5 nu grad u . grad v - v f with nu from the network, compliance
