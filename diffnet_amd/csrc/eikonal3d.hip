@@ -29,6 +29,7 @@
 #include <cstdio>
 
 #include "dn_reduce.h"
+#include "elem_args.h"
 
 namespace dn {
 
@@ -532,19 +533,11 @@ extern "C" int dn_eikonal3d_apply(const dn_mesh* m, const dn_eikonal_args* a, vo
     if (rc) return rc;
     if (!a || !a->u) return DN_E_BADARG;
     if (!a->out && !a->sumsq && !a->norm) return DN_E_BADARG;
-    if (a->f && a->f_gp) return DN_E_BADARG;
-    if (a->in_den && !a->in_num) return DN_E_BADARG;
-    if ((a->vjp | a->f_batched) & ~1) return DN_E_BADARG;
+    if ((a->in_den && !a->in_num) || (a->vjp & ~1)) return DN_E_BADARG;
     const bool vjp = a->vjp != 0;
     if (vjp && !a->cot) return DN_E_BADARG;                                  // a VJP without its cotangent
     if (!vjp && a->in_num) return DN_E_BADARG;                               // the scaling applies to the cotangent only
-    for (int k = 0; k < 2; ++k) {
-        const dn_dirichlet& d = a->bc[k];
-        if (d.mask_kind == DN_MASK_BITS || d.mask_kind == DN_MASK_BOX) return DN_E_UNSUPPORTED;     // expand them: dn_unpack_mask_bits
-        if (d.mask_kind != DN_MASK_F32 && d.mask_kind != DN_MASK_U8) return DN_E_BADARG;
-        if ((d.mask_batched | d.field_batched) & ~1) return DN_E_BADARG;
-        if (d.field && !d.mask) return DN_E_BADARG;                           // a value field without its mask
-    }
+    if ((rc = elem_check_conditions(a)) != 0) return rc;
     const int64_t nel = (int64_t)(m->nx - 1) * (m->ny - 1) * (m->nz - 1);
     if (a->f_gp && !vjp && nel * m->ngp * m->ngp * m->ngp >= (1ll << 30)) return DN_E_UNSUPPORTED;
     const Ek3Geom g = ek3_plan(m);
@@ -569,21 +562,9 @@ extern "C" int dn_eikonal3d_apply(const dn_mesh* m, const dn_eikonal_args* a, vo
     pp.u = a->u;
     pp.cot = vjp ? a->cot : nullptr;
     pp.in_num = a->in_num; pp.in_den = a->in_den;
-    pp.f = vjp ? nullptr : a->f;                                             // the VJP does not read the forcing
-    pp.fgp = vjp ? nullptr : a->f_gp;
-    pp.f_batched = a->f_batched;
-    for (int k = 0; k < 2; ++k) {
-        const dn_dirichlet& d = a->bc[k];
-        pp.mask[k] = d.mask;
-        pp.mask_kind[k] = !d.mask ? 0 : (d.mask_kind == DN_MASK_U8 ? 1 : 2);
-        pp.mask_batched[k] = d.mask_batched;
-        pp.bcf[k] = d.field;
-        pp.bcf_batched[k] = d.field_batched;
-        pp.bcv[k] = d.value;
-    }
+    elem_fill_conditions(pp, a);
+    if (vjp) pp.f = pp.fgp = nullptr;                                        // the VJP does not read the forcing
     pp.out = a->out; pp.sumsq = a->sumsq; pp.norm = a->norm;
-    pp.counter = reinterpret_cast<unsigned*>(a->workspace);
-    pp.part = a->workspace ? reinterpret_cast<double*>(reinterpret_cast<char*>(a->workspace) + DN_WS_HEADER) : nullptr;
     pp.nx = m->nx; pp.ny = m->ny; pp.nz = m->nz;
     pp.nelx = m->nx - 1; pp.nely = m->ny - 1; pp.nelz = m->nz - 1;
     pp.rows_per_strip = g.R;

@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "dn_reduce.h"
+#include "elem_args.h"
 
 namespace dn {
 
@@ -105,18 +106,10 @@ static inline int64_t elem2d_workspace_bytes(const dn_mesh* m, int nsums) {
 }
 
 // The checks dn_strongform_args, dn_fosls_args, dn_helmholtz_args and dn_eikonal_args have in common, after the operator's own DN_E_BADARG checks: the
-// forcing, the two conditions and the workspace of a call that reduces nsums sums (0: none)
+// forcing and the two conditions (elem_args.h), and the workspace of a call that reduces nsums sums (0: none)
 template <class Args>
 static int elem2d_check_args(const dn_mesh* m, const Args* a, int nsums) {
-    if (a->f && a->f_gp) return DN_E_BADARG;
-    if (a->f_batched & ~1) return DN_E_BADARG;
-    for (int k = 0; k < 2; ++k) {
-        const dn_dirichlet& d = a->bc[k];
-        if (d.mask_kind == DN_MASK_BITS || d.mask_kind == DN_MASK_BOX) return DN_E_UNSUPPORTED;     // expand them: dn_unpack_mask_bits
-        if (d.mask_kind != DN_MASK_F32 && d.mask_kind != DN_MASK_U8) return DN_E_BADARG;
-        if ((d.mask_batched | d.field_batched) & ~1) return DN_E_BADARG;
-        if (d.field && !d.mask) return DN_E_BADARG;                           // a value field without its mask
-    }
+    if (const int rc = elem_check_conditions(a)) return rc;
     if (nsums && (!a->workspace || a->workspace_bytes < elem2d_workspace_bytes(m, nsums))) return DN_E_WORKSPACE;
     return 0;
 }
@@ -132,18 +125,7 @@ static void elem2d_fill(Elem2dParams& pp, const dn_mesh* m, const Args* a, const
             pp.dy[i][j] = in ? (float)(m->dbasis[i][j] * sy) : 0.f;
             pp.w2[i][j] = (i < m->ngp && j < m->ngp) ? m->gpw[i] * (m->gpw[j] * a->wscale) : 0.f;
         }
-    pp.f = a->f; pp.fgp = a->f_gp; pp.f_batched = a->f_batched;
-    for (int k = 0; k < 2; ++k) {
-        const dn_dirichlet& d = a->bc[k];
-        pp.mask[k] = d.mask;
-        pp.mask_kind[k] = !d.mask ? 0 : (d.mask_kind == DN_MASK_U8 ? 1 : 2);
-        pp.mask_batched[k] = d.mask_batched;
-        pp.bcf[k] = d.field;
-        pp.bcf_batched[k] = d.field_batched;
-        pp.bcv[k] = d.value;
-    }
-    pp.counter = reinterpret_cast<unsigned*>(a->workspace);
-    pp.part = a->workspace ? reinterpret_cast<double*>(reinterpret_cast<char*>(a->workspace) + DN_WS_HEADER) : nullptr;
+    elem_fill_conditions(pp, a);
     pp.nx = m->nx; pp.ny = m->ny;
     pp.nelx = (m->nx - 1) / m->degree; pp.nely = (m->ny - 1) / m->degree;
     pp.rows_per_strip = g.R;

@@ -598,25 +598,13 @@ def call_cache_clear():
     with _WS_LOCK:
         _CALL_CACHE.clear()
         _FSDT_CACHE.clear()
-        _STOKES.cache.clear()
-        _NS.cache.clear()
-        _TRANSPORT.cache.clear()
-        _STRONGFORM.cache.clear()
-        _FOSLS.cache.clear()
-        _HELMHOLTZ.cache.clear()
-        _EIKONAL.cache.clear()
-        _EIKONAL3D.cache.clear()
+        for op in _FUSED_OPS:
+            op.cache.clear()
         _PACK_CACHE.clear()
     _POISSON_WS_BYTES.clear()
     _FSDT_WS_BYTES.clear()
-    _STOKES.ws_bytes.clear()
-    _NS.ws_bytes.clear()
-    _TRANSPORT.ws_bytes.clear()
-    _STRONGFORM.ws_bytes.clear()
-    _FOSLS.ws_bytes.clear()
-    _HELMHOLTZ.ws_bytes.clear()
-    _EIKONAL.ws_bytes.clear()
-    _EIKONAL3D.ws_bytes.clear()
+    for op in _FUSED_OPS:
+        op.ws_bytes.clear()
 
 
 class PoissonPlan:
@@ -1561,28 +1549,31 @@ class FsdtPlan:
 
 
 
-# ---- the two three-field 2-D flow operators: dn_stokes_apply (PSPG) and dn_ns_apply (VMS residuals and their VJP) ------------------
-# Each operator has a reduction workspace of its OWN per (device, stream), never the one of _workspace or _fsdt_workspace nor the other
+# ---- the host call path of the flow, transport and element operators (stokes_apply ... eikonal3d_apply) --------------------------
+# Each operator has a reduction workspace of its OWN per (device, stream), never the one of _workspace or _fsdt_workspace nor another
 # operator's: an FSDT launch with defer_norms leaves its partials in its workspace for a later consumer, and a launch issued in between
-# must not overwrite them.  _Flow2dOp holds an operator's workspaces, their sizes, its prepared-call cache and its launch lock.
-class _Flow2dOp:
+# must not overwrite them.  _FusedOp holds an operator's workspaces, their sizes, its prepared-call cache and its launch lock; every one
+# is listed in _FUSED_OPS (call_cache_clear).  What the calls share is written once, for any dimension: the workspace (_op_workspace), the
+# look-up / prepare / cache step (_op_entry), the patch-under-lock / launch step (_op_launch), the check of a nodal field against the
+# mesh (_nodal_batched), the form of a Dirichlet mask (_bc_mask) and a Gauss-point forcing tensor (_gp_forcing).
+_FUSED_OPS = []
+
+
+class _FusedOp:
     def __init__(self, name, args_type):
-        self.name, self.args_type = name, args_type          # name: "stokes_apply" / "ns_apply", the prefix of its messages
+        self.name, self.args_type = name, args_type          # name: "stokes_apply", "ns_apply", ...: the prefix of its messages
         self.fn, self.ws_fn = "dn_" + name, "dn_" + name.replace("_apply", "_workspace_bytes")      # the C entry points
         self.ws = {}
         self.ws_bytes = {}
         self.cache = __import__("collections").OrderedDict()
         self.launch_lock = _threading.Lock()
-        self.entry = None                  # the bound C entry point, where a caller keeps it (_elem2d_launch)
+        self.entry = None                  # the bound C entry point (_op_launch)
+        _FUSED_OPS.append(self)
 
 
-_STOKES = _Flow2dOp("stokes_apply", DnStokesArgs)
-_NS = _Flow2dOp("ns_apply", DnNsArgs)
-
-
-def _flow2d_workspace(op, mesh, B, dev):
-    """The operator's reduction workspace on the current stream of `dev`, large enough for `mesh`."""
-    key = (mesh.nx, mesh.ny, mesh.degree, mesh.ngp, B)
+def _op_workspace(op, mesh, B, dev):
+    """The operator's reduction workspace on the current stream of `dev`, large enough for `mesh` under the launch plan in force."""
+    key = (mesh.nx, mesh.ny, mesh.nz, mesh.degree, mesh.ngp, B)
     nbytes = op.ws_bytes.get(key)
     if nbytes is None:
         nbytes = getattr(_lib.lib(), op.ws_fn)(C.byref(mesh))
@@ -1596,6 +1587,84 @@ def _flow2d_workspace(op, mesh, B, dev):
             ws = torch.zeros(max(nbytes, 1 << 16), dtype=torch.uint8, device=dev)   # ABI: zero-filled once
             op.ws[key] = ws
     return ws
+
+
+def _op_entry(op, key, prepare, pargs):
+    """The prepared call `key` (None: not cacheable) from the operator's cache, or prepare(*pargs) -- (mesh, args, tensors to keep alive,
+    the field shape or the batch size) -- inserted into it: (mesh, args, their two references, shape | B, tensors kept alive)."""
+    ent = None
+    if key is not None:
+        with _WS_LOCK:
+            ent = op.cache.get(key)
+            if ent is not None:
+                op.cache.move_to_end(key)
+    if ent is not None:
+        _CALL_STATS["hit"] += 1
+        return ent
+    _CALL_STATS["miss" if key is not None else "uncached"] += 1
+    mesh, args, keep, shape = prepare(*pargs)
+    with _WS_LOCK:
+        live_ws = list(op.ws.values())
+    # an uncached call keeps its (possibly converted) tensors alive until it has been issued; a cached one only the workspace
+    ent = (mesh, args, C.byref(mesh), C.byref(args), shape, keep if key is None else [t for t in keep if any(t is x for x in live_ws)])
+    if key is not None:
+        with _WS_LOCK:
+            op.cache[key] = ent
+            while len(op.cache) > _CALL_CACHE_MAX:
+                op.cache.popitem(last=False)
+    return ent
+
+
+def _op_launch(op, ent, u, patch, ptrs):
+    """patch(args, ptrs) sets the pointers of the call's fresh outputs in the (possibly shared, cached) argument struct; that and the
+    launch are one step under the operator's lock.  The hit path of a call is host time: no closure, the entry point bound once."""
+    fn = op.entry
+    if fn is None:
+        fn = op.entry = getattr(_lib.lib(), op.fn)
+    with op.launch_lock:
+        patch(ent[1], ptrs)
+        rc = fn(ent[2], ent[3], _stream(u))
+    if rc:
+        _lib.check(rc, op.fn)
+
+
+def _patch_out_sumsq_norm(args, ptrs):
+    args.out, args.sumsq, args.norm = ptrs
+
+
+def _nodal_batched(op, geom, B, t, what):
+    """Checks the nodal field `t` (B | 1, ., *node_shape) against the mesh; 1 when it is per sample, 0 when shared."""
+    nn = geom.nnode_total
+    if tuple(t.shape[-geom.nsd:]) != tuple(geom.node_shape) or t.numel() not in (B * nn, nn):
+        raise ValueError(f"{op.name}: {what} shape {tuple(t.shape)} does not match the mesh {(B, 1, *geom.node_shape)}")
+    return 1 if (t.numel() == B * nn and B > 1) else 0
+
+
+def _bc_mask(op, m, k):
+    """The Dirichlet mask of condition k as the kernels read it: (a contiguous uint8 or fp32 tensor, whether it is the uint8 one)."""
+    if not isinstance(m, torch.Tensor):
+        raise TypeError(f"{op.name}: bc[{k}] must be a tensor or None (expand a PackedMask / BoxFaces to its image)")
+    if not m.is_cuda:
+        raise DiffNetHipError(f"{op.name}: bc[{k}] is on {m.device}: the FEM ops run on the GPU only (no CPU fallback)")
+    if m.dtype in (torch.bool, torch.uint8):
+        m = m.contiguous()
+        return (m.view(torch.uint8) if m.dtype == torch.bool else m), True
+    return _require(m, f"bc[{k}]"), False
+
+
+def _gp_forcing(op, geom, keep, B, f, what):
+    """A Gauss-point forcing tensor (B | 1, G, *elem_shape): (its pointer, 1 when it is per sample)."""
+    f = _require(f, what)
+    G, nel = geom.ngp_total, geom.nelem_total
+    if tuple(f.shape[-1 - geom.nsd:]) != (G, *geom.elem_shape) or f.numel() not in (G * nel, B * G * nel):
+        raise ValueError(f"{op.name}: {what} shape {tuple(f.shape)} is not (B | 1, {G}, {', '.join(str(n) for n in geom.elem_shape)})")
+    keep.append(f)
+    return f.data_ptr(), 1 if (f.numel() == B * G * nel and B > 1) else 0
+
+
+# ---- the two three-field 2-D flow operators: dn_stokes_apply (PSPG) and dn_ns_apply (VMS residuals and their VJP) ------------------
+_STOKES = _FusedOp("stokes_apply", DnStokesArgs)
+_NS = _FusedOp("ns_apply", DnNsArgs)
 
 
 def stokes_bc3(bc):
@@ -1661,6 +1730,32 @@ def _flow2d_key(geom, flds, bc3, vals, f2, consts, in_num, in_den, flags, cot=()
     return tuple(parts)
 
 
+def _flow2d_conditions(op, geom, args, keep, B, masks, vals, forcing):
+    """The indexed members dn_stokes_args, dn_ns_args and dn_transport_args have in common: the masks into bc_mask[k] / mask_is_u8[k] /
+    mask_batched[k], their values into bc_field[k] / bc_field_batched[k] or bc_value[k].  `forcing`: (name, float or Gauss-point tensor)
+    pairs; returns (pointer | None, 1 when per sample, value) of each, for the caller's own members."""
+    for k, m in enumerate(masks):
+        if m is None:
+            continue
+        m, byte = _bc_mask(op, m, k)
+        args.mask_is_u8[k] = 1 if byte else 0
+        args.mask_batched[k] = _nodal_batched(op, geom, B, m, f"bc[{k}]")
+        args.bc_mask[k] = m.data_ptr()
+        keep.append(m)
+    for k, val in enumerate(vals):
+        if isinstance(val, torch.Tensor) and val.numel() > 1:
+            if masks[k] is None:
+                raise ValueError(f"{op.name}: bc_values[{k}] is a field but condition {k} has no mask")
+            val = _require(val, f"bc_values[{k}]")
+            args.bc_field_batched[k] = _nodal_batched(op, geom, B, val, f"bc_values[{k}]")
+            args.bc_field[k] = val.data_ptr()
+            keep.append(val)
+        else:
+            args.bc_value[k] = float(val)
+    return [(*_gp_forcing(op, geom, keep, B, f, what), 0.0) if isinstance(f, torch.Tensor) and f.numel() > 1 else (None, 0, float(f))
+            for what, f in forcing]
+
+
 def _prepare_flow2d(op, geom, flds, bc3, vals, f2, in_num, in_den, want_red):
     """Validation + the members dn_stokes_args and dn_ns_args have in common (fields, masks, values, forcing, in_num / in_den, workspace),
     outputs left unset: (mesh, args, tensors to keep alive, field shape).  `flds`: (name, tensor) pairs, u, v, p first; any further ones
@@ -1676,50 +1771,9 @@ def _prepare_flow2d(op, geom, flds, bc3, vals, f2, in_num, in_den, want_red):
     keep = list(flds)
     args = op.args_type()
     args.u, args.v, args.p = (t.data_ptr() for t in flds[:3])
-    nn = geom.nnode_total
-
-    def batched(t, what):
-        if tuple(t.shape[-2:]) != tuple(geom.node_shape) or t.numel() not in (B * nn, nn):
-            raise ValueError(f"{name}: {what} shape {tuple(t.shape)} does not match the mesh {shape}")
-        return 1 if (t.numel() == B * nn and B > 1) else 0
-
-    for k, m in enumerate(bc3):
-        if m is None:
-            continue
-        if not isinstance(m, torch.Tensor):
-            raise TypeError(f"{name}: bc[{k}] must be a tensor or None")
-        if not m.is_cuda:
-            raise DiffNetHipError(f"{name}: bc[{k}] is on {m.device}: the FEM ops run on the GPU only (no CPU fallback)")
-        if m.dtype in (torch.bool, torch.uint8):
-            m = m.contiguous()
-            m = m.view(torch.uint8) if m.dtype == torch.bool else m
-            args.mask_is_u8[k] = 1
-        else:
-            m = _require(m, f"bc[{k}]")
-        args.mask_batched[k] = batched(m, f"bc[{k}]")
-        args.bc_mask[k] = m.data_ptr()
-        keep.append(m)
-    for k, val in enumerate(vals):
-        if isinstance(val, torch.Tensor) and val.numel() > 1:
-            if bc3[k] is None:
-                raise ValueError(f"{name}: bc_values[{k}] is a field but field {k} has no Dirichlet mask")
-            val = _require(val, f"bc_values[{k}]")
-            args.bc_field_batched[k] = batched(val, f"bc_values[{k}]")
-            args.bc_field[k] = val.data_ptr()
-            keep.append(val)
-        else:
-            args.bc_value[k] = float(val)
-    G, nel = geom.ngp_total, geom.nelem_total
-    for k, f in enumerate(f2):
-        if isinstance(f, torch.Tensor) and f.numel() > 1:
-            f = _require(f, f"f_gp[{k}]")
-            if tuple(f.shape[-3:]) != (G, *geom.elem_shape) or f.numel() not in (G * nel, B * G * nel):
-                raise ValueError(f"{name}: f_gp[{k}] shape {tuple(f.shape)} is not (B | 1, {G}, {geom.elem_shape[0]}, {geom.elem_shape[1]})")
-            args.f_batched[k] = 1 if (f.numel() == B * G * nel and B > 1) else 0
-            args.f_gp[k] = f.data_ptr()
-            keep.append(f)
-        else:
-            args.f_value[k] = float(f)
+    forcing = _flow2d_conditions(op, geom, args, keep, B, bc3, vals, [(f"f_gp[{k}]", f) for k, f in enumerate(f2)])
+    for k, (ptr, per_sample, value) in enumerate(forcing):
+        args.f_gp[k], args.f_batched[k], args.f_value[k] = ptr, per_sample, value
     if (in_num is None) != (in_den is None):
         raise ValueError(f"{name}: in_num and in_den go together")
     for what, t in (("in_num", in_num), ("in_den", in_den)):
@@ -1731,55 +1785,36 @@ def _prepare_flow2d(op, geom, flds, bc3, vals, f2, in_num, in_den, want_red):
             keep.append(t)
     mesh = geom.mesh_struct(B)
     if want_red:
-        ws = _flow2d_workspace(op, mesh, B, flds[0].device)
+        ws = _op_workspace(op, mesh, B, flds[0].device)
         keep.append(ws)
         args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
     return mesh, args, keep, shape
 
 
-def _flow2d_call(op, key, prepare, u, want_out, want_sums, want_norms):
-    """Look up the prepared call `key` (None: not cacheable) or prepare() it, allocate fresh outputs, patch their three pointers into the
-    (possibly shared, cached) argument struct and launch.  Returns (outs | None, sums | None[, norms])."""
-    ent = None
-    if key is not None:
-        with _WS_LOCK:
-            ent = op.cache.get(key)
-            if ent is not None:
-                op.cache.move_to_end(key)
-    if ent is None:
-        _CALL_STATS["miss" if key is not None else "uncached"] += 1
-        mesh, args, keep, shape = prepare()
-        with _WS_LOCK:
-            live_ws = list(op.ws.values())
-        ent = (mesh, args, C.byref(mesh), C.byref(args), shape, [t for t in keep if any(t is x for x in live_ws)])
-        if key is not None:
-            with _WS_LOCK:
-                op.cache[key] = ent
-                while len(op.cache) > _CALL_CACHE_MAX:
-                    op.cache.popitem(last=False)
+def _flow2d_patch(args, ptrs):
+    p0, step, args.sumsq, args.norms = ptrs
+    if p0 is None:
+        args.out[0] = args.out[1] = args.out[2] = None
     else:
-        _CALL_STATS["hit"] += 1
-    mesh, args, mref, aref, shape = ent[:5]
+        args.out[0], args.out[1], args.out[2] = p0, p0 + step, p0 + 2 * step
+
+
+def _flow2d_call(op, key, prepare, pargs, u, want_out, want_sums, want_norms):
+    """Look up the prepared call `key` (None: not cacheable) or prepare(*pargs) it, allocate fresh outputs, patch their three pointers
+    into the (possibly shared, cached) argument struct and launch.  Returns (outs | None, sums | None[, norms])."""
+    ent = _op_entry(op, key, prepare, pargs)
     dev = u.device
-    outs = sums = norms = None
+    outs = sums = norms = p0 = None
     if want_out:
-        o3 = torch.empty((3, *shape), dtype=torch.float32, device=dev)      # one allocation, three views
+        o3 = torch.empty((3, *ent[4]), dtype=torch.float32, device=dev)      # one allocation, three views
         outs = list(o3.unbind(0))
+        p0 = o3.data_ptr()
     if want_sums:
         sums = torch.empty(3, dtype=torch.float64, device=dev)
     if want_norms:
         norms = torch.empty(3, dtype=torch.float32, device=dev)
-    with op.launch_lock:               # pointer patch + launch of the (possibly shared, cached) argument struct as one step
-        if want_out:
-            p0, step = o3.data_ptr(), 4 * o3[0].numel()
-            args.out[0], args.out[1], args.out[2] = p0, p0 + step, p0 + 2 * step
-        else:
-            args.out[0] = args.out[1] = args.out[2] = None
-        args.sumsq = sums.data_ptr() if want_sums else None
-        args.norms = norms.data_ptr() if want_norms else None
-        rc = getattr(_lib.lib(), op.fn)(mref, aref, _stream(u))
-    if rc:
-        _lib.check(rc, op.fn)
+    _op_launch(op, ent, u, _flow2d_patch, (p0, 4 * outs[0].numel() if want_out else 0, sums.data_ptr() if want_sums else None,
+                                          norms.data_ptr() if want_norms else None))
     return (outs, sums, norms) if want_norms else (outs, sums)
 
 
@@ -1809,7 +1844,7 @@ def stokes_apply(geom, u, v, p, bc=None, bc_values=(0.0, 0.0, 0.0), visco=1.0, p
     consts = (float(visco), float(pspg), float(wscale), bool(transpose))
     want_red = want_sums or want_norms
     key = _flow2d_key(geom, (u, v, p), bc3, vals, f2, consts, in_num, in_den, (want_out, want_sums, want_norms))
-    return _flow2d_call(_STOKES, key, lambda: _prepare_stokes(geom, u, v, p, bc3, vals, f2, consts, in_num, in_den, want_red),
+    return _flow2d_call(_STOKES, key, _prepare_stokes, (geom, u, v, p, bc3, vals, f2, consts, in_num, in_den, want_red),
                         u, want_out, want_sums, want_norms)
 
 
@@ -1851,14 +1886,13 @@ def ns_apply(geom, u, v, p, bc=None, bc_values=(0.0, 0.0, 0.0), visco=1.0, f_gp=
     want_red = want_sums or want_norms
     key = _flow2d_key(geom, (u, v, p), bc3, vals, f2, consts, in_num, in_den, (want_out, want_sums, want_norms),
                       cot if cot is not None else (None, None, None))
-    return _flow2d_call(_NS, key, lambda: _prepare_ns(geom, u, v, p, cot, bc3, vals, f2, consts, in_num, in_den, want_red),
+    return _flow2d_call(_NS, key, _prepare_ns, (geom, u, v, p, cot, bc3, vals, f2, consts, in_num, in_den, want_red),
                         u, want_out, want_sums, want_norms)
 
 
 # ---- the one-field 2-D transport operator: dn_transport_apply (SUPG residual and its VJP) ------------------------------------------
-# Its own reduction workspace per (device, stream), prepared-call cache and launch lock, like _STOKES / _NS and for the same reason: an
-# FSDT deferring pair or a flow launch in between must not disturb its partial sums, nor it theirs.
-_TRANSPORT = _Flow2dOp("transport_apply", DnTransportArgs)
+# Its argument struct has the indexed members of the flow operators', for two conditions and one forcing term (_flow2d_conditions).
+_TRANSPORT = _FusedOp("transport_apply", DnTransportArgs)
 
 
 def transport_bc2(bc):
@@ -1905,24 +1939,11 @@ def _prepare_transport(geom, u, nu, cot, bc2, vals, f, consts, in_num, in_den, w
     """Validation + argument struct of a dn_transport_apply call, outputs left unset: (mesh, args, tensors to keep alive, field shape)."""
     name = _TRANSPORT.name
     _flow2d_check_mesh(_TRANSPORT, geom)
-    u = _require(u, "u", 4)
-    B = u.shape[0]
-    shape = (B, 1, *geom.node_shape)
-    if tuple(u.shape) != shape:
-        raise ValueError(f"{name}: field shape {tuple(u.shape)} != {shape}")
-    keep = [u]
-    args = DnTransportArgs()
-    args.u = u.data_ptr()
-    nn = geom.nnode_total
-
-    def batched(t, what):
-        if tuple(t.shape[-2:]) != tuple(geom.node_shape) or t.numel() not in (B * nn, nn):
-            raise ValueError(f"{name}: {what} shape {tuple(t.shape)} does not match the mesh {shape}")
-        return 1 if (t.numel() == B * nn and B > 1) else 0
-
+    args, keep = DnTransportArgs(), []
+    u, B, shape = _elem_u(_TRANSPORT, geom, u, args, keep)
     if nu is not None:
         nu = _require(nu, "nu")
-        args.nu_batched = batched(nu, "nu")
+        args.nu_batched = _nodal_batched(_TRANSPORT, geom, B, nu, "nu")
         args.nu = nu.data_ptr()
         keep.append(nu)
     if cot is not None:
@@ -1934,42 +1955,7 @@ def _prepare_transport(geom, u, nu, cot, bc2, vals, f, consts, in_num, in_den, w
     elif in_num is not None:
         raise ValueError(f"{name}: in_num / in_den scale the cotangent of a VJP (cot)")
     args.vjp = 1 if cot is not None else 0
-    for k, m in enumerate(bc2):
-        if m is None:
-            continue
-        if not isinstance(m, torch.Tensor):
-            raise TypeError(f"{name}: bc[{k}] must be a tensor or None")
-        if not m.is_cuda:
-            raise DiffNetHipError(f"{name}: bc[{k}] is on {m.device}: the FEM ops run on the GPU only (no CPU fallback)")
-        if m.dtype in (torch.bool, torch.uint8):
-            m = m.contiguous()
-            m = m.view(torch.uint8) if m.dtype == torch.bool else m
-            args.mask_is_u8[k] = 1
-        else:
-            m = _require(m, f"bc[{k}]")
-        args.mask_batched[k] = batched(m, f"bc[{k}]")
-        args.bc_mask[k] = m.data_ptr()
-        keep.append(m)
-    for k, val in enumerate(vals):
-        if isinstance(val, torch.Tensor) and val.numel() > 1:
-            if bc2[k] is None:
-                raise ValueError(f"{name}: bc_values[{k}] is a field but condition {k} has no mask")
-            val = _require(val, f"bc_values[{k}]")
-            args.bc_field_batched[k] = batched(val, f"bc_values[{k}]")
-            args.bc_field[k] = val.data_ptr()
-            keep.append(val)
-        else:
-            args.bc_value[k] = float(val)
-    G, nel = geom.ngp_total, geom.nelem_total
-    if isinstance(f, torch.Tensor) and f.numel() > 1:
-        f = _require(f, "f_gp")
-        if tuple(f.shape[-3:]) != (G, *geom.elem_shape) or f.numel() not in (G * nel, B * G * nel):
-            raise ValueError(f"{name}: f_gp shape {tuple(f.shape)} is not (B | 1, {G}, {geom.elem_shape[0]}, {geom.elem_shape[1]})")
-        args.f_batched = 1 if (f.numel() == B * G * nel and B > 1) else 0
-        args.f_gp = f.data_ptr()
-        keep.append(f)
-    else:
-        args.f_value = float(f)
+    (args.f_gp, args.f_batched, args.f_value), = _flow2d_conditions(_TRANSPORT, geom, args, keep, B, bc2, vals, [("f_gp", f)])
     if in_den is not None and in_num is None:
         raise ValueError(f"{name}: in_den needs in_num")
     for what, t in (("in_num", in_num), ("in_den", in_den)):
@@ -1984,7 +1970,7 @@ def _prepare_transport(geom, u, nu, cot, bc2, vals, f, consts, in_num, in_den, w
     args.r_first_wins = 1 if first else 0
     mesh = geom.mesh_struct(B)
     if want_red:
-        ws = _flow2d_workspace(_TRANSPORT, mesh, B, u.device)
+        ws = _op_workspace(_TRANSPORT, mesh, B, u.device)
         keep.append(ws)
         args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
     return mesh, args, keep, shape
@@ -2012,57 +1998,25 @@ def transport_apply(geom, u, nu=None, bc=None, bc_values=(0.0, 0.0), r_first_win
     f = 0.0 if f_gp is None else f_gp
     consts = (*(float(x) for x in adv), *(float(x) for x in kappa), float(tau), *(float(x) for x in react), float(wscale), bool(r_first_wins))
     want_red = want_sums or want_norm
-    op = _TRANSPORT
     key = _transport_key(geom, u, nu, bc2, vals, f, consts, in_num, in_den, (want_out, want_sums, want_norm), cot)
-    ent = None
-    if key is not None:
-        with _WS_LOCK:
-            ent = op.cache.get(key)
-            if ent is not None:
-                op.cache.move_to_end(key)
-    if ent is None:
-        _CALL_STATS["miss" if key is not None else "uncached"] += 1
-        mesh, args, keep, shape = _prepare_transport(geom, u, nu, cot, bc2, vals, f, consts, in_num, in_den, want_red)
-        with _WS_LOCK:
-            live_ws = list(op.ws.values())
-        # an uncached call keeps its (possibly converted) tensors alive until it has been issued; a cached one only the workspace
-        ent = (mesh, args, C.byref(mesh), C.byref(args), shape, keep if key is None else [t for t in keep if any(t is x for x in live_ws)])
-        if key is not None:
-            with _WS_LOCK:
-                op.cache[key] = ent
-                while len(op.cache) > _CALL_CACHE_MAX:
-                    op.cache.popitem(last=False)
-    else:
-        _CALL_STATS["hit"] += 1
-    mesh, args, mref, aref, shape = ent[:5]
+    ent = _op_entry(_TRANSPORT, key, _prepare_transport, (geom, u, nu, cot, bc2, vals, f, consts, in_num, in_den, want_red))
     dev = u.device
-    out = sums = norm = None
-    if want_out:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
-    if want_sums:
-        sums = torch.empty(1, dtype=torch.float64, device=dev)
-    if want_norm:
-        norm = torch.empty(1, dtype=torch.float32, device=dev)
-    with op.launch_lock:               # pointer patch + launch of the (possibly shared, cached) argument struct as one step
-        args.out = out.data_ptr() if want_out else None
-        args.sumsq = sums.data_ptr() if want_sums else None
-        args.norm = norm.data_ptr() if want_norm else None
-        rc = _lib.lib().dn_transport_apply(mref, aref, _stream(u))
-    if rc:
-        _lib.check(rc, op.fn)
+    out = torch.empty(ent[4], dtype=torch.float32, device=dev) if want_out else None
+    sums = torch.empty(1, dtype=torch.float64, device=dev) if want_sums else None
+    norm = torch.empty(1, dtype=torch.float32, device=dev) if want_norm else None
+    _op_launch(_TRANSPORT, ent, u, _patch_out_sumsq_norm, (out.data_ptr() if want_out else None, sums.data_ptr() if want_sums else None,
+                                                          norm.data_ptr() if want_norm else None))
     return (out, sums, norm) if want_norm else (out, sums)
 
 
-# ---- the element-march operators on 2-D Q_P meshes: dn_strongform_apply, dn_fosls_apply, dn_helmholtz_apply, dn_eikonal_apply ----
-# Each has its own reduction workspace per (device, stream), prepared-call cache and launch lock, like _TRANSPORT and for the same
-# reason.  What their calls share -- the mesh check, the key of a prepared call, the two conditions, the forcing, in_scale, the
-# workspace, the look-up / prepare / cache step and the patch-under-lock / launch step -- is written once (_elem2d_*); an operator's own
+# ---- the element operators: dn_strongform_apply, dn_fosls_apply, dn_helmholtz_apply, dn_eikonal_apply on 2-D Q_P meshes and
+# dn_eikonal3d_apply on 3-D Q1 meshes ----
+# What their calls share beyond the above -- the key of a prepared call, the field u, the two conditions (dn_dirichlet bc[2]), the
+# forcing, in_scale and the workspace -- is written once (_elem_*), with the number of mesh axes from geom.nsd; an operator's own
 # functions name its own arguments and allocate its outputs.
-_STRONGFORM = _Flow2dOp("strongform_apply", DnStrongformArgs)
-_FOSLS = _Flow2dOp("fosls_apply", DnFoslsArgs)
-_HELMHOLTZ = _Flow2dOp("helmholtz_apply", DnHelmholtzArgs)
-_EIKONAL = _Flow2dOp("eikonal_apply", DnEikonalArgs)
-_EIKONAL3D = _Flow2dOp("eikonal3d_apply", DnEikonalArgs)
+_STRONGFORM = _FusedOp("strongform_apply", DnStrongformArgs)
+_FOSLS = _FusedOp("fosls_apply", DnFoslsArgs)
+_HELMHOLTZ = _FusedOp("helmholtz_apply", DnHelmholtzArgs)
 
 
 def _elem2d_check_mesh(op, geom):
@@ -2073,7 +2027,7 @@ def _elem2d_check_mesh(op, geom):
         raise ValueError(f"{op.name}: a degree-{geom.deg} mesh needs (n - 1) % {geom.deg} == 0 nodes per axis, got {geom.sizes}")
 
 
-def _elem2d_key(parts, masks, scalars, optional):
+def _elem_key(parts, masks, scalars, optional):
     """Completes the key of a cached prepared call (see _call_key) that starts with `parts`: the masks (fp32 / uint8 / bool or None),
     the float-or-fp32-tensor arguments `scalars` and the optional fp32 tensors; None when an argument needs a conversion copy."""
     for m in masks:
@@ -2097,8 +2051,8 @@ def _elem2d_key(parts, masks, scalars, optional):
     return tuple(parts)
 
 
-def _elem2d_u_key(geom, u, consts, flags):
-    """The head of the key of a call on one field u (B,1,ny,nx), or None."""
+def _elem_u_key(geom, u, consts, flags):
+    """The head of the key of a call on one field u (B,1,*node_shape), or None."""
     if not (isinstance(u, torch.Tensor) and u.is_cuda and tuple(u.shape[1:]) == (1, *geom.node_shape)):
         return None
     k = _tkey(u)
@@ -2107,54 +2061,39 @@ def _elem2d_u_key(geom, u, consts, flags):
     return [geom.key, u.device.index, _raw_stream(u.device), consts, flags, k]
 
 
-def _elem2d_field(op, geom, args, keep, B, t, what, member, fp32=True):
-    """A nodal field (B | 1, ., ny, nx) into args.<member> and args.<member>_batched."""
-    nn = geom.nnode_total
-    if fp32:
-        t = _require(t, what)
-    if tuple(t.shape[-2:]) != tuple(geom.node_shape) or t.numel() not in (B * nn, nn):
-        raise ValueError(f"{op.name}: {what} shape {tuple(t.shape)} does not match the mesh {(B, 1, *geom.node_shape)}")
-    setattr(args, member + "_batched", 1 if (t.numel() == B * nn and B > 1) else 0)
+def _elem_field(op, geom, args, keep, B, t, what, member):
+    """A nodal fp32 field (B | 1, ., *node_shape) into args.<member> and args.<member>_batched."""
+    t = _require(t, what)
+    setattr(args, member + "_batched", _nodal_batched(op, geom, B, t, what))
     setattr(args, member, t.data_ptr())
     keep.append(t)
 
 
-def _prepare_elem2d(op, geom, args, keep, B, dev, bc2, vals, f, f_gp, want_sums, in_scale=None, in_scale_on=None):
-    """The members the three argument structs have in common, after the operator's own: the two conditions, the forcing, in_scale (where
-    the struct has one) and the workspace of a reducing call.  Returns the mesh struct."""
+def _prepare_elem(op, geom, args, keep, B, dev, bc2, vals, f, f_gp, want_sums, in_scale=None, in_scale_on=None):
+    """The members the element operators' argument structs have in common, after the operator's own: the two conditions, the forcing,
+    in_scale (where the struct has one) and the workspace of a reducing call.  Returns the mesh struct."""
     name = op.name
     for k, m in enumerate(bc2):
         if m is None:
             continue
-        if not isinstance(m, torch.Tensor):
-            raise TypeError(f"{name}: bc[{k}] must be a tensor or None (expand a PackedMask / BoxFaces to its image)")
-        if not m.is_cuda:
-            raise DiffNetHipError(f"{name}: bc[{k}] is on {m.device}: the FEM ops run on the GPU only (no CPU fallback)")
-        byte = m.dtype in (torch.bool, torch.uint8)
-        if byte:
-            m = m.contiguous()
-            m = m.view(torch.uint8) if m.dtype == torch.bool else m
-        args.bc[k].mask_kind = _lib.MASK_U8 if byte else _lib.MASK_F32
-        _elem2d_field(op, geom, args.bc[k], keep, B, m, f"bc[{k}]", "mask", fp32=not byte)
+        m, byte = _bc_mask(op, m, k)
+        d = args.bc[k]
+        d.mask_kind = _lib.MASK_U8 if byte else _lib.MASK_F32
+        d.mask_batched, d.mask = _nodal_batched(op, geom, B, m, f"bc[{k}]"), m.data_ptr()
+        keep.append(m)
     for k, val in enumerate(vals):
         if isinstance(val, torch.Tensor) and val.numel() > 1:
             if bc2[k] is None:
                 raise ValueError(f"{name}: bc_values[{k}] is a field but condition {k} has no mask")
-            _elem2d_field(op, geom, args.bc[k], keep, B, val, f"bc_values[{k}]", "field")
+            _elem_field(op, geom, args.bc[k], keep, B, val, f"bc_values[{k}]", "field")
         else:
             args.bc[k].value = float(val)
-    G, nel = geom.ngp_total, geom.nelem_total
     if f is not None:
         if isinstance(f_gp, torch.Tensor) and f_gp.numel() > 1:
             raise ValueError(f"{name}: nodal forcing f and Gauss-point forcing f_gp exclude each other")
-        _elem2d_field(op, geom, args, keep, B, f, "f", "f")
+        _elem_field(op, geom, args, keep, B, f, "f", "f")
     elif isinstance(f_gp, torch.Tensor) and f_gp.numel() > 1:
-        f_gp = _require(f_gp, "f_gp")
-        if tuple(f_gp.shape[-3:]) != (G, *geom.elem_shape) or f_gp.numel() not in (G * nel, B * G * nel):
-            raise ValueError(f"{name}: f_gp shape {tuple(f_gp.shape)} is not (B | 1, {G}, {geom.elem_shape[0]}, {geom.elem_shape[1]})")
-        args.f_batched = 1 if (f_gp.numel() == B * G * nel and B > 1) else 0
-        args.f_gp = f_gp.data_ptr()
-        keep.append(f_gp)
+        args.f_gp, args.f_batched = _gp_forcing(op, geom, keep, B, f_gp, "f_gp")
     else:
         args.f_value = float(f_gp)
     if in_scale is not None:
@@ -2165,54 +2104,15 @@ def _prepare_elem2d(op, geom, args, keep, B, dev, bc2, vals, f, f_gp, want_sums,
         keep.append(in_scale)
     mesh = geom.mesh_struct(B)
     if want_sums:
-        ws = _flow2d_workspace(op, mesh, B, dev)
+        ws = _op_workspace(op, mesh, B, dev)
         keep.append(ws)
         args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
     return mesh
 
 
-def _elem2d_entry(op, key, prepare, pargs):
-    """The prepared call `key` (None: not cacheable) from the operator's cache, or prepare(*pargs) -- (mesh, args, tensors to keep alive,
-    the field shape or the batch size) -- inserted into it: (mesh, args, their two references, shape | B, tensors kept alive)."""
-    ent = None
-    if key is not None:
-        with _WS_LOCK:
-            ent = op.cache.get(key)
-            if ent is not None:
-                op.cache.move_to_end(key)
-    if ent is not None:
-        _CALL_STATS["hit"] += 1
-        return ent
-    _CALL_STATS["miss" if key is not None else "uncached"] += 1
-    mesh, args, keep, shape = prepare(*pargs)
-    with _WS_LOCK:
-        live_ws = list(op.ws.values())
-    # an uncached call keeps its (possibly converted) tensors alive until it has been issued; a cached one only the workspace
-    ent = (mesh, args, C.byref(mesh), C.byref(args), shape, keep if key is None else [t for t in keep if any(t is x for x in live_ws)])
-    if key is not None:
-        with _WS_LOCK:
-            op.cache[key] = ent
-            while len(op.cache) > _CALL_CACHE_MAX:
-                op.cache.popitem(last=False)
-    return ent
-
-
-def _elem2d_launch(op, ent, u, patch, ptrs):
-    """patch(args, ptrs) sets the pointers of the call's fresh outputs in the (possibly shared, cached) argument struct; that and the
-    launch are one step under the operator's lock.  The hit path of a call is host time: no closure, the entry point bound once."""
-    fn = op.entry
-    if fn is None:
-        fn = op.entry = getattr(_lib.lib(), op.fn)
-    with op.launch_lock:
-        patch(ent[1], ptrs)
-        rc = fn(ent[2], ent[3], _stream(u))
-    if rc:
-        _lib.check(rc, op.fn)
-
-
-def _elem2d_u(op, geom, u, args, keep):
-    """The field u (B,1,ny,nx) of a one-field operator into args.u; returns (u, B, its shape)."""
-    u = _require(u, "u", 4)
+def _elem_u(op, geom, u, args, keep):
+    """The field u (B,1,*node_shape) of a one-field operator into args.u; returns (u, B, its shape)."""
+    u = _require(u, "u", 2 + geom.nsd)
     B = u.shape[0]
     shape = (B, 1, *geom.node_shape)
     if tuple(u.shape) != shape:
@@ -2224,8 +2124,8 @@ def _elem2d_u(op, geom, u, args, keep):
 
 # ---- the fused 2-D strong-form least-squares loss and its gradient: dn_strongform_apply ----------------------------------------
 def _strongform_key(geom, u, bc2, vals, f, f_gp, consts, in_scale, flags):
-    parts = _elem2d_u_key(geom, u, consts, flags)
-    return parts and _elem2d_key(parts, bc2, (*vals, f_gp), (f, in_scale))
+    parts = _elem_u_key(geom, u, consts, flags)
+    return parts and _elem_key(parts, bc2, (*vals, f_gp), (f, in_scale))
 
 
 def _prepare_strongform(geom, u, bc2, vals, f, f_gp, consts, in_scale, want_sum):
@@ -2233,12 +2133,12 @@ def _prepare_strongform(geom, u, bc2, vals, f, f_gp, consts, in_scale, want_sum)
     op = _STRONGFORM
     _elem2d_check_mesh(op, geom)
     args, keep = DnStrongformArgs(), []
-    u, B, shape = _elem2d_u(op, geom, u, args, keep)
+    u, B, shape = _elem_u(op, geom, u, args, keep)
     args.ax, args.ay, args.b, args.dxx, args.dyy, args.fs, args.wscale, args.out_scale = consts
     for i in range(geom.ngp_1d):             # phi''(xi_ig) from the rule's own (truncated) abscissae, as the reference's tables
         for j in range(geom.deg + 1):
             args.d2basis[i][j] = geom.d2basis[i, j]
-    mesh = _prepare_elem2d(op, geom, args, keep, B, u.device, bc2, vals, f, f_gp, want_sum, in_scale, "u's")
+    mesh = _prepare_elem(op, geom, args, keep, B, u.device, bc2, vals, f, f_gp, want_sum, in_scale, "u's")
     return mesh, args, keep, shape
 
 
@@ -2266,10 +2166,10 @@ def strongform_apply(geom, u, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=None, 
     fg = 0.0 if f_gp is None else f_gp
     consts = (*coef, float(wscale), float(out_scale))
     key = _strongform_key(geom, u, bc2, vals, f, fg, consts, in_scale, (want_grad, want_sum))
-    ent = _elem2d_entry(_STRONGFORM, key, _prepare_strongform, (geom, u, bc2, vals, f, fg, consts, in_scale, want_sum))
+    ent = _op_entry(_STRONGFORM, key, _prepare_strongform, (geom, u, bc2, vals, f, fg, consts, in_scale, want_sum))
     grad = torch.empty(ent[4], dtype=torch.float32, device=u.device) if want_grad else None
     sums = torch.empty(1, dtype=torch.float64, device=u.device) if want_sum else None
-    _elem2d_launch(_STRONGFORM, ent, u, _strongform_patch, (grad.data_ptr() if want_grad else None, sums.data_ptr() if want_sum else None))
+    _op_launch(_STRONGFORM, ent, u, _strongform_patch, (grad.data_ptr() if want_grad else None, sums.data_ptr() if want_sum else None))
     return grad, sums
 
 
@@ -2284,7 +2184,7 @@ def _fosls_key(geom, flds, packed, nu, bc2, vals, f, f_gp, consts, in_scale, fla
         if k is None or k == 0 or k[1] != torch.float32 or tuple(k[2][1:]) != ((3 if packed else 1), *geom.node_shape):
             return None
         parts.append(k)
-    return _elem2d_key(parts, bc2, (*vals, f_gp, nu), (f, in_scale))
+    return _elem_key(parts, bc2, (*vals, f_gp, nu), (f, in_scale))
 
 
 def _prepare_fosls(geom, flds, packed, nu, bc2, vals, f, f_gp, consts, in_scale, want_sum):
@@ -2317,11 +2217,11 @@ def _prepare_fosls(geom, flds, packed, nu, bc2, vals, f, f_gp, consts, in_scale,
         args.field_stride = nn
     dev = keep[0].device
     if isinstance(nu, torch.Tensor) and nu.numel() > 1:
-        _elem2d_field(op, geom, args, keep, B, nu, "nu", "nu")
+        _elem_field(op, geom, args, keep, B, nu, "nu", "nu")
     else:
         args.nu_value = float(nu)
     args.wq, args.wd, args.fs, args.wscale, args.out_scale = consts
-    mesh = _prepare_elem2d(op, geom, args, keep, B, dev, bc2, vals, f, f_gp, want_sum, in_scale, "the fields'")
+    mesh = _prepare_elem(op, geom, args, keep, B, dev, bc2, vals, f, f_gp, want_sum, in_scale, "the fields'")
     return mesh, args, keep, B
 
 
@@ -2364,7 +2264,7 @@ def fosls_apply(geom, u=None, mx=None, my=None, nu=None, bc=None, bc_values=(0.0
     consts = (*weights, float(fs), float(wscale), float(out_scale))
     flds = (fields,) if packed else (u, mx, my)
     key = _fosls_key(geom, flds, packed, nuv, bc2, vals, f, fg, consts, in_scale, (want3, want_sum))
-    ent = _elem2d_entry(_FOSLS, key, _prepare_fosls, (geom, flds, packed, nuv, bc2, vals, f, fg, consts, in_scale, want_sum))
+    ent = _op_entry(_FOSLS, key, _prepare_fosls, (geom, flds, packed, nuv, bc2, vals, f, fg, consts, in_scale, want_sum))
     B = ent[4]
     dev = flds[0].device
     nn = geom.nnode_total
@@ -2379,14 +2279,14 @@ def fosls_apply(geom, u=None, mx=None, my=None, nu=None, bc=None, bc_values=(0.0
         if not any(want3):
             grads = None
     sums = torch.empty(1, dtype=torch.float64, device=dev) if want_sum else None
-    _elem2d_launch(_FOSLS, ent, flds[0], _fosls_patch, (ptrs, gstride, sums.data_ptr() if want_sum else None))
+    _op_launch(_FOSLS, ent, flds[0], _fosls_patch, (ptrs, gstride, sums.data_ptr() if want_sum else None))
     return grads, sums
 
 
 # ---- the fused 2-D Helmholtz energy and weak-form residual: dn_helmholtz_apply ---------------------------------------------------
 def _helmholtz_key(geom, u, nu, sigma, bc2, vals, f, f_gp, consts, flags):
-    parts = _elem2d_u_key(geom, u, consts, flags)
-    return parts and _elem2d_key(parts, bc2, (*vals, f_gp, sigma), (nu, f))
+    parts = _elem_u_key(geom, u, consts, flags)
+    return parts and _elem_key(parts, bc2, (*vals, f_gp, sigma), (nu, f))
 
 
 def _prepare_helmholtz(geom, u, nu, sigma, bc2, vals, f, f_gp, consts, want_sums):
@@ -2394,15 +2294,15 @@ def _prepare_helmholtz(geom, u, nu, sigma, bc2, vals, f, f_gp, consts, want_sums
     op = _HELMHOLTZ
     _elem2d_check_mesh(op, geom)
     args, keep = DnHelmholtzArgs(), []
-    u, B, shape = _elem2d_u(op, geom, u, args, keep)
+    u, B, shape = _elem_u(op, geom, u, args, keep)
     if nu is not None:
-        _elem2d_field(op, geom, args, keep, B, nu, "nu", "nu")
+        _elem_field(op, geom, args, keep, B, nu, "nu", "nu")
     if isinstance(sigma, torch.Tensor) and sigma.numel() > 1:
-        _elem2d_field(op, geom, args, keep, B, sigma, "sigma", "sigma")
+        _elem_field(op, geom, args, keep, B, sigma, "sigma", "sigma")
     else:
         args.sigma_value = float(sigma)
     args.c, args.cr, args.fs, args.alpha, args.gamma, args.beta, args.wscale, args.out_scale = consts
-    mesh = _prepare_elem2d(op, geom, args, keep, B, u.device, bc2, vals, f, f_gp, want_sums)
+    mesh = _prepare_elem(op, geom, args, keep, B, u.device, bc2, vals, f, f_gp, want_sums)
     return mesh, args, keep, shape
 
 
@@ -2435,36 +2335,48 @@ def helmholtz_apply(geom, u, nu=None, sigma=0.0, bc=None, bc_values=(0.0, 0.0), 
     consts = (*energy_coef, *out_coef, float(wscale), float(out_scale))
     want_sums = want_energy or want_sumsq
     key = _helmholtz_key(geom, u, nu, sigma, bc2, vals, f, fg, consts, (want_out, want_sums))
-    ent = _elem2d_entry(_HELMHOLTZ, key, _prepare_helmholtz, (geom, u, nu, sigma, bc2, vals, f, fg, consts, want_sums))
+    ent = _op_entry(_HELMHOLTZ, key, _prepare_helmholtz, (geom, u, nu, sigma, bc2, vals, f, fg, consts, want_sums))
     out = torch.empty(ent[4], dtype=torch.float32, device=u.device) if want_out else None
     sums = torch.empty(2, dtype=torch.float64, device=u.device) if want_sums else None
-    _elem2d_launch(_HELMHOLTZ, ent, u, _helmholtz_patch, (out.data_ptr() if want_out else None, sums.data_ptr() if want_energy else None,
+    _op_launch(_HELMHOLTZ, ent, u, _helmholtz_patch, (out.data_ptr() if want_out else None, sums.data_ptr() if want_energy else None,
                                                           sums.data_ptr() + 8 if want_sumsq else None))
     return out, (sums[0:1] if want_energy else None), (sums[1:2] if want_sumsq else None)
 
 
-# ---- the fused 2-D eikonal weak-form residual and its VJP: dn_eikonal_apply --------------------------------------------------------
+# ---- the fused eikonal weak-form residual and its VJP: dn_eikonal_apply (2-D Q_P meshes) and dn_eikonal3d_apply (3-D Q1 meshes) --------
+# One argument struct (DnEikonalArgs) and one host path; what differs is the operator object and its mesh check.
+_EIKONAL = _FusedOp("eikonal_apply", DnEikonalArgs)
+_EIKONAL3D = _FusedOp("eikonal3d_apply", DnEikonalArgs)
+
+
+def _eikonal3d_check_mesh(op, geom):
+    if geom.nsd != 3:
+        raise DiffNetHipError(f"{op.name}: 3-D meshes only (nsd {geom.nsd}); 2-D meshes: eikonal_apply")
+    if geom.deg != 1 or not 2 <= geom.ngp_1d <= 4:
+        raise DiffNetHipError(f"{op.name}: 3-D Q1 meshes with 2..4 Gauss points per axis only (degree {geom.deg}, ngp {geom.ngp_1d}); "
+                              "any degree: eikonal.eikonal_residual_composed")
+
 
 def _eikonal_key(geom, u, bc2, vals, f, f_gp, consts, cot, in_num, in_den, flags):
-    parts = _elem2d_u_key(geom, u, consts, flags)
+    parts = _elem_u_key(geom, u, consts, flags)
     if not parts:
         return None
     for t in (in_num, in_den):
         k = _tkey(t)
         if k is None or (k != 0 and k[2] != (1,)):
             return None
-    return _elem2d_key(parts, bc2, (*vals, f_gp), (f, cot, in_num, in_den))
+    return _elem_key(parts, bc2, (*vals, f_gp), (f, cot, in_num, in_den))
 
 
-def _prepare_eikonal(geom, u, bc2, vals, f, f_gp, consts, cot, in_num, in_den, want_sums):
-    """Validation + argument struct of a dn_eikonal_apply call, outputs left unset: (mesh, args, tensors to keep alive, field shape)."""
-    op = _EIKONAL
-    _elem2d_check_mesh(op, geom)
+def _prepare_eikonal(op, check_mesh, geom, u, bc2, vals, f, f_gp, consts, cot, in_num, in_den, want_sums):
+    """Validation + argument struct of a call of either eikonal operator, outputs left unset: (mesh, args, tensors to keep alive, field
+    shape)."""
+    check_mesh(op, geom)
     args, keep = DnEikonalArgs(), []
-    u, B, shape = _elem2d_u(op, geom, u, args, keep)
+    u, B, shape = _elem_u(op, geom, u, args, keep)
     args.tau, args.sq, args.wscale = consts
     if cot is not None:
-        cot = _require(cot, "cot", 4)
+        cot = _require(cot, "cot", 2 + geom.nsd)
         if tuple(cot.shape) != shape or cot.device != u.device:
             raise ValueError(f"{op.name}: cotangent shape {tuple(cot.shape)} != {shape} (on u's device)")
         args.vjp, args.cot = 1, cot.data_ptr()
@@ -2477,12 +2389,34 @@ def _prepare_eikonal(geom, u, bc2, vals, f, f_gp, consts, cot, in_num, in_den, w
             raise ValueError(f"{op.name}: {what} must hold one float on u's device")
         setattr(args, what, t.data_ptr())
         keep.append(t)
-    mesh = _prepare_elem2d(op, geom, args, keep, B, u.device, bc2, vals, f, f_gp, want_sums)
+    mesh = _prepare_elem(op, geom, args, keep, B, u.device, bc2, vals, f, f_gp, want_sums)
     return mesh, args, keep, shape
 
 
-def _eikonal_patch(args, ptrs):
-    args.out, args.sumsq, args.norm = ptrs
+def _eikonal_call(op, check_mesh, geom, u, bc, bc_values, f, f_gp, tau, sq, wscale, cot, in_num, in_den, want_out, want_sumsq, want_norm):
+    """The body of eikonal_apply and eikonal3d_apply."""
+    check_mesh(op, geom)
+    bc2, vals = transport_bc2(bc), tuple(bc_values)
+    if len(vals) != 2:
+        raise ValueError(f"{op.name}: bc_values must hold two entries")
+    if not (want_out or want_sumsq or want_norm):
+        raise ValueError(f"{op.name}: nothing to compute (want_out, want_sumsq and want_norm are all off)")
+    if cot is None and (in_num is not None or in_den is not None):
+        raise ValueError(f"{op.name}: in_num / in_den scale the cotangent of a VJP launch (cot is None)")
+    if in_den is not None and in_num is None:
+        raise ValueError(f"{op.name}: in_den needs in_num")
+    fg = 1.0 if f_gp is None else f_gp
+    tau = float(tau)
+    consts = (tau, 1.0 + tau if sq is None else float(sq), float(wscale))
+    want_sums = want_sumsq or want_norm
+    key = _eikonal_key(geom, u, bc2, vals, f, fg, consts, cot, in_num, in_den, (want_out, want_sums))
+    ent = _op_entry(op, key, _prepare_eikonal, (op, check_mesh, geom, u, bc2, vals, f, fg, consts, cot, in_num, in_den, want_sums))
+    out = torch.empty(ent[4], dtype=torch.float32, device=u.device) if want_out else None
+    ss = torch.empty(1, dtype=torch.float64, device=u.device) if want_sumsq else None
+    nrm = torch.empty(1, dtype=torch.float32, device=u.device) if want_norm else None
+    _op_launch(op, ent, u, _patch_out_sumsq_norm, (out.data_ptr() if want_out else None, ss.data_ptr() if want_sumsq else None,
+                                                  nrm.data_ptr() if want_norm else None))
+    return out, ss, nrm
 
 
 def eikonal_apply(geom, u, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=1.0, tau=0.0, sq=None, wscale=1.0, cot=None, in_num=None, in_den=None,
@@ -2496,138 +2430,8 @@ def eikonal_apply(geom, u, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=1.0, tau=
     (B | 1, G, nely, nelx).  Degree 1..3.  Returns (out | None, sumsq | None, norm | None): the sum of out^2 as a float64 device tensor
     (1,), its square root as a float32 one.  Calls on the same buffers reuse their prepared argument structs (small LRU, fresh outputs
     per call: see poisson_apply)."""
-    _elem2d_check_mesh(_EIKONAL, geom)
-    bc2, vals = transport_bc2(bc), tuple(bc_values)
-    if len(vals) != 2:
-        raise ValueError("eikonal_apply: bc_values must hold two entries")
-    if not (want_out or want_sumsq or want_norm):
-        raise ValueError("eikonal_apply: nothing to compute (want_out, want_sumsq and want_norm are all off)")
-    if cot is None and (in_num is not None or in_den is not None):
-        raise ValueError("eikonal_apply: in_num / in_den scale the cotangent of a VJP launch (cot is None)")
-    if in_den is not None and in_num is None:
-        raise ValueError("eikonal_apply: in_den needs in_num")
-    fg = 1.0 if f_gp is None else f_gp
-    tau = float(tau)
-    consts = (tau, 1.0 + tau if sq is None else float(sq), float(wscale))
-    want_sums = want_sumsq or want_norm
-    key = _eikonal_key(geom, u, bc2, vals, f, fg, consts, cot, in_num, in_den, (want_out, want_sums))
-    ent = _elem2d_entry(_EIKONAL, key, _prepare_eikonal, (geom, u, bc2, vals, f, fg, consts, cot, in_num, in_den, want_sums))
-    out = torch.empty(ent[4], dtype=torch.float32, device=u.device) if want_out else None
-    ss = torch.empty(1, dtype=torch.float64, device=u.device) if want_sumsq else None
-    nrm = torch.empty(1, dtype=torch.float32, device=u.device) if want_norm else None
-    _elem2d_launch(_EIKONAL, ent, u, _eikonal_patch, (out.data_ptr() if want_out else None, ss.data_ptr() if want_sumsq else None,
-                                                      nrm.data_ptr() if want_norm else None))
-    return out, ss, nrm
-
-
-# ---- the fused 3-D eikonal weak-form residual and its VJP: dn_eikonal3d_apply ----------------------------------------------------
-
-def _eikonal3d_check_mesh(geom):
-    if geom.nsd != 3:
-        raise DiffNetHipError(f"eikonal3d_apply: 3-D meshes only (nsd {geom.nsd}); 2-D meshes: eikonal_apply")
-    if geom.deg != 1 or not 2 <= geom.ngp_1d <= 4:
-        raise DiffNetHipError(f"eikonal3d_apply: 3-D Q1 meshes with 2..4 Gauss points per axis only (degree {geom.deg}, ngp {geom.ngp_1d}); "
-                              "any degree: eikonal.eikonal_residual_composed")
-
-
-def _eikonal3d_workspace(mesh, B, dev):
-    """The operator's own reduction workspace on the current stream of `dev`, large enough for `mesh` under the launch plan in force."""
-    op = _EIKONAL3D
-    key = (mesh.nx, mesh.ny, mesh.nz, mesh.ngp, B)
-    nbytes = op.ws_bytes.get(key)
-    if nbytes is None:
-        nbytes = getattr(_lib.lib(), op.ws_fn)(C.byref(mesh))
-        if nbytes < 0:
-            _lib.check(int(nbytes), op.ws_fn)
-        op.ws_bytes[key] = nbytes
-    key = (dev.index, _raw_stream(dev))
-    with _WS_LOCK:
-        ws = op.ws.get(key)
-        if ws is None or ws.numel() < nbytes:
-            ws = torch.zeros(max(nbytes, 1 << 16), dtype=torch.uint8, device=dev)   # ABI: zero-filled once
-            op.ws[key] = ws
-    return ws
-
-
-def _eikonal3d_field(geom, args, keep, B, t, what, member, fp32=True):
-    """A nodal field (B | 1, ., nz, ny, nx) into args.<member> and args.<member>_batched."""
-    nn = geom.nnode_total
-    if fp32:
-        t = _require(t, what)
-    if tuple(t.shape[-3:]) != tuple(geom.node_shape) or t.numel() not in (B * nn, nn):
-        raise ValueError(f"eikonal3d_apply: {what} shape {tuple(t.shape)} does not match the mesh {(B, 1, *geom.node_shape)}")
-    setattr(args, member + "_batched", 1 if (t.numel() == B * nn and B > 1) else 0)
-    setattr(args, member, t.data_ptr())
-    keep.append(t)
-
-
-def _prepare_eikonal3d(geom, u, bc2, vals, f, f_gp, consts, cot, in_num, in_den, want_sums):
-    """Validation + argument struct of a dn_eikonal3d_apply call, outputs left unset: (mesh, args, tensors to keep alive, field shape)."""
-    name = "eikonal3d_apply"
-    _eikonal3d_check_mesh(geom)
-    args, keep = DnEikonalArgs(), []
-    u = _require(u, "u", 5)
-    B = u.shape[0]
-    shape = (B, 1, *geom.node_shape)
-    if tuple(u.shape) != shape:
-        raise ValueError(f"{name}: field shape {tuple(u.shape)} != {shape}")
-    keep.append(u)
-    args.u = u.data_ptr()
-    args.tau, args.sq, args.wscale = consts
-    if cot is not None:
-        cot = _require(cot, "cot", 5)
-        if tuple(cot.shape) != shape or cot.device != u.device:
-            raise ValueError(f"{name}: cotangent shape {tuple(cot.shape)} != {shape} (on u's device)")
-        args.vjp, args.cot = 1, cot.data_ptr()
-        keep.append(cot)
-    for what, t in (("in_num", in_num), ("in_den", in_den)):
-        if t is None:
-            continue
-        t = _require(t, what)
-        if t.numel() != 1 or t.device != u.device:
-            raise ValueError(f"{name}: {what} must hold one float on u's device")
-        setattr(args, what, t.data_ptr())
-        keep.append(t)
-    for k, m in enumerate(bc2):
-        if m is None:
-            continue
-        if not isinstance(m, torch.Tensor):
-            raise TypeError(f"{name}: bc[{k}] must be a tensor or None (expand a PackedMask / BoxFaces to its image)")
-        if not m.is_cuda:
-            raise DiffNetHipError(f"{name}: bc[{k}] is on {m.device}: the FEM ops run on the GPU only (no CPU fallback)")
-        byte = m.dtype in (torch.bool, torch.uint8)
-        if byte:
-            m = m.contiguous()
-            m = m.view(torch.uint8) if m.dtype == torch.bool else m
-        args.bc[k].mask_kind = _lib.MASK_U8 if byte else _lib.MASK_F32
-        _eikonal3d_field(geom, args.bc[k], keep, B, m, f"bc[{k}]", "mask", fp32=not byte)
-    for k, val in enumerate(vals):
-        if isinstance(val, torch.Tensor) and val.numel() > 1:
-            if bc2[k] is None:
-                raise ValueError(f"{name}: bc_values[{k}] is a field but condition {k} has no mask")
-            _eikonal3d_field(geom, args.bc[k], keep, B, val, f"bc_values[{k}]", "field")
-        else:
-            args.bc[k].value = float(val)
-    G, nel = geom.ngp_total, geom.nelem_total
-    if f is not None:
-        if isinstance(f_gp, torch.Tensor) and f_gp.numel() > 1:
-            raise ValueError(f"{name}: nodal forcing f and Gauss-point forcing f_gp exclude each other")
-        _eikonal3d_field(geom, args, keep, B, f, "f", "f")
-    elif isinstance(f_gp, torch.Tensor) and f_gp.numel() > 1:
-        f_gp = _require(f_gp, "f_gp")
-        if tuple(f_gp.shape[-4:]) != (G, *geom.elem_shape) or f_gp.numel() not in (G * nel, B * G * nel):
-            raise ValueError(f"{name}: f_gp shape {tuple(f_gp.shape)} is not (B | 1, {G}, {', '.join(str(n) for n in geom.elem_shape)})")
-        args.f_batched = 1 if (f_gp.numel() == B * G * nel and B > 1) else 0
-        args.f_gp = f_gp.data_ptr()
-        keep.append(f_gp)
-    else:
-        args.f_value = float(f_gp)
-    mesh = geom.mesh_struct(B)
-    if want_sums:
-        ws = _eikonal3d_workspace(mesh, B, u.device)
-        keep.append(ws)
-        args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
-    return mesh, args, keep, shape
+    return _eikonal_call(_EIKONAL, _elem2d_check_mesh, geom, u, bc, bc_values, f, f_gp, tau, sq, wscale, cot, in_num, in_den, want_out,
+                         want_sumsq, want_norm)
 
 
 def eikonal3d_apply(geom, u, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=1.0, tau=0.0, sq=None, wscale=1.0, cot=None, in_num=None, in_den=None,
@@ -2642,28 +2446,8 @@ def eikonal3d_apply(geom, u, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=1.0, ta
     (B | 1, G, nelz, nely, nelx) in the order of `gauss_pt_evaluation`.  Returns (out | None, sumsq | None, norm | None): the sum of
     out^2 as a float64 device tensor (1,), its square root as a float32 one.  Calls on the same buffers reuse their prepared argument
     structs; the reduction workspace is the operator's own, one per stream."""
-    _eikonal3d_check_mesh(geom)
-    bc2, vals = transport_bc2(bc), tuple(bc_values)
-    if len(vals) != 2:
-        raise ValueError("eikonal3d_apply: bc_values must hold two entries")
-    if not (want_out or want_sumsq or want_norm):
-        raise ValueError("eikonal3d_apply: nothing to compute (want_out, want_sumsq and want_norm are all off)")
-    if cot is None and (in_num is not None or in_den is not None):
-        raise ValueError("eikonal3d_apply: in_num / in_den scale the cotangent of a VJP launch (cot is None)")
-    if in_den is not None and in_num is None:
-        raise ValueError("eikonal3d_apply: in_den needs in_num")
-    fg = 1.0 if f_gp is None else f_gp
-    tau = float(tau)
-    consts = (tau, 1.0 + tau if sq is None else float(sq), float(wscale))
-    want_sums = want_sumsq or want_norm
-    key = _eikonal_key(geom, u, bc2, vals, f, fg, consts, cot, in_num, in_den, (want_out, want_sums))
-    ent = _elem2d_entry(_EIKONAL3D, key, _prepare_eikonal3d, (geom, u, bc2, vals, f, fg, consts, cot, in_num, in_den, want_sums))
-    out = torch.empty(ent[4], dtype=torch.float32, device=u.device) if want_out else None
-    ss = torch.empty(1, dtype=torch.float64, device=u.device) if want_sumsq else None
-    nrm = torch.empty(1, dtype=torch.float32, device=u.device) if want_norm else None
-    _elem2d_launch(_EIKONAL3D, ent, u, _eikonal_patch, (out.data_ptr() if want_out else None, ss.data_ptr() if want_sumsq else None,
-                                                        nrm.data_ptr() if want_norm else None))
-    return out, ss, nrm
+    return _eikonal_call(_EIKONAL3D, _eikonal3d_check_mesh, geom, u, bc, bc_values, f, f_gp, tau, sq, wscale, cot, in_num, in_den, want_out,
+                         want_sumsq, want_norm)
 
 
 def compute_winding_nodes(points, normals, area, q):
