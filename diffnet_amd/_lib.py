@@ -128,6 +128,17 @@ class DnCoefGradArgs(C.Structure):
                 ("in_scale", C.c_void_p), ("g_nu", C.c_void_p), ("g_f", C.c_void_p)]
 
 
+class DnFdmPoissonArgs(C.Structure):
+    _fields_ = [("B", C.c_int32), ("ny", C.c_int32), ("nx", C.c_int32),
+                ("u", C.c_void_p), ("nu", C.c_void_p), ("f", C.c_void_p), ("nu_batched", C.c_int32), ("f_batched", C.c_int32),
+                ("nu_value", C.c_float), ("f_value", C.c_float), ("fs", C.c_float),
+                ("bc", DnDirichlet * 2),
+                ("kx", C.c_float * 9), ("ky", C.c_float * 9), ("kxx", C.c_float * 9), ("kyy", C.c_float * 9),
+                ("out_scale", C.c_float), ("nbc_scale", C.c_float),
+                ("in_scale", C.c_void_p), ("res", C.c_void_p), ("sums", C.c_void_p), ("grad", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 I32x3 = C.c_int32 * 3
 
 # name -> (restype, argtypes); must list every symbol of include/diffnet_hip.h
@@ -178,6 +189,8 @@ SYMBOLS = {
     "dn_eikonal3d_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
     "dn_eikonal3d_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnEikonalArgs), C.c_void_p]),
     "dn_poisson_coef_grad": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnCoefGradArgs), C.c_void_p]),
+    "dn_fdm_poisson_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "dn_fdm_poisson_apply": (C.c_int, [C.POINTER(DnFdmPoissonArgs), C.c_void_p]),
     "dn_upconv_out_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "dn_upconv_out_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                     C.c_void_p, C.c_int64, C.c_void_p]),

@@ -94,6 +94,34 @@ class _StencilFused(torch.autograd.Function):
         return gu, None, None, None, None
 
 
+def _bc_pair(bc):
+    """The conditions of a loss call as a pair of masks: none, one mask, or up to two in a sequence (either may be None)."""
+    if bc is None:
+        return (None, None)
+    if isinstance(bc, torch.Tensor):
+        return (bc, None)
+    bc = tuple(bc)
+    if len(bc) > 2:
+        raise ValueError(f"poisson_residual_loss: at most two conditions (got {len(bc)})")
+    return bc + (None,) * (2 - len(bc))
+
+
+class _PoissonResidualLoss(torch.autograd.Function):
+    """DiffNetFDM.poisson_residual_loss: the fused loss; its gradient with respect to u is taken in the forward, by the same launch."""
+
+    @staticmethod
+    def forward(ctx, u, fdm, nu, f, bc, bc_values, norm, fs, neumann):
+        loss, grad = fdm._poisson_loss_and_grad(u, nu, f, bc, bc_values, norm, fs, neumann, want_grad=ctx.needs_input_grad[0])
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, go):
+        grad, = ctx.saved_tensors
+        return (grad * go,) + (None,) * 8
+
+
 class DiffNetFDM(PDE):
     def __init__(self, network, dataset=None, **kwargs):
         super().__init__(network, dataset, **kwargs)
@@ -140,6 +168,73 @@ class DiffNetFDM(PDE):
 
     def dyy(self, u):
         return _StencilFused.apply(u, self._k["yy"], 1, 0.0, 1.0)
+
+    # fused loss level (new): the whole residual loss of the reference's FDM scripts and its gradient (dn_fdm_poisson_apply)
+    def _loss_kernels(self):
+        return self._k["x"], self._k["y"], self._k["xx"], self._k["yy"]
+
+    def _poisson_loss_and_grad(self, u, nu, f, bc, bc_values, norm, fs, neumann, want_grad=True):
+        from . import ops
+        if norm not in ("mean_sq", "l2"):
+            raise ValueError(f"poisson_residual_loss: norm must be 'mean_sq' or 'l2' (the scripts keep their L1 term commented out), got {norm!r}")
+        B, _, ny, nx = u.shape
+        nin, neumann = (ny - 2) * (nx - 2), float(neumann)
+        common = dict(nu=nu, f=f, bc=_bc_pair(bc), bc_values=bc_values, kernels=self._loss_kernels(), fs=fs)
+        if norm == "mean_sq":                # mean(res^2) + neumann * mean_x(down^2 + up^2), averaged over the samples: one launch
+            grad, s, _ = ops.fdm_poisson_apply(u, out_scale=1.0 / (B * nin), nbc_scale=neumann * nin / nx, want_grad=want_grad, **common)
+            loss = s[:, 0].sum() / (B * nin)
+        else:                                # mean over the samples of ||res_b||_2: the sums first, the gradient from them
+            _, s, _ = ops.fdm_poisson_apply(u, want_grad=False, **common)
+            nrm = torch.sqrt(s[:, 0])
+            loss = nrm.mean()
+            grad = None
+            if want_grad:                    # d||r|| / du = d(sum r^2) / du / (2 ||r||); torch's convention at ||r|| == 0: zero
+                half_inv = torch.where(nrm > 0, 0.5 / nrm, torch.zeros_like(nrm)).float()
+                grad, _, _ = ops.fdm_poisson_apply(u, out_scale=1.0 / B, nbc_scale=neumann / nx, in_scale=half_inv, want_sums=False, **common)
+        if neumann != 0.0:
+            loss = loss + neumann * (s[:, 1] + s[:, 2]).sum() / (B * nx)
+        return loss.float(), grad
+
+    def poisson_residual_loss_and_grad(self, u, nu, f=None, bc=(), bc_values=(0.0, 0.0), norm="mean_sq", fs=1.0, neumann=0.0):
+        """(loss, dloss/du) of the finite-difference Poisson residual loss, fused (ops.fdm_poisson_apply): with u~ the field after the
+        conditions `bc` (none, one or two masks; u~ takes `bc_values[k]` under condition k, condition 2 wins) and the class's kernels,
+            res = fs f + conv2d(u~, sobelx) conv2d(nu, sobelx) + conv2d(u~, sobely) conv2d(nu, sobely)
+                  + nu[1:-1, 1:-1] (conv2d(u~, sobelxx) + conv2d(u~, sobelyy))
+            norm "mean_sq":  mean(res^2)                      -- 12_klsum_fdm.py (its loss(...).mean()), one launch
+            norm "l2":       mean over the samples of ||res_b||_2   -- 12_fdm_mms.py, two launches
+            neumann c != 0:  + c * mean over samples and x of (u~[0] - u~[1])^2 + (u~[-1] - u~[-2])^2
+        "mean_sq" with neumann = 0.1 is 12_klsum_fdm_nbc.py at B = 1: that script adds a (B, 1) Neumann term to a (B, N-2, N-2) residual,
+        a broadcast that exists only for B = 1; for B > 1 this method averages the per-sample losses.  `nu`: tensor (B | 1,1,ny,nx),
+        float or None (1); `f`: likewise (None: no forcing).  The loss is a float32 scalar on u's device."""
+        return self._poisson_loss_and_grad(u, nu, f, bc, bc_values, norm, fs, neumann)
+
+    def poisson_residual_loss(self, u, nu, f=None, bc=(), bc_values=(0.0, 0.0), norm="mean_sq", fs=1.0, neumann=0.0):
+        """The loss of `poisson_residual_loss_and_grad`, differentiable with respect to u: `loss.backward()` works (the gradient is
+        taken by the same launch as the loss, or by the second one of norm "l2", when u requires it)."""
+        return _PoissonResidualLoss.apply(u, self, nu, f, bc, bc_values, norm, fs, neumann)
+
+    def composed_poisson_residual_loss(self, u, nu, f=None, bc=(), bc_values=(0.0, 0.0), norm="mean_sq", fs=1.0, neumann=0.0):
+        """The same loss from torch's own operators, as the reference's scripts compose it (torch.where, six conv2d calls, elementwise
+        passes, autograd): any device, differentiable with respect to every tensor input.  The twin the fused loss is compared with."""
+        conv = nn.functional.conv2d
+        if not isinstance(nu, torch.Tensor):
+            nu = torch.full_like(u[:1], 1.0 if nu is None else float(nu))
+        if norm not in ("mean_sq", "l2"):
+            raise ValueError(f"composed_poisson_residual_loss: norm must be 'mean_sq' or 'l2', got {norm!r}")
+        for m, v in zip(_bc_pair(bc), bc_values):
+            if m is not None:
+                cond = m > 0.5 if m.dtype.is_floating_point else m.bool()
+                u = torch.where(cond, v if isinstance(v, torch.Tensor) else u * 0.0 + float(v), u)
+        lap = conv(u, self.sobelxx) + conv(u, self.sobelyy)
+        res = conv(u, self.sobelx) * conv(nu, self.sobelx) + conv(u, self.sobely) * conv(nu, self.sobely) + nu[:, :, 1:-1, 1:-1] * lap
+        if f is not None:
+            res = fs * (f[:, :, 1:-1, 1:-1] if isinstance(f, torch.Tensor) else float(f)) + res
+        res = res.reshape(u.shape[0], -1)
+        loss = (res ** 2).mean() if norm == "mean_sq" else torch.norm(res, p=2, dim=1).mean()
+        if float(neumann) != 0.0:
+            nbc = (u[:, :, 0, :] - u[:, :, 1, :]) ** 2 + (u[:, :, -1, :] - u[:, :, -2, :]) ** 2
+            loss = loss + float(neumann) * nbc.mean()
+        return loss
 
     def derivative_z(self, g):
         raise NotImplementedError("the reference class is hard-wired to nsd = 2 (DiffNetFDM.py:128); z-derivatives are unreachable there")

@@ -11,7 +11,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import DnCoefGradArgs, DnDirichlet, DnEikonalArgs, DnFoslsArgs, DnFsdtArgs, DnHelmholtzArgs, DnMesh, DnNsArgs, DnPoissonArgs, DnStokesArgs, DnStrongformArgs, DnTransportArgs, I32x3, DiffNetHipError
+from ._lib import DnCoefGradArgs, DnDirichlet, DnEikonalArgs, DnFdmPoissonArgs, DnFoslsArgs, DnFsdtArgs, DnHelmholtzArgs, DnMesh, DnNsArgs, DnPoissonArgs, DnStokesArgs, DnStrongformArgs, DnTransportArgs, I32x3, DiffNetHipError
 
 
 def _require(t, name, ndim=None, strict=False):
@@ -1560,8 +1560,9 @@ _FUSED_OPS = []
 
 
 class _FusedOp:
-    def __init__(self, name, args_type):
+    def __init__(self, name, args_type, meshless=False):
         self.name, self.args_type = name, args_type          # name: "stokes_apply", "ns_apply", ...: the prefix of its messages
+        self.meshless = meshless           # the C entry points take no dn_mesh (a finite-difference grid: B, ny, nx in the arguments)
         self.fn, self.ws_fn = "dn_" + name, "dn_" + name.replace("_apply", "_workspace_bytes")      # the C entry points
         self.ws = {}
         self.ws_bytes = {}
@@ -1576,7 +1577,8 @@ def _op_workspace(op, mesh, B, dev):
     key = (mesh.nx, mesh.ny, mesh.nz, mesh.degree, mesh.ngp, B)
     nbytes = op.ws_bytes.get(key)
     if nbytes is None:
-        nbytes = getattr(_lib.lib(), op.ws_fn)(C.byref(mesh))
+        ws_fn = getattr(_lib.lib(), op.ws_fn)
+        nbytes = ws_fn(B, mesh.ny, mesh.nx) if op.meshless else ws_fn(C.byref(mesh))
         if nbytes < 0:
             _lib.check(int(nbytes), op.ws_fn)
         op.ws_bytes[key] = nbytes
@@ -1623,7 +1625,7 @@ def _op_launch(op, ent, u, patch, ptrs):
         fn = op.entry = getattr(_lib.lib(), op.fn)
     with op.launch_lock:
         patch(ent[1], ptrs)
-        rc = fn(ent[2], ent[3], _stream(u))
+        rc = fn(ent[3], _stream(u)) if op.meshless else fn(ent[2], ent[3], _stream(u))
     if rc:
         _lib.check(rc, op.fn)
 
@@ -2448,6 +2450,139 @@ def eikonal3d_apply(geom, u, bc=None, bc_values=(0.0, 0.0), f=None, f_gp=1.0, ta
     structs; the reduction workspace is the operator's own, one per stream."""
     return _eikonal_call(_EIKONAL3D, _eikonal3d_check_mesh, geom, u, bc, bc_values, f, f_gp, tau, sq, wscale, cot, in_num, in_den, want_out,
                          want_sumsq, want_norm)
+
+
+# ---- the fused 2-D finite-difference Poisson residual, its sums and its gradient: dn_fdm_poisson_apply --------------------------
+_FDM_POISSON = _FusedOp("fdm_poisson_apply", DnFdmPoissonArgs, meshless=True)
+_FDM_KERNELS = {}
+
+
+class _FdmGrid:
+    """What the shared argument checks ask of a geometry, for a finite-difference grid of ny x nx nodes (it has no element tables)."""
+    nsd = 2
+
+    def __init__(self, ny, nx):
+        self.node_shape, self.nnode_total = (ny, nx), ny * nx
+
+
+def fdm_default_kernels(nx):
+    """(kx, ky, kxx, kyy), nine floats each, row-major: the 'fdm' kernels of get_deriv_kernels for a domain of `nx` nodes -- the values of
+    DiffNetFDM's sobelx / sobely / sobelxx / sobelyy parameters."""
+    ks = _FDM_KERNELS.get(nx)
+    if ks is None:
+        from .fdm import get_deriv_kernels
+        _, kx, ky, _, _, kxx, kyy, _ = get_deriv_kernels(2, "fdm", 3, nx)
+        ks = _FDM_KERNELS[nx] = tuple(tuple(float(v) for v in k.astype("float32").reshape(-1)) for k in (kx, ky, kxx, kyy))
+    return ks
+
+
+def _fdm_k9(k):
+    if isinstance(k, tuple) and len(k) == 9 and all(type(v) is float for v in k):
+        return k
+    v = torch.as_tensor(k, dtype=torch.float32).reshape(-1).tolist()
+    if len(v) != 9:
+        raise ValueError(f"fdm_poisson_apply: a kernel holds 3 x 3 values, got {len(v)}")
+    return tuple(v)
+
+
+def _fdm_poisson_key(u, nu_t, f_t, bc2, vals, consts, in_scale, flags):
+    if not (isinstance(u, torch.Tensor) and u.is_cuda):
+        return None
+    k = _tkey(u)
+    if k is None or k == 0 or k[1] != torch.float32:
+        return None
+    return _elem_key(["fdm", u.device.index, _raw_stream(u.device), consts, flags, k], bc2, vals, (nu_t, f_t, in_scale))
+
+
+def _prepare_fdm_poisson(u, nu_t, f_t, bc2, vals, consts, in_scale, want_sums):
+    """Validation + argument struct of a dn_fdm_poisson_apply call, outputs left unset: (grid, args, tensors to keep alive, field shape)."""
+    op = _FDM_POISSON
+    args, keep = DnFdmPoissonArgs(), []
+    u = _require(u, "u", 4)
+    B, ch, ny, nx = u.shape
+    if ch != 1 or ny < 3 or nx < 3:
+        raise ValueError(f"{op.name}: u must be (B,1,ny,nx) with ny, nx >= 3, got {tuple(u.shape)}")
+    grid = _FdmGrid(ny, nx)
+    keep.append(u)
+    args.u, args.B, args.ny, args.nx = u.data_ptr(), B, ny, nx
+    ks, args.fs, args.out_scale, args.nbc_scale, args.nu_value, args.f_value = consts
+    args.kx[:], args.ky[:], args.kxx[:], args.kyy[:] = ks
+    if nu_t is not None:
+        _elem_field(op, grid, args, keep, B, nu_t, "nu", "nu")
+    if f_t is not None:
+        _elem_field(op, grid, args, keep, B, f_t, "f", "f")
+    for k, m in enumerate(bc2):
+        if m is None:
+            continue
+        m, byte = _bc_mask(op, m, k)
+        d = args.bc[k]
+        d.mask_kind = _lib.MASK_U8 if byte else _lib.MASK_F32
+        d.mask_batched, d.mask = _nodal_batched(op, grid, B, m, f"bc[{k}]"), m.data_ptr()
+        keep.append(m)
+    for k, val in enumerate(vals):
+        if isinstance(val, torch.Tensor) and val.numel() > 1:
+            if bc2[k] is None:
+                raise ValueError(f"{op.name}: bc_values[{k}] is a field but condition {k} has no mask")
+            _elem_field(op, grid, args.bc[k], keep, B, val, f"bc_values[{k}]", "field")
+        else:
+            args.bc[k].value = float(val)
+    if in_scale is not None:
+        in_scale = _require(in_scale, "in_scale")
+        if in_scale.numel() != B or in_scale.device != u.device:
+            raise ValueError(f"{op.name}: in_scale must hold one float per sample ({B}) on u's device")
+        args.in_scale = in_scale.data_ptr()
+        keep.append(in_scale)
+    mesh = DnMesh()                          # no element tables: only what keys the workspace size
+    mesh.nsd, mesh.batch, mesh.nx, mesh.ny, mesh.nz = 2, B, nx, ny, 1
+    if want_sums:
+        ws = _op_workspace(op, mesh, B, u.device)
+        keep.append(ws)
+        args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    return mesh, args, keep, (B, 1, ny, nx)
+
+
+def _fdm_poisson_patch(args, ptrs):
+    args.grad, args.sums, args.res = ptrs
+
+
+def fdm_poisson_apply(u, nu=None, f=None, bc=None, bc_values=(0.0, 0.0), kernels=None, fs=1.0, out_scale=1.0, nbc_scale=0.0, in_scale=None,
+                      want_res=False, want_grad=True, want_sums=True):
+    """One launch of dn_fdm_poisson_apply (include/diffnet_hip.h) on the field u (B,1,ny,nx) of a finite-difference grid: the residual
+    r = fs f + (kx * u~)(kx * nu) + (ky * u~)(ky * nu) + nu (kxx * u~ + kyy * u~) on the interior, `*` the valid 3x3 correlation of
+    nn.functional.conv2d and u~ the field after the two conditions.  Returns (grad | None, sums | None, res | None):
+    res (B,1,ny-2,nx-2); sums (B,3) float64 per sample: sum r^2, sum_x (u~[0,x] - u~[1,x])^2, sum_x (u~[ny-1,x] - u~[ny-2,x])^2;
+    grad (B,1,ny,nx) = out_scale (in_scale[b] d(sum r^2)/du + nbc_scale d(the two row sums)/du), zero on the Dirichlet nodes
+    (`in_scale`: a float32 device tensor of B, or None for 1).  `nu`: a tensor (B | 1,1,ny,nx), a float, or None for 1; `f`: likewise,
+    None for 0.  `bc`: None, one mask or a pair (either None), fp32 (`> 0.5`) or bool / uint8, per sample or shared; `bc_values[k]`:
+    float or tensor u takes under condition k (where both hold, condition 2's).  `kernels`: (kx, ky, kxx, kyy), 3x3 each, any values;
+    None: the 'fdm' kernels of get_deriv_kernels for nx.  Calls on the same buffers reuse their prepared argument structs (small LRU,
+    fresh outputs per call: see poisson_apply); the reduction workspace is the operator's own, one per stream."""
+    op = _FDM_POISSON
+    bc2, vals = transport_bc2(bc), tuple(bc_values)
+    if len(vals) != 2:
+        raise ValueError("fdm_poisson_apply: bc_values must hold two entries")
+    if not (want_res or want_grad or want_sums):
+        raise ValueError("fdm_poisson_apply: nothing to compute (want_res, want_grad and want_sums are all off)")
+    if not isinstance(u, torch.Tensor) or u.dim() != 4:
+        raise ValueError("fdm_poisson_apply: u must be a tensor (B,1,ny,nx)")
+    if kernels is None:
+        ks = fdm_default_kernels(u.shape[3])
+    else:
+        ks = tuple(_fdm_k9(k) for k in kernels)
+        if len(ks) != 4:
+            raise ValueError("fdm_poisson_apply: kernels holds (kx, ky, kxx, kyy)")
+    nu_t, nu_v = (nu, 0.0) if isinstance(nu, torch.Tensor) else (None, 1.0 if nu is None else float(nu))
+    f_t, f_v = (f, 0.0) if isinstance(f, torch.Tensor) else (None, 0.0 if f is None else float(f))
+    consts = (ks, float(fs), float(out_scale), float(nbc_scale), nu_v, f_v)
+    key = _fdm_poisson_key(u, nu_t, f_t, bc2, vals, consts, in_scale, (want_res, want_grad, want_sums))
+    ent = _op_entry(op, key, _prepare_fdm_poisson, (u, nu_t, f_t, bc2, vals, consts, in_scale, want_sums))
+    B, _, ny, nx = ent[4]
+    grad = torch.empty(ent[4], dtype=torch.float32, device=u.device) if want_grad else None
+    sums = torch.empty((B, 3), dtype=torch.float64, device=u.device) if want_sums else None
+    res = torch.empty((B, 1, ny - 2, nx - 2), dtype=torch.float32, device=u.device) if want_res else None
+    _op_launch(op, ent, u, _fdm_poisson_patch, (grad.data_ptr() if want_grad else None, sums.data_ptr() if want_sums else None,
+                                                res.data_ptr() if want_res else None))
+    return grad, sums, res
 
 
 def compute_winding_nodes(points, normals, area, q):

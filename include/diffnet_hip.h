@@ -744,6 +744,61 @@ typedef struct dn_coef_grad_args {
 } dn_coef_grad_args;
 int dn_poisson_coef_grad(const dn_mesh *mesh, const dn_coef_grad_args *args, void *stream);
 
+/* ---- fused 2-D finite-difference Poisson residual, its sums of squares and its gradient ------------------------------------
+ * Replaces the loss bodies of the three DiffNetFDM scripts of the reference under examples/poisson/single_instance/:
+ * 12_fdm_mms.py:76-118, 12_klsum_fdm.py:69-111 and 12_klsum_fdm_nbc.py:69-158 -- the two Dirichlet substitutions, six valid 3x3
+ * conv2d calls (sobelx / sobely / sobelxx / sobelyy on u, sobelx / sobely on nu), six elementwise passes, the sum of squares or the
+ * L2 norm, the two Neumann row terms of the _nbc script and the autograd backward through all of it, in ONE launch that reads u, nu
+ * and f once.  No dn_mesh: a finite-difference grid has no element geometry, only B samples of ny x nx nodes (x is the fastest axis).
+ *   u~ = u after bc[0] then bc[1] (applied in order, as in dn_strongform_args: where both hold, condition 2's value is used); nu and
+ *   f are taken as they are.  (k * v)_i = sum over the 3x3 neighbourhood of k[dy+1][dx+1] v[y+dy][x+dx]: the VALID CORRELATION, what
+ *   nn.functional.conv2d(v, k) gives; kx, ky, kxx, kyy are passed by value, row-major, and may hold any values (the class's 'fdm'
+ *   weights are only what the Python layer passes by default).  On the interior, (ny-2) x (nx-2) nodes:
+ *   r      = fs f + (kx * u~)(kx * nu) + (ky * u~)(ky * nu) + nu (kxx * u~ + kyy * u~)
+ *   res    (B,1,ny-2,nx-2) = r
+ *   sums   (B,3) float64, per sample (unscaled; fixed-order fp64 reduction in the kernel):
+ *          sum r^2 | sum_x (u~[0,x] - u~[1,x])^2 | sum_x (u~[ny-1,x] - u~[ny-2,x])^2        (nbc_down / nbc_up of 12_klsum_fdm_nbc.py:137-147)
+ *   grad   (B,1,ny,nx) = out_scale ( s_b d(sum r^2)/du + nbc_scale d(sums[b][1] + sums[b][2])/du ),  exactly zero on the Dirichlet nodes;
+ *          s_b = in_scale[b] when that device array of B floats is given, else 1;
+ *          d(sum r^2)/du_j = 2 sum_i r_i ( kx[j-i] (kx * nu)_i + ky[j-i] (ky * nu)_i + nu_i (kxx + kyy)[j-i] ) over the interior nodes i
+ *          within one step of j (the hand-derived pullback: three 3x3 adjoint stencils on three per-node products).
+ * nu: (B | 1,1,ny,nx) or NULL = the constant nu_value; f likewise with f_value.  Conditions: DN_MASK_F32 / DN_MASK_U8 images, shared
+ * or per sample, constant value or value field.  Each of res, sums, grad may be NULL (not all).  sums needs `workspace` (zero-filled
+ * once before first use, dn_fdm_poisson_workspace_bytes = 4160 + 24 ceil(nx / 60) ny B bytes; every call leaves it ready for the
+ * next; one per stream, not shared with other operators).  The mean-of-squares losses of 12_klsum_fdm.py and 12_klsum_fdm_nbc.py take
+ * one launch (out_scale = 1 / (B (ny-2)(nx-2)); nbc_scale = 0.1 (ny-2)(nx-2) / nx); the per-sample L2 norm of 12_fdm_mms.py two: sums
+ * first, then grad with in_scale[b] = 1 / (2 sqrt(sums[b][0])) and out_scale = 1 / B.
+ * A row march for wave64: 60 owner columns and two ghost lanes on either side per wave, x neighbours by cross-lane moves, strips of
+ * node rows with the seams recomputed.  No atomics on the data path: res and grad are bitwise independent of the batch a sample sits
+ * in and of the launch plan ("PLAN_FSDT" "T,R" overrides the plan, as for dn_strongform_apply: T = 64 x waves per workgroup, R node
+ * rows per strip); sums are reproducible for a given shape and plan.  Samples of 2^30 nodes or more are DN_E_UNSUPPORTED.
+ * Out of scope: the replicate-padded and corrected form of DiffNetFDM.derivative_* (dn_fdm_stencil_fwd / dn_fdm_fused_fwd serve it),
+ * gradients with respect to nu and f, the L1 norm the scripts keep commented out, 3-D grids.
+ * DN_E_UNSUPPORTED for DN_MASK_BITS / DN_MASK_BOX conditions (expand them: dn_unpack_mask_bits); DN_E_BADARG for ny < 3 or nx < 3,
+ * B outside 1..65535, a NULL u, no output at all, a value field without its mask, an unknown mask kind or flags outside {0, 1};
+ * DN_E_WORKSPACE for sums without a large enough workspace; nothing is launched then. */
+typedef struct dn_fdm_poisson_args {
+    int32_t B, ny, nx;     /* samples, node rows, nodes per row                         */
+    const float *u;        /* (B,1,ny,nx) nodal field                                   */
+    const float *nu;       /* (B | 1,1,ny,nx) coefficient or NULL (nu_value)            */
+    const float *f;        /* (B | 1,1,ny,nx) forcing or NULL (f_value)                 */
+    int32_t nu_batched;    /* 0: one field for the whole batch                          */
+    int32_t f_batched;
+    float nu_value, f_value;
+    float fs;              /* the forcing coefficient                                   */
+    dn_dirichlet bc[2];    /* applied in order                                          */
+    float kx[9], ky[9], kxx[9], kyy[9];
+    float out_scale, nbc_scale;
+    const float *in_scale; /* optional: B device floats                                 */
+    float *res;            /* (B,1,ny-2,nx-2) or NULL                                   */
+    double *sums;          /* (B,3) device doubles or NULL                              */
+    float *grad;           /* (B,1,ny,nx) or NULL                                       */
+    void *workspace;
+    int64_t workspace_bytes;
+} dn_fdm_poisson_args;
+int64_t dn_fdm_poisson_workspace_bytes(int32_t B, int32_t ny, int32_t nx);
+int dn_fdm_poisson_apply(const dn_fdm_poisson_args *args, void *stream);
+
 /* ---- fused output block of the 2-D U-Net generator ----------------------------------------------------------
  * Upsample(x2, nearest) -> ZeroPad2d((1,0,1,0)) -> Conv2d(C -> 1, 4x4, padding 1, bias) -> Sigmoid
  * (DiffNet/networks/unets.py:68-74, `self.final`) without materialising the upsampled tensor.
