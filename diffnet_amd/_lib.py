@@ -139,6 +139,12 @@ class DnFdmPoissonArgs(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class DnConvK4s2Kernel(C.Structure):
+    _fields_ = [("gen", C.c_int32), ("targ", C.c_int32 * 3), ("nz", C.c_int32), ("per_slice", C.c_int32), ("sum_kernel", C.c_int32)]
+
+
+CONV_DOWN, CONV_UP, CONV_WRW = 0, 1, 2
+
 I32x3 = C.c_int32 * 3
 
 # name -> (restype, argtypes); must list every symbol of include/diffnet_hip.h
@@ -213,6 +219,8 @@ SYMBOLS = {
     "dn_conv3d_k4s2_workspace_bytes": (C.c_int64, [C.c_int32] + [C.c_int64] * 6),
     "dn_conv3d_k4s2_down_ws": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int64] * 6 + [C.c_void_p, C.c_int64, C.c_void_p]),
     "dn_conv3d_k4s2_up_ws": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int64] * 6 + [C.c_void_p, C.c_int64, C.c_void_p]),
+    "dn_conv2d_k4s2_query": (C.c_int, [C.c_int32] + [C.c_int64] * 5 + [C.POINTER(DnConvK4s2Kernel)]),
+    "dn_conv3d_k4s2_query": (C.c_int, [C.c_int32] + [C.c_int64] * 6 + [C.c_int32, C.POINTER(DnConvK4s2Kernel)]),
     "dn_conv2d_valid_fwd": (C.c_int, [C.c_void_p] * 4 + [C.c_int64] * 6 + [C.c_void_p]),
     "dn_conv2d_valid_bwd_data": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] * 6 + [C.c_void_p]),
     "dn_conv2d_valid_bwd_weight": (C.c_int, [C.c_void_p] * 4 + [C.c_int64] * 6 + [C.c_void_p]),

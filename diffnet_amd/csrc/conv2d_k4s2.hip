@@ -24,14 +24,16 @@
 
 namespace dn {
 
-// round 4: raw-row-tile forms (conv2d_k4s2_v2.hip); false = preconditions not met (or "CONV2D_V1" set): run the kernels above
-bool conv2d_down_v2(const float* fine, const float* w, float* coarse, int64_t B, int64_t C, int64_t M, int64_t H, int64_t W, hipStream_t s);
-bool conv2d_up_v2(const float* coarse, const float* w, float* fine, int64_t B, int64_t C, int64_t M, int64_t H, int64_t W, hipStream_t s);
-bool conv2d_wrw_v2_ok(const float* fine, const float* coarse, int64_t C, int64_t H, int64_t W);
-bool conv2d_wrw_v2_shape_ok(int64_t C, int64_t H, int64_t W);
-int conv2d_wrw_v2_ncw(int64_t C);
-bool conv2d_wrw_v2(const float* fine, const float* coarse, float* part, int64_t B, int64_t C, int64_t M, int64_t H, int64_t W, int nz, int tiles_per_wg,
-                   hipStream_t s);
+// round 4: raw-row-tile forms (conv2d_k4s2_v2.hip).  *_choose: false = preconditions not met (or "CONV2D_V1" set), run the kernels of this file;
+// the down / up launches return false (nothing launched) for tensors that are not 16-byte aligned
+bool conv2d_down_v2(const float* fine, const float* w, float* coarse, int64_t B, int64_t C, int64_t M, int64_t H, int64_t W, int tm, int tw, int nt,
+                    hipStream_t s);
+bool conv2d_up_v2(const float* coarse, const float* w, float* fine, int64_t B, int64_t C, int64_t M, int64_t H, int64_t W, int tc, int tw, int nt,
+                  hipStream_t s);
+bool conv2d_v2_choose(int64_t B, int64_t rows, int64_t H, int64_t W, int& tm, int& tw, int& nt);
+bool conv2d_wrw_v2_choose(int64_t C, int64_t H, int64_t W, int& tw, int& nt, int& ncw);
+void conv2d_wrw_v2(const float* fine, const float* coarse, float* part, int64_t B, int64_t C, int64_t M, int64_t H, int64_t W, int tw, int ncw, int nz,
+                   int tiles_per_wg, hipStream_t s);
 
 
 typedef float c2_f32x4 __attribute__((ext_vector_type(4)));
@@ -455,20 +457,48 @@ __global__ void __launch_bounds__(256) conv2d_k4s2_wsum_wave_kernel(const float*
     if (lane == 0) gw[k] = (float)s;
 }
 
-static void c2_wrw_plan(int64_t B, int64_t C, int64_t M, int64_t H, int64_t W, int& nz, int& tiles_per_wg) {
+// ---- host: "choose" (one function per operation, shared by the launches and dn_conv2d_k4s2_query) and "launch" -------------------------------
+static inline int c2_v1_rows(int64_t rows) { return rows <= 32 ? 32 : 64; }   // TM / TC of the kernels of this file
+
+// down (rows = M) and up (rows = C): which kernel a launch with 16-byte aligned tensors takes
+static void c2_choose(int64_t B, int64_t rows, int64_t H, int64_t W, dn_conv_k4s2_kernel& k) {
+    k = dn_conv_k4s2_kernel{};
+    k.nz = 1;
+    int tm, tw, nt;
+    if (conv2d_v2_choose(B, rows, H, W, tm, tw, nt)) {
+        k.gen = 2;
+        k.targ[0] = tm; k.targ[1] = tw; k.targ[2] = nt;
+    } else {
+        k.gen = 1;
+        k.targ[0] = c2_v1_rows(rows);
+    }
+}
+
+// wrw: the kernel, its K-split (k.nz slices of k.per_slice tiles of 64 positions) and the kernel that sums the slices
+static void c2_wrw_choose(int64_t B, int64_t C, int64_t M, int64_t H, int64_t W, dn_conv_k4s2_kernel& k) {
+    k = dn_conv_k4s2_kernel{};
+    int tw, nt, ncw;
+    if (conv2d_wrw_v2_choose(C, H, W, tw, nt, ncw)) {
+        k.gen = 2;
+        k.targ[0] = tw; k.targ[1] = nt; k.targ[2] = ncw;
+    } else {
+        k.gen = 1;
+        ncw = 4;
+    }
     const int64_t tiles = (B * H * W + C2_TN - 1) / C2_TN;
-    const int64_t ncw = conv2d_wrw_v2_shape_ok(C, H, W) ? conv2d_wrw_v2_ncw(C) : 4;       // fine channels per workgroup of the kernel that will run
-    const int64_t groups = ((C + ncw - 1) / ncw) * ((M + 63) / 64);
-    const char* tw = config(CFG_CONV_WRW_WGS);             // (tuning switch: workgroups a weight-gradient launch aims at)
-    const int64_t total = tw ? std::max(256, std::atoi(tw)) : 1024;      // round 4: 2048 -> 1024 with the v2 kernels (3-4 resident per CU): fewer, longer K-slices and
+    const int64_t groups = ((C + ncw - 1) / ncw) * ((M + 63) / 64);                       // ncw: fine channels per workgroup of the kernel that will run
+    const char* wgs = config(CFG_CONV_WRW_WGS);            // (tuning switch: workgroups a weight-gradient launch aims at)
+    const int64_t total = wgs ? std::max(256, std::atoi(wgs)) : 1024;    // round 4: 2048 -> 1024 with the v2 kernels (3-4 resident per CU): fewer, longer K-slices and
                                                                          // half the partial arrays to sum -- U-Net step 7.28 -> 7.12 ms (2048 / 1280 / 1024 / 768: 7.28 / 7.26 / 7.12 / 7.19)
     int64_t want = (total + groups - 1) / groups;
     if (want < 1) want = 1;
     if (want > tiles) want = tiles;
     if (want > 1024) want = 1024;                         // (round 4: 256 -> 1024 for layers with ONE (channel group, row group) pair -- the U-Net's first, 2 -> 32,
                                                           // was a launch of 256 workgroups of 64 dependent chunks each; their partials are summed a wave per output)
-    tiles_per_wg = (int)((tiles + want - 1) / want);
-    nz = (int)((tiles + tiles_per_wg - 1) / tiles_per_wg);
+    k.per_slice = (int)((tiles + want - 1) / want);
+    k.nz = (int)((tiles + k.per_slice - 1) / k.per_slice);
+    // many K-slices and few outputs: one WAVE per output (conv2d_k4s2_wsum_wave_kernel); else one thread per output
+    k.sum_kernel = k.nz == 1 ? 0 : (k.nz >= 128 && M * C * 16 <= 16384) ? 2 : 1;
 }
 
 static int c2_check(int64_t B, int64_t C, int64_t M, int64_t H, int64_t W) {
@@ -486,13 +516,15 @@ extern "C" int dn_conv2d_k4s2_down(const float* fine, const float* w, float* coa
     if (int rc = c2_check(B, C, M, H, W)) return rc;
     if (!fine || !w || !coarse) return DN_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (conv2d_down_v2(fine, w, coarse, B, C, M, H, W, s)) {
+    dn_conv_k4s2_kernel k;
+    c2_choose(B, M, H, W, k);
+    if (k.gen == 2 && conv2d_down_v2(fine, w, coarse, B, C, M, H, W, k.targ[0], k.targ[1], k.targ[2], s)) {
         DN_LAUNCH_CHECK();
         return 0;
     }
     const int64_t tiles = B * ((H * W + C2_TN - 1) / C2_TN);
     if (tiles >= (1ll << 31)) return DN_E_UNSUPPORTED;
-    if (M <= 32) {
+    if (c2_v1_rows(M) == 32) {
         hipLaunchKernelGGL((conv2d_k4s2_down_kernel<32>), dim3((unsigned)tiles, (unsigned)((M + 31) / 32)), dim3(256), 0, s, fine, w, coarse, (int)B,
                            (int)C, (int)M, (int)H, (int)W);
     } else {
@@ -508,13 +540,15 @@ extern "C" int dn_conv2d_k4s2_up(const float* coarse, const float* w, float* fin
     if (int rc = c2_check(B, C, M, H, W)) return rc;
     if (!fine || !w || !coarse) return DN_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (conv2d_up_v2(coarse, w, fine, B, C, M, H, W, s)) {
+    dn_conv_k4s2_kernel k;
+    c2_choose(B, C, H, W, k);
+    if (k.gen == 2 && conv2d_up_v2(coarse, w, fine, B, C, M, H, W, k.targ[0], k.targ[1], k.targ[2], s)) {
         DN_LAUNCH_CHECK();
         return 0;
     }
     const int64_t tiles = B * ((H * W + C2_TN - 1) / C2_TN);
     if (tiles >= (1ll << 31)) return DN_E_UNSUPPORTED;
-    if (C <= 32) {
+    if (c2_v1_rows(C) == 32) {
         hipLaunchKernelGGL((conv2d_k4s2_up_kernel<32>), dim3((unsigned)tiles, (unsigned)((C + 31) / 32)), dim3(256), 0, s, coarse, w, fine, (int)B,
                            (int)C, (int)M, (int)H, (int)W);
     } else {
@@ -527,31 +561,42 @@ extern "C" int dn_conv2d_k4s2_up(const float* coarse, const float* w, float* fin
 
 extern "C" int64_t dn_conv2d_k4s2_wrw_workspace_bytes(int64_t B, int64_t C, int64_t M, int64_t H, int64_t W) {
     if (int rc = c2_check(B, C, M, H, W)) return rc;
-    int nz, tpw;
-    c2_wrw_plan(B, C, M, H, W, nz, tpw);
-    return nz == 1 ? 0 : (int64_t)sizeof(float) * M * C * 16 * nz;
+    dn_conv_k4s2_kernel k;
+    c2_wrw_choose(B, C, M, H, W, k);
+    return k.nz == 1 ? 0 : (int64_t)sizeof(float) * M * C * 16 * k.nz;
 }
 
 extern "C" int dn_conv2d_k4s2_wrw(const float* fine, const float* coarse, float* grad_weight, int64_t B, int64_t C, int64_t M, int64_t H,
                                   int64_t W, void* workspace, int64_t workspace_bytes, void* stream) {
     if (int rc = c2_check(B, C, M, H, W)) return rc;
     if (!fine || !coarse || !grad_weight) return DN_E_BADARG;
-    int nz, tpw;
-    c2_wrw_plan(B, C, M, H, W, nz, tpw);
-    if (nz > 1 && (!workspace || workspace_bytes < dn_conv2d_k4s2_wrw_workspace_bytes(B, C, M, H, W))) return DN_E_WORKSPACE;
+    dn_conv_k4s2_kernel k;
+    c2_wrw_choose(B, C, M, H, W, k);
+    const int nz = k.nz, tpw = k.per_slice;
+    if (nz > 1 && (!workspace || workspace_bytes < (int64_t)sizeof(float) * M * C * 16 * nz)) return DN_E_WORKSPACE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     float* part = nz == 1 ? grad_weight : static_cast<float*>(workspace);
     // (the K-split plan counts tiles of 64 flattened positions; the v2 kernel's tiles are 64 positions too: TR x TW blocks of one sample)
-    if (!(conv2d_wrw_v2_ok(fine, coarse, C, H, W) && conv2d_wrw_v2(fine, coarse, part, B, C, M, H, W, nz, tpw, s)))
+    if (k.gen == 2 && !(reinterpret_cast<uintptr_t>(fine) & 15) && !(reinterpret_cast<uintptr_t>(coarse) & 15))
+        conv2d_wrw_v2(fine, coarse, part, B, C, M, H, W, k.targ[0], k.targ[2], nz, tpw, s);
+    else
         hipLaunchKernelGGL(conv2d_k4s2_wrw_kernel, dim3((unsigned)((C + 3) / 4), (unsigned)((M + 63) / 64), (unsigned)nz), dim3(256), 0, s, fine, coarse,
                            part, (int)B, (int)C, (int)M, (int)H, (int)W, tpw);
     if (nz > 1) {
         const long nout = (long)M * C * 16;
-        if (nz >= 128 && nout <= 16384)
+        if (k.sum_kernel == 2)
             hipLaunchKernelGGL(conv2d_k4s2_wsum_wave_kernel, dim3((unsigned)((nout + 3) / 4)), dim3(256), 0, s, part, grad_weight, nz, nout);
         else
             hipLaunchKernelGGL(conv2d_k4s2_wsum_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, s, part, grad_weight, nz, nout);
     }
     DN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dn_conv2d_k4s2_query(int32_t op, int64_t B, int64_t C, int64_t M, int64_t H, int64_t W, dn_conv_k4s2_kernel* out) {
+    if (!out || op < DN_CONV_DOWN || op > DN_CONV_WRW) return DN_E_BADARG;
+    if (int rc = c2_check(B, C, M, H, W)) return rc;
+    if (op == DN_CONV_WRW) c2_wrw_choose(B, C, M, H, W, *out);
+    else c2_choose(B, op == DN_CONV_DOWN ? M : C, H, W, *out);
     return 0;
 }

@@ -173,14 +173,10 @@ __global__ void __launch_bounds__(256, 2) conv2d_down_v2_kernel(const float* __r
     }
 }
 
+// launch of the instantiation <TM, TW, NT> that conv2d_v2_choose picked (TW = 128 exists for NT = 128 only)
 template <int TM, int NT>
-static bool down_v2_launch(const float* fine, const float* w, float* coarse, int B, int C, int M, int H, int W, hipStream_t s) {
-    const int TW = W >= NT ? NT : W;                     // 16 .. NT (W % 16 == 0 checked by the caller; other widths: fall back)
-    if (TW != 16 && TW != 32 && TW != 64 && TW != 128) return false;
-    const int TR = NT / TW;
-    if (W % TW != 0 || H % TR != 0) return false;
-    const long long tiles = (long long)(W / TW) * (H / TR) * B;
-    if (tiles >= (1ll << 31)) return false;
+static void down_v2_launch(int TW, const float* fine, const float* w, float* coarse, int B, int C, int M, int H, int W, hipStream_t s) {
+    const long long tiles = (long long)(W / TW) * (H / (NT / TW)) * B;
     const dim3 grid((unsigned)tiles, (unsigned)((M + TM - 1) / TM)), block(256);
     switch (TW) {
         case 16: hipLaunchKernelGGL((conv2d_down_v2_kernel<TM, 16, NT>), grid, block, 0, s, fine, w, coarse, B, C, M, H, W); break;
@@ -188,9 +184,7 @@ static bool down_v2_launch(const float* fine, const float* w, float* coarse, int
         case 64: hipLaunchKernelGGL((conv2d_down_v2_kernel<TM, 64, NT>), grid, block, 0, s, fine, w, coarse, B, C, M, H, W); break;
         default:
             if constexpr (NT == 128) hipLaunchKernelGGL((conv2d_down_v2_kernel<TM, 128, NT>), grid, block, 0, s, fine, w, coarse, B, C, M, H, W);
-            else return false;
     }
-    return true;
 }
 
 // Tile choice: 128 positions x 64 channels per workgroup where that still gives the 256 CUs ~2 workgroups each; layers with few positions
@@ -198,16 +192,35 @@ static bool down_v2_launch(const float* fine, const float* w, float* coarse, int
 // chip idle (256 -> 256 channels at 16^2: 180 us with 128 x 64 tiles against 143 us for the round-2 kernel's 64 x 64)
 static inline long long v2_wgs(int64_t B, int64_t H, int64_t W, int64_t rows, int nt, int tm) { return B * ((H * W + nt - 1) / nt) * ((rows + tm - 1) / tm); }
 
-// true when the v2 kernel was launched; false: the caller runs the round-2 kernel
-bool conv2d_down_v2(const float* fine, const float* w, float* coarse, int64_t B, int64_t C, int64_t M, int64_t H, int64_t W, hipStream_t s) {
+// The ONE choice of the down / up instantiation <tm, tw, nt> for `rows` GEMM rows (M of down, C of up) on B samples of H x W coarse positions:
+// the launches below and dn_conv2d_k4s2_query both call it.  false: the v2 preconditions do not hold for the tile the workgroup count asks for
+// (or "CONV2D_V1" is set) and the round-2 kernel runs.  Shape only: the alignment of the tensors is the launch's own, second condition.
+bool conv2d_v2_choose(int64_t B, int64_t rows, int64_t H, int64_t W, int& tm, int& tw, int& nt) {
     if (config(CFG_CONV2D_V1) != nullptr) return false;
-    if (W % 16 != 0 || (reinterpret_cast<uintptr_t>(fine) & 15) || (reinterpret_cast<uintptr_t>(w) & 15)) return false;
+    if (W % 16 != 0) return false;
+    if (rows <= 32) { tm = 32; nt = v2_wgs(B, H, W, rows, 128, 32) >= 384 ? 128 : 64; }
+    else if (v2_wgs(B, H, W, rows, 128, 64) >= 384) { tm = 64; nt = 128; }
+    else if (v2_wgs(B, H, W, rows, 64, 64) >= 384) { tm = 64; nt = 64; }
+    else { tm = 32; nt = 64; }
+    tw = W >= nt ? nt : (int)W;                          // 16 .. nt
+    if (tw != 16 && tw != 32 && tw != 64 && tw != 128) return false;
+    const int tr = nt / tw;
+    if (W % tw != 0 || H % tr != 0) return false;
+    return (W / tw) * (H / tr) * B < (1ll << 31);
+}
+
+// launches the instantiation <tm, tw, nt> that conv2d_v2_choose picked; false (nothing launched): a tensor is not 16-byte aligned, the caller
+// runs the round-2 kernel
+bool conv2d_down_v2(const float* fine, const float* w, float* coarse, int64_t B, int64_t C, int64_t M, int64_t H, int64_t W, int tm, int tw, int nt,
+                    hipStream_t s) {
+    if ((reinterpret_cast<uintptr_t>(fine) & 15) || (reinterpret_cast<uintptr_t>(w) & 15)) return false;
     const int b = (int)B, c = (int)C, m = (int)M, h = (int)H, ww = (int)W;
-    if (M <= 32) return v2_wgs(B, H, W, M, 128, 32) >= 384 ? down_v2_launch<32, 128>(fine, w, coarse, b, c, m, h, ww, s)
-                                                            : down_v2_launch<32, 64>(fine, w, coarse, b, c, m, h, ww, s);
-    if (v2_wgs(B, H, W, M, 128, 64) >= 384) return down_v2_launch<64, 128>(fine, w, coarse, b, c, m, h, ww, s);
-    if (v2_wgs(B, H, W, M, 64, 64) >= 384) return down_v2_launch<64, 64>(fine, w, coarse, b, c, m, h, ww, s);
-    return down_v2_launch<32, 64>(fine, w, coarse, b, c, m, h, ww, s);
+    if (tm == 32) {
+        if (nt == 128) down_v2_launch<32, 128>(tw, fine, w, coarse, b, c, m, h, ww, s);
+        else down_v2_launch<32, 64>(tw, fine, w, coarse, b, c, m, h, ww, s);
+    } else if (nt == 128) down_v2_launch<64, 128>(tw, fine, w, coarse, b, c, m, h, ww, s);
+    else down_v2_launch<64, 64>(tw, fine, w, coarse, b, c, m, h, ww, s);
+    return true;
 }
 
 // =====================================================================================================================
@@ -357,13 +370,8 @@ __global__ void __launch_bounds__(256, 2) conv2d_up_v2_kernel(const float* __res
 }
 
 template <int TC, int NT>
-static bool up_v2_launch(const float* coarse, const float* w, float* fine, int B, int C, int M, int H, int W, hipStream_t s) {
-    const int TW = W >= NT ? NT : W;
-    if (TW != 16 && TW != 32 && TW != 64 && TW != 128) return false;
-    const int TR = NT / TW;
-    if (W % TW != 0 || H % TR != 0) return false;
-    const long long tiles = (long long)(W / TW) * (H / TR) * B;
-    if (tiles >= (1ll << 31)) return false;
+static void up_v2_launch(int TW, const float* coarse, const float* w, float* fine, int B, int C, int M, int H, int W, hipStream_t s) {
+    const long long tiles = (long long)(W / TW) * (H / (NT / TW)) * B;
     const dim3 grid((unsigned)tiles, (unsigned)((C + TC - 1) / TC)), block(256);
     switch (TW) {
         case 16: hipLaunchKernelGGL((conv2d_up_v2_kernel<TC, 16, NT>), grid, block, 0, s, coarse, w, fine, B, C, M, H, W); break;
@@ -371,20 +379,19 @@ static bool up_v2_launch(const float* coarse, const float* w, float* fine, int B
         case 64: hipLaunchKernelGGL((conv2d_up_v2_kernel<TC, 64, NT>), grid, block, 0, s, coarse, w, fine, B, C, M, H, W); break;
         default:
             if constexpr (NT == 128) hipLaunchKernelGGL((conv2d_up_v2_kernel<TC, 128, NT>), grid, block, 0, s, coarse, w, fine, B, C, M, H, W);
-            else return false;
     }
-    return true;
 }
 
-bool conv2d_up_v2(const float* coarse, const float* w, float* fine, int64_t B, int64_t C, int64_t M, int64_t H, int64_t W, hipStream_t s) {
-    if (config(CFG_CONV2D_V1) != nullptr) return false;
-    if (W % 16 != 0 || (reinterpret_cast<uintptr_t>(coarse) & 15) || (reinterpret_cast<uintptr_t>(w) & 15) || (reinterpret_cast<uintptr_t>(fine) & 7)) return false;
+bool conv2d_up_v2(const float* coarse, const float* w, float* fine, int64_t B, int64_t C, int64_t M, int64_t H, int64_t W, int tc, int tw, int nt,
+                  hipStream_t s) {
+    if ((reinterpret_cast<uintptr_t>(coarse) & 15) || (reinterpret_cast<uintptr_t>(w) & 15) || (reinterpret_cast<uintptr_t>(fine) & 7)) return false;
     const int b = (int)B, c = (int)C, m = (int)M, h = (int)H, ww = (int)W;
-    if (C <= 32) return v2_wgs(B, H, W, C, 128, 32) >= 384 ? up_v2_launch<32, 128>(coarse, w, fine, b, c, m, h, ww, s)
-                                                            : up_v2_launch<32, 64>(coarse, w, fine, b, c, m, h, ww, s);
-    if (v2_wgs(B, H, W, C, 128, 64) >= 384) return up_v2_launch<64, 128>(coarse, w, fine, b, c, m, h, ww, s);
-    if (v2_wgs(B, H, W, C, 64, 64) >= 384) return up_v2_launch<64, 64>(coarse, w, fine, b, c, m, h, ww, s);
-    return up_v2_launch<32, 64>(coarse, w, fine, b, c, m, h, ww, s);
+    if (tc == 32) {
+        if (nt == 128) up_v2_launch<32, 128>(tw, coarse, w, fine, b, c, m, h, ww, s);
+        else up_v2_launch<32, 64>(tw, coarse, w, fine, b, c, m, h, ww, s);
+    } else if (nt == 128) up_v2_launch<64, 128>(tw, coarse, w, fine, b, c, m, h, ww, s);
+    else up_v2_launch<64, 64>(tw, coarse, w, fine, b, c, m, h, ww, s);
+    return true;
 }
 
 constexpr int V2W_NT = 64;         // positions per K-split plan tile (conv2d_k4s2.hip: c2_wrw_plan)
@@ -518,46 +525,40 @@ __global__ void __launch_bounds__(256, 3) conv2d_wrw_v2_kernel(const float* __re
         }
 }
 
-// Channels per workgroup of the v2 weight-gradient kernel for a layer with C fine channels (8 from 8 channels on: see the kernel)
-int conv2d_wrw_v2_ncw(int64_t C) { return C >= 8 ? 8 : 4; }
+// The ONE choice of the v2 weight-gradient instantiation <tw, nt, ncw> for a layer with C fine channels on H x W coarse positions (8 channels per
+// workgroup from 8 channels on: see the kernel); the K-split plan (workspace size), the launch and dn_conv2d_k4s2_query call it.  false: the
+// preconditions are not met (or "CONV2D_V1" is set) and the round-2 kernel runs.  Shape only: 16-byte alignment is the launch's second condition.
+bool conv2d_wrw_v2_choose(int64_t C, int64_t H, int64_t W, int& tw, int& nt, int& ncw) {
+    if (config(CFG_CONV2D_V1) != nullptr) return false;
+    if (W % 16 != 0) return false;
+    ncw = C >= 8 ? 8 : 4;
+    if (ncw == 8) {
+        nt = 32;
+        tw = W >= 32 ? 32 : (int)W;
+        return (tw == 16 || tw == 32) && W % tw == 0 && H % (32 / tw) == 0 && (H * W) % 64 == 0;
+    }
+    nt = V2W_NT;
+    tw = W >= 64 ? 64 : (int)W;
+    if (tw != 16 && tw != 32 && tw != 64) return false;
+    return W % tw == 0 && H % (V2W_NT / tw) == 0;
+}
 
-// launches the v2 weight-gradient kernel over `nz` K-slices of `tiles_per_wg` 64-position plan tiles each; false: preconditions not met
-bool conv2d_wrw_v2(const float* fine, const float* coarse, float* part, int64_t B, int64_t C, int64_t M, int64_t H, int64_t W, int nz, int tiles_per_wg,
-                   hipStream_t s) {
-    const int ncw = conv2d_wrw_v2_ncw(C);
+// launches the instantiation <tw, ., ncw> that conv2d_wrw_v2_choose picked over `nz` K-slices of `tiles_per_wg` 64-position plan tiles each
+void conv2d_wrw_v2(const float* fine, const float* coarse, float* part, int64_t B, int64_t C, int64_t M, int64_t H, int64_t W, int tw, int ncw, int nz,
+                   int tiles_per_wg, hipStream_t s) {
     const dim3 grid((unsigned)((C + ncw - 1) / ncw), (unsigned)((M + 63) / 64), (unsigned)nz), block(256);
     const int b = (int)B, c = (int)C, m = (int)M, h = (int)H, w = (int)W;
     if (ncw == 8) {                                      // chunks of 32 positions: two per plan tile
-        const int TW = W >= 32 ? 32 : (int)W, tpw = 2 * tiles_per_wg;
-        if (TW == 32) hipLaunchKernelGGL((conv2d_wrw_v2_kernel<32, 32, 8>), grid, block, 0, s, fine, coarse, part, b, c, m, h, w, tpw);
-        else if (TW == 16) hipLaunchKernelGGL((conv2d_wrw_v2_kernel<16, 32, 8>), grid, block, 0, s, fine, coarse, part, b, c, m, h, w, tpw);
-        else return false;
-        return true;
+        const int tpw = 2 * tiles_per_wg;
+        if (tw == 32) hipLaunchKernelGGL((conv2d_wrw_v2_kernel<32, 32, 8>), grid, block, 0, s, fine, coarse, part, b, c, m, h, w, tpw);
+        else hipLaunchKernelGGL((conv2d_wrw_v2_kernel<16, 32, 8>), grid, block, 0, s, fine, coarse, part, b, c, m, h, w, tpw);
+        return;
     }
-    const int TW = W >= 64 ? 64 : (int)W;
-    switch (TW) {
+    switch (tw) {
         case 16: hipLaunchKernelGGL((conv2d_wrw_v2_kernel<16, 64, 4>), grid, block, 0, s, fine, coarse, part, b, c, m, h, w, tiles_per_wg); break;
         case 32: hipLaunchKernelGGL((conv2d_wrw_v2_kernel<32, 64, 4>), grid, block, 0, s, fine, coarse, part, b, c, m, h, w, tiles_per_wg); break;
-        case 64: hipLaunchKernelGGL((conv2d_wrw_v2_kernel<64, 64, 4>), grid, block, 0, s, fine, coarse, part, b, c, m, h, w, tiles_per_wg); break;
-        default: return false;
+        default: hipLaunchKernelGGL((conv2d_wrw_v2_kernel<64, 64, 4>), grid, block, 0, s, fine, coarse, part, b, c, m, h, w, tiles_per_wg); break;
     }
-    return true;
-}
-
-// are the preconditions of the v2 weight-gradient kernel met?  Shape-only part: the K-split plan (workspace size) depends on it
-bool conv2d_wrw_v2_shape_ok(int64_t C, int64_t H, int64_t W) {
-    if (config(CFG_CONV2D_V1) != nullptr) return false;
-    if (W % 16 != 0) return false;
-    if (conv2d_wrw_v2_ncw(C) == 8) {
-        const int64_t TW = W >= 32 ? 32 : W;
-        return (TW == 16 || TW == 32) && W % TW == 0 && H % (32 / TW) == 0 && (H * W) % 64 == 0;
-    }
-    const int64_t TW = W >= 64 ? 64 : W;
-    if (TW != 16 && TW != 32 && TW != 64) return false;
-    return W % TW == 0 && H % (V2W_NT / TW) == 0;
-}
-bool conv2d_wrw_v2_ok(const float* fine, const float* coarse, int64_t C, int64_t H, int64_t W) {
-    return conv2d_wrw_v2_shape_ok(C, H, W) && !(reinterpret_cast<uintptr_t>(fine) & 15) && !(reinterpret_cast<uintptr_t>(coarse) & 15);
 }
 
 }  // namespace dn

@@ -283,20 +283,33 @@ static int c3_check(int64_t B, int64_t C, int64_t M, int64_t D, int64_t H, int64
     return 0;
 }
 
+// The ONE choice of a down (up = 0) / up launch, shared by the launches, dn_conv3d_k4s2_workspace_bytes and dn_conv3d_k4s2_query: k.targ[0] = TM
+// (down) / TC (up), k.nz = the split S, k.per_slice = fine channels (down) / coarse channel pairs (up) per slice; `split` = a workspace is given
+static void c3_choose(int up, int64_t B, int64_t C, int64_t M, int64_t D, int64_t H, int64_t W, bool split, dn_conv_k4s2_kernel& k) {
+    k = dn_conv_k4s2_kernel{};
+    k.gen = 1;
+    const int64_t rows = up ? C : M;
+    k.targ[0] = rows <= 32 ? 32 : 64;
+    const int64_t tiles = B * ((D * H * W + C3_TN - 1) / C3_TN), rtiles = (rows + k.targ[0] - 1) / k.targ[0];
+    const int units = up ? (int)((M + 1) / 2) : (int)C;
+    int S = 1;
+    k.per_slice = split ? c3_split(tiles * rtiles * (up ? 2 : 1), units, &S) : units;
+    k.nz = S;
+    k.sum_kernel = S > 1 ? 1 : 0;
+}
+
+void conv3d_wrw_choose(int64_t B, int64_t CN, int64_t M, int64_t d, int64_t h, int64_t w, dn_conv_k4s2_kernel& k);      // conv3d_wrw.hip
+
 }  // namespace dn
 
 using namespace dn;
 
 extern "C" int64_t dn_conv3d_k4s2_workspace_bytes(int32_t up, int64_t B, int64_t C, int64_t M, int64_t D, int64_t H, int64_t W) {
     if (c3_check(B, C, M, D, H, W)) return DN_E_BADARG;
-    const int64_t tiles = B * ((D * H * W + C3_TN - 1) / C3_TN);
-    int S;
-    if (up) {
-        c3_split(tiles * ((C + (C <= 32 ? 31 : 63)) / (C <= 32 ? 32 : 64)) * 2, (int)((M + 1) / 2), &S);
-        return S > 1 ? (int64_t)S * B * C * 8 * D * H * W * (int64_t)sizeof(float) : 0;
-    }
-    c3_split(tiles * ((M + (M <= 32 ? 31 : 63)) / (M <= 32 ? 32 : 64)), (int)C, &S);
-    return S > 1 ? (int64_t)S * B * M * D * H * W * (int64_t)sizeof(float) : 0;
+    dn_conv_k4s2_kernel k;
+    c3_choose(up, B, C, M, D, H, W, true, k);
+    if (k.nz == 1) return 0;
+    return (int64_t)k.nz * B * (up ? C * 8 : M) * D * H * W * (int64_t)sizeof(float);
 }
 
 extern "C" int dn_conv3d_k4s2_down_ws(const float* fine, const float* w, float* coarse, int64_t B, int64_t C, int64_t M, int64_t D, int64_t H,
@@ -304,16 +317,15 @@ extern "C" int dn_conv3d_k4s2_down_ws(const float* fine, const float* w, float* 
     if (int rc = c3_check(B, C, M, D, H, W)) return rc;
     if (!fine || !w || !coarse) return DN_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    dn_conv_k4s2_kernel k;
+    c3_choose(0, B, C, M, D, H, W, workspace != nullptr, k);
+    const int TM = k.targ[0], S = k.nz, cs = k.per_slice;
     const unsigned tiles = (unsigned)(B * ((D * H * W + C3_TN - 1) / C3_TN));
-    const unsigned mtiles = (unsigned)(M <= 32 ? (M + 31) / 32 : (M + 63) / 64);
-    int S = 1, cs = (int)C;
+    const unsigned mtiles = (unsigned)((M + TM - 1) / TM);
     const size_t n = (size_t)(B * M * D * H * W);
-    if (workspace) {
-        cs = c3_split((int64_t)tiles * mtiles, (int)C, &S);
-        if (S > 1 && workspace_bytes < (int64_t)((size_t)S * n * sizeof(float))) return DN_E_WORKSPACE;
-    }
+    if (S > 1 && workspace_bytes < (int64_t)((size_t)S * n * sizeof(float))) return DN_E_WORKSPACE;
     float* dst = S > 1 ? reinterpret_cast<float*>(workspace) : coarse;
-    if (M <= 32) {
+    if (TM == 32) {
         hipLaunchKernelGGL((conv3d_k4s2_down_kernel<32>), dim3(tiles, mtiles, S), dim3(256), 0, s, fine, w, dst, (int)B, (int)C, (int)M, (int)D, (int)H, (int)W, cs, n);
     } else {
         hipLaunchKernelGGL((conv3d_k4s2_down_kernel<64>), dim3(tiles, mtiles, S), dim3(256), 0, s, fine, w, dst, (int)B, (int)C, (int)M, (int)D, (int)H, (int)W, cs, n);
@@ -331,17 +343,15 @@ extern "C" int dn_conv3d_k4s2_up_ws(const float* coarse, const float* w, float* 
     if (int rc = c3_check(B, C, M, D, H, W)) return rc;
     if (!fine || !w || !coarse) return DN_E_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    dn_conv_k4s2_kernel k;
+    c3_choose(1, B, C, M, D, H, W, workspace != nullptr, k);
+    const int TC = k.targ[0], S = k.nz, ss = k.per_slice;
     const unsigned tiles = (unsigned)(B * ((D * H * W + C3_TN - 1) / C3_TN));
-    const unsigned ctiles = (unsigned)(C <= 32 ? (C + 31) / 32 : (C + 63) / 64);
-    const int nsteps = (int)((M + 1) / 2);
-    int S = 1, ss = nsteps;
+    const unsigned ctiles = (unsigned)((C + TC - 1) / TC);
     const size_t n = (size_t)(B * C * 8 * D * H * W);
-    if (workspace) {
-        ss = c3_split((int64_t)tiles * ctiles * 2, nsteps, &S);
-        if (S > 1 && workspace_bytes < (int64_t)((size_t)S * n * sizeof(float))) return DN_E_WORKSPACE;
-    }
+    if (S > 1 && workspace_bytes < (int64_t)((size_t)S * n * sizeof(float))) return DN_E_WORKSPACE;
     float* dst = S > 1 ? reinterpret_cast<float*>(workspace) : fine;
-    if (C <= 32) {
+    if (TC == 32) {
         hipLaunchKernelGGL((conv3d_k4s2_up_kernel<32>), dim3(tiles, ctiles, 2 * S), dim3(256), 0, s, coarse, w, dst, (int)B, (int)C, (int)M, (int)D, (int)H, (int)W, ss, n);
     } else {
         hipLaunchKernelGGL((conv3d_k4s2_up_kernel<64>), dim3(tiles, ctiles, 2 * S), dim3(256), 0, s, coarse, w, dst, (int)B, (int)C, (int)M, (int)D, (int)H, (int)W, ss, n);
@@ -362,4 +372,18 @@ extern "C" int dn_conv3d_k4s2_down(const float* fine, const float* w, float* coa
 extern "C" int dn_conv3d_k4s2_up(const float* coarse, const float* w, float* fine, int64_t B, int64_t C, int64_t M, int64_t D, int64_t H,
                                  int64_t W, void* stream) {
     return dn_conv3d_k4s2_up_ws(coarse, w, fine, B, C, M, D, H, W, nullptr, 0, stream);
+}
+
+extern "C" int dn_conv3d_k4s2_query(int32_t op, int64_t B, int64_t C, int64_t M, int64_t D, int64_t H, int64_t W, int32_t with_workspace,
+                                    dn_conv_k4s2_kernel* out) {
+    if (!out || op < DN_CONV_DOWN || op > DN_CONV_WRW) return DN_E_BADARG;
+    if (op == DN_CONV_WRW) {
+        const int64_t nbytes = dn_conv3d_k4s2_wrw_workspace_bytes(B, C, M, D, H, W);      // (its argument check)
+        if (nbytes < 0) return (int)nbytes;
+        conv3d_wrw_choose(B, C, M, D, H, W, *out);
+        return 0;
+    }
+    if (int rc = c3_check(B, C, M, D, H, W)) return rc;
+    c3_choose(op == DN_CONV_UP, B, C, M, D, H, W, with_workspace != 0, *out);
+    return 0;
 }

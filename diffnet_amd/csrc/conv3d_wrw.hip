@@ -138,13 +138,20 @@ __global__ void __launch_bounds__(256) conv3d_wsum_kernel(const float* __restric
     if (lane == 0) gw[k] = (float)s;
 }
 
-static void wr_plan(int64_t npos, int64_t CN, int& nwg, int& tiles_per_wg) {
-    const int64_t tiles = (npos + WR_TP - 1) / WR_TP;
+// The ONE choice of a weight-gradient launch, shared by the launch, the workspace size and dn_conv3d_k4s2_query: k.targ[0] = MR (row tiles of 16
+// coarse channels), k.nz workgroups per fine channel of k.per_slice 64-position tiles each, k.sum_kernel = 0 none | 1 thread | 2 wave per output
+void conv3d_wrw_choose(int64_t B, int64_t CN, int64_t M, int64_t d, int64_t h, int64_t w, dn_conv_k4s2_kernel& k) {
+    k = dn_conv_k4s2_kernel{};
+    k.gen = 1;
+    const int mr = (int)((M + 15) / 16);
+    k.targ[0] = mr <= 2 ? mr : mr <= 4 ? 4 : 8;
+    const int64_t tiles = (B * d * h * w + WR_TP - 1) / WR_TP;
     int64_t want = (4096 + CN - 1) / CN;       // ~16 workgroups per CU over all fine channels
     if (want < 1) want = 1;
     if (want > tiles) want = tiles;
-    tiles_per_wg = (int)((tiles + want - 1) / want);
-    nwg = (int)((tiles + tiles_per_wg - 1) / tiles_per_wg);
+    k.per_slice = (int)((tiles + want - 1) / want);
+    k.nz = (int)((tiles + k.per_slice - 1) / k.per_slice);
+    k.sum_kernel = k.nz > WR_FEW ? 2 : k.nz > 1 ? 1 : 0;
 }
 
 }  // namespace dn
@@ -159,22 +166,22 @@ static int wr_check(int64_t B, int64_t CN, int64_t M, int64_t d, int64_t h, int6
 
 extern "C" int64_t dn_conv3d_k4s2_wrw_workspace_bytes(int64_t B, int64_t CN, int64_t M, int64_t d, int64_t h, int64_t w) {
     if (int rc = wr_check(B, CN, M, d, h, w)) return rc;
-    int nwg, tpw;
-    wr_plan(B * d * h * w, CN, nwg, tpw);
-    return nwg == 1 ? 0 : (int64_t)sizeof(float) * M * CN * 64 * nwg;
+    dn_conv_k4s2_kernel k;
+    conv3d_wrw_choose(B, CN, M, d, h, w, k);
+    return k.nz == 1 ? 0 : (int64_t)sizeof(float) * M * CN * 64 * k.nz;
 }
 
 extern "C" int dn_conv3d_k4s2_wrw(const float* fine, const float* coarse, float* grad_weight, int64_t B, int64_t CN, int64_t M, int64_t d,
                                   int64_t h, int64_t w, void* workspace, int64_t workspace_bytes, void* stream) {
     if (int rc = wr_check(B, CN, M, d, h, w)) return rc;
     if (!fine || !coarse || !grad_weight) return DN_E_BADARG;
-    int nwg, tpw;
-    wr_plan(B * d * h * w, CN, nwg, tpw);
+    dn_conv_k4s2_kernel k;
+    conv3d_wrw_choose(B, CN, M, d, h, w, k);
+    const int nwg = k.nz, tpw = k.per_slice;
     if (nwg > 1 && (!workspace || workspace_bytes < dn_conv3d_k4s2_wrw_workspace_bytes(B, CN, M, d, h, w))) return DN_E_WORKSPACE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     float* part = nwg == 1 ? grad_weight : static_cast<float*>(workspace);
     const dim3 grid((unsigned)nwg, (unsigned)CN), block(256);
-    const int MR = (int)((M + 15) / 16);
 #define DN_WR(R)                                                                                                                   \
     do {                                                                                                                           \
         const size_t lds_bytes = sizeof(float) * 2 * (WR_TP * 80 + (R) * 16 * 68);                                                 \
@@ -188,16 +195,16 @@ extern "C" int dn_conv3d_k4s2_wrw(const float* fine, const float* coarse, float*
         hipLaunchKernelGGL((conv3d_wrw_kernel<R>), grid, block, lds_bytes, s, fine, coarse, part, (int)B, (int)CN, (int)M, (int)d, (int)h, \
                            (int)w, tpw);                                                                                           \
     } while (0)
-    switch (MR) {
+    switch (k.targ[0]) {
         case 1: DN_WR(1); break;
         case 2: DN_WR(2); break;
-        case 3: case 4: DN_WR(4); break;
+        case 4: DN_WR(4); break;
         default: DN_WR(8); break;
     }
 #undef DN_WR
     const long n = (long)M * CN * 64;
-    if (nwg > WR_FEW) hipLaunchKernelGGL(conv3d_wsum_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, part, grad_weight, nwg, n);
-    else if (nwg > 1) hipLaunchKernelGGL(conv3d_wsum_few_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, grad_weight, nwg, n);
+    if (k.sum_kernel == 2) hipLaunchKernelGGL(conv3d_wsum_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, part, grad_weight, nwg, n);
+    else if (k.sum_kernel == 1) hipLaunchKernelGGL(conv3d_wsum_few_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, grad_weight, nwg, n);
     DN_LAUNCH_CHECK();
     return 0;
 }

@@ -884,6 +884,37 @@ int dn_conv3d_k4s2_down_ws(const float *fine, const float *w, float *coarse, int
 int dn_conv3d_k4s2_up_ws(const float *coarse, const float *w, float *fine, int64_t B, int64_t C, int64_t M, int64_t D, int64_t H,
                          int64_t W, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* Which kernel a launch of the two families above takes: a host-side query, nothing is launched and no device is needed.  The choice is
+ * computed by the function the launch itself calls ("choose", then "launch", in csrc/conv2d_k4s2.hip, conv2d_k4s2_v2.hip, conv3d_k4s2.hip
+ * and conv3d_wrw.hip), so the two cannot drift; the switches "CONV2D_V1" and "CONV_WRW_WGS" act on the query as they act on the launch.
+ * The answer is for 16-byte aligned tensors (a 2-D launch with a misaligned tensor takes the generation-1 kernel of the same plan).
+ *   op = DN_CONV_DOWN | DN_CONV_UP | DN_CONV_WRW; B, C, M and the COARSE sizes as in the launches (3-D wrw: C = CN fine channels).
+ *   gen        2-D: 1 = the im2col kernels conv2d_k4s2_{down,up,wrw}_kernel, 2 = the raw-row-tile kernels conv2d_{down,up,wrw}_v2_kernel; 3-D: 1
+ *   targ       the template arguments, unused ones 0 --  2-D gen 2: down <TM, TW, NT>, up <TC, TW, NT>, wrw <TW, NT, NCW>;
+ *              2-D gen 1: down <TM>, up <TC>, wrw none;  3-D: down <TM>, up <TC>, wrw <MR>
+ *   nz         slices the contraction is split into (1: the kernel writes the result itself, no workspace): gridDim.z of the 2-D wrw and
+ *              3-D down kernels, gridDim.z / 2 of 3-D up, gridDim.x of 3-D wrw
+ *   per_slice  2-D and 3-D wrw: tiles of 64 flattened positions (b, i, j[, k]) per slice -- slice z covers positions 64 per_slice z ...
+ *              (a generation-2 2-D kernel walks 64 / NT x per_slice blocks of TR x TW = NT positions instead: blocks in x fastest, then y, then sample);
+ *              3-D down: fine channels per slice; 3-D up: pairs of coarse channels per slice
+ *   sum_kernel the launch that adds the slices: 0 none, 1 one thread per output (conv2d_k4s2_wsum_kernel, conv3d_wsum_few_kernel,
+ *              conv3d_ksum_kernel), 2 one wave per output (conv2d_k4s2_wsum_wave_kernel, conv3d_wsum_kernel)
+ * dn_conv3d_k4s2_query: with_workspace != 0 describes dn_conv3d_k4s2_down_ws / _up_ws with a workspace, 0 the unsplit launch (ignored for wrw).
+ * Returns 0, or the DN_E_* code the launch would return for these sizes; DN_E_BADARG for a NULL `out` or an unknown op. */
+#define DN_CONV_DOWN 0
+#define DN_CONV_UP 1
+#define DN_CONV_WRW 2
+typedef struct dn_conv_k4s2_kernel {
+    int32_t gen;
+    int32_t targ[3];
+    int32_t nz;
+    int32_t per_slice;
+    int32_t sum_kernel;
+} dn_conv_k4s2_kernel;
+int dn_conv2d_k4s2_query(int32_t op, int64_t B, int64_t C, int64_t M, int64_t H, int64_t W, dn_conv_k4s2_kernel *out);
+int dn_conv3d_k4s2_query(int32_t op, int64_t B, int64_t C, int64_t M, int64_t D, int64_t H, int64_t W, int32_t with_workspace,
+                         dn_conv_k4s2_kernel *out);
+
 /* Stride-1 "valid" k x k convolutions (k <= 7) with optional bias: the auto-encoder's stem / head layers behind an explicit
  * ReflectionPad2d (DiffNet/networks/autoencoders.py:13 `nn.Conv2d(in_channels, dim*2, 7)`, :75 `nn.Conv2d(.., out_channels, 3)`,
  * `nn.Conv2d(out_channels, out_channels, 7)`).  x (B,Ci,H,W), w (Co,Ci,K,K), y / gy (B,Co,H-K+1,W-K+1); gbias may be NULL. */
