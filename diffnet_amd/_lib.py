@@ -233,6 +233,9 @@ SYMBOLS = {
     "dn_unpack_mask_bits": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "dn_winding_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_void_p]),
+    "dn_winding_field_tile": (C.c_int, [C.c_int32, C.c_int64]),
+    "dn_winding_field": (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                   C.c_int32, C.c_void_p]),
 }
 
 _LIB = None

@@ -2598,3 +2598,59 @@ def compute_winding_nodes(points, normals, area, q):
     rc = _lib.lib().dn_winding_nodes(_p(pts), _p(nrm), _p(nodes), _p(out), B, npts, ny, nx, _stream(pts))
     _lib.check(rc, "dn_winding_nodes")
     return out
+
+
+WINDING_TILES = (1, 2, 4)        # queries per thread dn_winding_field can be told to use (0: picked from the problem size)
+WINDING_CHUNK = 256              # points staged in LDS per pass
+WINDING_THREADS = 256            # threads per workgroup: a workgroup owns WINDING_THREADS * tile queries
+_WINDING_METRICS = {"l1": 0, "l2": 1, 0: 0, 1: 1}
+
+
+def winding_field(points, normals, area, queries, metric="l1", power=3, scale=1.0, threshold=0.5, want_field=True, want_mask=False,
+                  tile=0):
+    """w[b, q] = scale * sum_p area[b, p] ((x_p - q) . n_p) / dist(x_p - q)^power on a flat list of queries (dn_winding_field): one launch.
+    points, normals (B, Np, dim), dim 2 or 3; area (B, Np) / (B, Np, 1) or None (= 1); queries (dim, nq) or (dim, *grid), coordinate-major,
+    shared by all samples, on the points' device or on the host; metric "l1" (the reference's quirk) or "l2"; power 2 or 3.
+    Returns (field, mask): the float32 field (B, nq) if want_field, else None, and the uint8 mask (B, nq) = (w > threshold), compared
+    in the kernel, if want_mask, else None.  Every tensor must be float32 and contiguous.  Not differentiable: nothing is recorded for
+    autograd (the reference only thresholds the field)."""
+    named = [("points", points), ("normals", normals), ("queries", queries)] + ([("area", area)] if area is not None else [])
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"winding_field: {name} must be a torch.Tensor")
+        if t.dtype != torch.float32:
+            raise TypeError(f"winding_field: {name} must be float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"winding_field: {name} must be contiguous")
+    if points.dim() != 3 or points.shape[2] not in (2, 3):
+        raise ValueError(f"winding_field: points must be (B, Np, 2) or (B, Np, 3), got {tuple(points.shape)}")
+    B, npts, dim = points.shape
+    if normals.shape != points.shape:
+        raise ValueError(f"winding_field: normals {tuple(normals.shape)} do not match points {tuple(points.shape)}")
+    if area is not None and tuple(area.shape) not in ((B, npts), (B, npts, 1)):
+        raise ValueError(f"winding_field: area must be (B, Np) or (B, Np, 1) = ({B}, {npts}[, 1]), got {tuple(area.shape)}")
+    if queries.dim() < 2 or queries.shape[0] != dim:
+        raise ValueError(f"winding_field: queries must be ({dim}, nq) or ({dim}, *grid), got {tuple(queries.shape)}")
+    if metric not in _WINDING_METRICS:
+        raise ValueError(f"winding_field: metric must be 'l1' or 'l2', got {metric!r}")
+    if power not in (2, 3):
+        raise ValueError(f"winding_field: power must be 2 or 3, got {power!r}")
+    if tile not in (0,) + WINDING_TILES:
+        raise ValueError(f"winding_field: tile must be 0 (automatic) or one of {WINDING_TILES}, got {tile!r}")
+    if not (want_field or want_mask):
+        raise ValueError("winding_field: nothing to compute (want_field and want_mask are both off)")
+    for name, t in named:
+        if t.device != points.device and not (name == "queries" and t.device.type == "cpu"):
+            raise ValueError(f"winding_field: {name} is on {t.device}, points on {points.device}")
+    if not points.is_cuda:
+        raise DiffNetHipError(f"points are on {points.device}: winding_field runs on the GPU only (no CPU fallback); move them with .cuda()")
+    nq = queries[0].numel()
+    if B < 1 or npts < 1 or nq < 1:
+        raise ValueError(f"winding_field: empty problem (B = {B}, Np = {npts}, nq = {nq})")
+    qd = queries if queries.is_cuda else queries.to(points.device)
+    field = torch.empty((B, nq), dtype=torch.float32, device=points.device) if want_field else None
+    mask = torch.empty((B, nq), dtype=torch.uint8, device=points.device) if want_mask else None
+    rc = _lib.lib().dn_winding_field(_p(points), _p(normals), _p(area), _p(qd), _p(field), _p(mask), B, npts, nq, dim, _WINDING_METRICS[metric],
+                                     power, float(scale), float(threshold), tile, _stream(points))
+    _lib.check(rc, "dn_winding_field")
+    return field, mask

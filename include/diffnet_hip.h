@@ -245,6 +245,25 @@ int dn_assemble_bwd(const float *grad_out, float *grad_split, int32_t batch, int
 int dn_winding_nodes(const float *points, const float *normals, const float *nodes, float *out, int32_t batch,
                      int32_t npts, int32_t ny, int32_t nx, void *stream);
 
+/* General winding-number field of a point cloud, 2-D or 3-D, with area weights, on a flat list of queries shared by all samples:
+ *   w[b,q] = scale * sum_p area[b,p] * ((x_p - q) . n_p) / dist(x_p - q)^power
+ * dim = 2 or 3; metric 0: dist is the L1 norm (the reference's compute_winding_torch, compute_winding_gpts and
+ * compute_winding_nodes), metric 1: the Euclidean norm (the true generalised winding number at power = dim and
+ * scale = 1/(2 pi) or 1/(4 pi)); power = 2 or 3.
+ *   points, normals (B, npts, dim); area (B, npts) or NULL (= 1); queries (dim, nq), coordinate-major;
+ *   out (B, nq) fp32 and / or mask (B, nq) bytes, mask = (w > threshold) compared in the kernel: at least one of the two.
+ * tile = queries per thread: 0 picks it from the problem size (dn_winding_field_tile(batch, nq) returns that choice: the
+ * largest of 1, 2, 4 that leaves the chip about four waves per SIMD; DN_E_BADARG for batch < 1 or nq < 1), 1, 2 or 4 force it
+ * (a workgroup of 256 threads owns 256 * tile queries and stages the cloud through LDS 256 points at a time).  Each query sums
+ * its points in index order in one chain, so the result is bitwise the same for every tile and grid; no atomics.  A point that
+ * coincides with a query gives inf or nan, as in the reference.  Not differentiable: nothing is saved for a backward pass.
+ * DN_E_BADARG before any launch: a NULL points / normals / queries, both outputs NULL, dim, metric, power or tile outside
+ * the values above, batch outside 1..65535, npts < 1, nq < 1 or nq > 16777215 * 256 * tile (the grid's limit). */
+int dn_winding_field_tile(int32_t batch, int64_t nq);
+int dn_winding_field(const float *points, const float *normals, const float *area, const float *queries, float *out,
+                     uint8_t *mask, int32_t batch, int32_t npts, int64_t nq, int32_t dim, int32_t metric, int32_t power,
+                     float scale, float threshold, int32_t tile, void *stream);
+
 /* DiffNetFDM stencil derivatives (DiffNet/DiffNetFDM.py:158-199): out = Corr( conv2d(g_padded, kernel9) ) with
  * g_padded (B,1,ny+2,nx+2) replicate-padded by the caller as in the reference, out (B,1,ny,nx), kernel9 a HOST pointer to
  * the 3x3 correlation kernel (row-major), and the reference's dense correction matmul (:63-119) reduced to what it does:
