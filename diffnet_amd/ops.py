@@ -443,10 +443,7 @@ def _norm_dirichlet(dirichlet):
 
 
 _threading = __import__("threading")
-_WS = {}
 _WS_LOCK = _threading.Lock()
-_FSDT_LAUNCH_LOCK = _threading.Lock()
-_POISSON_WS_BYTES = {}
 
 
 _SIDE_STREAMS = {}
@@ -460,26 +457,13 @@ def _side_stream(dev):
     return s
 
 
-def _workspace(dev, nbytes):
-    """The reduction workspace of (device, current stream): launches on one stream are ordered, so they may share it; a launch on
-    another stream gets its own (the ABI asks for one workspace per concurrently used stream).  A prepared launch (PoissonPlan)
-    keeps the workspace of the stream it was prepared on and must be launched on that stream."""
-    key = (dev.index, _raw_stream(dev))
-    with _WS_LOCK:
-        ws = _WS.get(key)
-        if ws is None or ws.numel() < nbytes:
-            ws = torch.zeros(max(nbytes, 1 << 16), dtype=torch.uint8, device=dev)   # ABI: zero-filled once
-            _WS[key] = ws
-    return ws
-
-
 def workspace_status(device=None):
     """Health check of the shared launch workspaces of `device` (every stream that has used one): synchronises those streams and raises
     DiffNetHipError if a launch ran a bounded LDS hand-over poll to its limit (chained-strip plans; such a launch's outputs and sums are
     NaN -- never silently wrong).  Cheap enough for once per epoch; not for the launch path."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     with _WS_LOCK:
-        items = [(k, w) for d in (_WS, _FSDT_WS) for k, w in d.items() if k[0] == dev.index]
+        items = [(k, w) for op in (_POISSON, _FSDT) for k, w in op.ws.items() if k[0] == dev.index]
     for (_, stream), ws in items:
         _lib.check(_lib.lib().dn_workspace_status(C.c_void_p(ws.data_ptr()), C.c_void_p(stream)), "dn_workspace_status")
 
@@ -491,7 +475,7 @@ def workspace_status(device=None):
 # the output allocations and one ctypes call instead of the full preparation (22 -> ~8 us of host time: small meshes are bounded by
 # the device, not by Python).  An entry holds NO reference to the caller's tensors (a pointer + shape is all a launch needs, and the
 # caller passes live tensors to every call); outputs are allocated fresh per call (a cached call never overwrites an earlier result).
-_CALL_CACHE = __import__("collections").OrderedDict()
+# Every operator has a cache of its own (_FusedOp.cache below; the Poisson one is _POISSON.cache), bounded by _CALL_CACHE_MAX.
 _CALL_CACHE_MAX = 16
 _CALL_STATS = {"hit": 0, "miss": 0, "uncached": 0}
 
@@ -547,24 +531,25 @@ def poisson_apply(geom, u, nu=None, f=None, f_gp=None, dirichlet=(), alpha=1.0, 
     if key is None:            # something needs a conversion copy (or is invalid: the full preparation says what)
         _CALL_STATS["uncached"] += 1
         return PoissonPlan(geom, u, nu, f, f_gp, dl, alpha, beta, c, wscale, out_scale, want_out, want_sums, loss_scale, out, strict=False).launch()
+    cache = _POISSON.cache
     with _WS_LOCK:
-        ent = _CALL_CACHE.get(key)
+        ent = cache.get(key)
         if ent is not None:
-            _CALL_CACHE.move_to_end(key)
+            cache.move_to_end(key)
     if ent is None:
         _CALL_STATS["miss"] += 1
         plan = PoissonPlan(geom, u, nu, f, f_gp, dl, alpha, beta, c, wscale, out_scale, want_out, want_sums, loss_scale, out, strict=True)
         res = plan.launch()
         # keep the structs, the workspace and the condition objects' own cached images; drop the caller's tensors and this call's outputs
         with _WS_LOCK:
-            live_ws = list(_WS.values())
+            live_ws = list(_POISSON.ws.values())
         plan.keep = [t for t in plan.keep if any(t is w for w in live_ws)] + [d.mask for d in dl if not isinstance(d.mask, torch.Tensor)]
         plan.result = None
         plan.fresh = (want_out and out is None, want_sums, loss_scale is not None)
         with _WS_LOCK:
-            _CALL_CACHE[key] = plan
-            while len(_CALL_CACHE) > _CALL_CACHE_MAX:
-                _CALL_CACHE.popitem(last=False)
+            cache[key] = plan
+            while len(cache) > _CALL_CACHE_MAX:
+                cache.popitem(last=False)
         return res
     _CALL_STATS["hit"] += 1
     a = ent.args
@@ -596,15 +581,10 @@ def poisson_apply(geom, u, nu=None, f=None, f_gp=None, dirichlet=(), alpha=1.0, 
 def call_cache_clear():
     """Forget the cached prepared calls (after dn_config_set of a launch-plan switch: the workspace size depends on the plan)."""
     with _WS_LOCK:
-        _CALL_CACHE.clear()
-        _FSDT_CACHE.clear()
         for op in _FUSED_OPS:
             op.cache.clear()
+            op.ws_bytes.clear()
         _PACK_CACHE.clear()
-    _POISSON_WS_BYTES.clear()
-    _FSDT_WS_BYTES.clear()
-    for op in _FUSED_OPS:
-        op.ws_bytes.clear()
 
 
 class PoissonPlan:
@@ -759,6 +739,45 @@ class PoissonPlan:
             self._hip.hipStreamWaitEvent(C.c_void_p(_raw_stream(self.device)), self._ev_done, 0)
 
 
+def _dirichlet_image(bc, m, value, u, node_shape, keep, strict=False):
+    """One Dirichlet condition read as a mask image into the dn_dirichlet `bc` of a call on u (B,1,*node_shape): the mask `m` (any form) as
+    a contiguous float32 / uint8 image, the value as a constant or a nodal field.  Returns the image.  `strict` (PoissonPlan): a mask or a
+    value field that would need a conversion copy is refused."""
+    nsd, B = len(node_shape), u.shape[0]
+    m = _mask_image(m, u)
+    if not isinstance(m, torch.Tensor) or not m.is_cuda:
+        raise DiffNetHipError("Dirichlet mask must be a CUDA tensor")
+    if strict and (m.dtype == torch.bool or not m.is_contiguous()):
+        raise DiffNetHipError("PoissonPlan: a bool or non-contiguous Dirichlet mask would be converted into a one-time copy; pass a "
+                              "contiguous float32 / uint8 image (or a PackedMask / BoxFaces)")
+    if m.dtype == torch.bool:
+        m = m.to(torch.uint8)
+    if m.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("Dirichlet mask must be float32, uint8 or bool")
+    m = m.contiguous()
+    if m.dim() != nsd + 2 or tuple(m.shape[1:]) != (1, *node_shape) or m.shape[0] not in (1, B):
+        raise ValueError(f"Dirichlet mask shape {tuple(m.shape)} does not match u")
+    keep.append(m)
+    bc.mask = m.data_ptr()
+    bc.mask_kind = _lib.MASK_U8 if m.dtype == torch.uint8 else _lib.MASK_F32
+    bc.mask_batched = int(m.shape[0] == B)
+    if isinstance(value, torch.Tensor):
+        v = value
+        if v.dim() == nsd:
+            v = v[(None,) * 2]
+        if strict and not v.is_cuda:
+            raise DiffNetHipError("PoissonPlan: the Dirichlet value field must live on the GPU (a prepared launch would keep a one-time copy)")
+        v = _require(v.to(u.device) if not v.is_cuda else v, "Dirichlet value", nsd + 2, strict)
+        if tuple(v.shape[1:]) != (1, *node_shape) or v.shape[0] not in (1, B):
+            raise ValueError("Dirichlet value field shape does not match u")
+        keep.append(v)
+        bc.field = v.data_ptr()
+        bc.field_batched = int(v.shape[0] == B)
+    else:
+        bc.value = float(value)
+    return m
+
+
 def _prepare_poisson(geom, u, nu, f, f_gp, dirichlet, alpha, beta, c, wscale, out_scale, want_out, want_sums, loss_scale, out, strict=False, reuse=None):
     """Validation + argument structs of one dn_poisson_apply call: (mesh, args, tensors to keep alive, result tuple)."""
     nsd = geom.nsd
@@ -834,38 +853,7 @@ def _prepare_poisson(geom, u, nu, f, f_gp, dirichlet, alpha, beta, c, wscale, ou
                 bc.mask, bc.mask_kind, bc.row_words = m.bits.data_ptr(), _lib.MASK_BITS, m.row_words
                 bc.mask_batched = int(m.shape[0] == B)
             continue
-        m = _mask_image(m, u)
-        if not isinstance(m, torch.Tensor) or not m.is_cuda:
-            raise DiffNetHipError("Dirichlet mask must be a CUDA tensor")
-        if strict and (m.dtype == torch.bool or not m.is_contiguous()):
-            raise DiffNetHipError("PoissonPlan: a bool or non-contiguous Dirichlet mask would be converted into a one-time copy; pass a "
-                                  "contiguous float32 / uint8 image (or a PackedMask / BoxFaces)")
-        if m.dtype == torch.bool:
-            m = m.to(torch.uint8)
-        if m.dtype not in (torch.float32, torch.uint8):
-            raise TypeError("Dirichlet mask must be float32, uint8 or bool")
-        m = m.contiguous()
-        if m.dim() != nsd + 2 or tuple(m.shape[1:]) != (1, *node_shape) or m.shape[0] not in (1, B):
-            raise ValueError(f"Dirichlet mask shape {tuple(m.shape)} does not match u")
-        keep.append(m)
-        bc = args.bc[k]
-        bc.mask = m.data_ptr()
-        bc.mask_kind = _lib.MASK_U8 if m.dtype == torch.uint8 else _lib.MASK_F32
-        bc.mask_batched = int(m.shape[0] == B)
-        if isinstance(d.value, torch.Tensor):
-            v = d.value
-            if v.dim() == nsd:
-                v = v[(None,) * 2]
-            if strict and not v.is_cuda:
-                raise DiffNetHipError("PoissonPlan: the Dirichlet value field must live on the GPU (a prepared launch would keep a one-time copy)")
-            v = _require(v.to(u.device) if not v.is_cuda else v, "Dirichlet value", nsd + 2, strict)
-            if tuple(v.shape[1:]) != (1, *node_shape) or v.shape[0] not in (1, B):
-                raise ValueError("Dirichlet value field shape does not match u")
-            keep.append(v)
-            bc.field = v.data_ptr()
-            bc.field_batched = int(v.shape[0] == B)
-        else:
-            bc.value = float(d.value)
+        _dirichlet_image(args.bc[k], m, d.value, u, node_shape, keep, strict)
     args.alpha, args.beta, args.c, args.wscale, args.out_scale = alpha, beta, c, wscale, out_scale
     mesh = geom.mesh_struct(B)
     if out is not None:
@@ -877,14 +865,7 @@ def _prepare_poisson(geom, u, nu, f, f_gp, dirichlet, alpha, beta, c, wscale, ou
     if out is not None:
         args.out = out.data_ptr()
     if want_sums or (mesh.nsd == 3 and mesh.degree > 1):       # (3-D Q2 / Q3: the workspace also holds the element vectors)
-        key = (mesh.nsd, mesh.degree, mesh.ngp, mesh.nx, mesh.ny, mesh.nz, B)
-        nbytes = _POISSON_WS_BYTES.get(key)
-        if nbytes is None:
-            nbytes = _lib.lib().dn_poisson_workspace_bytes(C.byref(mesh))
-            if nbytes < 0:
-                _lib.check(int(nbytes), "dn_poisson_workspace_bytes")
-            _POISSON_WS_BYTES[key] = nbytes
-        ws = _workspace(u.device, nbytes)
+        ws = _op_workspace(_POISSON, mesh, B, u.device)
         keep.append(ws)
         args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
     if want_sums:
@@ -1152,39 +1133,13 @@ def poisson_coef_grad(geom, u, v=None, dirichlet=(), a_nu=1.0, a_f=1.0, wscale=1
         keep.append(v)
         args.v = v.data_ptr()
     dl = _norm_dirichlet(dirichlet)
-    imgs = []
-    for d in dl:
-        m = _mask_image(d.mask, u)
-        if not isinstance(m, torch.Tensor) or not m.is_cuda:
-            raise DiffNetHipError("Dirichlet mask must be a CUDA tensor")
-        if m.dtype == torch.bool:
-            m = m.to(torch.uint8)
-        if m.dtype not in (torch.float32, torch.uint8):
-            raise TypeError("Dirichlet mask must be float32, uint8 or bool")
-        m = m.contiguous()
-        if m.dim() != nsd + 2 or tuple(m.shape[1:]) != (1, *node_shape) or m.shape[0] not in (1, B):
-            raise ValueError(f"Dirichlet mask shape {tuple(m.shape)} does not match u")
-        imgs.append(m)
+    imgs = [_dirichlet_image(args.bc[k], d.mask, d.value.detach().to(u.device) if isinstance(d.value, torch.Tensor) else d.value, u,
+                             node_shape, keep) for k, d in enumerate(dl)]
     if len(imgs) == 2 and imgs[0].dtype != imgs[1].dtype:       # the kernels read both images in one format
-        imgs = [(m > 0.5).to(torch.uint8) if m.dtype == torch.float32 else m for m in imgs]
-    for k, (d, m) in enumerate(zip(dl, imgs)):
+        k = 0 if imgs[0].dtype == torch.float32 else 1
+        m = (imgs[k] > 0.5).to(torch.uint8)
         keep.append(m)
-        bc = args.bc[k]
-        bc.mask = m.data_ptr()
-        bc.mask_kind = _lib.MASK_U8 if m.dtype == torch.uint8 else _lib.MASK_F32
-        bc.mask_batched = int(m.shape[0] == B)
-        if isinstance(d.value, torch.Tensor):
-            val = d.value
-            if val.dim() == nsd:
-                val = val[(None,) * 2]
-            val = _require(val.detach().to(u.device), "Dirichlet value", nsd + 2)
-            if tuple(val.shape[1:]) != (1, *node_shape) or val.shape[0] not in (1, B):
-                raise ValueError("Dirichlet value field shape does not match u")
-            keep.append(val)
-            bc.field = val.data_ptr()
-            bc.field_batched = int(val.shape[0] == B)
-        else:
-            bc.value = float(d.value)
+        args.bc[k].mask, args.bc[k].mask_kind = m.data_ptr(), _lib.MASK_U8
     args.a_nu, args.a_f, args.wscale = float(a_nu), float(a_f), float(wscale)
     if in_scale is not None:
         in_scale = _require(in_scale, "in_scale")
@@ -1284,52 +1239,6 @@ def energy_loss_and_grads(geom, u, nu=None, f=None, dirichlet=(), c=1.0, jac=1.0
     return loss, grads
 
 
-_FSDT_WS_BYTES = {}
-_FSDT_CACHE = __import__("collections").OrderedDict()
-# The FSDT launches have a reduction workspace of their OWN per (device, stream), never the one of _workspace: a launch with defer_norms leaves its
-# partials there for a later `norms_from` consumer, and a reducing dn_poisson_apply launch issued in between must not overwrite them while the
-# pair's ticket still matches (only FSDT's own reductions clear the ticket).  Another reducing FSDT launch in between clears it: NaN, never stale.
-_FSDT_WS = {}
-
-
-def _fsdt_workspace(dev, nbytes):
-    key = (dev.index, _raw_stream(dev))
-    with _WS_LOCK:
-        ws = _FSDT_WS.get(key)
-        if ws is None or ws.numel() < nbytes:
-            ws = torch.zeros(max(nbytes, 1 << 16), dtype=torch.uint8, device=dev)   # ABI: zero-filled once
-            _FSDT_WS[key] = ws
-    return ws
-
-
-def _fsdt_key(geom, flds, bc, bc_values, consts, in_scale, in_num, in_den, flags):
-    """Key of a cached prepared dn_fsdt_apply call (see _call_key); None when an argument needs a conversion copy."""
-    parts = [geom.key, flds[0].device.index, _raw_stream(flds[0].device), consts, flags]
-    for t in flds:
-        k = _tkey(t)
-        if k is None or k == 0 or k[1] != torch.float32:
-            return None
-        parts.append(k)
-    kb = _tkey(bc)
-    if kb is None or (kb != 0 and kb[1] not in (torch.float32, torch.uint8)):
-        return None
-    parts.append(kb)
-    for v in bc_values:
-        if isinstance(v, torch.Tensor) and v.numel() > 1:
-            kv = _tkey(v)
-            if kv is None or kv[1] != torch.float32:
-                return None
-            parts.append(kv)
-        else:
-            parts.append(float(v))
-    for t in (in_scale, in_num, in_den):
-        k = _tkey(t)
-        if k is None or (k != 0 and (k[1] != torch.float32 or k[2] != (3,))):
-            return None
-        parts.append(k)
-    return tuple(parts)
-
-
 class DeferredNorms:
     """Handle of a dn_fsdt_apply launch that left its partial sums of squares in the stream's FSDT reduction workspace (`defer_norms=True`): pass it
     as `norms_from` to the NEXT FSDT launch on that stream, which forms the norms itself.  Any other reducing FSDT launch in between overwrites the
@@ -1366,61 +1275,39 @@ def fsdt_apply(geom, w, phi_x, phi_y, bc=None, bc_values=(0.0, 0.0, 0.0), D11=1.
     if norms_from is not None and (in_num is None or in_den is not None or want_sums):
         raise ValueError("fsdt_apply: norms_from goes with in_num, without in_den and without want_sums")
     consts = tuple(float(x) for x in (D11, D12, D22, D66, A44, A55, q, wscale))
-    flds = (w, phi_x, phi_y)
-    key = None
-    if all(isinstance(t, torch.Tensor) and t.is_cuda for t in flds) and tuple(w.shape[1:]) == (1, *geom.node_shape) and w.shape == phi_x.shape == phi_y.shape:
-        key = _fsdt_key(geom, flds, bc, bc_values, consts, in_scale, in_num, in_den,
-                        (want_out, want_sums, want_norms, bool(defer_norms), None if norms_from is None else norms_from.ws.data_ptr()))
-    ent = None
-    if key is not None:
-        with _WS_LOCK:
-            ent = _FSDT_CACHE.get(key)
-            if ent is not None:
-                _FSDT_CACHE.move_to_end(key)
-    if ent is None:
-        _CALL_STATS["miss" if key is not None else "uncached"] += 1
-        mesh, args, keep, shape = _prepare_fsdt(geom, w, phi_x, phi_y, bc, bc_values, consts, in_scale, in_num, in_den,
-                                                (want_sums or want_norms or defer_norms) and norms_from is None, defer_norms, norms_from)
-        with _WS_LOCK:
-            live_ws = list(_FSDT_WS.values())
-        ent = (mesh, args, C.byref(mesh), C.byref(args), shape, [t for t in keep if any(t is x for x in live_ws)],
-               next((t for t in keep if any(t is x for x in live_ws)), None))
-        if key is not None:
-            with _WS_LOCK:
-                _FSDT_CACHE[key] = ent
-                while len(_FSDT_CACHE) > _CALL_CACHE_MAX:
-                    _FSDT_CACHE.popitem(last=False)
-    else:
-        _CALL_STATS["hit"] += 1
-    mesh, args, mref, aref, shape = ent[:5]
+    # the key of the three-field flow operators, with one mask, no forcing and in_scale as the operator's own optional tensor
+    key = _flow2d_key(geom, (w, phi_x, phi_y), (bc,), bc_values, (), consts, in_num, in_den,
+                      (want_out, want_sums, want_norms, bool(defer_norms), None if norms_from is None else norms_from.ws.data_ptr()), (in_scale,))
+    ent = _op_entry(_FSDT, key, _prepare_fsdt, (geom, w, phi_x, phi_y, bc, bc_values, consts, in_scale, in_num, in_den,
+                                                (want_sums or want_norms or defer_norms) and norms_from is None, defer_norms, norms_from))
     dev = w.device
-    outs = sums = norms = None
+    outs = sums = norms = p0 = pair = None
     if want_out:
-        o3 = torch.empty((3, *shape), dtype=torch.float32, device=dev)      # one allocation, three views
+        o3 = torch.empty((3, *ent[4]), dtype=torch.float32, device=dev)      # one allocation, three views
         outs = list(o3.unbind(0))
+        p0 = o3.data_ptr()
     if want_sums:
         sums = torch.empty(3, dtype=torch.float64, device=dev)
     if want_norms:
         norms = torch.empty(3, dtype=torch.float32, device=dev)
-    with _FSDT_LAUNCH_LOCK:          # pointer patch + launch of the (possibly shared, cached) argument struct as one step
-        if want_out:
-            p0, step = o3.data_ptr(), 4 * o3[0].numel()
-            args.out[0], args.out[1], args.out[2] = p0, p0 + step, p0 + 2 * step
-        if want_sums:
-            args.sumsq = sums.data_ptr()
-        if want_norms:
-            args.norms = norms.data_ptr()
-        if defer_norms:
-            handle = DeferredNorms(ent[6])
-            args.defer_sums = handle.ticket
-        if norms_from is not None:
-            args.den_ticket = norms_from.ticket
-        rc = _lib.lib().dn_fsdt_apply(mref, aref, _stream(w))
-    if rc:
-        _lib.check(rc, "dn_fsdt_apply")
+    if defer_norms:                  # the workspace the prepared call holds: _fsdt_patch puts the launch's handle in its place
+        pair = [next(t for t in ent[5] if t.data_ptr() == ent[1].workspace)]
+    _op_launch(_FSDT, ent, w, _fsdt_patch, ((p0, 4 * outs[0].numel() if want_out else 0, sums.data_ptr() if want_sums else None,
+                                             norms.data_ptr() if want_norms else None), pair, norms_from))
     if defer_norms:
-        return outs, None, handle
+        return outs, None, pair[0]
     return (outs, sums, norms) if want_norms else (outs, sums)
+
+
+def _fsdt_patch(args, ptrs):
+    """_flow2d_patch and, per call, the ticket of a deferring launch (drawn here, under the operator's lock) and of the one it consumes."""
+    out4, pair, norms_from = ptrs
+    _flow2d_patch(args, out4)
+    if pair is not None:
+        pair[0] = DeferredNorms(pair[0])
+        args.defer_sums = pair[0].ticket
+    if norms_from is not None:
+        args.den_ticket = norms_from.ticket
 
 
 def _prepare_fsdt(geom, w, phi_x, phi_y, bc, bc_values, consts, in_scale, in_num, in_den, want_red, defer=False, norms_from=None):
@@ -1435,27 +1322,18 @@ def _prepare_fsdt(geom, w, phi_x, phi_y, bc, bc_values, consts, in_scale, in_num
     args = DnFsdtArgs()
     args.w, args.phi_x, args.phi_y = (t.data_ptr() for t in flds)
 
-    def batched(t, name):
-        if tuple(t.shape[-2:]) != tuple(geom.node_shape) or t.numel() not in (B * geom.nnode_total, geom.nnode_total):
-            raise ValueError(f"fsdt_apply: {name} shape {tuple(t.shape)} does not match the mesh {shape}")
-        return 1 if (t.numel() == B * geom.nnode_total and B > 1) else 0
-
     if bc is not None:
-        if not bc.is_cuda:
+        if isinstance(bc, torch.Tensor) and not bc.is_cuda:
             raise DiffNetHipError("fsdt_apply: bc mask must be on the GPU")
-        if bc.dtype in (torch.bool, torch.uint8):
-            m = bc.to(torch.uint8).contiguous()
-            args.mask_is_u8 = 1
-        else:
-            m = _require(bc, "bc")
-            args.mask_is_u8 = 0
-        args.mask_batched = batched(m, "bc")
+        m, byte = _bc_mask(_FSDT, bc, 0)
+        args.mask_is_u8 = 1 if byte else 0
+        args.mask_batched = _nodal_batched(_FSDT, geom, B, m, "bc")
         args.bc_mask = m.data_ptr()
         keep.append(m)
         for k, v in enumerate(bc_values):
             if isinstance(v, torch.Tensor) and v.numel() > 1:
                 v = _require(v, f"bc_values[{k}]")
-                args.bc_field_batched[k] = batched(v, f"bc_values[{k}]")
+                args.bc_field_batched[k] = _nodal_batched(_FSDT, geom, B, v, f"bc_values[{k}]")
                 args.bc_field[k] = v.data_ptr()
                 keep.append(v)
             else:
@@ -1477,14 +1355,7 @@ def _prepare_fsdt(geom, w, phi_x, phi_y, bc, bc_values, consts, in_scale, in_num
         keep.append(norms_from.ws)
     args.defer_sums = 1 if defer else 0          # (the caller patches the pair's ticket in: fsdt_apply per call, FsdtPlan once)
     if want_red:
-        key = (mesh.nx, mesh.ny, mesh.degree, mesh.ngp, B)
-        nbytes = _FSDT_WS_BYTES.get(key)
-        if nbytes is None:
-            nbytes = _lib.lib().dn_fsdt_workspace_bytes(C.byref(mesh))
-            if nbytes < 0:
-                _lib.check(int(nbytes), "dn_fsdt_workspace_bytes")
-            _FSDT_WS_BYTES[key] = nbytes
-        ws = _fsdt_workspace(flds[0].device, nbytes)
+        ws = _op_workspace(_FSDT, mesh, B, flds[0].device)
         keep.append(ws)
         args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
     return mesh, args, keep, shape
@@ -1549,13 +1420,16 @@ class FsdtPlan:
 
 
 
-# ---- the host call path of the flow, transport and element operators (stokes_apply ... eikonal3d_apply) --------------------------
-# Each operator has a reduction workspace of its OWN per (device, stream), never the one of _workspace or _fsdt_workspace nor another
-# operator's: an FSDT launch with defer_norms leaves its partials in its workspace for a later consumer, and a launch issued in between
-# must not overwrite them.  _FusedOp holds an operator's workspaces, their sizes, its prepared-call cache and its launch lock; every one
-# is listed in _FUSED_OPS (call_cache_clear).  What the calls share is written once, for any dimension: the workspace (_op_workspace), the
-# look-up / prepare / cache step (_op_entry), the patch-under-lock / launch step (_op_launch), the check of a nodal field against the
-# mesh (_nodal_batched), the form of a Dirichlet mask (_bc_mask) and a Gauss-point forcing tensor (_gp_forcing).
+# ---- the host call path of the fused operators (poisson_apply, fsdt_apply, stokes_apply ... fdm_poisson_apply) --------------------
+# Each operator has a reduction workspace of its OWN per (device, stream), never another operator's: an FSDT launch with defer_norms
+# leaves its partials in its workspace for a later `norms_from` consumer, and a reducing launch of another operator issued in between must
+# not overwrite them while the pair's ticket still matches (only FSDT's own reductions clear the ticket; another reducing FSDT launch in
+# between clears it: NaN, never stale).  Launches on one stream are ordered, so they share the operator's workspace of that stream; a
+# launch on another stream gets its own, and a prepared launch (PoissonPlan, FsdtPlan) keeps the one of the stream it was prepared on.
+# _FusedOp holds an operator's workspaces, their sizes, its prepared-call cache and its launch lock; every one is listed in _FUSED_OPS
+# (call_cache_clear).  What the calls share is written once, for any dimension: the workspace (_op_workspace), the look-up / prepare /
+# cache step (_op_entry), the patch-under-lock / launch step (_op_launch), the check of a nodal field against the mesh
+# (_nodal_batched), the form of a Dirichlet mask (_bc_mask) and a Gauss-point forcing tensor (_gp_forcing).
 _FUSED_OPS = []
 
 
@@ -1572,9 +1446,13 @@ class _FusedOp:
         _FUSED_OPS.append(self)
 
 
+_POISSON = _FusedOp("poisson_apply", DnPoissonArgs)      # its cache holds PoissonPlan objects, each with a lock of its own (poisson_apply)
+_FSDT = _FusedOp("fsdt_apply", DnFsdtArgs)
+
+
 def _op_workspace(op, mesh, B, dev):
     """The operator's reduction workspace on the current stream of `dev`, large enough for `mesh` under the launch plan in force."""
-    key = (mesh.nx, mesh.ny, mesh.nz, mesh.degree, mesh.ngp, B)
+    key = (mesh.nx, mesh.ny, mesh.nz, mesh.degree, mesh.ngp, B)          # (nz is 1 on 2-D meshes and on no 3-D one)
     nbytes = op.ws_bytes.get(key)
     if nbytes is None:
         ws_fn = getattr(_lib.lib(), op.ws_fn)

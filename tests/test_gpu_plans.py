@@ -107,7 +107,7 @@ def test_2d_paired_strips_any_strip_height(n, ngp, B):
         for R in (1, 2, 3, 5, 7, 16, 64):
             for E in (2, 4) if n % 4 == 0 else (2,):
                 _lib.config_set("PLAN2D", f"64,{E},{R}")
-                ops._POISSON_WS_BYTES.clear()                      # the workspace size depends on the launch plan
+                ops._POISSON.ws_bytes.clear()                      # the workspace size depends on the launch plan
                 for name, d in conds.items():
                     loss, grad = m.energy_loss_and_grad(u, nu, f, dirichlet=d, c=0.7)
                     l0, g0 = ref[name]
@@ -116,7 +116,7 @@ def test_2d_paired_strips_any_strip_height(n, ngp, B):
                     assert float((grad - g0).abs().max()) <= 1e-5 * scale, f"R={R} E={E} {name}"
     finally:
         _lib.config_set("PLAN2D", "")
-        ops._POISSON_WS_BYTES.clear()
+        ops._POISSON.ws_bytes.clear()
 
 
 @pytest.mark.parametrize("sizes,ngp,B", [((8, 8), 2, 1), ((64, 64), 3, 2), ((64, 40), 2, 3), ((516, 37), 3, 1), ((512, 512), 3, 2)])
@@ -149,7 +149,7 @@ def test_2d_chained_strips_equal_single_strips(sizes, ngp, B):
             res = {}
             for W in (1, 2):
                 _lib.config_set("PLAN2D", f"128,4,{R},{W}" if R else ("128,4,16,1" if W == 1 else ""))
-                ops._POISSON_WS_BYTES.clear()
+                ops._POISSON.ws_bytes.clear()
                 for name, (a, b, d) in cases.items():
                     res[name, W] = m.energy_loss_and_grad(u, a, b, dirichlet=d, c=0.7)
             for name in cases:
@@ -163,7 +163,7 @@ def test_2d_chained_strips_equal_single_strips(sizes, ngp, B):
                     assert float((g2 - g0).abs().max()) <= 1e-5 * scale, f"R={R} {name} vs per-point kernel"
     finally:
         _lib.config_set("PLAN2D", "")
-        ops._POISSON_WS_BYTES.clear()
+        ops._POISSON.ws_bytes.clear()
 
 
 @pytest.mark.parametrize("sizes,B", [((321, 9), 3), ((513, 40), 2), ((385, 17), 1), ((1025, 5), 2), ((325, 33), 2)])

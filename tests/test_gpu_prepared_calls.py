@@ -1,11 +1,12 @@
-"""GPU tests of the host call path of the flow, transport and element operators of diffnet_amd/ops.py (stokes_apply, ns_apply,
-transport_apply, strongform_apply, fosls_apply, helmholtz_apply, eikonal_apply, eikonal3d_apply): the prepared-call cache directly -- a
+"""GPU tests of the host call path of the plate, flow, transport and element operators of diffnet_amd/ops.py (fsdt_apply, stokes_apply,
+ns_apply, transport_apply, strongform_apply, fosls_apply, helmholtz_apply, eikonal_apply, eikonal3d_apply): the prepared-call cache directly -- a
 miss, then a hit; a hit reads the buffers as they are now; a call that needs a conversion copy is not cached and agrees bitwise; the LRU
 bound; call_cache_clear() -- and the type of every argument error, all of which are raised before a launch.
 
 The meshes are the smallest that tell the axes apart: 9 x 7 nodes (Q1 with 2 Gauss points per axis; Q2 with 3 for the element operators),
 6 x 5 x 4 nodes in 3-D, two samples.  Every call has a shared uint8 mask as condition 1, a per-sample fp32 mask with a per-sample value
-field as condition 2, a Gauss-point forcing and its reductions on; the operators with a VJP mode are called in both modes."""
+field as condition 2, a Gauss-point forcing and its reductions on (fsdt_apply, with one mask and no forcing: condition 2 only); the
+operators with a VJP mode are called in both modes."""
 import pytest
 import torch
 
@@ -80,8 +81,21 @@ def _eikonal(ops, g, a):
               in_num=a["in_num"], in_den=a["in_den"], want_sumsq=True, want_norm=True)
 
 
+FSDT_CONSTS = dict(D11=1.0, D12=0.3, D22=1.2, D66=0.35, A44=0.8, A55=0.9, q=1.0, wscale=0.01)
+
+
+def _fsdt(ops, g, a):
+    """One mask (the per-sample one, `m2`), the value field on the second of the three fields; `in_num` / `in_den` where the case has them"""
+    return ops.fsdt_apply(g, a["u"], a["v"], a["p"], a["m2"], (0.0, a["val2"], 0.0), want_sums=True, want_norms=True, in_num=a["in_num"],
+                          in_den=a["in_den"], **FSDT_CONSTS)
+
+
 # id: (operator object's name in ops, caller, mesh, VJP mode, length of in_num / in_den or None, takes nodal f)
 CASES = {
+    "fsdt_q1": ("_FSDT", _fsdt, "q1", False, 3, False),
+    "fsdt_q2": ("_FSDT", _fsdt, "q2", False, 3, False),
+    "fsdt_scaled_q2": ("_FSDT", _fsdt, "q2", True, 3, False),
+    "fsdt_bool_mask_q2": ("_FSDT", _fsdt, "q2", False, 3, False),
     "stokes": ("_STOKES", _stokes, "q1", False, 3, False),
     "ns": ("_NS", _ns, "q1", False, 3, False),
     "ns_vjp": ("_NS", _ns, "q1", True, 3, False),
@@ -100,16 +114,18 @@ CASES = {
     "eikonal3d": ("_EIKONAL3D", _eikonal, "3d", False, 1, True),
     "eikonal3d_vjp": ("_EIKONAL3D", _eikonal, "3d", True, 1, True),
 }
-OPERATORS = ("_STOKES", "_NS", "_TRANSPORT", "_STRONGFORM", "_FOSLS", "_HELMHOLTZ", "_EIKONAL", "_EIKONAL3D")
+OPERATORS = ("_STOKES", "_NS", "_TRANSPORT", "_STRONGFORM", "_FOSLS", "_HELMHOLTZ", "_EIKONAL", "_EIKONAL3D", "_FSDT", "_POISSON", "_FDM_POISSON")
 
 
 class Case:
     def __init__(self, name):
         from diffnet_amd import ops
-        opname, self.fn, mesh, self.vjp, self.nscale, self.nodal_f = CASES[name]
-        self.ops, self.op = ops, getattr(ops, opname)
+        self.opname, self.fn, mesh, self.vjp, self.nscale, self.nodal_f = CASES[name]
+        self.ops, self.op = ops, getattr(ops, self.opname)
         self.geom = _geom(*MESHES[mesh])
         self.args = _inputs(self.geom, self.vjp, self.nscale)
+        if name == "fsdt_bool_mask_q2":
+            self.args["m2"] = self.args["m2"] > 0.5
 
     def __call__(self, **over):
         """The results of one call as a flat list of tensors, with `over` replacing arguments"""
@@ -204,13 +220,52 @@ def test_call_cache_clear_clears_every_operator():
     from diffnet_amd import ops
     objs = [getattr(ops, n) for n in OPERATORS]
     assert len({id(o) for o in objs}) == len(objs) and ops._EIKONAL3D.args_type is ops._EIKONAL.args_type
-    for name in ("stokes", "ns", "transport", "strongform_q1", "fosls_q1", "helmholtz_q1", "eikonal_q1", "eikonal3d"):
+    for name in ("stokes", "ns", "transport", "strongform_q1", "fosls_q1", "helmholtz_q1", "eikonal_q1", "eikonal3d", "fsdt_q1"):
         Case(name)()
+    c = Case("strongform_q1")
+    ops.energy_loss_and_grad(c.geom, c.args["u"], dirichlet=[(c.args["m1"], 0.0)])
+    ops.fdm_poisson_apply(c.args["u"])
     for n, o in zip(OPERATORS, objs):
         assert len(o.cache) >= 1 and len(o.ws_bytes) >= 1 and len(o.ws) >= 1, n
     ops.call_cache_clear()
     for n, o in zip(OPERATORS, objs):
         assert len(o.cache) == 0 and len(o.ws_bytes) == 0, n
+
+
+def test_fsdt_bool_mask_equals_uint8_mask():
+    c = Case("fsdt_bool_mask_q2")
+    assert c.args["m2"].dtype == torch.bool
+    c.clear()
+    assert _same(c(), c(m2=c.args["m2"].to(torch.uint8)))
+    assert c.stats() == {"miss": 2, "hit": 0, "uncached": 0}
+
+
+def test_fsdt_deferred_pair_through_the_cache():
+    """A defer_norms launch and the norms_from launch that consumes its partials, twice on the same buffers (a miss, then a hit, for each
+    of the two calls): the same bits as the two-call form with in-kernel norms, with a Stokes launch between the two calls or without"""
+    c, stokes = Case("fsdt_q2"), Case("stokes")
+    ops, g, a = c.ops, c.geom, c.args
+    flds, bc, vals = (a["u"], a["v"], a["p"]), a["m2"], (0.0, a["val2"], 0.0)
+    wts = cu(torch.tensor([1.0, 2.0, 0.5]))
+    vconsts = dict(FSDT_CONSTS, q=0.0)
+    c.clear()
+    R0, _, n0 = ops.fsdt_apply(g, *flds, bc, vals, want_sums=False, want_norms=True, **FSDT_CONSTS)
+    g0, _ = ops.fsdt_apply(g, *R0, bc, (0.0, 0.0, 0.0), want_sums=False, in_num=wts, in_den=n0, **vconsts)
+    ref = [*R0, *g0, n0]
+    assert all(torch.isfinite(x).all() for x in ref) and float(n0.min()) > 0.0
+    Rbuf = [torch.empty_like(x) for x in R0]                # the consumer's fields: the same buffers in both pairs
+    c.clear()
+    # (the Stokes launch of the second pair is a miss of its own)
+    for between, want in ((False, {"miss": 2, "hit": 0, "uncached": 0}), (True, {"miss": 1, "hit": 2, "uncached": 0})):
+        R, none, h = ops.fsdt_apply(g, *flds, bc, vals, want_sums=False, defer_norms=True, **FSDT_CONSTS)
+        assert none is None and h.ws is c.op.ws[(torch.cuda.current_device(), ops._raw_stream(a["u"].device))]
+        for dst, src in zip(Rbuf, R):
+            dst.copy_(src)
+        if between:
+            assert all(torch.isfinite(x).all() for x in stokes())       # reduces in a workspace of its own
+        G, _, n = ops.fsdt_apply(g, *Rbuf, bc, (0.0, 0.0, 0.0), want_sums=False, want_norms=True, in_num=wts, norms_from=h, **vconsts)
+        assert c.stats() == want
+        assert _same([*R, *G, n], ref), between
 
 
 def _swapped(t):
@@ -227,17 +282,21 @@ def test_argument_errors_keep_their_type(name):
     a = c.args
     c.clear()
     ref = c()
-    with pytest.raises(ValueError):
-        c(m2=None)                                           # a value field without its mask
-    with pytest.raises(DiffNetHipError):
-        c(m1=a["m1"].cpu())
-    with pytest.raises(DiffNetHipError):
+    fsdt = c.opname == "_FSDT"                               # one mask (m2), no forcing: the checks of m1, fgp and f do not apply
+    if fsdt:
+        assert len(c(m2=None)) == len(ref)                   # fsdt_apply reads bc_values only under a mask: no error, as ever
+    else:
+        with pytest.raises(ValueError):
+            c(m2=None)                                       # a value field without its mask
+        with pytest.raises(DiffNetHipError):
+            c(m1=a["m1"].cpu())
+        with pytest.raises(TypeError):
+            c(m1=1.0)
+    with pytest.raises(DiffNetHipError, match="fsdt_apply: bc mask must be on the GPU" if fsdt else None):
         c(m2=a["m2"].cpu())
     with pytest.raises(TypeError):
-        c(m1=1.0)
-    with pytest.raises(TypeError):
         c(m2=a["m2"].cpu().numpy())
-    for key in ("m1", "m2", "val2", "fgp"):
+    for key in ("m2", "val2") if fsdt else ("m1", "m2", "val2", "fgp"):
         for bad in _swapped(a[key]):
             assert bad.shape != a[key].shape
             with pytest.raises(ValueError):

@@ -25,7 +25,7 @@ prepared = {}
 ref = {}
 for plan in plans:
     _lib.config_set("PLAN2D", "" if plan == "default" else plan)
-    ops._POISSON_WS_BYTES.clear()
+    ops._POISSON.ws_bytes.clear()
     for name, d in forms.items():
         pl = ops.PoissonPlan(m.geom, u, nu, f, None, d, alpha=2.0, beta=1.0, c=1.0, wscale=1.0, out_scale=scale, want_out=True, want_sums=True, loss_scale=scale)
         grad, sums, loss = pl.launch()

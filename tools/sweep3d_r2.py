@@ -24,7 +24,7 @@ def run(n, B, plans, reps=100):
     prepared, ref = {}, None
     for plan in plans:
         _lib.config_set("PLAN3D", plan)            # read by dn_poisson_apply at every launch; the workspace size depends on it
-        ops._POISSON_WS_BYTES.clear()
+        ops._POISSON.ws_bytes.clear()
         pl = ops.PoissonPlan(m.geom, u, nu, f, None, [(bc, 0.0)], alpha=2.0, beta=1.0, c=1.0, wscale=1.0, out_scale=scale, want_out=True,
                              want_sums=True, loss_scale=scale)
         grad, _, loss = pl.launch()

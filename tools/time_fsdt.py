@@ -19,7 +19,7 @@ for B in (1, 2, 4, 8):
     bc[..., 0] = 1; bc[..., -1] = 1; bc[..., 0, :] = 1; bc[..., -1, :] = 1
     for plan in plans:
         _lib.config_set("PLAN_FSDT", plan)
-        ops._FSDT_WS_BYTES.clear()
+        ops._FSDT.ws_bytes.clear()
         fn = lambda: ops.fsdt_apply(m.geom, *flds, bc, q=1.0, wscale=(0.5 * m.h) ** 2)
         for _ in range(3):
             fn()

@@ -16,7 +16,7 @@ bc[..., 0] = 1; bc[..., -1] = 1
 scale = 1.0 / (B * m.geom.nelem_total)
 for plan in [""] + sys.argv[4:]:
     _lib.config_set("PLAN2D", plan)
-    ops._POISSON_WS_BYTES.clear()
+    ops._POISSON.ws_bytes.clear()
     pl = ops.PoissonPlan(m.geom, u, nu, f, None, [(bc, 0.0)], alpha=2.0, beta=1.0, c=1.0, wscale=1.0, out_scale=scale, want_out=True, want_sums=True, loss_scale=scale)
     t0 = time.perf_counter()
     while time.perf_counter() - t0 < 0.04:
