@@ -145,6 +145,18 @@ class DnConvK4s2Kernel(C.Structure):
 
 CONV_DOWN, CONV_UP, CONV_WRW = 0, 1, 2
 
+
+class DnPoissonKernel(C.Structure):
+    _fields_ = [("family", C.c_int32), ("tile", C.c_int32 * 2), ("E", C.c_int32), ("R", C.c_int32), ("W", C.c_int32), ("ua", C.c_int32),
+                ("chunks", C.c_int32), ("tiles", C.c_int32), ("strips", C.c_int32), ("launched_strips", C.c_int32),
+                ("vec", C.c_int32), ("allow_e4", C.c_int32), ("compact", C.c_int32),
+                ("launched", C.c_int64), ("stride", C.c_int64), ("workspace_bytes", C.c_int64)]
+
+
+# dn_poisson_kernel.family (DN_POISSON_*)
+POISSON_FAMILIES = {1: "2d_q1_cf", 2: "2d_q1_rule", 3: "2d_q23", 4: "3d_q1_n1", 5: "3d_q1_t16", 6: "3d_q1_generic", 7: "3d_q1_n2", 8: "3d_q1_cfz",
+                    9: "3d_q23"}
+
 I32x3 = C.c_int32 * 3
 
 # name -> (restype, argtypes); must list every symbol of include/diffnet_hip.h
@@ -159,6 +171,7 @@ SYMBOLS = {
     "dn_poisson_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
     "dn_poisson_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnPoissonArgs), C.c_void_p]),
     "dn_poisson_finish_sums": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnPoissonArgs), C.c_void_p]),
+    "dn_poisson_query": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnPoissonArgs), C.POINTER(DnPoissonKernel)]),
     "dn_workspace_status": (C.c_int, [C.c_void_p, C.c_void_p]),
     "dn_gauss_pt_eval_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, I32x3, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_void_p]),

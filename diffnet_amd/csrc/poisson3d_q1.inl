@@ -1008,12 +1008,12 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1n2_kernel(const PoissonPar
 
 // ---- dispatch ---------------------------------------------------------------------------------------------
 template <int NGP, int E, bool VEC, int FL>
-static void launch3_one(const PoissonParams& pp, const Geom3D& g, int batch, hipStream_t s) {
+static void launch3_one(const PoissonParams& pp, const Geom3D& g, int family, int batch, hipStream_t s) {
     const dim3 grid((unsigned)((long long)g.chunks * g.tiles * g.strips * batch)), block(g.TX, g.TY);
     bool unit = true;                                   // the exact 2-point rule: all weights 1
     for (int i = 0; i < NGP; ++i) unit = unit && pp.T.w[i] == 1.0f;
     if constexpr (E == 1 && (FL & (FL3_FGP | FL3_BC)) == 0) {
-        if (g.TX == 16 && g.TY == 16 && pp.nx >= 2 && config(CFG_Q1_3D_T16) == nullptr) {      // node-owner form (every node requested once)
+        if (family == DN_POISSON_3D_Q1_N1) {      // node-owner form (every node requested once)
             constexpr int FL1 = (FL & FL3_BC_U8C) ? (FL | FL3_BC_ONE) : FL;
             const bool one = (FL & FL3_BC_U8C) && ((pp.bc[0].mask != nullptr) != (pp.bc[1].mask != nullptr));
             if constexpr (NGP == 2) {
@@ -1036,7 +1036,7 @@ static void launch3_one(const PoissonParams& pp, const Geom3D& g, int batch, hip
         }
     }
     if constexpr (E == 1) {
-        if (g.TX == 16 && pp.nx >= 2) {                // 16-wide tiles, one element per thread: DPP hand-over, paired loads
+        if (family == DN_POISSON_3D_Q1_T16) {          // 16-wide tiles, one element per thread: DPP hand-over, paired loads
             if constexpr (NGP == 2) {
                 if (unit) {
                     hipLaunchKernelGGL((poisson3d_q1w_kernel<NGP, 1, false, FL, true, true>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
@@ -1058,7 +1058,7 @@ static void launch3_one(const PoissonParams& pp, const Geom3D& g, int batch, hip
 
 // node-owner form with fp32 mask images (constant values); only instantiated for one element per thread and nodal / absent forcing
 template <int NGP, int E, bool VEC, int FL>
-static void launch3_f32n(const PoissonParams& pp, const Geom3D& g, int batch, hipStream_t s) {
+static void launch3_f32n(const PoissonParams& pp, const Geom3D& g, int family, int batch, hipStream_t s) {
     if constexpr (E == 1 && (FL & FL3_FGP) == 0) {
         const dim3 grid((unsigned)((long long)g.chunks * g.tiles * g.strips * batch)), block(16, 16);
         constexpr int F2 = FL | FL3_BC_U8C | FL3_BC_F32, F1 = F2 | FL3_BC_ONE;
@@ -1075,12 +1075,12 @@ static void launch3_f32n(const PoissonParams& pp, const Geom3D& g, int batch, hi
         if (one) hipLaunchKernelGGL((poisson3d_q1n_kernel<NGP, F1, false>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
         else hipLaunchKernelGGL((poisson3d_q1n_kernel<NGP, F2, false>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
     } else {
-        launch3_one<NGP, E, VEC, FL | FL3_BC>(pp, g, batch, s);
+        launch3_one<NGP, E, VEC, FL | FL3_BC>(pp, g, family, batch, s);
     }
 }
 
 template <int NGP, int E, bool VEC>
-static void launch3_flags(const PoissonParams& pp, const Geom3D& g, int batch, hipStream_t s) {
+static void launch3_flags(const PoissonParams& pp, const Geom3D& g, int family, int batch, hipStream_t s) {
     const int f = pp.fgp ? 2 : (pp.f ? 1 : 0);
     const bool bc = pp.bc[0].mask || pp.bc[1].mask;
     bool u8c = bc, f32c = bc;                        // all conditions uint8 / all fp32 images, constant values
@@ -1090,12 +1090,12 @@ static void launch3_flags(const PoissonParams& pp, const Geom3D& g, int batch, h
     }
     // fp32 images with constant values (the reference's masks): the node-owner form reads them as one dword per node; everything else
     // with fp32 masks or value fields goes through the generic form of the T16 kernel
-    const bool f32n = f32c && E == 1 && !pp.fgp && g.TX == 16 && g.TY == 16 && config(CFG_Q1_3D_T16) == nullptr;
+    const bool f32n = f32c && family == DN_POISSON_3D_Q1_N1;
 #define DN_L3(FLAGS)                                                                   \
-    (!bc ? launch3_one<NGP, E, VEC, (FLAGS)>(pp, g, batch, s)                          \
-         : u8c ? launch3_one<NGP, E, VEC, (FLAGS) | FL3_BC_U8C>(pp, g, batch, s)       \
-         : f32n ? launch3_f32n<NGP, E, VEC, (FLAGS)>(pp, g, batch, s)                  \
-               : launch3_one<NGP, E, VEC, (FLAGS) | FL3_BC>(pp, g, batch, s))
+    (!bc ? launch3_one<NGP, E, VEC, (FLAGS)>(pp, g, family, batch, s)                    \
+         : u8c ? launch3_one<NGP, E, VEC, (FLAGS) | FL3_BC_U8C>(pp, g, family, batch, s) \
+         : f32n ? launch3_f32n<NGP, E, VEC, (FLAGS)>(pp, g, family, batch, s)            \
+               : launch3_one<NGP, E, VEC, (FLAGS) | FL3_BC>(pp, g, family, batch, s))
     if (pp.nu) {
         if (f == 0) DN_L3(FL3_NU);
         else if (f == 1) DN_L3(FL3_NU | FL3_F);
@@ -1162,15 +1162,15 @@ static int launch3_n2(const PoissonParams& pp, const Geom3D& g, int batch, hipSt
 
 #define DN_CAT2(a, b) a##b
 #define DN_CAT(a, b) DN_CAT2(a, b)
-int DN_CAT(launch_poisson3d_q1_g, DN_NGP)(const PoissonParams& pp, const Geom3D& g, int batch, bool vec, hipStream_t s) {
+int DN_CAT(launch_poisson3d_q1_g, DN_NGP)(const PoissonParams& pp, const Geom3D& g, int family, int batch, bool vec, hipStream_t s) {
     if (pp.f && pp.f_is_load && !(DN_NGP == 2 && g.E == 2 && g.TX == 16 && g.TY == 16)) return DN_E_UNSUPPORTED;      // load vectors: two-element node-owner form only
-    if (g.E == 1) { launch3_flags<DN_NGP, 1, false>(pp, g, batch, s); return 0; }
+    if (g.E == 1) { launch3_flags<DN_NGP, 1, false>(pp, g, family, batch, s); return 0; }
 #if DN_NGP == 2
     if (g.E == 2 && g.TX == 16 && g.TY == 16) {
-        // round 4: the closed-form-in-z kernel (poisson3d_q1_cf.hip) wherever the launch has a stiffness part; dn_config_set("Q1_3D_N2") keeps the round-3 kernel
-        if (poisson3d_q1_cf_ok(pp) && (!pp.want_sums || pp.T.alpha != 0.f)) return launch_poisson3d_q1_cf(pp, g, batch, s);
+        // node-owner forms, two elements per thread (poisson_choose checked their preconditions): closed form in z (poisson3d_q1_cf.hip) or marching
+        if (family == DN_POISSON_3D_Q1_CFZ) return launch_poisson3d_q1_cf(pp, g, batch, s);
         return launch3_n2(pp, g, batch, s);
-    }       // node-owner form, two elements per thread (dn_poisson_apply checked its preconditions)
+    }
 #endif
     return DN_E_UNSUPPORTED;
 }

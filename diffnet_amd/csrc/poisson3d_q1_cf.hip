@@ -595,17 +595,8 @@ static void launch_cf3_bc(const PoissonParams& pp, const Cf3Consts& kc, const di
 #undef DN_CF3
 }
 
-// May this launch run the closed-form kernel?  (dn_poisson_apply has checked q1n2_ok(): exact 2-point rule, even nx, aligned pairs, nodal /
-// absent / pre-assembled forcing, constant-value conditions as images of one kind or box faces.)  It needs a stiffness part (the scales of its
-// records divide by alpha) and takes the energy from the nodal values.
-bool poisson3d_q1_cf_ok(const PoissonParams& pp) {
-    if (config(CFG_Q1_3D_N2) != nullptr || config(CFG_Q1_3D_E1SUM) != nullptr) return false;
-    if (!(pp.T.alpha != 0.f) || !std::isfinite(pp.T.alpha)) return false;
-    if (!(pp.T.kap[0] != 0.f && pp.T.kap[1] != 0.f && pp.T.kap[2] != 0.f)) return false;
-    if (std::fabs(pp.T.b[0][1] + pp.T.b[1][1] - 1.0f) > 1e-6f) return false;        // the closed form assumes the symmetric rule
-    return true;
-}
-
+// poisson_choose (poisson_fused.hip) sends a launch here when it has a stiffness part (the scales of the records divide by alpha), the rule is
+// the symmetric exact 2-point one and the preconditions of the two-element node-owner form hold.
 int launch_poisson3d_q1_cf(const PoissonParams& pp, const Geom3D& g, int batch, hipStream_t s) {
     if (!(g.E == 2 && g.TX == 16 && g.TY == 16)) return DN_E_UNSUPPORTED;
     // constants of the closed form, in double from the rule's own table entries (unit weights)

@@ -276,13 +276,12 @@ int launch_poisson2d_q1_g4(const PoissonParams& pp, const Geom2D& g, int batch, 
 // closed-form 2-D Q1 kernel (poisson2d_q1_cf.hip): any rule, nodal forcing
 int launch_poisson2d_q1_cf(const PoissonParams& pp, const Geom2D& g, int batch, bool vec, hipStream_t s);
 int poisson2d_q1_cf_chain();      // strips per workgroup the library's closed-form kernel was built to chain (1: none)
-// 3-D Q1 marching kernels likewise (poisson3d_q1_g{2,3,4}.hip)
-int launch_poisson3d_q1_g2(const PoissonParams& pp, const Geom3D& g, int batch, bool vec, hipStream_t s);
-int launch_poisson3d_q1_g3(const PoissonParams& pp, const Geom3D& g, int batch, bool vec, hipStream_t s);
-int launch_poisson3d_q1_g4(const PoissonParams& pp, const Geom3D& g, int batch, bool vec, hipStream_t s);
+// 3-D Q1 marching kernels likewise (poisson3d_q1_g{2,3,4}.hip); family: the DN_POISSON_3D_Q1_* value poisson_choose picked (poisson_fused.hip)
+int launch_poisson3d_q1_g2(const PoissonParams& pp, const Geom3D& g, int family, int batch, bool vec, hipStream_t s);
+int launch_poisson3d_q1_g3(const PoissonParams& pp, const Geom3D& g, int family, int batch, bool vec, hipStream_t s);
+int launch_poisson3d_q1_g4(const PoissonParams& pp, const Geom3D& g, int family, int batch, bool vec, hipStream_t s);
 
 // closed-form-in-z 3-D Q1 kernel (poisson3d_q1_cf.hip): exact 2-point rule, two elements per thread, energy from the nodal values
-bool poisson3d_q1_cf_ok(const PoissonParams& pp);
 int launch_poisson3d_q1_cf(const PoissonParams& pp, const Geom3D& g, int batch, hipStream_t s);
 
 // 3-D Q2 / Q3 (poisson3d_gen.hip): element vectors + fixed-order gather assembly; its workspace lies behind the common header (DN_WS_HEADER)

@@ -338,21 +338,38 @@ static Geom3D plan3d_env(const dn_mesh* m, bool allow_e2 = false, bool need_e2 =
     return g;
 }
 
-static long long num_workgroups(const dn_mesh* m, bool allow_e4 = true) {
+// What of (args, switches) the geometry of a mesh depends on.  poisson_choose derives the traits of one call; num_workgroups walks
+// through every combination a call on the mesh can have.
+struct PlanTraits {
+    bool e4;          // 2-D: rows of the call's arrays are 16-byte aligned (four elements per thread are legal)
+    bool cf;          // 2-D: the closed-form Q1 kernel takes the launch (it alone has the CF_UA geometry of 4 k + 1 wide rows)
+    bool chain;       // 2-D: chained strips allowed (closed-form kernel, no split evaluation)
+    bool e2;          // 3-D: the two-element node-owner forms are legal
+    bool need_e2;     // 3-D: ... and the call has something only they implement (plan3d_env)
+};
+
+// Geometry of (mesh, traits) into g2 / g3 (whichever the mesh's dimension needs); returns the workgroups of a launch over all strips, one
+// strip per workgroup.
+static long long plan_geometry(const dn_mesh* m, const PlanTraits& t, Geom2D& g2, Geom3D& g3) {
     if (m->nsd == 2) {
-        const Geom2D g = plan2d_env(m, m->degree, allow_e4);
-        const Geom2D gu = plan2d_env(m, m->degree, allow_e4, false, true);          // (the CF_UA form of 4 k + 1 wide meshes has its own geometry)
-        return std::max((long long)g.chunks * g.strips, (long long)gu.chunks * gu.strips) * m->batch;
+        g2 = plan2d_env(m, m->degree, t.e4, t.chain, t.cf);
+        if (!t.chain) g2.W = 1;                          // (a "PLAN2D" override may ask for chained strips where they do not exist)
+        return (long long)g2.chunks * g2.strips * m->batch;
     }
-    // 3-D: the launch is either the one-element forms or, where q1n2_ok() holds, the two-element node-owner form with its own tiling and strip
-    // height (and its own "PLAN3D" overrides): the partial-sum arrays are laid out for whichever has more workgroups
-    const Geom3D g = plan3d_env(m, false);
-    long long n = (long long)g.chunks * g.tiles * g.strips * m->batch;
-    if (m->ngp == 2) {
-        const Geom3D g2 = plan3d_env(m, true), g2n = plan3d_env(m, true, true);
-        n = std::max(n, (long long)g2.chunks * g2.tiles * g2.strips * m->batch);
-        n = std::max(n, (long long)g2n.chunks * g2n.tiles * g2n.strips * m->batch);
-    }
+    g3 = plan3d_env(m, t.e2, t.need_e2);
+    return (long long)g3.chunks * g3.tiles * g3.strips * m->batch;
+}
+
+// Workgroups the two partial-sum arrays of a call are laid out for: the most any launch plan of the mesh has, over the traits the call's
+// alignment leaves open -- 2-D: closed-form kernel (CF_UA geometry) or not; 3-D: one element per thread or, with the 2-point rule, two (with
+// and without the "PLAN3D" E = 1 override being ignored).
+static long long num_workgroups(const dn_mesh* m, bool e4) {
+    Geom2D g2;
+    Geom3D g3;
+    long long n = plan_geometry(m, {e4, false, false, false, false}, g2, g3);
+    if (m->nsd == 2) return std::max(n, plan_geometry(m, {e4, true, false, false, false}, g2, g3));
+    if (m->ngp == 2)
+        for (int need = 0; need < 2; ++need) n = std::max(n, plan_geometry(m, {e4, false, false, true, need != 0}, g2, g3));
     return n;
 }
 
@@ -397,11 +414,8 @@ static int launch2d_e(const PoissonParams& pp, const Geom2D& g, int batch, bool 
     return DN_E_UNSUPPORTED;
 }
 
-static int launch2d(const PoissonParams& pp, const Geom2D& g, int P, int ngp, int batch, bool vec, hipStream_t s) {
-    // Q1 with nodal (or absent) forcing: closed-form element kernel, cost independent of the number of Gauss points;
-    // forcing given at the Gauss points goes through the per-rule marching kernels
-    const bool force_rule = config(CFG_Q1_RULE_KERNEL) != nullptr;              // A/B switch (dn_config_set)
-    if (P == 1 && pp.fgp == nullptr && !force_rule) return launch_poisson2d_q1_cf(pp, g, batch, vec, s);
+static int launch2d(const PoissonParams& pp, const Geom2D& g, int family, int P, int ngp, int batch, bool vec, hipStream_t s) {
+    if (family == DN_POISSON_2D_Q1_CF) return launch_poisson2d_q1_cf(pp, g, batch, vec, s);
     switch (P * 10 + ngp) {
         case 12: return launch_poisson2d_q1_g2(pp, g, batch, vec, s);
         case 13: return launch_poisson2d_q1_g3(pp, g, batch, vec, s);
@@ -418,10 +432,10 @@ static int launch2d(const PoissonParams& pp, const Geom2D& g, int P, int ngp, in
 
 // May the launch of (mesh, args) run the 3-D node-owner kernel with two elements per thread?  (exact 2-point rule, even nx, 8-byte aligned
 // node pairs, nodal / absent forcing, constant-value conditions held as images of one kind)
+// The switches that keep such a launch on the one-element forms are poisson_choose's business.
 static bool q1n2_ok(const dn_mesh* m, const dn_poisson_args* a) {
     if (m->nsd != 3 || m->degree != 1 || m->ngp != 2 || (m->nx & 1) || a->f_gp) return false;
     if (m->gpw[0] != 1.0f || m->gpw[1] != 1.0f) return false;
-    if (dn::config(dn::CFG_Q1_3D_T16) != nullptr || dn::config(dn::CFG_Q1_3D_E1) != nullptr) return false;
     auto al = [](const void* p, uintptr_t bytes) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % bytes) == 0; };
     if (!al(a->u, 8) || !al(a->nu, 8) || !al(a->f, 8) || !al(a->out, 8)) return false;
     int kinds = 0;
@@ -434,14 +448,6 @@ static bool q1n2_ok(const dn_mesh* m, const dn_poisson_args* a) {
         else return false;
     }
     return kinds != 3;
-}
-
-// Does the launch of (mesh, args) need the 3-D two-element form (plan3d_env: need_e2)?  Box faces, a fold of an earlier launch and a load
-// vector have no one-element path.
-static bool q1n2_needed(const dn_poisson_args* a) {
-    for (int k = 0; k < 2; ++k)
-        if (a->bc[k].mask_kind == DN_MASK_BOX && a->bc[k].box_faces != 0) return true;
-    return a->fold_prev != nullptr || (a->f_is_load && a->f);
 }
 
 namespace dn {
@@ -471,11 +477,7 @@ extern "C" int64_t dn_poisson_workspace_bytes(const dn_mesh* mesh) {
     return DN_WS_HEADER + (int64_t)(2 * sizeof(double)) * n;
 }
 
-static long long launched_workgroups(const dn_mesh* m, const dn_poisson_args* a);
-
-// Vector loads / stores of NW nodes are legal when every row segment of every array of the call starts NW-element aligned.  ONE definition:
-// dn_poisson_apply picks the launch geometry with it, dn_poisson_finish_sums / launched_workgroups must arrive at the same geometry (the
-// stride between the two partial-sum arrays is the launch's workgroup count).
+// Vector loads / stores of NW nodes are legal when every row segment of every array of the call starts NW-element aligned.
 static bool poisson_vec_ok(const dn_mesh* m, const dn_poisson_args* a, int NW) {
     auto aligned = [](const void* p, int bytes) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % bytes) == 0; };
     bool ok = (NW == 2 || NW == 4) && (m->nx % NW == 0) && aligned(a->u, 4 * NW) && aligned(a->nu, 4 * NW) && aligned(a->f, 4 * NW) &&
@@ -486,7 +488,33 @@ static bool poisson_vec_ok(const dn_mesh* m, const dn_poisson_args* a, int NW) {
     return ok;
 }
 
-extern "C" int dn_poisson_apply(const dn_mesh* m, const dn_poisson_args* a, void* stream) {
+// kappa_d = alpha wscale (h_d / 2)^2 as the 3-D Q1 kernels take it (PoissonParams::T.kap); poisson_choose tests the same value
+static inline float q1_kap(const dn_mesh* m, const dn_poisson_args* a, int d) {
+    const float hs = 0.5f * m->scale[d];
+    const float hs2 = hs * hs;
+    return a->alpha * a->wscale * hs2;
+}
+
+// The launch plan of one call: everything dn_poisson_apply decides before its first launch.
+struct PoissonChoice {
+    int family = 0;               // DN_POISSON_* (include/diffnet_hip.h): one value per kernel template
+    Geom2D g2 = {};               // the geometry of the mesh's dimension, `strips` counting those of the whole mesh
+    Geom3D g3 = {};
+    bool vec = false;             // vector loads / stores of the E * P nodes a thread owns per row are legal
+    bool allow_e4 = false;        // 16-byte aligned rows throughout
+    int compact = 0;              // conditions taken without an image: 0 none, 1 box faces, 2 box faces and bit arrays
+    int strips = 0;               // strips this launch covers (strip_select applied)
+    long long launched = 0;       // workgroups of this launch = per-workgroup partial sums it leaves
+    long long stride = 0;         // workgroups the two partial-sum arrays are laid out for
+    int64_t ws_bytes = 0;         // workspace a reducing call needs
+    long long fold_launched = 0, fold_stride = 0;      // the same two numbers of the launch that fold_prev describes
+};
+
+// THE decision: which kernel family and which geometry the call (mesh, args) gets under the current switches, and the DN_E_* code
+// dn_poisson_apply returns for it (0: it launches).  Host only -- pointers are looked at for NULL-ness and alignment.  dn_poisson_apply launches
+// what it says, dn_poisson_finish_sums and a folding launch read an earlier call's partial count and stride from it, dn_poisson_query returns
+// it.  follow_fold = false: fold_prev counts only as present / absent (the asking side is itself the reader of those partials).
+static int poisson_choose(const dn_mesh* m, const dn_poisson_args* a, PoissonChoice& c, bool follow_fold = true) {
     int rc = validate_mesh(m);
     if (rc) return rc;
     if (!a || !a->u) return DN_E_BADARG;
@@ -495,7 +523,14 @@ extern "C" int dn_poisson_apply(const dn_mesh* m, const dn_poisson_args* a, void
     const int P = m->degree;
     const bool gen3d = m->nsd == 3 && P != 1;            // Q2 / Q3 in 3-D: poisson3d_gen.hip (needs its workspace even without sums)
     if (m->ngp < (P == 1 ? 2 : 3)) return DN_E_UNSUPPORTED;
-    bool packed_bc = false;                   // bit-packed / geometry-derived conditions: 2-D Q1, nodal or absent forcing, constant values
+    // Q1 with nodal (or absent) forcing: closed-form element kernel, cost independent of the number of Gauss points; forcing given at the
+    // Gauss points goes through the per-rule marching kernels ("Q1_RULE_KERNEL": A/B switch, all of Q1 through them)
+    const bool cf2d = m->nsd == 2 && P == 1 && a->f_gp == nullptr && config(CFG_Q1_RULE_KERNEL) == nullptr;
+    // 3-D, exact 2-point rule: two elements per thread unless a switch keeps the one-element forms ("Q1_3D_T16" also picks among those)
+    const bool t16 = config(CFG_Q1_3D_T16) != nullptr;
+    const bool e2 = !gen3d && q1n2_ok(m, a) && !t16 && config(CFG_Q1_3D_E1) == nullptr;
+    c.compact = cf2d ? 2 : (e2 ? 1 : 0);
+    bool packed_bc = false;                   // bit-packed / geometry-derived conditions: constant values
     for (int k = 0; k < 2; ++k) {
         const dn_dirichlet& d = a->bc[k];
         if (d.mask_kind < DN_MASK_F32 || d.mask_kind > DN_MASK_BOX) return DN_E_BADARG;
@@ -510,21 +545,125 @@ extern "C" int dn_poisson_apply(const dn_mesh* m, const dn_poisson_args* a, void
         // 3-D (round 4): box faces -- no bit arrays -- are taken by the two-element node-owner kernel, alone or beside mask images
         for (int k = 0; k < 2; ++k)
             if (a->bc[k].mask_kind == DN_MASK_BITS) return DN_E_UNSUPPORTED;
-        if (gen3d || !q1n2_ok(m, a)) return DN_E_UNSUPPORTED;
+        if (!e2) return DN_E_UNSUPPORTED;
     } else if (packed_bc) {
-        if (m->nsd != 2 || P != 1 || a->f_gp || config(CFG_Q1_RULE_KERNEL) != nullptr) return DN_E_UNSUPPORTED;
+        if (!cf2d) return DN_E_UNSUPPORTED;
         for (int k = 0; k < 2; ++k) {         // the compact form does not mix with per-node mask images
             const dn_dirichlet& d = a->bc[k];
             if (d.mask && (d.mask_kind == DN_MASK_F32 || d.mask_kind == DN_MASK_U8)) return DN_E_UNSUPPORTED;
         }
     }
     const bool want_red = a->energy || a->sumsq || a->energy_f32;
-    auto vec_ok = [&](int NW) { return poisson_vec_ok(m, a, NW); };
-    const bool allow_e4 = vec_ok(4);
-    const long long nwg = gen3d ? 1 : num_workgroups(m, allow_e4);
-    if (nwg >= (1ll << 31)) return DN_E_UNSUPPORTED;                  // the 3-D launch is a 1-D grid
-    if (!gen3d && want_red && (!a->workspace || a->workspace_bytes < DN_WS_HEADER + (int64_t)(2 * sizeof(double)) * nwg)) return DN_E_WORKSPACE;
+    c.allow_e4 = poisson_vec_ok(m, a, 4);
+    long long gen_n1 = 0, gen_n2 = 0, gen_floats = 0;
+    if (gen3d) gen3d_layout(m, gen_n1, gen_n2, gen_floats);
+    // the partial arrays are laid out for the most workgroups any plan of the mesh has at this alignment (3-D Q2 / Q3: its element kernel's)
+    c.stride = gen3d ? gen_n1 : num_workgroups(m, c.allow_e4);
+    c.ws_bytes = gen3d ? DN_WS_HEADER + (int64_t)sizeof(double) * (gen_n1 + gen_n2) + (int64_t)sizeof(float) * gen_floats
+                       : DN_WS_HEADER + (int64_t)(2 * sizeof(double)) * c.stride;
+    if (!gen3d && c.stride >= (1ll << 31)) return DN_E_UNSUPPORTED;                  // the 3-D launch is a 1-D grid
+    if (!gen3d && want_red && (!a->workspace || a->workspace_bytes < c.ws_bytes)) return DN_E_WORKSPACE;
     if ((int64_t)m->nx * m->ny * (m->nsd == 3 ? m->nz : 1) >= (1ll << 30)) return DN_E_UNSUPPORTED;   // 32-bit in-sample offsets
+    if (a->f_is_load && a->f && !e2) return DN_E_UNSUPPORTED;      // load vectors: the 3-D two-element kernels only (so far)
+    // fold_prev: this launch's first workgroup closes an earlier evaluation (its partial sums, left with defer_sums, lie in ITS workspace)
+    if (a->fold_prev && follow_fold) {
+        const dn_poisson_args* q = a->fold_prev;
+        if (gen3d || !q->defer_sums || !q->workspace || !(q->energy || q->sumsq || q->energy_f32)) return DN_E_BADARG;
+        if (q->accumulate_sums && !(q->energy && q->sumsq)) return DN_E_BADARG;
+        if (q->workspace == a->workspace && want_red) return DN_E_BADARG;        // this launch would overwrite the partials while they are read
+        PoissonChoice qc;                      // (the earlier call, planned on THIS launch's mesh)
+        if ((rc = poisson_choose(m, q, qc, false)) != 0) return rc;
+        if (qc.launched > qc.stride) return DN_E_WORKSPACE;
+        if (!cf2d && !e2) return DN_E_UNSUPPORTED;
+        c.fold_launched = qc.launched;
+        c.fold_stride = qc.stride;
+    }
+    // split evaluation (dn_poisson_args.strip_select): a launch over the first and the last strip of the marched axis, or over the rest
+    if (a->strip_select < 0 || a->strip_select > 2) return DN_E_BADARG;
+    if (a->accumulate_sums && want_red && !(a->energy && a->sumsq)) return DN_E_BADARG;      // the running sums live in the two double slots
+    if (gen3d) {
+        if (a->strip_select != 0 || a->accumulate_sums || a->defer_sums) return DN_E_UNSUPPORTED;      // no split evaluation of this form
+        if (gen_n1 >= (1ll << 31) || gen_n2 >= (1ll << 31)) return DN_E_UNSUPPORTED;
+        if (!a->workspace || a->workspace_bytes < c.ws_bytes) return DN_E_WORKSPACE;
+        c.family = DN_POISSON_3D_Q23;
+        c.launched = gen_n1;
+        return 0;
+    }
+    int strips_all;
+    long long per_strip;                       // workgroups per launched strip (2-D: per chain of W strips)
+    if (m->nsd == 2) {
+        // chained strips: only the closed-form Q1 kernel has them, and a split evaluation selects whole strips
+        plan_geometry(m, {c.allow_e4, cf2d, cf2d && a->strip_select == 0, false, false}, c.g2, c.g3);
+        c.family = P > 1 ? DN_POISSON_2D_Q23 : (cf2d ? DN_POISSON_2D_Q1_CF : DN_POISSON_2D_Q1_RULE);
+        c.vec = poisson_vec_ok(m, a, c.g2.E * P);
+        strips_all = c.g2.strips;
+        per_strip = (long long)c.g2.chunks * m->batch;
+    } else {
+        // box faces, a fold of an earlier launch and a load vector have no one-element path (plan3d_env: need_e2)
+        bool need_e2 = a->fold_prev != nullptr || (a->f_is_load && a->f);
+        for (int k = 0; k < 2; ++k) need_e2 = need_e2 || (a->bc[k].mask_kind == DN_MASK_BOX && a->bc[k].box_faces != 0);
+        plan_geometry(m, {c.allow_e4, false, false, e2, need_e2}, c.g2, c.g3);
+        const Geom3D& g = c.g3;
+        if (g.E == 2) {
+            // the closed-form-in-z kernel wherever the launch has a stiffness part (the scales of its records divide by alpha, and it takes the
+            // energy from the nodal values) and the rule is the symmetric one; "Q1_3D_N2" / "Q1_3D_E1SUM" keep the marching two-element kernel
+            const bool cfz = config(CFG_Q1_3D_N2) == nullptr && config(CFG_Q1_3D_E1SUM) == nullptr && a->alpha != 0.f && std::isfinite(a->alpha) &&
+                             q1_kap(m, a, 0) != 0.f && q1_kap(m, a, 1) != 0.f && q1_kap(m, a, 2) != 0.f &&
+                             !(std::fabs(m->basis[0][1] + m->basis[1][1] - 1.0f) > 1e-6f);
+            c.family = cfz ? DN_POISSON_3D_Q1_CFZ : DN_POISSON_3D_Q1_N2;
+        } else {
+            // one element per thread.  Node-owner form (every node requested once): 16 x 16 tiles, nodal / absent forcing, conditions that are
+            // all uint8 or all fp32 images with constant values; otherwise 16-wide tiles run the T16 form (DPP hand-over along x, paired
+            // loads) and every other width the generic one
+            bool img = false, u8c = true, f32c = true;
+            for (int k = 0; k < 2; ++k) {
+                const dn_dirichlet& d = a->bc[k];
+                if (d.mask_kind == DN_MASK_BOX || !d.mask) continue;
+                img = true;
+                if (d.mask_kind != DN_MASK_U8 || d.field) u8c = false;
+                if (d.mask_kind == DN_MASK_U8 || d.field) f32c = false;
+            }
+            const bool owner = g.TX == 16 && g.TY == 16 && !t16 && !a->f_gp && (!img || u8c || f32c);
+            c.family = owner ? DN_POISSON_3D_Q1_N1 : (g.TX == 16 ? DN_POISSON_3D_Q1_T16 : DN_POISSON_3D_Q1_GENERIC);
+        }
+        c.vec = poisson_vec_ok(m, a, g.E);
+        strips_all = g.strips;
+        per_strip = (long long)g.chunks * g.tiles * m->batch;
+    }
+    c.strips = a->strip_select == 1 ? std::min(strips_all, 2) : (a->strip_select == 2 ? std::max(strips_all - 2, 0) : strips_all);
+    c.launched = per_strip * (m->nsd == 2 ? (c.strips + c.g2.W - 1) / c.g2.W : c.strips);
+    // (the partial-sum arrays were laid out for `stride` workgroups: never launch more than that)
+    if (want_red && c.launched > c.stride) return DN_E_WORKSPACE;
+    return 0;
+}
+
+extern "C" int dn_poisson_query(const dn_mesh* m, const dn_poisson_args* a, dn_poisson_kernel* out) {
+    if (!out) return DN_E_BADARG;
+    PoissonChoice c;
+    const int rc = poisson_choose(m, a, c);
+    *out = dn_poisson_kernel{};
+    out->family = c.family;
+    if (m && m->nsd == 2) {
+        out->tile[0] = c.g2.T;
+        out->E = c.g2.E; out->R = c.g2.R; out->W = c.g2.W; out->ua = c.g2.ua;
+        out->chunks = c.g2.chunks; out->tiles = 1; out->strips = c.g2.strips;
+    } else if (c.family != DN_POISSON_3D_Q23) {
+        out->tile[0] = c.g3.TX; out->tile[1] = c.g3.TY;
+        out->E = c.g3.E; out->R = c.g3.R; out->W = 1;
+        out->chunks = c.g3.chunks; out->tiles = c.g3.tiles; out->strips = c.g3.strips;
+    }
+    out->launched_strips = c.strips;
+    out->vec = c.vec; out->allow_e4 = c.allow_e4; out->compact = c.compact;
+    out->launched = c.launched; out->stride = c.stride; out->workspace_bytes = c.ws_bytes;
+    return rc;
+}
+
+extern "C" int dn_poisson_apply(const dn_mesh* m, const dn_poisson_args* a, void* stream) {
+    PoissonChoice c;
+    int rc = poisson_choose(m, a, c);
+    if (rc) return rc;
+    const int P = m->degree;
+    const bool want_red = a->energy || a->sumsq || a->energy_f32;
 
     PoissonParams pp;
     for (int i = 0; i < 4; ++i) {
@@ -573,7 +712,7 @@ extern "C" int dn_poisson_apply(const dn_mesh* m, const dn_poisson_args* a, void
     for (int g = 0; g < 4; ++g) pp.T.wb[g] = m->gpw[g] * m->basis[g][1];
     for (int d = 0; d < 3; ++d) {
         pp.T.hs2[d] = pp.T.hs[d] * pp.T.hs[d];
-        pp.T.kap[d] = a->alpha * a->wscale * pp.T.hs2[d];
+        pp.T.kap[d] = q1_kap(m, a, d);
     }
     pp.T.m01 = pp.T.m[0] - pp.T.m[1]; pp.T.m12 = pp.T.m[1] - pp.T.m[2];
     pp.T.esc = a->wscale; pp.T.nbw = -a->beta * a->wscale;
@@ -581,7 +720,6 @@ extern "C" int dn_poisson_apply(const dn_mesh* m, const dn_poisson_args* a, void
     pp.u = a->u; pp.nu = a->nu; pp.f = a->f; pp.fgp = a->f_gp;
     pp.nu_batched = a->nu_batched; pp.f_batched = a->f_batched;
     pp.f_is_load = (a->f_is_load && a->f) ? 1 : 0;
-    if (pp.f_is_load && !(m->nsd == 3 && !gen3d && q1n2_ok(m, a))) return DN_E_UNSUPPORTED;      // load vectors: the 3-D two-element kernel only (so far)
     for (int k = 0; k < 2; ++k) {
         const dn_dirichlet& d = a->bc[k];
         const bool present = d.mask_kind == DN_MASK_BOX ? d.box_faces != 0 : d.mask != nullptr;
@@ -594,7 +732,7 @@ extern "C" int dn_poisson_apply(const dn_mesh* m, const dn_poisson_args* a, void
     pp.out_scale = a->out_scale; pp.out = a->out;
     pp.counter = reinterpret_cast<unsigned*>(a->workspace);
     pp.part_energy = a->workspace ? reinterpret_cast<double*>(reinterpret_cast<char*>(a->workspace) + DN_WS_HEADER) : nullptr;
-    pp.part_sumsq = pp.part_energy ? pp.part_energy + nwg : nullptr;
+    pp.part_sumsq = pp.part_energy ? pp.part_energy + c.stride : nullptr;
     pp.energy = a->energy; pp.sumsq = a->sumsq;
     pp.energy_f32 = a->energy_f32; pp.energy_scale = a->energy_scale;
     pp.nx = m->nx; pp.ny = m->ny; pp.nz = m->nsd == 3 ? m->nz : 1;
@@ -606,93 +744,53 @@ extern "C" int dn_poisson_apply(const dn_mesh* m, const dn_poisson_args* a, void
     pp.fold_n = 0;
     if (a->fold_prev) {
         const dn_poisson_args* q = a->fold_prev;
-        if (gen3d || !q->defer_sums || !q->workspace || !(q->energy || q->sumsq || q->energy_f32)) return DN_E_BADARG;
-        if (q->accumulate_sums && !(q->energy && q->sumsq)) return DN_E_BADARG;
-        if (q->workspace == a->workspace && want_red) return DN_E_BADARG;        // this launch would overwrite the partials while they are read
-        const long long qn = launched_workgroups(m, q), qstride = num_workgroups(m, poisson_vec_ok(m, q, 4));
-        if (q->workspace_bytes < DN_WS_HEADER + (int64_t)(2 * sizeof(double)) * qstride || qn > qstride) return DN_E_WORKSPACE;
-        const bool cf2d = m->nsd == 2 && P == 1 && a->f_gp == nullptr && config(CFG_Q1_RULE_KERNEL) == nullptr;
-        if (!cf2d && !(m->nsd == 3 && q1n2_ok(m, a))) return DN_E_UNSUPPORTED;
         pp.fold_pe = reinterpret_cast<const double*>(reinterpret_cast<const char*>(q->workspace) + DN_WS_HEADER);
-        pp.fold_ps = pp.fold_pe + qstride;
-        pp.fold_n = (int)qn;
+        pp.fold_ps = pp.fold_pe + c.fold_stride;
+        pp.fold_n = (int)c.fold_launched;
         pp.fold_energy = q->energy; pp.fold_sumsq = q->sumsq; pp.fold_energy_f32 = q->energy_f32;
         pp.fold_scale = q->energy_scale;
         pp.fold_acc = q->accumulate_sums ? 1 : 0;
     }
-
-    // split evaluation (dn_poisson_args.strip_select): a launch over the first and the last strip of the marched axis, or over the rest
-    if (a->strip_select < 0 || a->strip_select > 2) return DN_E_BADARG;
-    if (a->accumulate_sums && want_red && !(a->energy && a->sumsq)) return DN_E_BADARG;      // the running sums live in the two double slots
     pp.strip_sel = a->strip_select;
     pp.acc_sums = (a->accumulate_sums && want_red && !a->defer_sums) ? 1 : 0;      // (deferred: dn_poisson_finish_sums accumulates)
     pp.defer_sums = (a->defer_sums && want_red) ? 1 : 0;
-    auto launched = [&](int total) { return a->strip_select == 1 ? std::min(total, 2) : (a->strip_select == 2 ? std::max(total - 2, 0) : total); };
-    // a split launch left without strips still closes the evaluation it folds: the one-workgroup finish kernel forms prev's scalars
-    auto no_strips = [&]() {
+    if (c.family == DN_POISSON_3D_Q23) {
+        rc = launch_poisson3d_gen(pp, m, a->workspace, a->workspace_bytes, s);
+        if (rc) return rc;
+        DN_LAUNCH_CHECK();
+        return 0;
+    }
+    if (c.strips == 0) {
+        // fewer than three strips: the other launch of the split evaluation did everything.  This one still closes the evaluation it folds: the
+        // one-workgroup finish kernel forms prev's scalars
         if (pp.fold_n > 0) {
             hipLaunchKernelGGL(poisson_finish_sums_kernel, dim3(1), dim3(256), 0, s, pp.fold_pe, pp.fold_ps, pp.fold_n, pp.fold_energy, pp.fold_sumsq,
                                pp.fold_energy_f32, pp.fold_scale, pp.fold_acc);
             DN_LAUNCH_CHECK();
         }
         return 0;
-    };
-    if (gen3d) {
-        if (a->strip_select != 0 || a->accumulate_sums || a->defer_sums) return DN_E_UNSUPPORTED;      // no split evaluation of this form
-        rc = launch_poisson3d_gen(pp, m, a->workspace, a->workspace_bytes, s);
-        if (rc) return rc;
-        DN_LAUNCH_CHECK();
-        return 0;
     }
     if (m->nsd == 2) {
-        // chained strips: only the closed-form Q1 kernel has them, and a split evaluation selects whole strips
-        const bool chain_ok = P == 1 && a->f_gp == nullptr && config(CFG_Q1_RULE_KERNEL) == nullptr && a->strip_select == 0;
-        const bool cf_kernel = P == 1 && a->f_gp == nullptr && config(CFG_Q1_RULE_KERNEL) == nullptr;      // (launch2d)
-        Geom2D g = plan2d_env(m, P, allow_e4, chain_ok, cf_kernel);
-        if (!chain_ok) g.W = 1;                          // (a "PLAN2D" override may ask for chained strips where they do not exist)
+        Geom2D g = c.g2;
         pp.rows_per_strip = g.R;
         pp.nstrips = g.strips;
-        g.strips = launched(g.strips);
-        if (g.strips == 0) return no_strips();               // fewer than three strips: the other launch did everything
-        // (the partial-sum arrays were laid out for nwg workgroups: never launch more than that)
-        if (want_red && (long long)g.chunks * ((g.strips + g.W - 1) / g.W) * m->batch > nwg) return DN_E_WORKSPACE;
-        const int NW = g.E * P;
-        const bool vec = vec_ok(NW);
-        rc = launch2d(pp, g, P, m->ngp, m->batch, vec, s);
+        g.strips = c.strips;
+        rc = launch2d(pp, g, c.family, P, m->ngp, m->batch, c.vec, s);
     } else {
-        Geom3D g = plan3d_env(m, q1n2_ok(m, a), q1n2_needed(a));
+        Geom3D g = c.g3;
         pp.rows_per_strip = g.R;
         pp.nstrips = g.strips;
-        g.strips = launched(g.strips);
-        if (g.strips == 0) return no_strips();
-        if (want_red && (long long)g.chunks * g.tiles * g.strips * m->batch > nwg) return DN_E_WORKSPACE;
-        const int NW = g.E;
-        const bool vec = vec_ok(NW);
+        g.strips = c.strips;
         switch (m->ngp) {
-            case 2: rc = launch_poisson3d_q1_g2(pp, g, m->batch, vec, s); break;
-            case 3: rc = launch_poisson3d_q1_g3(pp, g, m->batch, vec, s); break;
-            case 4: rc = launch_poisson3d_q1_g4(pp, g, m->batch, vec, s); break;
+            case 2: rc = launch_poisson3d_q1_g2(pp, g, c.family, m->batch, c.vec, s); break;
+            case 3: rc = launch_poisson3d_q1_g3(pp, g, c.family, m->batch, c.vec, s); break;
+            case 4: rc = launch_poisson3d_q1_g4(pp, g, c.family, m->batch, c.vec, s); break;
             default: rc = DN_E_UNSUPPORTED;
         }
     }
     if (rc) return rc;
     DN_LAUNCH_CHECK();
     return 0;
-}
-
-// Workgroups the launch of (mesh, args) consists of = number of per-workgroup partial sums it leaves in the workspace.
-static long long launched_workgroups(const dn_mesh* m, const dn_poisson_args* a) {
-    const bool e4 = poisson_vec_ok(m, a, 4);
-    auto sel = [&](int total) { return a->strip_select == 1 ? std::min(total, 2) : (a->strip_select == 2 ? std::max(total - 2, 0) : total); };
-    if (m->nsd == 2) {
-        const bool chain_ok = m->degree == 1 && a->f_gp == nullptr && config(CFG_Q1_RULE_KERNEL) == nullptr && a->strip_select == 0;
-        const bool cf_kernel = m->degree == 1 && a->f_gp == nullptr && config(CFG_Q1_RULE_KERNEL) == nullptr;
-        Geom2D g = plan2d_env(m, m->degree, e4, chain_ok, cf_kernel);
-        if (!chain_ok) g.W = 1;
-        return (long long)g.chunks * ((sel(g.strips) + g.W - 1) / g.W) * m->batch;
-    }
-    Geom3D g = plan3d_env(m, q1n2_ok(m, a), q1n2_needed(a));
-    return (long long)g.chunks * g.tiles * sel(g.strips) * m->batch;
 }
 
 extern "C" int dn_poisson_finish_sums(const dn_mesh* m, const dn_poisson_args* a, void* stream) {
@@ -702,14 +800,12 @@ extern "C" int dn_poisson_finish_sums(const dn_mesh* m, const dn_poisson_args* a
     if (!a->defer_sums) return DN_E_BADARG;                               // only a launch with defer_sums leaves partials behind the header
     if (m->nsd == 3 && m->degree > 1) return DN_E_UNSUPPORTED;            // poisson3d_gen.hip: own workspace layout, no deferred sums
     if (a->accumulate_sums && !(a->energy && a->sumsq)) return DN_E_BADARG;
-    const long long n = launched_workgroups(m, a);
-    if (n <= 0) return 0;
-    const long long nall = num_workgroups(m, true) > num_workgroups(m, false) ? num_workgroups(m, true) : num_workgroups(m, false);
-    if (a->workspace_bytes < DN_WS_HEADER + (int64_t)(2 * sizeof(double)) * nall) return DN_E_WORKSPACE;
+    PoissonChoice c;                      // the launch that left the partials: their count and the stride between the two arrays
+    if ((rc = poisson_choose(m, a, c, false)) != 0) return rc;
+    if (c.launched <= 0) return 0;
+    if (a->workspace_bytes < dn_poisson_workspace_bytes(m)) return DN_E_WORKSPACE;
     const double* pe = reinterpret_cast<const double*>(reinterpret_cast<const char*>(a->workspace) + DN_WS_HEADER);
-    // the partial arrays are laid out for the launch's own workgroup count (dn_poisson_apply: part_sumsq = part_energy + nwg)
-    const long long stride = num_workgroups(m, poisson_vec_ok(m, a, 4));
-    hipLaunchKernelGGL(poisson_finish_sums_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pe, pe + stride, (int)n, a->energy,
+    hipLaunchKernelGGL(poisson_finish_sums_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), pe, pe + c.stride, (int)c.launched, a->energy,
                        a->sumsq, a->energy_f32, a->energy_scale, (int)(a->accumulate_sums != 0));
     DN_LAUNCH_CHECK();
     return 0;

@@ -406,12 +406,17 @@ def _packed_on_first_use(m):
     return pm
 
 
+def _compact_2d(geom, f_gp):
+    """Does a 2-D call of this geometry and forcing take bit-packed masks / box faces (all conditions of that kind, constant values)?  What
+    dn_poisson_query answers as `compact`, restated for the two places that must not make a foreign call: `_auto_pack` runs on every call
+    before the cache key, `_fused` under torch.compile.  tests/test_poisson_query_host.py holds the two equal."""
+    return geom.nsd == 2 and geom.deg == 1 and f_gp is None and not _lib.CONFIG_MIRROR.get("Q1_RULE_KERNEL")
+
+
 def _auto_pack(geom, u, f_gp, dl):
     """The conditions of a one-shot 2-D Q1 call with their mask IMAGES replaced by (cached) bit-packed masks, where the compact kernels
     take the whole call: every condition a constant value on a PackedMask / BoxFaces / contiguous float32, uint8 or bool CUDA image."""
-    if not (AUTO_PACK_MASKS and geom.nsd == 2 and geom.deg == 1 and f_gp is None and len(dl) > 0 and isinstance(u, torch.Tensor) and u.is_cuda):
-        return dl
-    if _lib.CONFIG_MIRROR.get("Q1_RULE_KERNEL"):
+    if not (AUTO_PACK_MASKS and _compact_2d(geom, f_gp) and len(dl) > 0 and isinstance(u, torch.Tensor) and u.is_cuda):
         return dl
     want = (1, *geom.node_shape)
     for d in dl:
@@ -818,42 +823,6 @@ def _prepare_poisson(geom, u, nu, f, f_gp, dirichlet, alpha, beta, c, wscale, ou
             raise ValueError(f"f_gp must have shape (B|1,{geom.ngp_total},{geom.elem_shape})")
         args.f_gp, args.f_batched = f_gp.data_ptr(), fb
     dl = _norm_dirichlet(dirichlet)
-    # bit-packed / geometry-derived conditions: read directly by the 2-D Q1 kernels with nodal or absent forcing when every
-    # condition of the call is one of them with a constant value; otherwise they are expanded to their (cached) uint8 images
-    compact = (nsd == 2 and geom.deg == 1 and f_gp is None and len(dl) > 0 and _lib.lib().dn_config_get(b"Q1_RULE_KERNEL") in (None, b"") and
-               all(isinstance(d.mask, (PackedMask, BoxFaces)) and not isinstance(d.value, torch.Tensor) for d in dl))
-    # 3-D (round 4): BoxFaces are taken as they are (no image, no load) by the two-element Q1 kernel -- exact 2-point rule, even nx, nodal /
-    # absent forcing, 8-byte aligned fields, constant values, at most one mask image beside them; anything else gets the expanded image
-    box3d = False
-    if nsd == 3 and geom.deg == 1 and f_gp is None and any(isinstance(d.mask, BoxFaces) for d in dl):
-        mesh0 = geom.mesh_struct(B)
-        imgs = [d.mask for d in dl if not isinstance(d.mask, BoxFaces)]
-        cfg = _lib.lib().dn_config_get
-        box3d = (mesh0.ngp == 2 and mesh0.nx % 2 == 0 and len(imgs) <= 1 and cfg(b"Q1_3D_T16") in (None, b"") and cfg(b"Q1_3D_E1") in (None, b"") and
-                 all(not isinstance(d.value, torch.Tensor) for d in dl) and
-                 all(isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype in (torch.uint8, torch.float32) and
-                     t.data_ptr() % 8 == 0 for t in imgs) and
-                 all(t is None or t.data_ptr() % 8 == 0 for t in (u, nu, f, out)))
-    for k, d in enumerate(dl):
-        m = d.mask
-        if box3d and isinstance(m, BoxFaces):
-            bc = args.bc[k]
-            bc.value = float(d.value)
-            bc.mask_kind, bc.box_faces = _lib.MASK_BOX, m.bits
-            continue
-        if compact:
-            bc = args.bc[k]
-            bc.value = float(d.value)
-            if isinstance(m, BoxFaces):
-                bc.mask_kind, bc.box_faces = _lib.MASK_BOX, m.bits
-            else:
-                if tuple(m.shape[1:]) != (1, *node_shape) or m.shape[0] not in (1, B) or m.bits.device != u.device:
-                    raise ValueError(f"packed Dirichlet mask of shape {m.shape} does not match u")
-                keep.append(m.bits)
-                bc.mask, bc.mask_kind, bc.row_words = m.bits.data_ptr(), _lib.MASK_BITS, m.row_words
-                bc.mask_batched = int(m.shape[0] == B)
-            continue
-        _dirichlet_image(args.bc[k], m, d.value, u, node_shape, keep, strict)
     args.alpha, args.beta, args.c, args.wscale, args.out_scale = alpha, beta, c, wscale, out_scale
     mesh = geom.mesh_struct(B)
     if out is not None:
@@ -878,6 +847,38 @@ def _prepare_poisson(geom, u, nu, f, f_gp, dirichlet, alpha, beta, c, wscale, ou
             raise ValueError("loss_scale needs want_sums=True")
         loss32 = reuse[2] if reuse is not None else torch.empty((), dtype=torch.float32, device=u.device)
         args.energy_f32, args.energy_scale = loss32.data_ptr(), float(loss_scale)
+
+    # Conditions last: every other pointer of the call is in `args` by now.  PackedMask / BoxFaces conditions with a constant value go in
+    # as they are (bit arrays / box faces: no image is read) and the library is asked whether the launch of exactly these arguments takes them
+    # (dn_poisson_query: the 2-D closed-form Q1 kernel takes both kinds, the 3-D two-element kernels box faces beside at most one image);
+    # where it answers DN_E_UNSUPPORTED they are expanded to their (cached) uint8 images.
+    def conditions(compact):
+        for k, d in enumerate(dl):
+            m, bc = d.mask, args.bc[k]
+            if not (compact and isinstance(m, (PackedMask, BoxFaces)) and not isinstance(d.value, torch.Tensor)):
+                _dirichlet_image(bc, m, d.value, u, node_shape, keep, strict)
+                continue
+            bc.value = float(d.value)
+            if isinstance(m, BoxFaces):
+                bc.mask_kind, bc.box_faces = _lib.MASK_BOX, m.bits
+            else:
+                if tuple(m.shape[1:]) != (1, *node_shape) or m.shape[0] not in (1, B) or m.bits.device != u.device:
+                    raise ValueError(f"packed Dirichlet mask of shape {m.shape} does not match u")
+                keep.append(m.bits)
+                bc.mask, bc.mask_kind, bc.row_words = m.bits.data_ptr(), _lib.MASK_BITS, m.row_words
+                bc.mask_batched = int(m.shape[0] == B)
+
+    compact = any(isinstance(d.mask, (PackedMask, BoxFaces)) and not isinstance(d.value, torch.Tensor) for d in dl)
+    if compact:
+        nkeep = len(keep)
+        conditions(True)
+        if _lib.lib().dn_poisson_query(C.byref(mesh), C.byref(args), C.byref(_lib.DnPoissonKernel())) == -2:      # DN_E_UNSUPPORTED
+            del keep[nkeep:]
+            for k in range(2):
+                args.bc[k] = _lib.DnDirichlet()
+            compact = False
+    if not compact:
+        conditions(False)
     keep += [t for t in (out, sums, loss32) if t is not None]
     return mesh, args, keep, ((out, sums, loss32) if loss_scale is not None else (out, sums))
 
@@ -1042,8 +1043,7 @@ def _fused(geom, u, nu, f, f_gp, dirichlet, alpha, beta, c, wscale, out_scale, l
         from . import torch_ops
         if isinstance(f, LoadVector):
             raise DiffNetHipError("LoadVector forcing is an eager-mode argument (the registered operator takes tensors); pass nodal f under torch.compile")
-        compact = (geom.nsd == 2 and geom.deg == 1 and f_gp is None and not _lib.CONFIG_MIRROR.get("Q1_RULE_KERNEL") and
-                   all(not isinstance(d.value, torch.Tensor) for d in dirichlet))
+        compact = _compact_2d(geom, f_gp) and all(not isinstance(d.value, torch.Tensor) for d in dirichlet)
         return torch_ops.poisson_apply(u, nu, f, f_gp, *torch_ops.dirichlet_args(dirichlet, u, compact), *torch_ops.geometry_args(geom),
                                        float(alpha), float(beta), float(c), float(wscale), float(out_scale), float(loss_scale))
     for d in dirichlet:

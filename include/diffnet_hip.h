@@ -211,6 +211,44 @@ int dn_poisson_apply(const dn_mesh *mesh, const dn_poisson_args *args, void *str
 /* Second half of a dn_poisson_apply launch with args->defer_sums set (same mesh, same args): the final scalars from the partial sums. */
 int dn_poisson_finish_sums(const dn_mesh *mesh, const dn_poisson_args *args, void *stream);
 
+/* Which kernel and which launch geometry dn_poisson_apply takes for (mesh, args) under the current switches: a host-side query, nothing is
+ * launched, no device is needed and no pointer is followed (pointers count as NULL / non-NULL and by their alignment, as in the launch).  The
+ * answer comes from the function the launch itself calls (poisson_choose in csrc/poisson_fused.hip), so the two cannot drift; the same function
+ * tells dn_poisson_finish_sums and a folding launch (fold_prev) how many partial sums an earlier launch left and how they are laid out.
+ * Returns 0, or the DN_E_* code dn_poisson_apply would return for these arguments (DN_E_BADARG also for a NULL `out`); on an error the
+ * fields decided up to that point are filled, the rest 0.  No reference counterpart (the reference has no launch plan).
+ *   family           DN_POISSON_*: one value per kernel template
+ *   tile             threads of a workgroup -- 2-D {T, 0}, 3-D {TX, TY} (0 for DN_POISSON_3D_Q23: fixed workgroups of 64 and 256 threads)
+ *   E, R, W          elements per thread along x, element layers per strip, strips chained per workgroup (2-D closed form only, else 1)
+ *   ua               2-D closed form: rows of 4 k + 1 nodes taken four elements per thread with unaligned vector accesses
+ *   chunks, tiles    workgroups along x and (3-D) y;  strips: strips of the whole mesh along the marched axis
+ *   launched_strips  strips this launch covers (strip_select applied; 0: the launch has nothing to do)
+ *   vec, allow_e4    vector accesses of the E * degree nodes a thread owns per row are legal / rows are 16-byte aligned throughout
+ *   compact          conditions the call may hold without an image: 0 none, 1 DN_MASK_BOX, 2 DN_MASK_BOX and DN_MASK_BITS (no image beside them)
+ *   launched         workgroups of the launch = per-workgroup partial sums it leaves (chunks x tiles x ceil(launched_strips / W) x batch)
+ *   stride           workgroups the two partial-sum arrays are laid out for: the sum-of-squares partials start `stride` doubles behind the energy partials
+ *   workspace_bytes  workspace a call with sums needs at this alignment (<= dn_poisson_workspace_bytes(mesh)) */
+enum {
+    DN_POISSON_2D_Q1_CF = 1,      /* poisson2d_q1_cf_kernel: closed-form Q1 element, nodal / absent forcing */
+    DN_POISSON_2D_Q1_RULE = 2,    /* poisson2d_q1_raw_kernel: Q1 marched per Gauss rule (f_gp, or "Q1_RULE_KERNEL") */
+    DN_POISSON_2D_Q23 = 3,        /* poisson2d_kernel: Q2 / Q3 */
+    DN_POISSON_3D_Q1_N1 = 4,      /* poisson3d_q1n_kernel: node-owner form, one element per thread */
+    DN_POISSON_3D_Q1_T16 = 5,     /* poisson3d_q1w_kernel, T16 form: tiles 16 threads wide */
+    DN_POISSON_3D_Q1_GENERIC = 6, /* poisson3d_q1w_kernel, any tile */
+    DN_POISSON_3D_Q1_N2 = 7,      /* poisson3d_q1n2_kernel: node-owner form, two elements per thread */
+    DN_POISSON_3D_Q1_CFZ = 8,     /* poisson3d_q1_cf_kernel: two elements per thread, closed form in z */
+    DN_POISSON_3D_Q23 = 9         /* poisson3d_gen_*_kernel: element vectors + gather assembly */
+};
+typedef struct dn_poisson_kernel {
+    int32_t family;
+    int32_t tile[2];
+    int32_t E, R, W, ua;
+    int32_t chunks, tiles, strips, launched_strips;
+    int32_t vec, allow_e4, compact;
+    int64_t launched, stride, workspace_bytes;
+} dn_poisson_kernel;
+int dn_poisson_query(const dn_mesh *mesh, const dn_poisson_args *args, dn_poisson_kernel *out);
+
 /* Sticky error state of the launches that used `workspace` (dn_poisson_apply, dn_fsdt_apply).  The chained-strip launch plans hand rows
  * from wave to wave through flag-guarded LDS words; every poll of such a flag is bounded so that a producer wave that never arrives
  * cannot hang the GPU.  A poll that reaches its bound is never silent: the wave adds NaN to every value it writes afterwards (its rows

@@ -27,6 +27,12 @@ bc = torch.zeros(shape, dtype=torch.uint8, device=dev); bc[..., 0] = 1
 out = torch.empty_like(u)
 print("energy_loss_and_grad 64^2            : %.1f us/call" % wall(lambda: m.energy_loss_and_grad(u, nu, f, dirichlet=[(bc, 0.0)], c=0.5)))
 print("energy_loss_and_grad 64^2, out=      : %.1f us/call" % wall(lambda: m.energy_loss_and_grad(u, nu, f, dirichlet=[(bc, 0.0)], c=0.5, out=out)))
+pkw = dict(dirichlet=[(bc, 0.0)], alpha=1.0, beta=1.0, c=0.5, loss_scale=1.0)
+print("PoissonPlan.launch 64^2 (prepared)   : %.1f us/call" % wall(ops.PoissonPlan(m.geom, u, nu, f, None, **pkw).launch))
+pipe = [ops.PoissonPlan(m.geom, u, nu, f, None, pipelined_sums=True, **pkw) for _ in range(2)]
+pipe[0].fold(pipe[1])
+pipe[1].fold(pipe[0])
+print("PoissonPlan.launch 64^2, folded sums : %.1f us/call" % (wall(lambda: (pipe[0].launch(), pipe[1].launch())) / 2))
 ur = u.clone().requires_grad_(True)
 
 
