@@ -139,6 +139,18 @@ class DnFdmPoissonArgs(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class DnPointsArgs(C.Structure):
+    _fields_ = [("u", C.c_void_p), ("elem", C.c_void_p), ("xi", C.c_void_p), ("offsets", C.c_void_p), ("npts", C.c_int64),
+                ("dscale", C.c_float * 3), ("kind", C.c_int32), ("penalty", C.c_int32),
+                ("target", C.c_void_p), ("target_value", C.c_float), ("normals", C.c_void_p), ("w_val", C.c_float), ("w_nrm", C.c_float),
+                ("values", C.c_void_p), ("pgrads", C.c_void_p), ("cot", C.c_void_p), ("sums", C.c_void_p),
+                ("gscale_dev", C.c_void_p), ("gscale", C.c_float), ("grad", C.c_void_p), ("accumulate", C.c_int32),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+POINTS_NONE, POINTS_DOT, POINTS_MATCH = 0, 1, 2
+
+
 class DnConvK4s2Kernel(C.Structure):
     _fields_ = [("gen", C.c_int32), ("targ", C.c_int32 * 3), ("nz", C.c_int32), ("per_slice", C.c_int32), ("sum_kernel", C.c_int32)]
 
@@ -210,6 +222,8 @@ SYMBOLS = {
     "dn_poisson_coef_grad": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnCoefGradArgs), C.c_void_p]),
     "dn_fdm_poisson_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "dn_fdm_poisson_apply": (C.c_int, [C.POINTER(DnFdmPoissonArgs), C.c_void_p]),
+    "dn_points_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
+    "dn_points_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnPointsArgs), C.c_void_p]),
     "dn_upconv_out_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "dn_upconv_out_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
                                     C.c_void_p, C.c_int64, C.c_void_p]),

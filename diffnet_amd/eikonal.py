@@ -8,7 +8,7 @@
 
 `sq` defaults to 1 + tau and `wscale` to (hx/2)(hy/2), as in the scripts; the right-hand side is the constant `f_gp` (default 1, the
 scripts' `N_values * 1.0`), a Gauss-point field `f_gp` or a nodal field `f` interpolated with the basis.  `tau = 0, sq = 1` is the
-unstabilised N (|grad u|^2 - 1) of the older scripts.  The scripts add two point-cloud terms to this loss; they stay in torch
+unstabilised N (|grad u|^2 - 1) of the older scripts.  The scripts add two point-cloud terms to this loss: `diffnet_amd.points.point_loss`
 (examples/eikonal_2d.py).
 
 `eikonal_residual` / `eikonal_loss` are ONE fused launch forward (dn_eikonal_apply, csrc/eikonal.hip) and one backward: the VJP launch

@@ -11,7 +11,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import DnCoefGradArgs, DnDirichlet, DnEikonalArgs, DnFdmPoissonArgs, DnFoslsArgs, DnFsdtArgs, DnHelmholtzArgs, DnMesh, DnNsArgs, DnPoissonArgs, DnStokesArgs, DnStrongformArgs, DnTransportArgs, I32x3, DiffNetHipError
+from ._lib import DnCoefGradArgs, DnDirichlet, DnEikonalArgs, DnFdmPoissonArgs, DnFoslsArgs, DnFsdtArgs, DnHelmholtzArgs, DnMesh, DnNsArgs, DnPointsArgs, DnPoissonArgs, DnStokesArgs, DnStrongformArgs, DnTransportArgs, I32x3, DiffNetHipError
 
 
 def _require(t, name, ndim=None, strict=False):
@@ -2532,3 +2532,132 @@ def winding_field(points, normals, area, queries, metric="l1", power=3, scale=1.
                                      power, float(scale), float(threshold), tile, _stream(points))
     _lib.check(rc, "dn_winding_field")
     return field, mask
+
+
+# ---- the fused point-cloud terms: evaluation at points, penalty loss and gradient: dn_points_apply ----------------------------------
+_POINTS = _FusedOp("points_apply", DnPointsArgs)
+_POINTS_KINDS = {"none": _lib.POINTS_NONE, "dot": _lib.POINTS_DOT, "match": _lib.POINTS_MATCH}
+
+
+def _points_check_mesh(op, geom):
+    if geom.nsd not in (2, 3) or geom.deg != 1:
+        raise DiffNetHipError(f"{op.name}: Q1 meshes only (nsd {geom.nsd}, degree {geom.deg}); any degree: points.point_terms_composed")
+
+
+def _points_key(geom, B, npts, consts, flags, f32s, i32s):
+    dev = next(t for t in f32s + i32s if t is not None).device
+    parts = [geom.key, B, npts, dev.index, _raw_stream(dev), consts, flags]
+    for ts, dt in ((f32s, torch.float32), (i32s, torch.int32)):
+        for t in ts:
+            k = _tkey(t)
+            if k is None or (k != 0 and k[1] != dt):
+                return None
+            parts.append(k)
+    return tuple(parts)
+
+
+def _prepare_points(geom, B, npts, consts, flags, f32s, i32s):
+    """Validation + argument struct of a dn_points_apply call, fresh outputs left unset: (mesh, args, tensors to keep alive, batch)."""
+    op = _POINTS
+    _points_check_mesh(op, geom)
+    u, xi, target, normals, cot, gscale_dev, grad_out = f32s
+    elem, offsets = i32s
+    dscale, kind, target_value, w_val, w_nrm, gscale = consts
+    penalty, want_sums, accumulate = flags
+    args, keep = DnPointsArgs(), []
+    T, nsd = B * npts, geom.nsd
+    dev = xi.device
+    node_shape = (B, 1, *geom.node_shape)
+
+    def put(member, t, what, numel, dtype=torch.float32, shape=None):
+        if t is None:
+            return
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != dev:
+            raise DiffNetHipError(f"{op.name}: {what} must be a tensor on {dev} (the fused point terms run on the GPU only)")
+        if t.dtype != dtype or not t.is_contiguous():
+            raise TypeError(f"{op.name}: {what} must be a contiguous {dtype} tensor, got {t.dtype}")
+        if t.numel() != numel or (shape is not None and tuple(t.shape) != shape):
+            raise ValueError(f"{op.name}: {what} holds {tuple(t.shape)}, expected {shape or numel} values")
+        setattr(args, member, t.data_ptr())
+        keep.append(t)
+
+    put("u", u, "u", B * geom.nnode_total, shape=node_shape)
+    put("xi", xi, "xi", nsd * T)
+    put("elem", elem, "elem", T, torch.int32)
+    put("offsets", offsets, "offsets", B * geom.nelem_total + 1, torch.int32)
+    put("target", target, "target", T)
+    put("normals", normals, "normals", nsd * T)
+    put("cot", cot, "cot", (1 + nsd) * T)
+    put("gscale_dev", gscale_dev, "gscale_dev", 1)
+    put("grad", grad_out, "grad_out", B * geom.nnode_total, shape=node_shape)
+    args.npts, args.kind, args.penalty, args.accumulate = npts, kind, int(penalty), int(accumulate)
+    args.dscale[:] = dscale
+    args.target_value, args.w_val, args.w_nrm, args.gscale = target_value, w_val, w_nrm, gscale
+    mesh = geom.mesh_struct(B)
+    if want_sums:
+        ws = _op_workspace(op, mesh, B, dev)
+        keep.append(ws)
+        args.workspace, args.workspace_bytes = ws.data_ptr(), ws.numel()
+    return mesh, args, keep, B
+
+
+def _points_patch(args, ptrs):
+    values, pgrads, sums, cot, grad = ptrs
+    args.values, args.pgrads, args.sums = values, pgrads, sums
+    if cot is not None:
+        args.cot = cot
+    if grad is not None:
+        args.grad = grad
+
+
+def points_apply(geom, batch, npts, xi, elem=None, offsets=None, u=None, dscale=(1.0, 1.0, 1.0), kind="none", penalty=False, target=None,
+                 normals=None, w_val=1.0, w_nrm=1.0, want_values=False, want_pgrads=False, want_sums=False, want_cot=False, cot=None,
+                 want_grad=False, grad_out=None, accumulate=False, gscale=1.0, gscale_dev=None):
+    """One call of dn_points_apply (include/diffnet_hip.h) on the sorted point list of a `points.PointPlan` (B = batch samples of npts
+    points; T = B npts): xi (nsd, T) float32, elem (T) int32, offsets (B nel + 1) int32, in the kernels' axis order (x, y[, z]).
+    Forward launch (needs u (B,1,*node_shape) and elem) when values, pgrads or the penalty are asked for: values (T), pgrads (nsd, T);
+    `penalty`: sums (3 float64: value term, normals term, total; `want_sums`) and the per-point cotangents cot (1 + nsd, T)
+    (`want_cot`), from `target` (a float or a (T) tensor), `normals` (nsd, T), `kind` "none" | "dot" | "match", w_val, w_nrm.
+    Adjoint launch (needs offsets) when `want_grad`: the pullback of `cot` -- the one just computed, or the tensor passed in -- times
+    gscale (and gscale_dev[0], a float32 device tensor of 1), into a fresh tensor, into `grad_out`, or added to `grad_out` with
+    `accumulate`.  Returns (values, pgrads, sums, cot, grad), None where not asked for.  Calls on the same buffers reuse their prepared
+    argument structs (small LRU, fresh outputs per call: see poisson_apply)."""
+    op = _POINTS
+    _points_check_mesh(op, geom)
+    if kind not in _POINTS_KINDS:
+        raise ValueError(f"{op.name}: kind must be one of {sorted(_POINTS_KINDS)}, got {kind!r}")
+    if not isinstance(xi, torch.Tensor) or not xi.is_cuda:
+        raise DiffNetHipError(f"{op.name}: the fused point terms run on the GPU only (no CPU fallback): points.point_terms_composed is the torch route")
+    if not (want_values or want_pgrads or penalty or want_grad):
+        raise ValueError(f"{op.name}: nothing to compute")
+    if penalty and not (want_sums or want_cot or want_grad):
+        raise ValueError(f"{op.name}: a penalty needs want_sums, want_cot or want_grad")
+    if (want_sums or want_cot) and not penalty:
+        raise ValueError(f"{op.name}: sums and cot are results of the penalty")
+    if want_grad and not penalty and cot is None:
+        raise ValueError(f"{op.name}: the adjoint needs per-point cotangents (cot, or a penalty in the same call)")
+    if accumulate and (grad_out is None or not want_grad):
+        raise ValueError(f"{op.name}: accumulate adds to grad_out")
+    if penalty and cot is not None:
+        raise ValueError(f"{op.name}: cot is an input of an adjoint-only call")
+    B, npts, dev = int(batch), int(npts), xi.device
+    if B * npts == 0 and not (want_sums or want_grad):          # nothing per point and nothing else: no launch
+        e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)      # noqa: E731
+        return e(0) if want_values else None, e(geom.nsd, 0) if want_pgrads else None, None, e(1 + geom.nsd, 0) if want_cot else None, None
+    tt, tv = (target, 0.0) if isinstance(target, torch.Tensor) else (None, 0.0 if target is None else float(target))
+    ds = tuple(float(x) for x in dscale) + (1.0,) * (3 - len(dscale))
+    consts = (ds, _POINTS_KINDS[kind], tv, float(w_val), float(w_nrm), float(gscale))
+    flags = (bool(penalty), bool(want_sums), bool(accumulate), want_values, want_pgrads, want_cot, want_grad)
+    f32s = (u, xi, tt, normals if penalty else None, cot, gscale_dev, grad_out if want_grad else None)
+    i32s = (elem, offsets if want_grad else None)
+    key = _points_key(geom, B, npts, consts, flags, f32s, i32s)
+    ent = _op_entry(op, key, _prepare_points, (geom, B, npts, consts, flags[:3], f32s, i32s))
+    T, nsd = B * npts, geom.nsd
+    new = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)      # noqa: E731
+    values = new(T) if want_values else None
+    pgrads = new(nsd, T) if want_pgrads else None
+    sums = new(3, dtype=torch.float64) if want_sums else None
+    cot_new = new(1 + nsd, T) if penalty and (want_cot or want_grad) else None
+    grad = new(B, 1, *geom.node_shape) if want_grad and grad_out is None else None
+    _op_launch(op, ent, xi, _points_patch, tuple(None if t is None else t.data_ptr() for t in (values, pgrads, sums, cot_new, grad)))
+    return values, pgrads, sums, cot_new if want_cot else None, (grad_out if grad is None else grad) if want_grad else None

@@ -8,12 +8,16 @@ reference's `examples/eiqonal/single_instance/e01_curve_reconstruction.py` (loss
 
 with the points x_p on a circle of radius 0.3 around the centre and n_p their outward normals.  The scripts' domain term (3 Gauss-point
 evaluations, elementwise passes over (B, nbf, G, nel, nel) tensors, the assembly, the norm and the autograd backward through all of it) is
-ONE launch forward and one backward (diffnet_amd.eikonal.eikonal_loss); the two point terms stay in torch.
+ONE launch forward and one backward (diffnet_amd.eikonal.eikonal_loss); the two point terms -- an index gather, three weighted sums, two
+reductions and their autograd replay -- are one launch forward and one backward too (diffnet_amd.points.point_loss on a `PointPlan`).
 
-    python examples/eikonal_2d.py [--n 65] [--degree 1] [--tau 0.25] [--mode fused|composed] [--optimizer lbfgs|adam] [--steps 20]
+    python examples/eikonal_2d.py [--n 65] [--degree 1] [--tau 0.25] [--mode fused|composed] [--points fused|composed]
+                                  [--optimizer lbfgs|adam] [--steps 20]
 
---mode fused     the fused HIP operator (dn_eikonal_apply)
-       composed  the same residual on the drop-in operators (gauss_pt_evaluation*, assemble)
+--mode fused       the fused HIP operator (dn_eikonal_apply)
+       composed    the same residual on the drop-in operators (gauss_pt_evaluation*, assemble)
+--points fused     the fused point terms (dn_points_apply; Q1 meshes: on a Q2 / Q3 mesh point_loss composes torch ops itself)
+         composed  the same terms in plain torch ops (points.point_terms_composed)
 It prints the error against the exact signed distance (the 2-norm of the nodal difference over n).
 """
 import argparse
@@ -29,41 +33,31 @@ from torch import nn
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from DiffNet.DiffNetFEM import DiffNet2DFEM  # noqa: E402  (reference import path, MI355X implementation)
 from diffnet_amd import eikonal as ek  # noqa: E402
-from diffnet_amd.tables import Basis1D  # noqa: E402
+from diffnet_amd import points as pt  # noqa: E402
 
 RADIUS, NPTS = 0.3, 64
 
 
 class Eikonal(DiffNet2DFEM):
-    """One nodal parameter; the point cloud as interpolation weights of u, u_x and u_y on the nodes of each point's element."""
+    """One nodal parameter; the point cloud as a `PointPlan` of the mesh."""
 
-    def __init__(self, field, n, degree=1, tau=0.25, mode="fused"):
+    def __init__(self, field, n, degree=1, tau=0.25, mode="fused", points="fused"):
         super().__init__(None, None, domain_size=n, fem_basis_deg=degree)
-        self.net, self.tau, self.mode = field, float(tau), mode
+        self.net, self.tau, self.mode, self.points = field, float(tau), mode, points
         t = 2.0 * math.pi * (np.arange(NPTS) + 0.5) / NPTS
         nrm = np.stack((np.cos(t), np.sin(t)), 1)
-        pts = 0.5 + RADIUS * nrm
-        P, nb = degree, degree + 1
-        he = self.hx                                       # element width
-        e = np.minimum((pts / he).astype(np.int64), (n - 1) // P - 1)
-        xi = 2.0 * (pts - e * he) / he - 1.0               # (NPTS, 2) in the element's [-1, 1]^2
-        b = Basis1D(P)
-        Bx, By, Dx, Dy = b.val(xi[:, 0]), b.val(xi[:, 1]), b.der(xi[:, 0]) * 2.0 / he, b.der(xi[:, 1]) * 2.0 / he      # (nb, NPTS)
-        idx = ((e[:, 1] * P)[:, None, None] + np.arange(nb)[None, :, None]) * n + (e[:, 0] * P)[:, None, None] + np.arange(nb)[None, None, :]
-        w = lambda fy, fx: torch.from_numpy((fy.T[:, :, None] * fx.T[:, None, :]).reshape(NPTS, -1).astype(np.float32))      # noqa: E731
-        self.register_buffer("pidx", torch.from_numpy(idx.reshape(NPTS, -1)))
-        self.register_buffer("wN", w(By, Bx))
-        self.register_buffer("wX", w(By, Dx))
-        self.register_buffer("wY", w(Dy, Bx))
-        self.register_buffer("normals", torch.from_numpy(nrm.astype(np.float32)))
+        self.register_buffer("pts", torch.from_numpy((0.5 + RADIUS * nrm).astype(np.float32))[None].contiguous())       # (1, NPTS, 2)
+        self.register_buffer("normals", torch.from_numpy(nrm.astype(np.float32))[None].contiguous())
+        self.plan = None                                   # the cloud is fixed: classified and sorted once, on the field's device
         x = np.linspace(0.0, 1.0, n)
         xx, yy = np.meshgrid(x, x)
         self.register_buffer("u_exact", torch.from_numpy((np.hypot(xx - 0.5, yy - 0.5) - RADIUS).astype(np.float32))[None, None].contiguous())
 
     def point_terms(self, u):
-        up = u.reshape(-1)[self.pidx]                      # (NPTS, nb * nb)
-        val, ux, uy = (up * self.wN).sum(1), (up * self.wX).sum(1), (up * self.wY).sum(1)
-        return torch.sum(val ** 2) + torch.sum((ux * self.normals[:, 0] + uy * self.normals[:, 1] - 1.0) ** 2)
+        if self.plan is None or self.plan.device != u.device:
+            self.plan = pt.PointPlan(self, self.pts)
+        terms = pt.point_loss if self.points == "fused" else pt.point_terms_composed
+        return terms(self, u, self.plan, target=0.0, normals=self.normals, kind="dot", dscale="physical")
 
     def domain_term(self, u):
         if self.mode == "fused":
@@ -79,9 +73,9 @@ class Eikonal(DiffNet2DFEM):
         return float(torch.linalg.vector_norm(u - self.u_exact)) / u.shape[-1]
 
 
-def run(n=65, degree=1, tau=0.25, steps=20, optimizer="lbfgs", mode="fused", lr=1e-2, verbose=True):
-    if mode not in ("fused", "composed"):
-        raise ValueError(f"mode must be 'fused' or 'composed', got {mode!r}")
+def run(n=65, degree=1, tau=0.25, steps=20, optimizer="lbfgs", mode="fused", lr=1e-2, verbose=True, points="fused"):
+    if mode not in ("fused", "composed") or points not in ("fused", "composed"):
+        raise ValueError(f"mode and points must be 'fused' or 'composed', got {mode!r}, {points!r}")
     if (n - 1) % degree:
         raise ValueError(f"degree-{degree} elements need (n - 1) % {degree} == 0 nodes per axis")
     dev = torch.device("cuda")
@@ -89,7 +83,7 @@ def run(n=65, degree=1, tau=0.25, steps=20, optimizer="lbfgs", mode="fused", lr=
     # start from a field with a minimum inside the circle's centre and the wrong slope: |grad u| = 0.4
     u0 = 0.4 * (torch.hypot(x[None, :] - 0.5, x[:, None] - 0.5) - RADIUS)
     field = nn.ParameterList([nn.Parameter(u0.reshape(1, 1, n, n).contiguous().to(dev))])
-    m = Eikonal(field, n, degree, tau, mode).to(dev)
+    m = Eikonal(field, n, degree, tau, mode, points).to(dev)
     if optimizer == "lbfgs":
         opt = torch.optim.LBFGS(field, lr=1.0, max_iter=5)
     elif optimizer == "adam":
@@ -114,7 +108,7 @@ def run(n=65, degree=1, tau=0.25, steps=20, optimizer="lbfgs", mode="fused", lr=
         hist.append(float(m.loss()))
     torch.cuda.synchronize()
     if verbose:
-        print(f"{steps} steps in {time.perf_counter() - t0:.2f} s ({mode}, {optimizer}, {n}^2 nodes Q{degree}, tau {tau}); final loss {hist[-1]:.6e}; "
+        print(f"{steps} steps in {time.perf_counter() - t0:.2f} s ({mode}, points {points}, {optimizer}, {n}^2 nodes Q{degree}, tau {tau}); final loss {hist[-1]:.6e}; "
               f"|| u - u_exact || / n = {m.error():.4e}")
     return field[0].detach(), hist
 
@@ -125,11 +119,12 @@ def main():
     ap.add_argument("--degree", type=int, default=1)
     ap.add_argument("--tau", type=float, default=0.25)
     ap.add_argument("--mode", choices=("fused", "composed"), default="fused")
+    ap.add_argument("--points", choices=("fused", "composed"), default="fused")
     ap.add_argument("--optimizer", choices=("lbfgs", "adam"), default="lbfgs")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--lr", type=float, default=1e-2)
     a = ap.parse_args()
-    run(a.n, a.degree, a.tau, a.steps, a.optimizer, a.mode, a.lr)
+    run(a.n, a.degree, a.tau, a.steps, a.optimizer, a.mode, a.lr, points=a.points)
 
 
 if __name__ == "__main__":

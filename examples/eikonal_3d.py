@@ -8,12 +8,16 @@ reference's `examples/eiqonal/single_instance/05_3d_sphere_loss4.py` (loss4) wit
 with the points x_p on a sphere of radius 0.3 around the centre and n_p their outward normals.  The script's domain term (4 Gauss-point
 evaluations, elementwise passes over (B, 8, G, nel, nel, nel) tensors, the assembly, the norm and the autograd backward through all of it)
 is ONE launch forward and one backward (diffnet_amd.eikonal.eikonal_loss on a DiffNet3DFEM: dn_eikonal3d_apply); the two point terms
-stay in torch.
+-- an index gather, four weighted sums, two reductions and their autograd replay -- are one launch forward and one backward too
+(diffnet_amd.points.point_loss on a `PointPlan`).
 
-    python examples/eikonal_3d.py [--n 33] [--tau 0.25] [--mode fused|composed] [--optimizer lbfgs|adam] [--steps 20]
+    python examples/eikonal_3d.py [--n 33] [--tau 0.25] [--mode fused|composed] [--points fused|composed] [--optimizer lbfgs|adam]
+                                  [--steps 20]
 
---mode fused     the fused HIP operator (dn_eikonal3d_apply)
-       composed  the same residual on the drop-in operators (gauss_pt_evaluation*, assemble)
+--mode fused       the fused HIP operator (dn_eikonal3d_apply)
+       composed    the same residual on the drop-in operators (gauss_pt_evaluation*, assemble)
+--points fused     the fused point terms (dn_points_apply)
+         composed  the same terms in plain torch ops (points.point_terms_composed)
 It prints the error against the exact signed distance (the 2-norm of the nodal difference over n^1.5).
 """
 import argparse
@@ -29,7 +33,7 @@ from torch import nn
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from DiffNet.DiffNetFEM import DiffNet3DFEM  # noqa: E402  (reference import path, MI355X implementation)
 from diffnet_amd import eikonal as ek  # noqa: E402
-from diffnet_amd.tables import Basis1D  # noqa: E402
+from diffnet_amd import points as pt  # noqa: E402
 
 RADIUS, NPTS = 0.3, 256
 
@@ -44,39 +48,24 @@ def sphere_points(npts):
 
 
 class Eikonal3D(DiffNet3DFEM):
-    """One nodal parameter; the point cloud as interpolation weights of u, u_x, u_y and u_z on the 8 nodes of each point's element."""
+    """One nodal parameter; the point cloud as a `PointPlan` of the mesh."""
 
-    def __init__(self, field, n, tau=0.25, mode="fused"):
+    def __init__(self, field, n, tau=0.25, mode="fused", points="fused"):
         super().__init__(None, None, domain_size=n, nsd=3)
-        self.net, self.tau, self.mode = field, float(tau), mode
+        self.net, self.tau, self.mode, self.points = field, float(tau), mode, points
         nrm = sphere_points(NPTS)
-        pts = 0.5 + RADIUS * nrm
-        he = self.hx
-        e = np.minimum((pts / he).astype(np.int64), n - 2)
-        xi = 2.0 * (pts - e * he) / he - 1.0               # (NPTS, 3) in the element's [-1, 1]^3
-        b = Basis1D(1)
-        Bv = [b.val(xi[:, d]) for d in range(3)]           # (2, NPTS) per axis
-        Dv = [b.der(xi[:, d]) * 2.0 / he for d in range(3)]
-        o = np.arange(2)
-        idx = (((e[:, 2])[:, None, None, None] + o[None, :, None, None]) * n + (e[:, 1])[:, None, None, None] + o[None, None, :, None]) * n \
-            + (e[:, 0])[:, None, None, None] + o[None, None, None, :]
-        w = lambda fz, fy, fx: torch.from_numpy((fz.T[:, :, None, None] * fy.T[:, None, :, None] * fx.T[:, None, None, :])      # noqa: E731
-                                                .reshape(NPTS, -1).astype(np.float32))
-        self.register_buffer("pidx", torch.from_numpy(idx.reshape(NPTS, -1)))
-        self.register_buffer("wN", w(Bv[2], Bv[1], Bv[0]))
-        self.register_buffer("wX", w(Bv[2], Bv[1], Dv[0]))
-        self.register_buffer("wY", w(Bv[2], Dv[1], Bv[0]))
-        self.register_buffer("wZ", w(Dv[2], Bv[1], Bv[0]))
-        self.register_buffer("normals", torch.from_numpy(nrm.astype(np.float32)))
+        self.register_buffer("pts", torch.from_numpy((0.5 + RADIUS * nrm).astype(np.float32))[None].contiguous())       # (1, NPTS, 3)
+        self.register_buffer("normals", torch.from_numpy(nrm.astype(np.float32))[None].contiguous())
+        self.plan = None                                   # the cloud is fixed: classified and sorted once, on the field's device
         x = np.linspace(0.0, 1.0, n)
         r = np.sqrt((x[None, None, :] - 0.5) ** 2 + (x[None, :, None] - 0.5) ** 2 + (x[:, None, None] - 0.5) ** 2)
         self.register_buffer("u_exact", torch.from_numpy((r - RADIUS).astype(np.float32))[None, None].contiguous())
 
     def point_terms(self, u):
-        up = u.reshape(-1)[self.pidx]                      # (NPTS, 8)
-        val, ux, uy, uz = ((up * w).sum(1) for w in (self.wN, self.wX, self.wY, self.wZ))
-        nr = self.normals
-        return torch.sum(val ** 2) + torch.sum((ux * nr[:, 0] + uy * nr[:, 1] + uz * nr[:, 2] - 1.0) ** 2)
+        if self.plan is None or self.plan.device != u.device:
+            self.plan = pt.PointPlan(self, self.pts)
+        terms = pt.point_loss if self.points == "fused" else pt.point_terms_composed
+        return terms(self, u, self.plan, target=0.0, normals=self.normals, kind="dot", dscale="physical")
 
     def domain_term(self, u):
         if self.mode == "fused":
@@ -92,16 +81,16 @@ class Eikonal3D(DiffNet3DFEM):
         return float(torch.linalg.vector_norm(u - self.u_exact)) / u.shape[-1] ** 1.5
 
 
-def run(n=33, steps=20, optimizer="lbfgs", mode="fused", verbose=True, tau=0.25, lr=1e-2):
-    if mode not in ("fused", "composed"):
-        raise ValueError(f"mode must be 'fused' or 'composed', got {mode!r}")
+def run(n=33, steps=20, optimizer="lbfgs", mode="fused", verbose=True, tau=0.25, lr=1e-2, points="fused"):
+    if mode not in ("fused", "composed") or points not in ("fused", "composed"):
+        raise ValueError(f"mode and points must be 'fused' or 'composed', got {mode!r}, {points!r}")
     dev = torch.device("cuda")
     x = torch.linspace(0.0, 1.0, n)
     # start from a field with a minimum in the sphere's centre and the wrong slope: |grad u| = 0.4
     r = torch.sqrt((x[None, None, :] - 0.5) ** 2 + (x[None, :, None] - 0.5) ** 2 + (x[:, None, None] - 0.5) ** 2)
     u0 = 0.4 * (r - RADIUS)
     field = nn.ParameterList([nn.Parameter(u0.reshape(1, 1, n, n, n).contiguous().to(dev))])
-    m = Eikonal3D(field, n, tau, mode).to(dev)
+    m = Eikonal3D(field, n, tau, mode, points).to(dev)
     if optimizer == "lbfgs":
         opt = torch.optim.LBFGS(field, lr=1.0, max_iter=5)
     elif optimizer == "adam":
@@ -126,7 +115,7 @@ def run(n=33, steps=20, optimizer="lbfgs", mode="fused", verbose=True, tau=0.25,
         hist.append(float(m.loss()))
     torch.cuda.synchronize()
     if verbose:
-        print(f"{steps} steps in {time.perf_counter() - t0:.2f} s ({mode}, {optimizer}, {n}^3 nodes Q1, tau {tau}); final loss {hist[-1]:.6e}; "
+        print(f"{steps} steps in {time.perf_counter() - t0:.2f} s ({mode}, points {points}, {optimizer}, {n}^3 nodes Q1, tau {tau}); final loss {hist[-1]:.6e}; "
               f"|| u - u_exact || / n^1.5 = {m.error():.4e}")
     return field[0].detach(), hist
 
@@ -136,11 +125,12 @@ def main():
     ap.add_argument("--n", type=int, default=33)
     ap.add_argument("--tau", type=float, default=0.25)
     ap.add_argument("--mode", choices=("fused", "composed"), default="fused")
+    ap.add_argument("--points", choices=("fused", "composed"), default="fused")
     ap.add_argument("--optimizer", choices=("lbfgs", "adam"), default="lbfgs")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--lr", type=float, default=1e-2)
     a = ap.parse_args()
-    run(a.n, a.steps, a.optimizer, a.mode, True, a.tau, a.lr)
+    run(a.n, a.steps, a.optimizer, a.mode, True, a.tau, a.lr, a.points)
 
 
 if __name__ == "__main__":

@@ -856,6 +856,69 @@ typedef struct dn_fdm_poisson_args {
 int64_t dn_fdm_poisson_workspace_bytes(int32_t B, int32_t ny, int32_t nx);
 int dn_fdm_poisson_apply(const dn_fdm_poisson_args *args, void *stream);
 
+/* ---- fused point-cloud terms on a Q1 mesh (2-D, 3-D): u and its gradient at points, the penalty loss, its gradient ----------
+ * Replaces the point terms the point-cloud scripts of the reference add to their losses -- the four "+1" neighbour gathers, the
+ * bf_1d_th / bf_1d_der_th products, the weighted sums, the squares and their sums, and the autograd backward that ends in an
+ * index_put with accumulation: examples/poisson/single_instance/pc_poisson_disk.py and pc_complex_immersed_background.py (loss:
+ * sum (u_p - 1)^2), examples/eiqonal/parametric/10_fixed_bc.py:186-208 and single_instance/05_3d_sphere_loss4.py:345-389 (value and
+ * "dot" terms), single_instance/e01_curve_reconstruction.py:270 ("match").  Of those bodies only the two Poisson scripts' are a
+ * usable definition; the terms are defined by the formulas here.
+ *   The points arrive classified and sorted (diffnet_amd/points.py: PointPlan): B samples of npts points each, sorted by (sample,
+ *   element); T = B npts.  elem[q]: the point's element within its sample, (ez nely + ey) nelx + ex;  xi: (nsd, T), the local
+ *   coordinates in [-1, 1], one array per axis (x, y[, z]);  offsets: (B nel + 1) CSR of the sorted list over (sample, element).
+ *   With N0 = (1 - xi)/2, N1 = (1 + xi)/2 per axis and N_a their products over the 2^nsd nodes a of the element:
+ *   u_p = sum_a N_a u_a            g_d = dscale[d] sum_a d_d N_a u_a      (dscale 1: the scripts' reference-coordinate derivative;
+ *                                                                          2 / h_d: the physical gradient)
+ *   values (T) = u_p,  pgrads (nsd, T) = g_d                               where asked
+ *   penalty != 0:  sums[0] = w_val sum_p (u_p - t_p)^2                     t_p = target[q], or target_value when target is NULL
+ *                  sums[1] = w_nrm sum_p (g . n - 1)^2                     kind DN_POINTS_DOT     (normals: (nsd, T))
+ *                          = w_nrm sum_p sum_d (g_d - n_d)^2               kind DN_POINTS_MATCH;   0 for DN_POINTS_NONE
+ *                  sums[2] = sums[0] + sums[1]                             (3 device doubles; fixed-order fp64 reduction in the kernel)
+ *                  cot (1 + nsd, T) = c0 = 2 w_val (u_p - t_p);  c_d = 2 w_nrm (g . n - 1) n_d  |  2 w_nrm (g_d - n_d)  |  0
+ *   grad != NULL:  grad (B,1,*N) = gs sum_p ( c0 N_a + sum_d c_d dscale[d] d_d N_a )  over the points of the node's adjacent elements,
+ *                  gs = gscale (x gscale_dev[0] when that device float is given); with accumulate the sum is added to grad instead,
+ *                  and a node whose adjacent elements hold no point is not written.  cot is then an INPUT unless the same call
+ *                  computes the penalty (forward launch, then adjoint launch): any per-point cotangents of (u_p, g_d) are pulled back.
+ * Forward: one thread per point.  Adjoint: one thread per node, gather form: the node's at most 2^nsd elements in the order z, y, x,
+ * each element's points in stored order, one fp32 fma chain; no atomics, bitwise reproducible.  Element ids and offsets are clamped
+ * into their ranges before they address anything.  npts = 0 is valid: zero sums; grad zero-filled, or left as it is under accumulate.
+ * sums needs `workspace` (zero-filled once before first use, dn_points_workspace_bytes = 4160 + 16 * 1024 bytes whatever the
+ * sizes; every call leaves it ready for the next; one per stream, not shared with other operators).
+ * DN_E_UNSUPPORTED for a Q2 / Q3 mesh (the Python layer composes torch ops there) and for samples of 2^30 nodes or more;
+ * DN_E_BADARG for a NULL mesh or args, nsd outside {2, 3}, fewer than 2 nodes on an axis, B outside 1..65535, npts < 0 or B npts
+ * >= 2^31, an unknown kind, flags outside {0, 1}, nothing to compute, accumulate without grad, sums without penalty, a penalty with
+ * neither sums nor cot, and, where there are points, a NULL u / elem / xi, missing normals for the kind, or an adjoint without
+ * offsets or cot;  DN_E_WORKSPACE for sums without a large enough workspace.  Nothing is launched then. */
+#define DN_POINTS_NONE 0
+#define DN_POINTS_DOT 1
+#define DN_POINTS_MATCH 2
+typedef struct dn_points_args {
+    const float *u;          /* (B,1,*N) nodal field (forward)                              */
+    const int32_t *elem;     /* (T) sorted element ids within the sample (forward)          */
+    const float *xi;         /* (nsd, T) local coordinates                                  */
+    const int32_t *offsets;  /* (B nel + 1) CSR of the sorted list (adjoint)                */
+    int64_t npts;            /* points per sample                                           */
+    float dscale[3];         /* derivative scale per axis (x, y, z)                         */
+    int32_t kind;            /* DN_POINTS_*: the normals term                               */
+    int32_t penalty;         /* 1: form the penalty terms (sums and / or cot)               */
+    const float *target;     /* (T) or NULL (target_value)                                  */
+    float target_value;
+    const float *normals;    /* (nsd, T) or NULL (DN_POINTS_NONE)                           */
+    float w_val, w_nrm;
+    float *values;           /* (T) or NULL                                                 */
+    float *pgrads;           /* (nsd, T) or NULL                                            */
+    float *cot;              /* (1 + nsd, T): written by the penalty, read by the adjoint   */
+    double *sums;            /* 3 device doubles or NULL                                    */
+    const float *gscale_dev; /* optional: one device float                                  */
+    float gscale;
+    float *grad;             /* (B,1,*N) or NULL                                            */
+    int32_t accumulate;      /* 1: grad += instead of grad =                                */
+    void *workspace;
+    int64_t workspace_bytes;
+} dn_points_args;
+int64_t dn_points_workspace_bytes(const dn_mesh *mesh);
+int dn_points_apply(const dn_mesh *mesh, const dn_points_args *args, void *stream);
+
 /* ---- fused output block of the 2-D U-Net generator ----------------------------------------------------------
  * Upsample(x2, nearest) -> ZeroPad2d((1,0,1,0)) -> Conv2d(C -> 1, 4x4, padding 1, bias) -> Sigmoid
  * (DiffNet/networks/unets.py:68-74, `self.final`) without materialising the upsampled tensor.
