@@ -263,6 +263,10 @@ SYMBOLS = {
     "dn_winding_field_tile": (C.c_int, [C.c_int32, C.c_int64]),
     "dn_winding_field": (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                    C.c_int32, C.c_void_p]),
+    "dn_winding_field_vjp_slices": (C.c_int, [C.c_int32, C.c_int32, C.c_int64]),
+    "dn_winding_field_vjp_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "dn_winding_field_vjp": (C.c_int, [C.c_void_p] * 9 + [C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_float, C.c_int32, C.c_void_p]),
 }
 
 _LIB = None

@@ -2491,7 +2491,7 @@ def winding_field(points, normals, area, queries, metric="l1", power=3, scale=1.
     shared by all samples, on the points' device or on the host; metric "l1" (the reference's quirk) or "l2"; power 2 or 3.
     Returns (field, mask): the float32 field (B, nq) if want_field, else None, and the uint8 mask (B, nq) = (w > threshold), compared
     in the kernel, if want_mask, else None.  Every tensor must be float32 and contiguous.  Not differentiable: nothing is recorded for
-    autograd (the reference only thresholds the field)."""
+    autograd (the reference only thresholds the field); winding_field_vjp is its vector-Jacobian product, diffnet_amd.winding wires the two."""
     named = [("points", points), ("normals", normals), ("queries", queries)] + ([("area", area)] if area is not None else [])
     for name, t in named:
         if not isinstance(t, torch.Tensor):
@@ -2532,6 +2532,74 @@ def winding_field(points, normals, area, queries, metric="l1", power=3, scale=1.
                                      power, float(scale), float(threshold), tile, _stream(points))
     _lib.check(rc, "dn_winding_field")
     return field, mask
+
+
+WINDING_VJP_MAX_SLICES = 1024    # most slices of the query range dn_winding_field_vjp takes (0: picked from the problem size)
+_WINDING_VJP_WANT = ("points", "normals", "area")
+
+
+def winding_field_vjp(points, normals, area, queries, grad_field, metric="l1", power=3, scale=1.0, want=_WINDING_VJP_WANT, slices=0):
+    """The vector-Jacobian product of winding_field with respect to the cloud (dn_winding_field_vjp; queries are constants): with
+    d = x_p - q, num = d . n_p and the cotangent g = grad_field (B, nq),
+        grad_area = scale sum_q g num inv,   grad_normals_i = scale a_p sum_q g d_i inv,   grad_points_i = scale a_p sum_q g (n_i inv + num dinv_i).
+    Arguments as winding_field: every tensor float32 and contiguous, on the GPU, queries (dim, nq) or (dim, *grid) possibly on the host.
+    want: the subset of ("points", "normals", "area") to compute; "area" needs an area.  slices: 0 picks the split of the query range
+    from the problem size, 1..1024 force it (the bits are repeatable for a given value and the same for every `want`).
+    Returns (grad_points | None, grad_normals | None, grad_area | None); grad_area has the shape the area was given in."""
+    named = [("points", points), ("normals", normals), ("queries", queries), ("grad_field", grad_field)] + ([("area", area)] if area is not None else [])
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"winding_field_vjp: {name} must be a torch.Tensor")
+        if t.dtype != torch.float32:
+            raise TypeError(f"winding_field_vjp: {name} must be float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"winding_field_vjp: {name} must be contiguous")
+    if points.dim() != 3 or points.shape[2] not in (2, 3):
+        raise ValueError(f"winding_field_vjp: points must be (B, Np, 2) or (B, Np, 3), got {tuple(points.shape)}")
+    B, npts, dim = points.shape
+    if normals.shape != points.shape:
+        raise ValueError(f"winding_field_vjp: normals {tuple(normals.shape)} do not match points {tuple(points.shape)}")
+    if area is not None and tuple(area.shape) not in ((B, npts), (B, npts, 1)):
+        raise ValueError(f"winding_field_vjp: area must be (B, Np) or (B, Np, 1) = ({B}, {npts}[, 1]), got {tuple(area.shape)}")
+    if queries.dim() < 2 or queries.shape[0] != dim:
+        raise ValueError(f"winding_field_vjp: queries must be ({dim}, nq) or ({dim}, *grid), got {tuple(queries.shape)}")
+    nq = queries[0].numel()
+    if grad_field.dim() != 2 or tuple(grad_field.shape) != (B, nq):
+        raise ValueError(f"winding_field_vjp: grad_field must be (B, nq) = ({B}, {nq}), got {tuple(grad_field.shape)}")
+    if metric not in _WINDING_METRICS:
+        raise ValueError(f"winding_field_vjp: metric must be 'l1' or 'l2', got {metric!r}")
+    if power not in (2, 3):
+        raise ValueError(f"winding_field_vjp: power must be 2 or 3, got {power!r}")
+    if not isinstance(slices, int) or not 0 <= slices <= WINDING_VJP_MAX_SLICES:
+        raise ValueError(f"winding_field_vjp: slices must be 0 (automatic) or 1..{WINDING_VJP_MAX_SLICES}, got {slices!r}")
+    want = tuple(want)
+    if not want or any(w not in _WINDING_VJP_WANT for w in want):
+        raise ValueError(f"winding_field_vjp: want must be a non-empty subset of {_WINDING_VJP_WANT}, got {want!r}")
+    if "area" in want and area is None:
+        raise ValueError("winding_field_vjp: the gradient with respect to the area was asked for, but no area was given")
+    for name, t in named:
+        if t.device != points.device and not (name == "queries" and t.device.type == "cpu"):
+            raise ValueError(f"winding_field_vjp: {name} is on {t.device}, points on {points.device}")
+    if not points.is_cuda:
+        raise DiffNetHipError(f"points are on {points.device}: winding_field_vjp runs on the GPU only (no CPU fallback); the composed "
+                              "route for CPU tensors is diffnet_amd.winding.winding_field_composed")
+    if B < 1 or npts < 1 or nq < 1:
+        raise ValueError(f"winding_field_vjp: empty problem (B = {B}, Np = {npts}, nq = {nq})")
+    h = _lib.lib()
+    qd = queries if queries.is_cuda else queries.to(points.device)
+    s = min(slices or h.dn_winding_field_vjp_slices(B, npts, nq), (nq + WINDING_CHUNK - 1) // WINDING_CHUNK)
+    ws, ws_bytes = None, 0
+    if s > 1:
+        ws_bytes = h.dn_winding_field_vjp_workspace_bytes(B, npts, dim, s)
+        _lib.check(min(ws_bytes, 0), "dn_winding_field_vjp_workspace_bytes")
+        ws = torch.empty((ws_bytes // 8,), dtype=torch.float64, device=points.device)
+    gp = torch.empty_like(points) if "points" in want else None
+    gn = torch.empty_like(points) if "normals" in want else None
+    ga = torch.empty_like(area) if "area" in want else None
+    rc = h.dn_winding_field_vjp(_p(points), _p(normals), _p(area), _p(qd), _p(grad_field), _p(gp), _p(gn), _p(ga), _p(ws), ws_bytes, B, npts, nq,
+                                dim, _WINDING_METRICS[metric], power, float(scale), s, _stream(points))
+    _lib.check(rc, "dn_winding_field_vjp")
+    return gp, gn, ga
 
 
 # ---- the fused point-cloud terms: evaluation at points, penalty loss and gradient: dn_points_apply ----------------------------------

@@ -302,6 +302,36 @@ int dn_winding_field(const float *points, const float *normals, const float *are
                      uint8_t *mask, int32_t batch, int32_t npts, int64_t nq, int32_t dim, int32_t metric, int32_t power,
                      float scale, float threshold, int32_t tile, void *stream);
 
+/* Vector-Jacobian product of dn_winding_field with respect to the cloud (queries are constants), same layouts and parameters.  With
+ * d = x_p - q, num = d . n_p, a_p = 1 without area and the cotangent g = grad_field (B, nq):
+ *   L2 (metric 1): inv = r^-power, r = |d|_2,     dinv_i = -power d_i r^-(power + 2)
+ *   L1 (metric 0): inv = s^-power, s = sum |d_i|, dinv_i = -power sgn(d_i) s^-(power + 1),  sgn(0) = 0 (torch's convention)
+ *   grad_area[b,p]      = scale     sum_q g num inv                       (B, npts); needs `area`
+ *   grad_normals[b,p,i] = scale a_p sum_q g d_i inv                       (B, npts, dim)
+ *   grad_points[b,p,i]  = scale a_p sum_q g (n_i inv + num dinv_i)        (B, npts, dim)
+ * Any of the three outputs may be NULL, not all.  This differentiates the reference forms the forward covers (compute_winding_torch,
+ * examples/eiqonal/single_instance/02_differentiable_winding_number.py:15-30, plain differentiable torch there; compute_winding_gpts and
+ * compute_winding_nodes in 2-D).
+ * A workgroup owns 256 points of one sample and the queries pass through LDS 256 at a time; the query range is split over
+ * `slices` workgroups (0: dn_winding_field_vjp_slices(batch, npts, nq), the count that gives each of the 256 CUs about 64 workgroups, at
+ * most the number of 256-query chunks and at most 1024; a larger request than chunks is clamped to the chunks).  Order: inside a chunk
+ * fp32 chains from zero in query order, chunks added in float64, slices added in float64 in index order by a second small launch, one
+ * rounding to float32; no atomics.  Results are bitwise repeatable for a given slice count and the same whichever outputs are
+ * requested; across slice counts the last bits may differ (the forward's bits do not depend on its tile).  With more than one
+ * effective slice the launch needs `workspace` of dn_winding_field_vjp_workspace_bytes(batch, npts, dim, slices) =
+ * slices * batch * npts * (1 + 2 dim) * 8 bytes, 8-byte aligned; it is not read between calls.  A point that coincides with a query
+ * gives inf or nan, as in the forward.
+ * All checks come before any launch.  DN_E_BADARG: a NULL points / normals / queries / grad_field, all three outputs NULL, grad_area
+ * without area, dim, metric or power outside the forward's values, batch outside 1..65535, npts < 1, nq < 1, slices < 0 or > 1024
+ * (dn_winding_field_vjp_slices: batch, npts or nq < 1; ..._workspace_bytes: also slices < 1).  DN_E_WORKSPACE: more than one effective
+ * slice and a NULL or too small workspace. */
+int dn_winding_field_vjp_slices(int32_t batch, int32_t npts, int64_t nq);
+int64_t dn_winding_field_vjp_workspace_bytes(int32_t batch, int32_t npts, int32_t dim, int32_t slices);
+int dn_winding_field_vjp(const float *points, const float *normals, const float *area, const float *queries,
+                         const float *grad_field, float *grad_points, float *grad_normals, float *grad_area, void *workspace,
+                         int64_t workspace_bytes, int32_t batch, int32_t npts, int64_t nq, int32_t dim, int32_t metric, int32_t power,
+                         float scale, int32_t slices, void *stream);
+
 /* DiffNetFDM stencil derivatives (DiffNet/DiffNetFDM.py:158-199): out = Corr( conv2d(g_padded, kernel9) ) with
  * g_padded (B,1,ny+2,nx+2) replicate-padded by the caller as in the reference, out (B,1,ny,nx), kernel9 a HOST pointer to
  * the 3x3 correlation kernel (row-major), and the reference's dense correction matmul (:63-119) reduced to what it does:
