@@ -81,7 +81,8 @@ __device__ __forceinline__ V ld_at(const T* __restrict__ base, unsigned index) {
 template <typename V, typename T>
 __device__ __forceinline__ void st_at(T* __restrict__ base, unsigned index, const V& v) {
 #if DN_NT_STORES            // the operators' outputs are written once and not read again by the launch: non-temporal stores (2-D bench
-                            // kernel 54.3 -> 52.8 us, profiles/r2_ab2d_nt.txt; non-temporal LOADS are 20 % slower: halo rows and shared nodes are re-read)
+                            // kernel 54.3 -> 52.8 us, profiles/r2_ab2d_nt.txt; measured again beside non-temporal loads, against plain and
+                            // write-through stores: 3-6 us ahead of both, profiles/q1cf_cache_policy.txt)
     char* a = reinterpret_cast<char*>(base) + (index * (unsigned)sizeof(T));
     if constexpr (sizeof(V) == 16) {
         typedef float v4f __attribute__((ext_vector_type(4)));
@@ -150,6 +151,30 @@ __device__ __forceinline__ void load_seg_stream(const T* __restrict__ base, unsi
     } else {
         load_seg<NW, VEC>(base, rowoff, x0, nx, dst);
     }
+}
+
+// Row segment of four float nodes whose fifth node -- the one shared with the right neighbour -- comes from the neighbouring LANE
+// once the row has landed (seg_take_shared) instead of from a strided dword load per lane: the four own nodes as one vector load
+// (NT: non-temporal -- with nothing of the segment read twice inside the workgroup this holds for a re-read field like u as well), and
+// ONE dword at node xs: the shared node for a lane that has no neighbour lane to take it from (lane 63 of a wave, the last thread of
+// a chunk), one wave-uniform node for every other lane, so the instruction touches one line per wave instead of sixteen.  xs < nx.
+template <bool NT>
+__device__ __forceinline__ void load_seg4_xs(const float* __restrict__ base, unsigned rowoff, int x0, int nx, unsigned xs, float (&dst)[5]) {
+    typedef float v4t __attribute__((ext_vector_type(4)));
+    const unsigned xl = (unsigned)min(x0, nx - 4);
+    const v4t* a = reinterpret_cast<const v4t*>(reinterpret_cast<const char*>(base) + (rowoff + xl) * 4u);
+    v4t v;
+    if constexpr (NT) v = __builtin_nontemporal_load(a);
+    else v = *a;
+    dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w;
+    dst[4] = ld_at<float>(base, rowoff + xs);
+}
+// dst[4] <- dst[0] of the next lane where has_nb, else it stays what load_seg4_xs fetched.  A DPP move (wave_shl:1: lane l reads lane
+// l + 1, lane 63 keeps its own value) and a select: no LDS traffic, and no branch for the compiler to put the move into (a
+// `lane63 ? other : __shfl_down(v)` becomes a divergent branch in which lane 63, the source of lane 62, is masked off).
+__device__ __forceinline__ void seg_take_shared(float (&dst)[5], bool has_nb) {
+    const int t = __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, dst[4]), __builtin_bit_cast(int, dst[0]), 0x130, 0xf, 0xf, false);
+    dst[4] = has_nb ? __builtin_bit_cast(float, t) : dst[4];
 }
 
 // Exactly NW consecutive nodes starting at x0 (clamped like load_seg, no shared +1 node).

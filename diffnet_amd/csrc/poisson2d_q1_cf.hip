@@ -12,8 +12,9 @@
 // This is algebra, not a change of rule: the moments are computed from the rule's own points and weights (including the reference's
 // truncated 3- and 4-point literals), so the value equals the Gauss sum over any ngp x ngp points to rounding
 // (tests/test_q1cf_rowstaged.py: 1e-12 in float64).  Main loop of the bench instantiation <4, true, nu | f | one bit-packed condition, 1>,
-// two node rows = eight elements per thread: 552 VALU instructions, 16 loads, 2 stores, 2 barriers, 98 VGPRs (the element on raw nodal
-// values it replaced: 724 and 105; tools/q1cf_loop_count.py, profiles/q1cf_rowstaged.txt).  The generic mask / value-field form (CF_BC)
+// two node rows = eight elements per thread: 569 VALU instructions, 16 loads, 2 stores, 2 barriers, 100 VGPRs (552 and 98 before the shared
+// node came from the neighbouring lane, profiles/q1cf_cache_policy.txt; the element on raw nodal values: 724 and 105; tools/q1cf_loop_count.py,
+// profiles/q1cf_rowstaged.txt).  The generic mask / value-field form (CF_BC)
 // keeps the element on raw nodal values (ROWSTAGED below).
 //
 // Mapping as the other 2-D kernels: a thread owns E consecutive elements of a strip and marches over element rows; it
@@ -22,7 +23,10 @@
 #include <cstdlib>
 #include <type_traits>
 
-#define DN_NT_STORES 1            // the gradient rows are written once and never re-read by the launch: 54.3 -> 52.8 us (profiles/r2_ab2d_nt.txt)
+#define DN_NT_STORES 1            // the gradient rows are written once and never re-read by the launch: 54.3 -> 52.8 us when every load was plain
+                                  // (profiles/r2_ab2d_nt.txt); with today's non-temporal loads, on the rotation: plain stores 58.7-59.2 us, write-through
+                                  // (sc1) 58.6-58.9, non-temporal 55.3-55.9 -- and 56.3-57.9 / 55.4-57.0 / 51.5-51.7 with the shared node from the
+                                  // neighbouring lane and non-temporal u (profiles/q1cf_cache_policy.txt).  The flat-stream probe's ranking (plain ahead) does not carry over
 #include "poisson_common.h"
 
 namespace dn {
@@ -49,8 +53,11 @@ struct CfRow {
 };
 
 // Measured and removed (code in the history):
-//  - the shared node x0 + 4 from the neighbouring lane instead of a strided per-lane load: over DPP equal (profiles/r2_2d_ab.txt), over ds_bpermute
-//    with non-temporal row loads slower, 60-69 us
+//  - the shared node x0 + 4 from the neighbouring lane, exchanged when the row is ISSUED: over DPP equal (profiles/r2_2d_ab.txt), over ds_bpermute
+//    with non-temporal row loads slower, 60-69 us -- every row load waited for the one before.  Exchanged when the row has
+//    LANDED it is what the kernel does now (XCH below)
+//  - plain or write-through (sc1) stores of the gradient rows in place of non-temporal ones: +3 us without, +4 to +6 us with the lane exchange;
+//    u's loads non-temporal on the rows a neighbouring strip reads as well: +0.6 to +1.0 us (profiles/q1cf_cache_policy.txt)
 //  - neighbouring strips marching in opposite directions on one XCD: traffic 1.09x -> 1.002x of the algorithmic bytes, but slower where every
 //    launch streams from HBM (59.5 vs 56.4 us, profiles/r2_rotate_variants.txt)
 //  - software-pipelined rows (one / two raw rows in flight): 48.1 / 50.6 us against 46.9 on the default plan (profiles/r2_plan2d_steady.txt)
@@ -113,6 +120,13 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : 2) poisso
     const int x0 = ex0;
     const bool col_owner = !(chunk > 0 && tid == 0);
     const bool lastcol = UA && x0 + NW == p.nx - 1;      // this thread's shared node is the mesh's last node column: nobody to the right owns it
+    // XCH (four elements per thread, one strip per workgroup; not the generic mask / value-field form, which it would push from 4 to 3
+    // waves per SIMD): the node x0 + NW of u, nu and f comes from the right neighbour's lane once the row has landed (row_bc) instead of
+    // from a strided dword load per lane.  has_nb: the neighbour is a lane of this wave; every other lane -- lane 63, the chunk's last
+    // thread, the CF_UA thread whose shared node is the mesh's last column -- keeps its own load (xs: load_seg4_xs)
+    constexpr bool XCH = W == 1 && VEC && E == 4 && (FL & CF_BC) == 0;
+    const bool has_nb = XCH && ((int)threadIdx.x & 63) < 63 && (int)threadIdx.x + 1 < (int)blockDim.x && !lastcol;
+    const unsigned xs = (unsigned)min((has_nb ? __builtin_amdgcn_readfirstlane(q) + 63 : q) * E + NW, p.nx - 1);
     const int64_t nps = (int64_t)p.nx * p.ny;
     const SampleBases sb = sample_bases(p, b, nps);
     const int R = p.rows_per_strip;
@@ -217,15 +231,25 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : 2) poisso
         }
     };
 
-    auto row_issue = [&](int yr, CfRow<E>& r) {
+    // nt_u (XCH): u's vector load non-temporal
+    auto row_issue = [&](auto nt_u, int yr, CfRow<E>& r) {
         const int yp = min(yr, p.ny - 1);
         const unsigned rowoff = (unsigned)yp * (unsigned)p.nx;
-        load_seg<NW, VEC>(sb.u, rowoff, x0, p.nx, r.u);
-        // nu and f (read once per launch) as non-temporal vector loads, the node shared with the right neighbour as a plain load.  On one
-        // re-evaluated batch this gives up the Infinity-Cache hits (47 -> 53 us); on batches in rotation -- every launch streams from HBM, the
-        // regime bench.py times -- it wins: mask bits 58.3 -> 55.5 us, box 56.5 -> 56.0; u as well was slower: 59.8 (profiles/r3_rotate_nt.txt)
-        if constexpr (HAS_NU) load_seg_stream<NW, VEC>(sb.nu, rowoff, x0, p.nx, r.n);
-        if constexpr (HAS_F) load_seg_stream<NW, VEC>(sb.f, rowoff, x0, p.nx, r.f);
+        // nu and f (read once per launch) as non-temporal vector loads.  On one re-evaluated batch this gives up the Infinity-Cache hits
+        // (47 -> 53 us); on batches in rotation -- every launch streams from HBM, the regime bench.py times -- it wins: mask bits 58.3 -> 55.5 us,
+        // box 56.5 -> 56.0 (profiles/r3_rotate_nt.txt).  u as well was slower (59.8) as long as every lane re-read its shared node with a dword
+        // load; with the shared node taken from the neighbouring lane (XCH) the rotation goes 55.5 -> 52.8 us with plain u loads,
+        // -> 51.6 with non-temporal ones on every row and -> 50.3 (against 51.2 in that series) with the rows a neighbouring strip reads
+        // as well kept plain (nt_u, see the march below; profiles/q1cf_cache_policy.txt)
+        if constexpr (XCH) {
+            load_seg4_xs<decltype(nt_u)::value>(sb.u, rowoff, x0, p.nx, xs, r.u);
+            if constexpr (HAS_NU) load_seg4_xs<true>(sb.nu, rowoff, x0, p.nx, xs, r.n);
+            if constexpr (HAS_F) load_seg4_xs<true>(sb.f, rowoff, x0, p.nx, xs, r.f);
+        } else {
+            load_seg<NW, VEC>(sb.u, rowoff, x0, p.nx, r.u);
+            if constexpr (HAS_NU) load_seg_stream<NW, VEC>(sb.nu, rowoff, x0, p.nx, r.n);
+            if constexpr (HAS_F) load_seg_stream<NW, VEC>(sb.f, rowoff, x0, p.nx, r.f);
+        }
         if constexpr (BC_PACKED) {
             packed_issue(yp, r);
         } else if constexpr (BC_U8C && ONE) {
@@ -253,8 +277,14 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : 2) poisso
             bc_issue<NW, VEC>(p, sb, rowoff, x0, r.bc);
         }
     };
-    // u <- where(mask, value, u) on a landed row, keep[] = 0 on its Dirichlet nodes
+    // u <- where(mask, value, u) on a landed row, keep[] = 0 on its Dirichlet nodes; before that (XCH) the row's shared nodes, as they
+    // landed: every thread applies the conditions to its five nodes itself, from its own mask bits
     auto row_bc = [&](CfRow<E>& r) {
+        if constexpr (XCH) {
+            seg_take_shared(r.u, has_nb);
+            if constexpr (HAS_NU) seg_take_shared(r.n, has_nb);
+            if constexpr (HAS_F) seg_take_shared(r.f, has_nb);
+        }
 #pragma unroll
         for (int n = 0; n < NW; ++n) r.keep[n] = 1.f;
         if constexpr (UA) r.keepx = 1.f;
@@ -419,7 +449,7 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : 2) poisso
     // one element layer between the lower row L (Dirichlet applied) and the freshly landed upper row U; cin holds the
     // contributions of the layer below to L's nodes, cout receives this layer's contributions to U's nodes
     // fresh: U has just landed from HBM (Dirichlet select and forcing x-stage still to do); not fresh: U came finished from the strip above
-    auto layer = [&](auto fresh, int ey, const CfRow<E>& L, CfRow<E>& U, const float (&cin)[NW + 1], float (&cout)[NW + 1]) {
+    auto layer = [&](auto fresh, int ey, const CfRow<E>& L, CfRow<E>& U, const float (&cin)[NW + 1], float (&cout)[NW + 1]) __attribute__((always_inline)) {
         const bool own_layer = ey >= e_from && ey <= e_until;
         const float cnt = (own_layer && col_owner) ? 1.f : 0.f;
         if constexpr (decltype(fresh)::value) { row_bc(U); fstage(U); }
@@ -561,7 +591,9 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : 2) poisso
     float carryA[NW + 1], carryB[NW + 1];
 #pragma unroll
     for (int n = 0; n <= NW; ++n) carryA[n] = carryB[n] = 0.f;
-    row_issue(ey_begin, RA);
+    constexpr std::true_type NT_U{};
+    constexpr std::false_type PLAIN_U{};
+    row_issue(PLAIN_U, ey_begin, RA);
     row_bc(RA);
     fstage(RA);
     sstage(RA);
@@ -571,16 +603,32 @@ __global__ void __launch_bounds__(W > 1 ? CF_TS * W : 256, W > 1 ? 4 : 2) poisso
     int ey = ey_begin;
     bool odd = false;
     const int n_main = chain_up ? ey_end - 1 : ey_end;         // chain_up: the strip's last layer takes its upper row from the strip above (LDS)
-    for (; ey + 1 < n_main; ey += 2) {
+    auto trip2 = [&](auto nt_u) __attribute__((always_inline)) {
         set_prio(ey);
-        row_issue(ey + 1, RB);
+        row_issue(nt_u, ey + 1, RB);
         layer(FRESH, ey, RA, RB, carryA, carryB);
-        row_issue(ey + 2, RA);
+        row_issue(nt_u, ey + 2, RA);
         layer(FRESH, ey + 1, RB, RA, carryB, carryA);
+        ey += 2;
+    };
+    if constexpr (XCH) {
+        // the rows a neighbouring strip reads as well (the strip's first two and last two) with plain loads, the rows it owns alone
+        // non-temporal: the first and the last two-row trip peeled out of the loop, no branch inside it
+        if (ey + 1 < n_main) trip2(PLAIN_U);
+        while (ey + 3 < n_main) trip2(NT_U);
+        if (ey + 1 < n_main) trip2(PLAIN_U);
+    } else {                          // (the loop as every other form has always had it: through trip2 the two-element forms compile to a few instructions more)
+        for (; ey + 1 < n_main; ey += 2) {
+            set_prio(ey);
+            row_issue(PLAIN_U, ey + 1, RB);
+            layer(FRESH, ey, RA, RB, carryA, carryB);
+            row_issue(PLAIN_U, ey + 2, RA);
+            layer(FRESH, ey + 1, RB, RA, carryB, carryA);
+        }
     }
     if (ey < n_main) {
         set_prio(ey);
-        row_issue(ey + 1, RB);
+        row_issue(PLAIN_U, ey + 1, RB);
         layer(FRESH, ey, RA, RB, carryA, carryB);
         odd = true;
         ++ey;
