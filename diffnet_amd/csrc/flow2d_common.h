@@ -1,12 +1,13 @@
 // Shared by the two three-field 2-D flow operators (stokes.hip, navier_stokes.hip): everything that is not their mathematics.  The
-// kernel parameters both use, the wave's place in the launch, the per-sample base pointers, the row loader, the Dirichlet test, the
-// in_num / in_den scale; on the host the mesh check, the launch plan, the reduction workspace, the argument checks common to
+// kernel parameters both use, the per-sample base pointers, the row loader, the Dirichlet test, the in_num / in_den scale (the wave's
+// place in the launch, the lane's column and the hand-over between lanes: q1_owner_march.h, which transport.hip and
+// poisson_coef_grad.hip share too); on the host the mesh check, the launch plan, the reduction workspace, the argument checks common to
 // dn_stokes_args and dn_ns_args (same member names), their copy into the parameters and the (MASK, BCF, FGP) launch switch.
 // Nothing here asks which operator it serves: what differs stays in the operator's own file, after or around these calls.
 #pragma once
 #include <algorithm>
 
-#include "dn_reduce.h"
+#include "q1_owner_march.h"
 
 namespace dn {
 
@@ -32,28 +33,9 @@ struct Flow2dParams {
     int nx, ny, nelx, nely, chunks, rows_per_strip, strips, want_sums;
 };
 
-constexpr int FLOW2D_OWNERS = 62;          // owner lanes per wave (lanes 1 .. 62); lanes 0 and 63 are ghosts that only supply the x halo
-
-// One wave per (62-column chunk, strip of node rows, sample): the wave's chunk and strip (strip >= p.strips: a wave of the last
-// workgroup with nothing to do) and the lane.  Params: anything with `chunks` (transport.hip places its waves the same way)
-template <class Params>
-__device__ __forceinline__ void flow2d_wave(const Params& p, int& lane, int& chunk, int& strip) {
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    lane = (int)threadIdx.x & 63;
-    const int wid = (int)blockIdx.x * ((int)blockDim.x >> 6) + wave;
-    chunk = wid % p.chunks;
-    strip = wid / p.chunks;
-}
-
-// A lane's column and the base pointers of its sample.  NX: extra node arrays a row carries (the caller sets xb)
+// A lane's column (Q1Lane, q1_owner_march.h) and the base pointers of its sample.  NX: extra node arrays a row carries (the caller sets xb)
 template <int NX>
-struct Flow2dLane {
-    int q;                                 // node column of the lane
-    bool owner;
-    unsigned qc;                           // q clamped into the mesh
-    bool elem_x;                           // the element to the right of the lane's column exists
-    unsigned qe;                           // its column, clamped
-    int nel;
+struct Flow2dLane : Q1Lane {
     const float* fb[3];
     const float* xb[NX ? NX : 1];
     const float* bcf[3];
@@ -65,13 +47,7 @@ struct Flow2dLane {
 
 template <int NX>
 __device__ __forceinline__ void flow2d_lane(const Flow2dParams& p, int chunk, int lane, Flow2dLane<NX>& L) {
-    const int nx = p.nx;
-    L.q = chunk * FLOW2D_OWNERS + lane - 1;
-    L.owner = lane >= 1 && lane <= FLOW2D_OWNERS && L.q < nx;
-    L.qc = (unsigned)min(max(L.q, 0), nx - 1);
-    L.elem_x = L.q >= 0 && L.q < p.nelx;
-    L.qe = (unsigned)min(max(L.q, 0), p.nelx - 1);
-    L.nel = p.nelx * p.nely;
+    q1_lane(chunk, lane, p.nx, p.nelx, p.nely, L);
 }
 
 // Base pointers of field k (k < 3) in sample b.  The kernels call it in a loop over k of their own: until that loop is unrolled the

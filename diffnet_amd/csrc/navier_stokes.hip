@@ -13,20 +13,15 @@
 // cotangents evaluated like fields (L_k, L_k,x, L_k,y) the pullback of s = sum_k (L_k A_k + L_k,x B_k + L_k,y C_k) with tau held fixed is
 // again N_a G + Nx_a G_x + Ny_a G_y per field (ns_vjp_flux below; DESIGN.md section 3.2 has the derivation), so both modes share the march.
 //
-// Element-owner march: one wave = 62 owner columns + two ghost lanes; lane q owns node column q and the element to its right.  A lane
-// marches the node rows of a strip, loads every node row once (the x neighbour comes over ds_bpermute), computes its element's four local
-// contributions, hands the two right-hand ones to its neighbour lane (shuffle) and carries the top pair in registers into the next element
-// row.  A strip recomputes one halo element row under it, so every output node is written once, by its owner lane, with the same additions
-// in any launch plan: no atomics on the data path, results bitwise independent of the plan and of the other samples of the batch.
-// Sums of squares: fixed-order fp64 reduction (finish_sums3).
+// The mapping is the element-owner march of q1_owner_march.h (one wave = 62 owner columns + two ghost lanes, every output node written
+// once by its owner lane with the same additions in any launch plan); the kernel supplies its rows, its element and its Dirichlet-row
+// rule.  Sums of squares: fixed-order fp64 reduction (finish_sums3).
 #include "flow2d_common.h"      // everything the kernel shares with stokes.hip: parameters, lane set-up, row loader, plan, checks, launch switch
 
 namespace dn {
 
 struct NsParams : Flow2dParams {
-    float bx[4][2], dx[4][2];              // 1-D Q1 basis / derivative (times 2 / hx) at the Gauss points along x
-    float by[4][2], dy[4][2];              // along y
-    float wg[16];                          // wscale w_ig w_jg, point jg * ngp + ig
+    Q1Tables tb;
     float visco;
     float Gx, Gy, diff, gg_inv;            // tau: Gx = 4 / hx^2, Gy = 4 / hy^2, diff = cinv visco^2 (Gx^2 + Gy^2), gg_inv = 1 / (gx^2 + gy^2)
     const float* cot[3];                   // VJP: the cotangents of R1..R3 (fld: the linearisation point)
@@ -36,20 +31,10 @@ struct NsParams : Flow2dParams {
 template <bool VJP>
 struct NsRow {
     float c[3], n[3];
-    float lc[VJP ? 3 : 1], ln[VJP ? 3 : 1];
+    float lc[VJP ? 3 : 1] = {}, ln[VJP ? 3 : 1] = {};      // the forward does not set them
     unsigned fixed;
     float bv[3];
 };
-
-// value and derivatives at one point from the element's four nodal values (local node ly * 2 + lx)
-__device__ __forceinline__ void ns_eval(float bx0, float bx1, float dx0, float dx1, float by0, float by1, float dy0, float dy1,
-                                        float f0, float f1, float f2, float f3, float& val, float& fx, float& fy) {
-    const float vb = fmaf(bx0, f0, bx1 * f1), vt = fmaf(bx0, f2, bx1 * f3);
-    const float db = fmaf(dx0, f0, dx1 * f1), dt = fmaf(dx0, f2, dx1 * f3);
-    val = fmaf(by0, vb, by1 * vt);
-    fx = fmaf(by0, db, by1 * dt);
-    fy = fmaf(dy0, vb, dy1 * vt);
-}
 
 // forward coefficients (A, B, C) of the three weak forms at a point
 __device__ __forceinline__ void ns_fwd_flux(const NsParams& p, float u, float ux, float uy, float v, float vx, float vy, float pg, float px,
@@ -159,15 +144,15 @@ __global__ void __launch_bounds__(256) ns2d_kernel(const NsParams p) {
                 for (int a = 0; a < 4; ++a) acc[k][a] = 0.f;
 #pragma unroll
             for (int jg = 0; jg < NGP; ++jg) {
-                const float by0 = p.by[jg][0], by1 = p.by[jg][1], dy0 = p.dy[jg][0], dy1 = p.dy[jg][1];
+                const float by0 = p.tb.by[jg][0], by1 = p.tb.by[jg][1], dy0 = p.tb.dy[jg][0], dy1 = p.tb.dy[jg][1];
 #pragma unroll
                 for (int ig = 0; ig < NGP; ++ig) {
                     const int g = jg * NGP + ig;
-                    const float bx0 = p.bx[ig][0], bx1 = p.bx[ig][1], dx0 = p.dx[ig][0], dx1 = p.dx[ig][1];
+                    const float bx0 = p.tb.bx[ig][0], bx1 = p.tb.bx[ig][1], dx0 = p.tb.dx[ig][0], dx1 = p.tb.dx[ig][1];
                     float val[3], gx[3], gy[3];
 #pragma unroll
                     for (int k = 0; k < 3; ++k)
-                        ns_eval(bx0, bx1, dx0, dx1, by0, by1, dy0, dy1, Bm.c[k], Bm.n[k], Tp.c[k], Tp.n[k], val[k], gx[k], gy[k]);
+                        q1_eval(bx0, bx1, dx0, dx1, by0, by1, dy0, dy1, Bm.c[k], Bm.n[k], Tp.c[k], Tp.n[k], val[k], gx[k], gy[k]);
                     float f1 = p.fconst[0], f2 = p.fconst[1];
                     if constexpr (FGP) {
                         f1 = p.fgp[0] ? w.f[0][g] : f1;
@@ -178,78 +163,40 @@ __global__ void __launch_bounds__(256) ns2d_kernel(const NsParams p) {
                         float L[3], Lx[3], Ly[3];
 #pragma unroll
                         for (int k = 0; k < 3; ++k)
-                            ns_eval(bx0, bx1, dx0, dx1, by0, by1, dy0, dy1, Bm.lc[k], Bm.ln[k], Tp.lc[k], Tp.ln[k], L[k], Lx[k], Ly[k]);
+                            q1_eval(bx0, bx1, dx0, dx1, by0, by1, dy0, dy1, Bm.lc[k], Bm.ln[k], Tp.lc[k], Tp.ln[k], L[k], Lx[k], Ly[k]);
                         ns_vjp_flux(p, val[0], gx[0], gy[0], val[1], gx[1], gy[1], gx[2], gy[2], f1, f2, L, Lx, Ly, A, Bc, Cc);
                     } else {
                         ns_fwd_flux(p, val[0], gx[0], gy[0], val[1], gx[1], gy[1], val[2], gx[2], gy[2], f1, f2, A, Bc, Cc);
                     }
-                    const float wq = p.wg[g];
+                    const float wq = p.tb.wg[g];
 #pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        const float Aw = wq * A[k], Bw = wq * Bc[k], Cw = wq * Cc[k];
-                        const float s0 = fmaf(by0, Aw, dy0 * Cw), s1 = fmaf(by1, Aw, dy1 * Cw);     // per ly: N_ly A + N'_ly C
-                        const float t0 = by0 * Bw, t1 = by1 * Bw;
-                        acc[k][0] = fmaf(bx0, s0, fmaf(dx0, t0, acc[k][0]));
-                        acc[k][1] = fmaf(bx1, s0, fmaf(dx1, t0, acc[k][1]));
-                        acc[k][2] = fmaf(bx0, s1, fmaf(dx0, t1, acc[k][2]));
-                        acc[k][3] = fmaf(bx1, s1, fmaf(dx1, t1, acc[k][3]));
-                    }
+                    for (int k = 0; k < 3; ++k) q1_flux_scatter(bx0, bx1, dx0, dx1, by0, by1, dy0, dy1, wq, A[k], Bc[k], Cc[k], acc[k]);
                 }
             }
             const bool ok = L.elem_x && e >= 0 && e < p.nely;
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                float c[4];
+            for (int k = 0; k < 3; ++k) q1_owner_handover(ok, acc[k], bot[k], top[k]);
+        };
+
+        // node row e of the three residuals
+        auto finish = [&](int e, const Row& R, const float (&carry)[3], const float (&bot)[3]) {
+            const unsigned rowoff = (unsigned)e * (unsigned)nx + L.qc;
 #pragma unroll
-                for (int a = 0; a < 4; ++a) c[a] = ok ? acc[k][a] : 0.f;
-                // the node's own element (right) as local node lx = 0, the left neighbour's element as lx = 1
-                bot[k] = c[0] + __shfl_up(c[1], 1, 64);
-                top[k] = c[2] + __shfl_up(c[3], 1, 64);
+            for (int k = 0; k < 3; ++k) {
+                float r = carry[k] + bot[k];
+                if constexpr (MASK) {
+                    // forward: Dirichlet rows take the boundary value (the scripts' torch.where); VJP: no gradient reaches a substituted node
+                    const bool fx = (R.fixed & (1u << k)) != 0u;
+                    r = fx ? (VJP ? 0.f : R.bv[k]) : r;
+                }
+                sq[k] = L.owner ? fmaf(r, r, sq[k]) : sq[k];
+                if (L.owner && L.ob[k]) st_at<float>(L.ob[k], rowoff, r);
             }
         };
 
         const int j0 = strip * p.rows_per_strip, j1 = min(j0 + p.rows_per_strip, ny);
-        Row prev, cur;
-        float carry[3] = {0.f, 0.f, 0.f};
-        // two rows in flight ahead of the element row being computed (W0, W1 alternate; unrolled by two so that no register with a load
-        // outstanding is ever copied)
-        Raw W0, W1;
-        {
-            Raw A;
-            issue(j0 - 1, A);
-            issue(j0, W0);
-            issue(j0 + 1, W1);
-            consume(A, prev);
-        }
-        // element row e (from e = j0 - 1, the halo row): W holds the raw node row e + 1 and the element layer e; refilled with row e + 3.
-        // Node row e is finished here.
-        auto step = [&](int e, Raw& W) {
-            consume(W, cur);
-            float bot[3], top[3];
-            element(prev, cur, W, e, bot, top);
-            issue(e + 3, W);
-            if (e >= j0) {
-                const unsigned rowoff = (unsigned)e * (unsigned)nx + L.qc;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    float r = carry[k] + bot[k];
-                    if constexpr (MASK) {
-                        // forward: Dirichlet rows take the boundary value (the scripts' torch.where); VJP: no gradient reaches a substituted node
-                        const bool fx = (prev.fixed & (1u << k)) != 0u;
-                        r = fx ? (VJP ? 0.f : prev.bv[k]) : r;
-                    }
-                    sq[k] = L.owner ? fmaf(r, r, sq[k]) : sq[k];
-                    if (L.owner && L.ob[k]) st_at<float>(L.ob[k], rowoff, r);
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 3; ++k) carry[k] = top[k];
-            prev = cur;
-        };
-        for (int e = j0 - 1; e < j1; e += 2) {
-            step(e, W0);
-            if (e + 1 < j1) step(e + 1, W1);
-        }
+        constexpr int NF = 3;
+#include "q1_owner_march.inl"
     }
     if (p.want_sums) finish_sums3(p.part, p.counter, p.sumsq, p.norms, sq, (int)threadIdx.x, (int)blockDim.x, red, &last_flag);
 }
@@ -293,19 +240,7 @@ extern "C" int dn_ns_apply(const dn_mesh* m, const dn_ns_args* a, void* stream) 
 
     NsParams pp;
     const int ngp = m->ngp;
-    const double sx = m->scale[0], sy = m->scale[1], J = a->wscale;
-    for (int ig = 0; ig < 4; ++ig)
-        for (int i = 0; i < 2; ++i) {
-            const bool in = ig < ngp;
-            pp.bx[ig][i] = in ? m->basis[ig][i] : 0.f;
-            pp.by[ig][i] = in ? m->basis[ig][i] : 0.f;
-            pp.dx[ig][i] = in ? (float)(m->dbasis[ig][i] * sx) : 0.f;
-            pp.dy[ig][i] = in ? (float)(m->dbasis[ig][i] * sy) : 0.f;
-        }
-    for (int gq = 0; gq < 16; ++gq) {
-        const int ig = gq % ngp, jg = gq / ngp;
-        pp.wg[gq] = gq < ngp * ngp ? (float)(J * m->gpw[ig] * m->gpw[jg]) : 0.f;
-    }
+    q1_tables_fill(pp.tb, m, a->wscale);
     // calc_tau of the scripts: g and G are float32 tensors, the diffusion part a float32 product
     const float visco = a->visco;
     const double hx = a->tau_h[0], hy = a->tau_h[1];

@@ -8,11 +8,9 @@
 // v = u~, values included).  It replaces what autograd does for the coefficient of the reference's topology optimisation
 // (examples/poisson/single_instance/16_topopt.py:119-195).  No reduction, no workspace, no atomics.
 //
-// 2-D Q1, rules of 2 to 4 points per axis: the element-owner march of transport.hip -- one wave = 62 owner columns + two ghost lanes,
-// lane q owns node column q and the element to its right, every node row is loaded once (the x neighbour comes over ds_bpermute), the
-// element's four local contributions are formed per Gauss point, the two right-hand ones go to the neighbour lane and the top pair is
-// carried in registers into the next element row.  A strip recomputes one halo element row under it, so every node is written once, by its
-// owner lane, with the same additions in the same order under any launch plan and any batch size: bitwise reproducible.
+// 2-D Q1, rules of 2 to 4 points per axis: the element-owner march of q1_owner_march.h with two outputs -- one wave = 62 owner columns +
+// two ghost lanes, every node written once, by its owner lane, with the same additions in the same order under any launch plan and any
+// batch size: bitwise reproducible.
 // Compile-time forms: HASV (v present), WANT (bit 0 g_nu, bit 1 g_f), MK (mask images: none / uint8 / fp32), BCF (a value field).  A call
 // with one condition runs the two-condition form with the condition given twice (a substitution is idempotent), and a condition with a
 // constant value in a BCF form loads from u and selects the constant: no load sits inside a wave-uniform branch.
@@ -40,10 +38,8 @@ struct CoefGradParams {
     float* gnu;
     float* gf;
     float a_nu, a_f;
-    float bx[4][2], dx[4][2];              // 1-D Q1 basis / derivative (times 2 / hx) at the Gauss points along x
-    float by[4][2], dy[4][2];
-    float bz[4][2], dz[4][2];              // 3-D
-    float wg[16];                          // 2-D: wscale w_ig w_jg, point jg * ngp + ig
+    Q1Tables tb;                           // wg: 2-D
+    float bz[4][2], dz[4][2];              // 3-D: the tables along z
     float w1[4];                           // 3-D: the 1-D weights (wscale rides on a_nu, a_f)
     int nx, ny, nz, nelx, nely, nelz, chunks, rows_per_strip, strips;
 };
@@ -69,7 +65,7 @@ struct CgRaw {
 
 // A landed node row: u~ and v of the lane's node (c) and of its right neighbour (n)
 struct CgRow {
-    float uc, un, vc, vn;
+    float uc = 0.f, un = 0.f, vc = 0.f, vn = 0.f;      // a form sets the ones it reads
 };
 
 template <int NGP, bool HASV, int WANT, int MK, bool BCF>
@@ -85,10 +81,8 @@ __global__ void __launch_bounds__(256) coef_grad2d_kernel(const CoefGradParams p
     if (strip >= p.strips) return;
 
     const int nx = p.nx, ny = p.ny;
-    const int q = chunk * FLOW2D_OWNERS + lane - 1;
-    const bool owner = lane >= 1 && lane <= FLOW2D_OWNERS && q < nx;
-    const unsigned qc = (unsigned)min(max(q, 0), nx - 1);
-    const bool elem_x = q >= 0 && q < p.nelx;
+    Q1Lane L;
+    q1_lane(chunk, lane, nx, p.nelx, p.nely, L);
     const int b = blockIdx.y;
     const int64_t nps = (int64_t)nx * ny;
 
@@ -111,7 +105,7 @@ __global__ void __launch_bounds__(256) coef_grad2d_kernel(const CoefGradParams p
     using Row = CgRow;
 
     auto issue = [&](int r, Raw& w) {
-        const unsigned rowoff = (unsigned)min(max(r, 0), ny - 1) * (unsigned)nx + qc;
+        const unsigned rowoff = (unsigned)min(max(r, 0), ny - 1) * (unsigned)nx + L.qc;
         if constexpr (NEEDU) w.u = ld_at<float>(ub, rowoff);
         if constexpr (HASV) w.v = ld_at<float>(vb, rowoff);
         if constexpr (MASK) {
@@ -155,15 +149,15 @@ __global__ void __launch_bounds__(256) coef_grad2d_kernel(const CoefGradParams p
 
     // the lane's element in element row e (node rows e, e + 1: Bm, Tp): its four local contributions to each output, zero where the element
     // does not exist; returns the parts that belong to the lane's node in rows e (bot) and e + 1 (top)
-    auto element = [&](const Row& Bm, const Row& Tp, int e, float (&bot)[2], float (&top)[2]) {
+    auto element = [&](const Row& Bm, const Row& Tp, const Raw&, int e, float (&bot)[2], float (&top)[2]) {
         float an[4] = {0.f, 0.f, 0.f, 0.f}, af[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int jg = 0; jg < NGP; ++jg) {
-            const float by0 = p.by[jg][0], by1 = p.by[jg][1], dy1 = p.dy[jg][1];
+            const float by0 = p.tb.by[jg][0], by1 = p.tb.by[jg][1], dy1 = p.tb.dy[jg][1];
 #pragma unroll
             for (int ig = 0; ig < NGP; ++ig) {
-                const float bx0 = p.bx[ig][0], bx1 = p.bx[ig][1], dx1 = p.dx[ig][1];
-                const float wq = p.wg[jg * NGP + ig];
+                const float bx0 = p.tb.bx[ig][0], bx1 = p.tb.bx[ig][1], dx1 = p.tb.dx[ig][1];
+                const float wq = p.tb.wg[jg * NGP + ig];
                 // v at the point and its derivatives.  On a Q1 element N0' = -N1', so a derivative is the table entry times a DIFFERENCE of
                 // nodal values: a constant field has exactly zero gradient on any mesh
                 const float vb_ = fmaf(bx0, Bm.vc, bx1 * Bm.vn), vt_ = fmaf(bx0, Tp.vc, bx1 * Tp.vn);
@@ -192,60 +186,27 @@ __global__ void __launch_bounds__(256) coef_grad2d_kernel(const CoefGradParams p
                 }
             }
         }
-        const bool ok = elem_x && e >= 0 && e < p.nely;
-        // the node's own element (right) as local node lx = 0, the left neighbour's element as lx = 1
+        const bool ok = L.elem_x && e >= 0 && e < p.nely;
+        // an output that is not wanted: zeros, so that the march carries a defined value
+        bot[0] = bot[1] = top[0] = top[1] = 0.f;
+        if constexpr (WNU) q1_owner_handover(ok, an, bot[0], top[0]);
+        if constexpr (WF) q1_owner_handover(ok, af, bot[1], top[1]);
+    };
+
+    // node row e of the wanted outputs
+    auto finish = [&](int e, const Row&, const float (&carry)[2], const float (&bot)[2]) {
+        const unsigned rowoff = (unsigned)e * (unsigned)nx + L.qc;
         if constexpr (WNU) {
-            float c[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) c[a] = ok ? an[a] : 0.f;
-            bot[0] = c[0] + __shfl_up(c[1], 1, 64);
-            top[0] = c[2] + __shfl_up(c[3], 1, 64);
+            if (L.owner) st_at<float>(onu, rowoff, snu * (carry[0] + bot[0]));
         }
         if constexpr (WF) {
-            float c[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) c[a] = ok ? af[a] : 0.f;
-            bot[1] = c[0] + __shfl_up(c[1], 1, 64);
-            top[1] = c[2] + __shfl_up(c[3], 1, 64);
+            if (L.owner) st_at<float>(of, rowoff, sf * (carry[1] + bot[1]));
         }
     };
 
     const int j0 = strip * p.rows_per_strip, j1 = min(j0 + p.rows_per_strip, ny);
-    Row prev = {}, cur = {};
-    float carry[2] = {0.f, 0.f};
-    // two rows in flight ahead of the element row being computed (W0, W1 alternate; unrolled by two so that no register with a load
-    // outstanding is ever copied)
-    Raw W0, W1;
-    {
-        Raw A;
-        issue(j0 - 1, A);
-        issue(j0, W0);
-        issue(j0 + 1, W1);
-        consume(A, prev);
-    }
-    // element row e (from e = j0 - 1, the halo row): W holds the raw node row e + 1; refilled with row e + 3.  Node row e is finished here.
-    auto step = [&](int e, Raw& W) {
-        consume(W, cur);
-        float bot[2] = {0.f, 0.f}, top[2] = {0.f, 0.f};
-        element(prev, cur, e, bot, top);
-        issue(e + 3, W);
-        if (e >= j0) {
-            const unsigned rowoff = (unsigned)e * (unsigned)nx + qc;
-            if constexpr (WNU) {
-                if (owner) st_at<float>(onu, rowoff, snu * (carry[0] + bot[0]));
-            }
-            if constexpr (WF) {
-                if (owner) st_at<float>(of, rowoff, sf * (carry[1] + bot[1]));
-            }
-        }
-        carry[0] = top[0];
-        carry[1] = top[1];
-        prev = cur;
-    };
-    for (int e = j0 - 1; e < j1; e += 2) {
-        step(e, W0);
-        if (e + 1 < j1) step(e + 1, W1);
-    }
+    constexpr int NF = 2;
+#include "q1_owner_march.inl"
 }
 
 // ---- 3-D Q1, the plain form ------------------------------------------------------------------------------------------------------
@@ -305,8 +266,8 @@ __global__ void __launch_bounds__(256) coef_grad3d_kernel(const CoefGradParams p
     __shared__ float tb[3][4][2], td[3][4][2], tw[4];
     if (threadIdx.x < 8) {
         const int g = (int)threadIdx.x >> 1, l = (int)threadIdx.x & 1;
-        tb[0][g][l] = p.bx[g][l]; td[0][g][l] = p.dx[g][l];
-        tb[1][g][l] = p.by[g][l]; td[1][g][l] = p.dy[g][l];
+        tb[0][g][l] = p.tb.bx[g][l]; td[0][g][l] = p.tb.dx[g][l];
+        tb[1][g][l] = p.tb.by[g][l]; td[1][g][l] = p.tb.dy[g][l];
         tb[2][g][l] = p.bz[g][l]; td[2][g][l] = p.dz[g][l];
         if (l == 0) tw[g] = p.w1[g];
     }
@@ -503,13 +464,11 @@ extern "C" int dn_poisson_coef_grad(const dn_mesh* m, const dn_coef_grad_args* a
     pp.gnu = a->g_nu;
     pp.gf = a->g_f;
     const int ngp = m->ngp;
+    q1_tables_fill(pp.tb, m, a->wscale);       // 3-D too: its kernel reads bx .. dy of it and never wg
     for (int ig = 0; ig < 4; ++ig)
         for (int i = 0; i < 2; ++i) {
-            const bool in = ig < ngp;
-            pp.bx[ig][i] = pp.by[ig][i] = pp.bz[ig][i] = in ? m->basis[ig][i] : 0.f;
-            pp.dx[ig][i] = in ? (float)(m->dbasis[ig][i] * (double)m->scale[0]) : 0.f;
-            pp.dy[ig][i] = in ? (float)(m->dbasis[ig][i] * (double)m->scale[1]) : 0.f;
-            pp.dz[ig][i] = in ? (float)(m->dbasis[ig][i] * (double)m->scale[2]) : 0.f;
+            pp.bz[ig][i] = pp.tb.bx[ig][i];
+            pp.dz[ig][i] = ig < ngp ? (float)(m->dbasis[ig][i] * (double)m->scale[2]) : 0.f;
         }
     for (int ig = 0; ig < 4; ++ig) pp.w1[ig] = ig < ngp ? m->gpw[ig] : 0.f;
     pp.nx = m->nx; pp.ny = m->ny; pp.nz = m->nsd == 3 ? m->nz : 1;
@@ -517,11 +476,6 @@ extern "C" int dn_poisson_coef_grad(const dn_mesh* m, const dn_coef_grad_args* a
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
 
     if (m->nsd == 2) {
-        const double J = a->wscale;
-        for (int gq = 0; gq < 16; ++gq) {
-            const int ig = gq % ngp, jg = gq / ngp;
-            pp.wg[gq] = gq < ngp * ngp ? (float)(J * m->gpw[ig] * m->gpw[jg]) : 0.f;
-        }
         pp.a_nu = a->a_nu;
         pp.a_f = a->a_f;
         const Flow2dGeom g = coef_grad_plan(m);

@@ -124,9 +124,7 @@ __global__ void __launch_bounds__(256) stokes2d_kernel(const StokesParams p) {
                         for (int g = 0; g < G; ++g) s = fmaf(p.fw[a][g], w.f[k][g], s);
                         c[a] = ok * s;
                     }
-                    // the node's own element (right) as local node lx = 0, the left neighbour's element as lx = 1
-                    bot[k] = c[0] + __shfl_up(c[1], 1, 64);
-                    top[k] = c[2] + __shfl_up(c[3], 1, 64);
+                    q1_owner_handover(c, bot[k], top[k]);
                 }
             } else {
                 bot[0] = bot[1] = top[0] = top[1] = 0.f;

@@ -12,16 +12,13 @@
 //     A' = L r'(u)      B' = ax q + kx nu L_x      C' = ay q + ky nu L_y
 // so both modes share the march (DESIGN.md section 3.2 has the derivation).  Without a reaction the VJP does not read u.
 //
-// Element-owner march, as in navier_stokes.hip with one field: one wave = 62 owner columns + two ghost lanes; lane q owns node column q
-// and the element to its right.  A lane marches the node rows of a strip, loads every node row once (the x neighbour comes over
-// ds_bpermute), computes its element's four local contributions, hands the two right-hand ones to its neighbour lane and carries the top
-// pair in registers into the next element row.  A strip recomputes one halo element row under it, so every output node is written once,
-// by its owner lane, with the same additions in any launch plan: no atomics on the data path, results bitwise independent of the plan
-// and of the other samples of the batch.  Sum of squares: fixed-order fp64 reduction (finish_sums<1> in dn_reduce.h).
+// The mapping is the element-owner march of q1_owner_march.h with one output (one wave = 62 owner columns + two ghost lanes, every output
+// node written once by its owner lane with the same additions in any launch plan); the kernel supplies its rows, its element and its
+// Dirichlet-row rule.  Sum of squares: fixed-order fp64 reduction (finish_sums<1> in dn_reduce.h).
 //
 // Optional inputs are compile-time forms: MASK (any condition), BCF (any value field), NU (nodal coefficient), FGP (Gauss-point forcing),
 // REACT (c1..c3 != 0: the cubic in the forward, u in the VJP).
-#include "flow2d_common.h"      // the wave's place in the launch, the mesh check and the launch plan (nothing of the three-field parameters)
+#include "flow2d_common.h"      // the mesh check and the launch plan (nothing of the three-field parameters); through it q1_owner_march.h
 
 namespace dn {
 
@@ -49,9 +46,7 @@ struct TransportParams {
     float* norm;
     float ax, ay, kx, ky, tax, tay;        // tax = tau ax, tay = tau ay
     float c0, c1, c2, c3;
-    float bx[4][2], dx[4][2];              // 1-D Q1 basis / derivative (times 2 / hx) at the Gauss points along x
-    float by[4][2], dy[4][2];              // along y
-    float wg[16];                          // wscale w_ig w_jg, point jg * ngp + ig
+    Q1Tables tb;
     int nx, ny, nelx, nely, chunks, rows_per_strip, strips, want_sums;
 };
 
@@ -69,20 +64,10 @@ struct TransportRaw {
 
 // A landed node row: substituted value of the lane's node (c) and of its right neighbour (n), nu and the cotangent likewise
 struct TransportRow {
-    float c, n, nuc, nun, lc, ln;
-    bool fixed;
-    float bv;                              // the value a Dirichlet row of R takes
+    float c = 0.f, n = 0.f, nuc = 0.f, nun = 0.f, lc = 0.f, ln = 0.f;      // a form sets the ones it reads
+    bool fixed = false;
+    float bv = 0.f;                        // the value a Dirichlet row of R takes
 };
-
-// value and derivatives at one point from the element's four nodal values (local node ly * 2 + lx)
-__device__ __forceinline__ void tr_eval(float bx0, float bx1, float dx0, float dx1, float by0, float by1, float dy0, float dy1,
-                                        float f0, float f1, float f2, float f3, float& val, float& fx, float& fy) {
-    const float vb = fmaf(bx0, f0, bx1 * f1), vt = fmaf(bx0, f2, bx1 * f3);
-    const float db = fmaf(dx0, f0, dx1 * f1), dt = fmaf(dx0, f2, dx1 * f3);
-    val = fmaf(by0, vb, by1 * vt);
-    fx = fmaf(by0, db, by1 * dt);
-    fy = fmaf(dy0, vb, dy1 * vt);
-}
 
 template <int NGP, bool MASK, bool BCF, bool NU, bool FGP, bool REACT, bool VJP>
 __global__ void __launch_bounds__(256) transport2d_kernel(const TransportParams p) {
@@ -99,12 +84,8 @@ __global__ void __launch_bounds__(256) transport2d_kernel(const TransportParams 
 
     if (strip < p.strips) {
         const int nx = p.nx, ny = p.ny;
-        const int q = chunk * FLOW2D_OWNERS + lane - 1;
-        const bool owner = lane >= 1 && lane <= FLOW2D_OWNERS && q < nx;
-        const unsigned qc = (unsigned)min(max(q, 0), nx - 1);
-        const bool elem_x = q >= 0 && q < p.nelx;
-        const unsigned qe = (unsigned)min(max(q, 0), p.nelx - 1);
-        const int nel = p.nelx * p.nely;
+        Q1Lane L;
+        q1_lane(chunk, lane, nx, p.nelx, p.nely, L);
         const int b = blockIdx.y;
         const int64_t nps = (int64_t)nx * ny;
 
@@ -113,7 +94,7 @@ __global__ void __launch_bounds__(256) transport2d_kernel(const TransportParams 
         const float* nub = NU ? p.nu + (p.nu_batched ? (int64_t)b * nps : 0) : ub;
         const float* xb = VJP ? p.cot + (int64_t)b * nps : ub;
         float* ob = p.out ? p.out + (int64_t)b * nps : nullptr;
-        const float* fg = FGP ? p.fgp + (p.fgp_batched ? (int64_t)b * G * nel : 0) : ub;
+        const float* fg = FGP ? p.fgp + (p.fgp_batched ? (int64_t)b * G * L.nel : 0) : ub;
         const float* bcfb[2];
         const float* mfp[2];
         const uint8_t* mbp[2];
@@ -140,7 +121,7 @@ __global__ void __launch_bounds__(256) transport2d_kernel(const TransportParams 
         using Row = TransportRow;
 
         auto issue = [&](int r, Raw& w) {
-            const unsigned rowoff = (unsigned)min(max(r, 0), ny - 1) * (unsigned)nx + qc;
+            const unsigned rowoff = (unsigned)min(max(r, 0), ny - 1) * (unsigned)nx + L.qc;
             if constexpr (NEEDU) w.v = ld_at<float>(ub, rowoff);
             if constexpr (NU) w.nu = ld_at<float>(nub, rowoff);
             if constexpr (VJP) w.x = ld_at<float>(xb, rowoff);
@@ -161,9 +142,9 @@ __global__ void __launch_bounds__(256) transport2d_kernel(const TransportParams 
                 }
             }
             if constexpr (FGP) {
-                const unsigned eoff = (unsigned)min(max(r - 1, 0), p.nely - 1) * (unsigned)p.nelx + qe;
+                const unsigned eoff = (unsigned)min(max(r - 1, 0), p.nely - 1) * (unsigned)p.nelx + L.qe;
 #pragma unroll
-                for (int g = 0; g < G; ++g) w.f[g] = ld_at<float>(fg, eoff + (unsigned)(g * nel));
+                for (int g = 0; g < G; ++g) w.f[g] = ld_at<float>(fg, eoff + (unsigned)(g * L.nel));
             }
         };
 
@@ -206,17 +187,17 @@ __global__ void __launch_bounds__(256) transport2d_kernel(const TransportParams 
 
         // the lane's element in element row e (node rows e, e + 1: Bm, Tp): its four local contributions, zero where the element does
         // not exist; returns the parts that belong to the lane's node in rows e (bot) and e + 1 (top)
-        auto element = [&](const Row& Bm, const Row& Tp, const Raw& w, int e, float& bot, float& top) {
+        auto element = [&](const Row& Bm, const Row& Tp, const Raw& w, int e, float (&bot)[1], float (&top)[1]) {
             float acc[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int jg = 0; jg < NGP; ++jg) {
-                const float by0 = p.by[jg][0], by1 = p.by[jg][1], dy0 = p.dy[jg][0], dy1 = p.dy[jg][1];
+                const float by0 = p.tb.by[jg][0], by1 = p.tb.by[jg][1], dy0 = p.tb.dy[jg][0], dy1 = p.tb.dy[jg][1];
 #pragma unroll
                 for (int ig = 0; ig < NGP; ++ig) {
                     const int g = jg * NGP + ig;
-                    const float bx0 = p.bx[ig][0], bx1 = p.bx[ig][1], dx0 = p.dx[ig][0], dx1 = p.dx[ig][1];
+                    const float bx0 = p.tb.bx[ig][0], bx1 = p.tb.bx[ig][1], dx0 = p.tb.dx[ig][0], dx1 = p.tb.dx[ig][1];
                     float ug = 0.f, ux = 0.f, uy = 0.f;
-                    if constexpr (NEEDU) tr_eval(bx0, bx1, dx0, dx1, by0, by1, dy0, dy1, Bm.c, Bm.n, Tp.c, Tp.n, ug, ux, uy);
+                    if constexpr (NEEDU) q1_eval(bx0, bx1, dx0, dx1, by0, by1, dy0, dy1, Bm.c, Bm.n, Tp.c, Tp.n, ug, ux, uy);
                     float kxn = p.kx, kyn = p.ky;
                     if constexpr (NU) {
                         const float nug = fmaf(by0, fmaf(bx0, Bm.nuc, bx1 * Bm.nun), by1 * fmaf(bx0, Tp.nuc, bx1 * Tp.nun));
@@ -226,7 +207,7 @@ __global__ void __launch_bounds__(256) transport2d_kernel(const TransportParams 
                     float A, Bc, Cc;
                     if constexpr (VJP) {
                         float L, Lx, Ly;
-                        tr_eval(bx0, bx1, dx0, dx1, by0, by1, dy0, dy1, Bm.lc, Bm.ln, Tp.lc, Tp.ln, L, Lx, Ly);
+                        q1_eval(bx0, bx1, dx0, dx1, by0, by1, dy0, dy1, Bm.lc, Bm.ln, Tp.lc, Tp.ln, L, Lx, Ly);
                         const float qq = fmaf(p.tax, Lx, fmaf(p.tay, Ly, L));
                         A = 0.f;
                         if constexpr (REACT) A = L * fmaf(fmaf(3.f * p.c3, ug, 2.f * p.c2), ug, p.c1);
@@ -241,60 +222,25 @@ __global__ void __launch_bounds__(256) transport2d_kernel(const TransportParams 
                         Bc = fmaf(kxn, ux, p.tax * s);
                         Cc = fmaf(kyn, uy, p.tay * s);
                     }
-                    const float wq = p.wg[g];
-                    const float Aw = wq * A, Bw = wq * Bc, Cw = wq * Cc;
-                    const float s0 = fmaf(by0, Aw, dy0 * Cw), s1 = fmaf(by1, Aw, dy1 * Cw);     // per ly: N_ly A + N'_ly C
-                    const float t0 = by0 * Bw, t1 = by1 * Bw;
-                    acc[0] = fmaf(bx0, s0, fmaf(dx0, t0, acc[0]));
-                    acc[1] = fmaf(bx1, s0, fmaf(dx1, t0, acc[1]));
-                    acc[2] = fmaf(bx0, s1, fmaf(dx0, t1, acc[2]));
-                    acc[3] = fmaf(bx1, s1, fmaf(dx1, t1, acc[3]));
+                    q1_flux_scatter(bx0, bx1, dx0, dx1, by0, by1, dy0, dy1, p.tb.wg[g], A, Bc, Cc, acc);
                 }
             }
-            const bool ok = elem_x && e >= 0 && e < p.nely;
-            float c[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) c[a] = ok ? acc[a] : 0.f;
-            // the node's own element (right) as local node lx = 0, the left neighbour's element as lx = 1
-            bot = c[0] + __shfl_up(c[1], 1, 64);
-            top = c[2] + __shfl_up(c[3], 1, 64);
+            q1_owner_handover(L.elem_x && e >= 0 && e < p.nely, acc, bot[0], top[0]);
+        };
+
+        // node row e of the residual
+        auto finish = [&](int e, const Row& R, const float (&carry)[1], const float (&bot)[1]) {
+            const unsigned rowoff = (unsigned)e * (unsigned)nx + L.qc;
+            float r = carry[0] + bot[0];
+            // forward: Dirichlet rows take the boundary value (the scripts' torch.where); VJP: no gradient reaches a substituted node
+            if constexpr (MASK) r = R.fixed ? (VJP ? 0.f : R.bv) : r;
+            sq[0] = L.owner ? fmaf(r, r, sq[0]) : sq[0];
+            if (L.owner && ob) st_at<float>(ob, rowoff, r);
         };
 
         const int j0 = strip * p.rows_per_strip, j1 = min(j0 + p.rows_per_strip, ny);
-        Row prev = {}, cur = {};
-        float carry = 0.f;
-        // two rows in flight ahead of the element row being computed (W0, W1 alternate; unrolled by two so that no register with a load
-        // outstanding is ever copied)
-        Raw W0, W1;
-        {
-            Raw A;
-            issue(j0 - 1, A);
-            issue(j0, W0);
-            issue(j0 + 1, W1);
-            consume(A, prev);
-        }
-        // element row e (from e = j0 - 1, the halo row): W holds the raw node row e + 1 and the element layer e; refilled with row e + 3.
-        // Node row e is finished here.
-        auto step = [&](int e, Raw& W) {
-            consume(W, cur);
-            float bot, top;
-            element(prev, cur, W, e, bot, top);
-            issue(e + 3, W);
-            if (e >= j0) {
-                const unsigned rowoff = (unsigned)e * (unsigned)nx + qc;
-                float r = carry + bot;
-                // forward: Dirichlet rows take the boundary value (the scripts' torch.where); VJP: no gradient reaches a substituted node
-                if constexpr (MASK) r = prev.fixed ? (VJP ? 0.f : prev.bv) : r;
-                sq[0] = owner ? fmaf(r, r, sq[0]) : sq[0];
-                if (owner && ob) st_at<float>(ob, rowoff, r);
-            }
-            carry = top;
-            prev = cur;
-        };
-        for (int e = j0 - 1; e < j1; e += 2) {
-            step(e, W0);
-            if (e + 1 < j1) step(e + 1, W1);
-        }
+        constexpr int NF = 1;
+#include "q1_owner_march.inl"
     }
     if (p.want_sums) finish_sums<1>(p.part, p.counter, p.sumsq, p.norm, sq, (int)threadIdx.x, (int)blockDim.x, red, &last_flag);
 }
@@ -365,19 +311,7 @@ extern "C" int dn_transport_apply(const dn_mesh* m, const dn_transport_args* a, 
 
     TransportParams pp;
     const int ngp = m->ngp;
-    const double sx = m->scale[0], sy = m->scale[1], J = a->wscale;
-    for (int ig = 0; ig < 4; ++ig)
-        for (int i = 0; i < 2; ++i) {
-            const bool in = ig < ngp;
-            pp.bx[ig][i] = in ? m->basis[ig][i] : 0.f;
-            pp.by[ig][i] = in ? m->basis[ig][i] : 0.f;
-            pp.dx[ig][i] = in ? (float)(m->dbasis[ig][i] * sx) : 0.f;
-            pp.dy[ig][i] = in ? (float)(m->dbasis[ig][i] * sy) : 0.f;
-        }
-    for (int gq = 0; gq < 16; ++gq) {
-        const int ig = gq % ngp, jg = gq / ngp;
-        pp.wg[gq] = gq < ngp * ngp ? (float)(J * m->gpw[ig] * m->gpw[jg]) : 0.f;
-    }
+    q1_tables_fill(pp.tb, m, a->wscale);
     const bool react = a->react[1] != 0.f || a->react[2] != 0.f || a->react[3] != 0.f;
     const bool needu = !vjp || react;
     pp.u = a->u;
