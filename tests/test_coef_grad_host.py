@@ -119,30 +119,42 @@ def _corner(x, idx):
     return x[tuple(sl)]
 
 
-def restate(o, u, v, dirichlet, a_nu, a_f, wscale):
+def restate(o, u, v, dirichlet, a_nu, a_f, wscale, *, scale=False, dtype=None):
     """(g_nu, g_f) as csrc/poisson_coef_grad.hip forms them, Gauss point by Gauss point, from the oracle's own tables:
         g_nu[a] = a_nu sum_e sum_g W_g N_a(g) grad v_g . grad u~_g,   g_f[a] = a_f sum_e sum_g W_g N_a(g) v_g
-    u~: u after the conditions, in order; v: zero on every Dirichlet node (None: v = u~)."""
+    u~: u after the conditions, in order; v: zero on every Dirichlet node (None: v = u~).
+    dtype: the same statements in that type, with the oracle's tables, the constants and the inputs cast once at entry (None: as they
+    come); scale: also returns (S_nu, S_f), the sum of |placed term| over the terms that make up each node's value."""
     nsd = o.nsd
+    dtype = u.dtype if dtype is None else dtype
+    u = u.to(dtype)
+    v = None if v is None else v.to(dtype)
+    dirichlet = [(mask, val.to(dtype) if isinstance(val, torch.Tensor) else val) for mask, val in dirichlet]
     ut, free = u, torch.ones_like(u, dtype=torch.bool)
     for mask, val in dirichlet:
         fixed = mask > 0.5
         ut = torch.where(fixed, val + u * 0.0, ut)
         free = free & ~fixed
     vv = ut if v is None else torch.where(free, v, torch.zeros_like(v))
-    N = o.t["N_gp"]
-    dN = [o.t[n] for n in ("dN_x_gp", "dN_y_gp", "dN_z_gp")[:nsd]]
-    W = o.gpw * wscale
+    N = o.t["N_gp"].to(dtype)
+    dN = [o.t[n].to(dtype) for n in ("dN_x_gp", "dN_y_gp", "dN_z_gp")[:nsd]]
+    W = o.gpw.to(dtype) * wscale
     locs = list(itertools.product((0, 1), repeat=nsd))
     g_nu, g_f = torch.zeros_like(u), torch.zeros_like(u)
+    s_nu, s_f = torch.zeros_like(u), torch.zeros_like(u)
     for g in range(N.shape[0]):
         vg = sum(N[g, 0, 0][i] * _corner(vv, i) for i in locs)
         dot = sum(sum(t[g, 0, 0][i] * _corner(vv, i) for i in locs) * sum(t[g, 0, 0][i] * _corner(ut, i) for i in locs) for t in dN)
         for i in locs:
             sl = (slice(None), 0) + tuple(slice(k, u.shape[2 + d] - 1 + k) for d, k in enumerate(i))
-            g_nu[sl] = g_nu[sl] + a_nu * W[g] * N[g, 0, 0][i] * dot
-            g_f[sl] = g_f[sl] + a_f * W[g] * N[g, 0, 0][i] * vg
-    return g_nu, g_f
+            t_nu, t_f = a_nu * W[g] * N[g, 0, 0][i] * dot, a_f * W[g] * N[g, 0, 0][i] * vg
+            g_nu[sl] = g_nu[sl] + t_nu
+            g_f[sl] = g_f[sl] + t_f
+            if scale:
+                s_nu[sl] = s_nu[sl] + t_nu.abs()
+                s_f[sl] = s_f[sl] + t_f.abs()
+    assert g_nu.dtype == dtype and g_f.dtype == dtype, (g_nu.dtype, g_f.dtype)
+    return (g_nu, g_f, s_nu, s_f) if scale else (g_nu, g_f)
 
 
 def _rand(shape, seed, lo=-1.0, hi=1.0):

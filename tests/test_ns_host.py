@@ -99,10 +99,27 @@ def test_ns_ops_refuse_cpu_tensors_and_unsupported_meshes():
 # ---------------------------------------------------------------------------------------------
 # float64 restatement of the operator (include/diffnet_hip.h, dn_ns_args)
 # ---------------------------------------------------------------------------------------------
-def _tau_consts(visco, tau_h, cinv):
-    hx, hy = tau_h
-    Gx, Gy = 4.0 / hx ** 2, 4.0 / hy ** 2
-    return Gx, Gy, cinv * visco ** 2 * (Gx ** 2 + Gy ** 2), 1.0 / (4.0 / hx ** 2 + 4.0 / hy ** 2)
+def _tau_consts(visco, tau_h, cinv, dt=float):
+    """(Gx, Gy, diffusion part, 1 / (gx^2 + gy^2)) as Python floats, the arithmetic in the type `dt`"""
+    hx, hy, visco, cinv = dt(tau_h[0]), dt(tau_h[1]), dt(visco), dt(cinv)
+    Gx, Gy = dt(4.0) / hx ** 2, dt(4.0) / hy ** 2
+    out = Gx, Gy, cinv * visco ** 2 * (Gx ** 2 + Gy ** 2), dt(1.0) / (dt(4.0) / hx ** 2 + dt(4.0) / hy ** 2)
+    assert all(isinstance(x, dt) for x in out)
+    return tuple(float(x) for x in out)
+
+
+def _np_type(dtype):
+    """the numpy scalar type of a torch or numpy dtype"""
+    return {torch.float64: np.float64, torch.float32: np.float32}.get(dtype) or np.dtype(dtype).type
+
+
+def _q1_point_tables(N, dN, sx, sy, ig, jg, as_float=False):
+    """N_a, Nx_a, Ny_a of the four local nodes (ly, lx) at Gauss point (ig, jg), in the type of the tables (as Python floats for torch)"""
+    cv = float if as_float else (lambda x: x)
+    Na = {(ly, lx): cv(N[ig, lx] * N[jg, ly]) for ly in (0, 1) for lx in (0, 1)}
+    Nxa = {(ly, lx): cv(dN[ig, lx] * sx * N[jg, ly]) for ly in (0, 1) for lx in (0, 1)}
+    Nya = {(ly, lx): cv(N[ig, lx] * dN[jg, ly] * sy) for ly in (0, 1) for lx in (0, 1)}
+    return Na, Nxa, Nya
 
 
 def _place(t, ly, lx):
@@ -110,23 +127,28 @@ def _place(t, ly, lx):
     return torch.nn.functional.pad(t, (lx, 1 - lx, ly, 1 - ly))
 
 
-def ns_torch(u, v, p, masks, vals, f1, f2, visco, J, hx, hy, tau_h, cinv, ngp):
+def ns_torch(u, v, p, masks, vals, f1, f2, visco, J, hx, hy, tau_h, cinv, ngp, *, scale=False, dtype=torch.float64, tables=None):
     """u, v, p: (ny, nx) float64 tensors; masks[k]: bool arrays or None; vals[k]: float or (ny, nx); f1, f2: (G, nely, nelx), g = jg * ngp + ig.
-    The scripts' weak forms term by term, tau from detached values.  Returns (R1, R2, R3), differentiable wrt u, v, p."""
-    N, dN, w = q1_tables(ngp)
+    The scripts' weak forms term by term, tau from detached values.  Returns (R1, R2, R3), differentiable wrt u, v, p.
+    dtype: the same statements in that type, with tables, constants and inputs cast once at entry; tables: the 1-D (N, dN, w) to use in
+    place of q1_tables(ngp); scale: also returns (S1, S2, S3), S_k the sum of |w_g t| over the placed terms that make up the node's value
+    (0 on the Dirichlet nodes of field k)."""
+    dt = _np_type(dtype)
+    N, dN, w = (np.asarray(t, dtype=dt) for t in (q1_tables(ngp) if tables is None else tables))
+    u, v, p = (t.to(dtype) for t in (u, v, p))
     ny, nx = u.shape
     masks = [None if m is None else torch.as_tensor(m) for m in masks]
-    vals = [torch.as_tensor(x, dtype=torch.float64) for x in vals]
-    f1, f2 = torch.as_tensor(f1, dtype=torch.float64), torch.as_tensor(f2, dtype=torch.float64)
+    vals = [torch.as_tensor(x, dtype=dtype) for x in vals]
+    f1, f2 = torch.as_tensor(f1, dtype=dtype), torch.as_tensor(f2, dtype=dtype)
     fld = [t if m is None else torch.where(m, val.expand(ny, nx), t) for t, m, val in zip((u, v, p), masks, vals)]
-    Gx, Gy, diff, gg_inv = _tau_consts(visco, tau_h, cinv)
-    R = [torch.zeros((ny, nx), dtype=torch.float64) for _ in range(3)]
+    Gx, Gy, diff, gg_inv = _tau_consts(visco, tau_h, cinv, float if dt is np.float64 else dt)
+    visco, J, sx, sy = float(dt(visco)), dt(J), dt(2) / dt(hx), dt(2) / dt(hy)
+    R = [torch.zeros((ny, nx), dtype=dtype) for _ in range(3)]
+    S = [torch.zeros((ny, nx), dtype=dtype) for _ in range(3)]
     for jg in range(ngp):
         for ig in range(ngp):
-            g, wg = jg * ngp + ig, J * w[ig] * w[jg]
-            Na = {(ly, lx): N[ig, lx] * N[jg, ly] for ly in (0, 1) for lx in (0, 1)}
-            Nxa = {(ly, lx): dN[ig, lx] * (2 / hx) * N[jg, ly] for ly in (0, 1) for lx in (0, 1)}
-            Nya = {(ly, lx): N[ig, lx] * dN[jg, ly] * (2 / hy) for ly in (0, 1) for lx in (0, 1)}
+            g, wg = jg * ngp + ig, float(J * w[ig] * w[jg])
+            Na, Nxa, Nya = _q1_point_tables(N, dN, sx, sy, ig, jg, as_float=True)
 
             def at(t, tab):
                 return sum(tab[ly, lx] * t[ly:ny - 1 + ly, lx:nx - 1 + lx] for ly in (0, 1) for lx in (0, 1))
@@ -147,7 +169,13 @@ def ns_torch(u, v, p, masks, vals, f1, f2, visco, J, hx, hy, tau_h, cinv, ngp):
                 t3 = n_ * d + tm * (nx_ * r1 + ny_ * r2)
                 for k, t in enumerate((t1, t2, t3)):
                     R[k] = R[k] + _place(wg * t, ly, lx)
-    return tuple(r if m is None else torch.where(m, val.expand(ny, nx), r) for r, m, val in zip(R, masks, vals))
+                    if scale:
+                        S[k] = S[k] + _place((wg * t).detach().abs(), ly, lx)
+    R = tuple(r if m is None else torch.where(m, val.expand(ny, nx), r) for r, m, val in zip(R, masks, vals))
+    assert all(r.dtype == dtype for r in R), [r.dtype for r in R]
+    if not scale:
+        return R
+    return R, tuple(s if m is None else torch.where(m, torch.zeros_like(s), s) for s, m in zip(S, masks))
 
 
 def fixture_case(z):
@@ -183,21 +211,26 @@ def test_ns_fixtures_agree_with_float64_restatement(name):
 # ---------------------------------------------------------------------------------------------
 # the pullback of the VJP launch (csrc/navier_stokes.hip: ns_vjp_flux), restated in numpy
 # ---------------------------------------------------------------------------------------------
-def ns_vjp_np(u, v, p, lam, masks, vals, f1, f2, visco, J, hx, hy, tau_h, cinv, ngp):
+def ns_vjp_np(u, v, p, lam, masks, vals, f1, f2, visco, J, hx, hy, tau_h, cinv, ngp, *, scale=False, dtype=np.float64, tables=None):
     """d/d(u, v, p) of sum_k <lam_k, R_k> with tau held fixed: the cotangents (zeroed on the Dirichlet rows of their residual) evaluated
-    like fields, the hand-derived pointwise coefficients, pulled back through N, Nx, Ny and zeroed on each field's Dirichlet nodes."""
-    N, dN, w = q1_tables(ngp)
+    like fields, the hand-derived pointwise coefficients, pulled back through N, Nx, Ny and zeroed on each field's Dirichlet nodes.
+    scale, dtype, tables: as in ns_torch."""
+    dt = np.dtype(dtype).type
+    c = lambda x: np.asarray(x, dtype=dt)                                  # noqa: E731
+    N, dN, w = (c(t) for t in (q1_tables(ngp) if tables is None else tables))
+    u, v, p, f1, f2 = (c(x) for x in (u, v, p, f1, f2))
+    lam, vals = [c(x) for x in lam], [c(x) for x in vals]
     ny, nx = u.shape
     fld = [t if m is None else np.where(m, val, t) for t, m, val in zip((u, v, p), masks, vals)]
-    lam = [l_ if m is None else np.where(m, 0.0, l_) for l_, m in zip(lam, masks)]
-    Gx, Gy, diff, gg_inv = _tau_consts(visco, tau_h, cinv)
-    out = [np.zeros((ny, nx)) for _ in range(3)]
+    lam = [l_ if m is None else np.where(m, dt(0), l_) for l_, m in zip(lam, masks)]
+    Gx, Gy, diff, gg_inv = (dt(x) for x in _tau_consts(visco, tau_h, cinv, float if dt is np.float64 else dt))
+    visco, J, sx, sy = dt(visco), dt(J), dt(2) / dt(hx), dt(2) / dt(hy)
+    out = [np.zeros((ny, nx), dtype=dt) for _ in range(3)]
+    S = [np.zeros((ny, nx), dtype=dt) for _ in range(3)]
     for jg in range(ngp):
         for ig in range(ngp):
             g, wg = jg * ngp + ig, J * w[ig] * w[jg]
-            Na = {(ly, lx): N[ig, lx] * N[jg, ly] for ly in (0, 1) for lx in (0, 1)}
-            Nxa = {(ly, lx): dN[ig, lx] * (2 / hx) * N[jg, ly] for ly in (0, 1) for lx in (0, 1)}
-            Nya = {(ly, lx): N[ig, lx] * dN[jg, ly] * (2 / hy) for ly in (0, 1) for lx in (0, 1)}
+            Na, Nxa, Nya = _q1_point_tables(N, dN, sx, sy, ig, jg)
 
             def at(t, tab):
                 return sum(tab[ly, lx] * t[ly:ny - 1 + ly, lx:nx - 1 + lx] for ly in (0, 1) for lx in (0, 1))
@@ -223,8 +256,14 @@ def ns_vjp_np(u, v, p, lam, masks, vals, f1, f2, visco, J, hx, hy, tau_h, cinv, 
                     (-(Lx[0] + Ly[1]), g1, g2)]
             for (ly, lx), n_ in Na.items():
                 for k, (A, B, Cc) in enumerate(coef):
-                    out[k][ly:ny - 1 + ly, lx:nx - 1 + lx] += wg * (n_ * A + Nxa[ly, lx] * B + Nya[ly, lx] * Cc)
-    return [o if m is None else np.where(m, 0.0, o) for o, m in zip(out, masks)]
+                    t = wg * (n_ * A + Nxa[ly, lx] * B + Nya[ly, lx] * Cc)
+                    out[k][ly:ny - 1 + ly, lx:nx - 1 + lx] += t
+                    S[k][ly:ny - 1 + ly, lx:nx - 1 + lx] += np.abs(t)
+    out = [o if m is None else np.where(m, dt(0), o) for o, m in zip(out, masks)]
+    assert all(o.dtype == dt for o in out), [o.dtype for o in out]             # numpy promotes silently
+    if not scale:
+        return out
+    return out, [s if m is None else np.where(m, dt(0), s) for s, m in zip(S, masks)]
 
 
 @pytest.mark.parametrize("ngp,ny,nx", [(2, 6, 7), (3, 5, 6), (4, 4, 5)])

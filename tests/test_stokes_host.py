@@ -118,19 +118,28 @@ def q1_tables(ngp):
     return N, dN, w
 
 
-def stokes_np(u, v, p, masks, vals, f1, f2, visco, pspg, J, hx, hy, ngp):
-    """u, v, p, masks[k], vals[k]: (ny, nx); f1, f2: (G, nely, nelx), g = jg * ngp + ig.  Returns (R1, R2, R3), float64."""
-    N, dN, w = q1_tables(ngp)
+def stokes_np(u, v, p, masks, vals, f1, f2, visco, pspg, J, hx, hy, ngp, *, scale=False, dtype=np.float64, tables=None):
+    """u, v, p, masks[k], vals[k]: (ny, nx); f1, f2: (G, nely, nelx), g = jg * ngp + ig.  Returns (R1, R2, R3), float64.
+    dtype: the same statements in that type, with tables, constants and inputs cast once at entry; tables: the 1-D (N, dN, w) to use in
+    place of q1_tables(ngp); scale: also returns (S1, S2, S3), S_k the sum of |w_g t| over the placed terms that make up the node's value
+    (0 on the Dirichlet nodes of field k, whose value is no sum)."""
+    dt = np.dtype(dtype).type
+    c = lambda x: np.asarray(x, dtype=dt)                                  # noqa: E731
+    N, dN, w = (c(t) for t in (q1_tables(ngp) if tables is None else tables))
+    u, v, p, f1, f2 = (c(x) for x in (u, v, p, f1, f2))
+    vals = [c(x) for x in vals]
+    visco, pspg, J, sx, sy = dt(visco), dt(pspg), dt(J), dt(2) / dt(hx), dt(2) / dt(hy)
     ny, nx = u.shape
     fld = [np.where(m, val, t) if m is not None else t for t, m, val in zip((u, v, p), masks, vals)]
-    R = [np.zeros((ny, nx)) for _ in range(3)]
+    R = [np.zeros((ny, nx), dtype=dt) for _ in range(3)]
+    S = [np.zeros((ny, nx), dtype=dt) for _ in range(3)]
     for jg in range(ngp):
         for ig in range(ngp):
             g, wg = jg * ngp + ig, J * w[ig] * w[jg]
             # basis of local node (ly, lx) at the point, its x / y derivatives
             Na = {(ly, lx): N[ig, lx] * N[jg, ly] for ly in (0, 1) for lx in (0, 1)}
-            Nxa = {(ly, lx): dN[ig, lx] * (2 / hx) * N[jg, ly] for ly in (0, 1) for lx in (0, 1)}
-            Nya = {(ly, lx): N[ig, lx] * dN[jg, ly] * (2 / hy) for ly in (0, 1) for lx in (0, 1)}
+            Nxa = {(ly, lx): dN[ig, lx] * sx * N[jg, ly] for ly in (0, 1) for lx in (0, 1)}
+            Nya = {(ly, lx): N[ig, lx] * dN[jg, ly] * sy for ly in (0, 1) for lx in (0, 1)}
 
             def at(t, tab):
                 return sum(tab[ly, lx] * t[ly:ny - 1 + ly, lx:nx - 1 + lx] for ly in (0, 1) for lx in (0, 1))
@@ -141,10 +150,17 @@ def stokes_np(u, v, p, masks, vals, f1, f2, visco, pspg, J, hx, hy, ngp):
                 for lx in (0, 1):
                     a = (ly, lx)
                     sl = (slice(ly, ny - 1 + ly), slice(lx, nx - 1 + lx))
-                    R[0][sl] += wg * (visco * (Nxa[a] * ux + Nya[a] * uy) - Nxa[a] * pg - Na[a] * f1[g])
-                    R[1][sl] += wg * (visco * (Nxa[a] * vx + Nya[a] * vy) - Nya[a] * pg - Na[a] * f2[g])
-                    R[2][sl] += wg * (Na[a] * (ux + vy) + pspg * (Nxa[a] * px + Nya[a] * py))
-    return tuple(np.where(m, val, r) if m is not None else r for r, m, val in zip(R, masks, vals))
+                    terms = (wg * (visco * (Nxa[a] * ux + Nya[a] * uy) - Nxa[a] * pg - Na[a] * f1[g]),
+                             wg * (visco * (Nxa[a] * vx + Nya[a] * vy) - Nya[a] * pg - Na[a] * f2[g]),
+                             wg * (Na[a] * (ux + vy) + pspg * (Nxa[a] * px + Nya[a] * py)))
+                    for k, t in enumerate(terms):
+                        R[k][sl] += t
+                        S[k][sl] += np.abs(t)
+    R = tuple(np.where(m, val, r) if m is not None else r for r, m, val in zip(R, masks, vals))
+    assert all(r.dtype == dt for r in R), [r.dtype for r in R]                 # numpy promotes silently
+    if not scale:
+        return R
+    return R, tuple(np.where(m, dt(0), s) if m is not None else s for s, m in zip(S, masks))
 
 
 def fixture_case(z):

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from test_ns_host import _np_type, _q1_point_tables
 from test_stokes_host import header_struct, q1_tables, stokes_mesh
 
 FIXTURES = ["loss_transport_advdiff_n17.npz", "loss_transport_stheat_n33_g3.npz", "loss_transport_allencahn_n17.npz",
@@ -136,12 +137,10 @@ def test_transport_coefficient_helpers_return_the_scripts_values():
 # ---------------------------------------------------------------------------------------------
 # float64 restatement of the operator (include/diffnet_hip.h, dn_transport_args)
 # ---------------------------------------------------------------------------------------------
-def _tables(ngp, hx, hy, ig, jg):
-    N, dN, _ = q1_tables(ngp)
-    Na = {(ly, lx): N[ig, lx] * N[jg, ly] for ly in (0, 1) for lx in (0, 1)}
-    Nxa = {(ly, lx): dN[ig, lx] * (2 / hx) * N[jg, ly] for ly in (0, 1) for lx in (0, 1)}
-    Nya = {(ly, lx): N[ig, lx] * dN[jg, ly] * (2 / hy) for ly in (0, 1) for lx in (0, 1)}
-    return Na, Nxa, Nya
+def _tables(ngp, hx, hy, ig, jg, tables=None, dt=np.float64, as_float=False):
+    """N_a, Nx_a, Ny_a of the four local nodes at Gauss point (ig, jg), computed in the type `dt` (as Python floats for torch)"""
+    N, dN, _ = (np.asarray(t, dtype=dt) for t in (q1_tables(ngp) if tables is None else tables))
+    return _q1_point_tables(N, dN, dt(2) / dt(hx), dt(2) / dt(hy), ig, jg, as_float=as_float)
 
 
 def _place(t, ly, lx):
@@ -149,25 +148,35 @@ def _place(t, ly, lx):
     return torch.nn.functional.pad(t, (lx, 1 - lx, ly, 1 - ly))
 
 
-def transport_torch(u, nu, masks, vals, f, adv, kappa, tau, react, J, hx, hy, ngp, first):
+def transport_torch(u, nu, masks, vals, f, adv, kappa, tau, react, J, hx, hy, ngp, first, *, scale=False, dtype=torch.float64, tables=None):
     """u: (ny, nx) float64 tensor; nu: (ny, nx) or None; masks[k]: bool arrays or None; vals[k]: float or (ny, nx); f: (G, nely, nelx) or a
-    float, g = jg * ngp + ig.  The formulas of the header, term by term.  Returns R (ny, nx), differentiable wrt u."""
-    _, _, w = q1_tables(ngp)
+    float, g = jg * ngp + ig.  The formulas of the header, term by term.  Returns R (ny, nx), differentiable wrt u.
+    dtype: the same statements in that type, with tables, constants and inputs cast once at entry; tables: the 1-D (N, dN, w) to use in
+    place of q1_tables(ngp); scale: also returns S, the sum of |w_g t| over the placed terms that make up the node's value (0 on the
+    Dirichlet nodes)."""
+    dt = _np_type(dtype)
+    w = np.asarray((q1_tables(ngp) if tables is None else tables)[2], dtype=dt)
+    u = u.to(dtype)
+    # tau adv[k]: one product (float64: of the caller's own scalars, as before there were types to choose)
+    tadv = [float(tau * a) if dt is np.float64 else float(dt(tau) * dt(a)) for a in adv]
+    adv, kappa, react, J = [float(dt(x)) for x in adv], [float(dt(x)) for x in kappa], [float(dt(x)) for x in react], dt(J)
     ny, nx = u.shape
     masks = [None if m is None else torch.as_tensor(m) for m in masks]
-    vals = [torch.as_tensor(x, dtype=torch.float64).expand(ny, nx) for x in vals]
-    f = torch.as_tensor(f, dtype=torch.float64)
+    vals = [torch.as_tensor(x, dtype=dtype).expand(ny, nx) for x in vals]
+    f = torch.as_tensor(f, dtype=dtype)
     f = f.expand(ngp * ngp, ny - 1, nx - 1) if f.dim() == 0 else f
     ut = u
     for k in (0, 1):                                  # condition 2 last: it wins on u
         if masks[k] is not None:
             ut = torch.where(masks[k], vals[k], ut)
-    nut = torch.ones((ny, nx), dtype=torch.float64) if nu is None else torch.as_tensor(nu, dtype=torch.float64)
-    R = torch.zeros((ny, nx), dtype=torch.float64)
+    nut = torch.ones((ny, nx), dtype=dtype) if nu is None else torch.as_tensor(nu, dtype=dtype)
+    R = torch.zeros((ny, nx), dtype=dtype)
+    S = torch.zeros((ny, nx), dtype=dtype)
+    fixed = torch.zeros((ny, nx), dtype=torch.bool)
     for jg in range(ngp):
         for ig in range(ngp):
-            g, wg = jg * ngp + ig, J * w[ig] * w[jg]
-            Na, Nxa, Nya = _tables(ngp, hx, hy, ig, jg)
+            g, wg = jg * ngp + ig, float(J * w[ig] * w[jg])
+            Na, Nxa, Nya = _tables(ngp, hx, hy, ig, jg, tables, dt, as_float=True)
 
             def at(t, tab):
                 return sum(tab[ly, lx] * t[ly:ny - 1 + ly, lx:nx - 1 + lx] for ly in (0, 1) for lx in (0, 1))
@@ -175,14 +184,19 @@ def transport_torch(u, nu, masks, vals, f, adv, kappa, tau, react, J, hx, hy, ng
             ug, ux, uy, nug = at(ut, Na), at(ut, Nxa), at(ut, Nya), at(nut, Na)
             a_ = adv[0] * ux + adv[1] * uy
             A = a_ + react[0] + react[1] * ug + react[2] * ug ** 2 + react[3] * ug ** 3 - f[g]
-            B = kappa[0] * nug * ux + tau * adv[0] * (a_ - f[g])
-            Cc = kappa[1] * nug * uy + tau * adv[1] * (a_ - f[g])
+            B = kappa[0] * nug * ux + tadv[0] * (a_ - f[g])
+            Cc = kappa[1] * nug * uy + tadv[1] * (a_ - f[g])
             for (ly, lx), n_ in Na.items():
-                R = R + _place(wg * (n_ * A + Nxa[ly, lx] * B + Nya[ly, lx] * Cc), ly, lx)
+                t = wg * (n_ * A + Nxa[ly, lx] * B + Nya[ly, lx] * Cc)
+                R = R + _place(t, ly, lx)
+                if scale:
+                    S = S + _place(t.detach().abs(), ly, lx)
     for k in ((1, 0) if first else (0, 1)):           # the condition applied last wins on the rows of R
         if masks[k] is not None:
             R = torch.where(masks[k], vals[k], R)
-    return R
+            fixed = fixed | masks[k]
+    assert R.dtype == dtype, R.dtype
+    return (R, torch.where(fixed, torch.zeros_like(S), S)) if scale else R
 
 
 def fixture_case(z):
@@ -260,11 +274,15 @@ def test_transport_every_term_is_visible_in_its_fixture(name):
 # ---------------------------------------------------------------------------------------------
 # the pullback of the VJP launch (csrc/transport.hip), restated in numpy
 # ---------------------------------------------------------------------------------------------
-def transport_vjp_np(u, lam, nu, masks, vals, f, adv, kappa, tau, react, J, hx, hy, ngp, first):
+def transport_vjp_np(u, lam, nu, masks, vals, f, adv, kappa, tau, react, J, hx, hy, ngp, first, *, scale=False, dtype=np.float64, tables=None):
     """d/du <lam, R>: the cotangent (zeroed on the Dirichlet rows of R) evaluated like a field, the hand-derived pointwise coefficients
     A' = L r'(u), B' = ax q + kx nu L_x, C' = ay q + ky nu L_y with q = L + tau (ax L_x + ay L_y), pulled back through N, Nx, Ny and
-    zeroed on the Dirichlet nodes of u.  Neither the forcing nor `first` enters."""
-    _, _, w = q1_tables(ngp)
+    zeroed on the Dirichlet nodes of u.  Neither the forcing nor `first` enters.  scale, dtype, tables: as in transport_torch."""
+    dt = np.dtype(dtype).type
+    c = lambda x: np.asarray(x, dtype=dt)                                  # noqa: E731
+    w = c((q1_tables(ngp) if tables is None else tables)[2])
+    u, lam, vals = c(u), c(lam), [c(x) for x in vals]
+    adv, kappa, react, tau, J = [dt(x) for x in adv], [dt(x) for x in kappa], [dt(x) for x in react], dt(tau), dt(J)
     ny, nx = u.shape
     fixed = np.zeros((ny, nx), dtype=bool)
     ut = u.copy()
@@ -272,13 +290,14 @@ def transport_vjp_np(u, lam, nu, masks, vals, f, adv, kappa, tau, react, J, hx, 
         if masks[k] is not None:
             ut = np.where(masks[k], vals[k], ut)
             fixed |= masks[k]
-    lam = np.where(fixed, 0.0, lam)
-    nut = np.ones((ny, nx)) if nu is None else nu
-    out = np.zeros((ny, nx))
+    lam = np.where(fixed, dt(0), lam)
+    nut = np.ones((ny, nx), dtype=dt) if nu is None else c(nu)
+    out = np.zeros((ny, nx), dtype=dt)
+    S = np.zeros((ny, nx), dtype=dt)
     for jg in range(ngp):
         for ig in range(ngp):
             wg = J * w[ig] * w[jg]
-            Na, Nxa, Nya = _tables(ngp, hx, hy, ig, jg)
+            Na, Nxa, Nya = _tables(ngp, hx, hy, ig, jg, tables, dt)
 
             def at(t, tab):
                 return sum(tab[ly, lx] * t[ly:ny - 1 + ly, lx:nx - 1 + lx] for ly in (0, 1) for lx in (0, 1))
@@ -290,8 +309,12 @@ def transport_vjp_np(u, lam, nu, masks, vals, f, adv, kappa, tau, react, J, hx, 
             B = adv[0] * q + kappa[0] * nug * Lx
             Cc = adv[1] * q + kappa[1] * nug * Ly
             for (ly, lx), n_ in Na.items():
-                out[ly:ny - 1 + ly, lx:nx - 1 + lx] += wg * (n_ * A + Nxa[ly, lx] * B + Nya[ly, lx] * Cc)
-    return np.where(fixed, 0.0, out)
+                t = wg * (n_ * A + Nxa[ly, lx] * B + Nya[ly, lx] * Cc)
+                out[ly:ny - 1 + ly, lx:nx - 1 + lx] += t
+                S[ly:ny - 1 + ly, lx:nx - 1 + lx] += np.abs(t)
+    out = np.where(fixed, dt(0), out)
+    assert out.dtype == dt, out.dtype                                          # numpy promotes silently
+    return (out, np.where(fixed, dt(0), S)) if scale else out
 
 
 @pytest.mark.parametrize("react", [(0.0, 0.0, 0.0, 0.0), (-0.7, 8.0, -24.0, 16.0)])
