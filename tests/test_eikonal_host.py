@@ -158,100 +158,134 @@ def test_eikonal_ops_refuse_cpu_tensors_and_bad_arguments():
 # ---------------------------------------------------------------------------------------------
 # float64 restatement of the operator, in the scripts' spelling (torch, differentiable) and the pullback by hand (numpy)
 # ---------------------------------------------------------------------------------------------
-def _tables(P, ngp, hx, hy):
-    from diffnet_amd.tables import Basis1D, gauss_rule
-    gx, gw = gauss_rule(ngp)
-    Bt, Dt = Basis1D(P).at_gauss(gx)[:2]            # (ngp, nbf)
-    return np.asarray(Bt, dtype=np.float64), np.asarray(Dt, dtype=np.float64), np.asarray(gw, dtype=np.float64), 2.0 / hx, 2.0 / hy
-
-
 def _loc(P, nely, nelx, jb, ib):
     return (slice(jb, jb + P * (nely - 1) + 1, P), slice(ib, ib + P * (nelx - 1) + 1, P))
 
 
-def eikonal_t64(u, hx, hy, P, ngp, tau, sq=None, f=1.0, wscale=None, masks=(None, None), vals=(0.0, 0.0), drop=None):
+def _tables_kw(P, ngp, hx, hy, wscale, tables, npd):
+    """(N, dN, W[jg][ig], 2 / hx, 2 / hy) in the numpy type npd; tables: see test_strongform_host.elem_tables"""
+    from test_strongform_host import elem_tables
+    Bt, Dt, _, Wt = elem_tables(P, ngp, tables, npd, wscale)
+    return Bt, Dt, Wt, npd(2) / npd(hx), npd(2) / npd(hy)
+
+
+def eikonal_t64(u, hx, hy, P, ngp, tau, sq=None, f=1.0, wscale=None, masks=(None, None), vals=(0.0, 0.0), drop=None, *, tables=None,
+                dtype=torch.float64, scale=False):
     """R (ny, nx) of the header's formula from u (ny, nx), a float64 torch tensor (differentiable): the scripts' sum over the Gauss points of
     JxW (tau u (dN_x u_x + dN_y u_y) + sq N (u_x^2 + u_y^2) - N f), assembled, zero on the Dirichlet nodes.  f: a float, a nodal (ny, nx)
-    tensor or a Gauss-point (G, nely, nelx) one, g = jg * ngp + ig.  drop: "stab" | "sq" | "rhs" leaves that term out."""
-    Bt, Dt, gw, sx, sy = _tables(P, ngp, hx, hy)
+    tensor or a Gauss-point (G, nely, nelx) one, g = jg * ngp + ig.  drop: "stab" | "sq" | "rhs" leaves that term out.  dtype: the same
+    statements in that torch type, inputs, tables and constants cast once at entry; tables: see test_strongform_host.elem_tables; scale:
+    returns (R, S), S the magnitude field -- the same formula with every input, table entry and constant replaced by its absolute value
+    and the subtraction made an addition, after the Dirichlet substitutions; 0 on the Dirichlet nodes."""
+    npd = np.float32 if dtype == torch.float32 else np.float64
     sq = 1.0 + tau if sq is None else sq
     wscale = (0.5 * hx) * (0.5 * hy) if wscale is None else wscale
     ny, nx = u.shape
     nely, nelx = (ny - 1) // P, (nx - 1) // P
-    ut = u
+    nb = P + 1
     fixed = torch.zeros((ny, nx), dtype=torch.bool)
     for k in (0, 1):
         if masks[k] is not None:
-            mk = torch.as_tensor(masks[k], dtype=torch.bool)
-            v = vals[k] if isinstance(vals[k], torch.Tensor) else torch.full_like(u, float(vals[k]))
-            ut = torch.where(mk, v, ut)
-            fixed |= mk
-    nb = P + 1
-    out = torch.zeros((ny, nx), dtype=torch.float64)
-    for jg in range(ngp):
-        for ig in range(ngp):
-            W = wscale * gw[ig] * gw[jg]
-            N = {(jb, ib): Bt[ig, ib] * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
-            Nx = {(jb, ib): Dt[ig, ib] * sx * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
-            Ny = {(jb, ib): Bt[ig, ib] * Dt[jg, jb] * sy for jb in range(nb) for ib in range(nb)}
+            fixed |= torch.as_tensor(masks[k], dtype=torch.bool)
 
-            def at(t, tab):
-                return sum(tab[a] * t[_loc(P, nely, nelx, *a)] for a in tab)
+    def run(A, minus):
+        Bt, Dt, Wt, sx, sy = (A(t) for t in _tables_kw(P, ngp, hx, hy, wscale, tables, npd))
+        c = lambda x: A(x.to(dtype)) if isinstance(x, torch.Tensor) else float(A(npd(x)))            # noqa: E731
+        tau_, sq_ = c(tau), c(sq)
+        ut = c(u)
+        for k in (0, 1):
+            if masks[k] is not None:
+                mk = torch.as_tensor(masks[k], dtype=torch.bool)
+                v = c(vals[k]) if isinstance(vals[k], torch.Tensor) else torch.full_like(ut, c(vals[k]))
+                ut = torch.where(mk, v, ut)
+        out = torch.zeros((ny, nx), dtype=dtype)
+        for jg in range(ngp):
+            for ig in range(ngp):
+                W = float(Wt[jg, ig])
+                N = {(jb, ib): float(Bt[ig, ib] * Bt[jg, jb]) for jb in range(nb) for ib in range(nb)}
+                Nx = {(jb, ib): float(Dt[ig, ib] * sx * Bt[jg, jb]) for jb in range(nb) for ib in range(nb)}
+                Ny = {(jb, ib): float(Bt[ig, ib] * Dt[jg, jb] * sy) for jb in range(nb) for ib in range(nb)}
 
-            ug, ux, uy = at(ut, N), at(ut, Nx), at(ut, Ny)
-            if isinstance(f, torch.Tensor) and f.dim() == 3:
-                fg = f[jg * ngp + ig]
-            elif isinstance(f, torch.Tensor):
-                fg = at(f, N)
-            else:
-                fg = torch.full_like(ug, float(f))
-            for a in N:
-                t = 0.0
-                if drop != "stab":
-                    t = t + tau * ug * (Nx[a] * ux + Ny[a] * uy)
-                if drop != "sq":
-                    t = t + sq * N[a] * (ux ** 2 + uy ** 2)
-                if drop != "rhs":
-                    t = t - N[a] * fg
-                sl = _loc(P, nely, nelx, *a)
-                out[sl] = out[sl] + W * t
-    return torch.where(fixed, torch.zeros_like(out), out)
+                def at(t, tab):
+                    return sum(tab[a] * t[_loc(P, nely, nelx, *a)] for a in tab)
+
+                ug, ux, uy = at(ut, N), at(ut, Nx), at(ut, Ny)
+                if isinstance(f, torch.Tensor) and f.dim() == 3:
+                    fg = c(f)[jg * ngp + ig]
+                elif isinstance(f, torch.Tensor):
+                    fg = at(c(f), N)
+                else:
+                    fg = torch.full_like(ug, c(f))
+                for a in N:
+                    t = 0.0
+                    if drop != "stab":
+                        t = t + tau_ * ug * (Nx[a] * ux + Ny[a] * uy)
+                    if drop != "sq":
+                        t = t + sq_ * N[a] * (ux ** 2 + uy ** 2)
+                    if drop != "rhs":
+                        t = t + minus * N[a] * fg
+                    sl = _loc(P, nely, nelx, *a)
+                    out[sl] = out[sl] + W * t
+        assert out.dtype == dtype, out.dtype
+        return torch.where(fixed, torch.zeros_like(out), out)
+
+    R = run(lambda x: x, -1.0)
+    if not scale:
+        return R
+    with torch.no_grad():
+        return R, run(abs, 1.0)
 
 
-def eikonal_pullback_np(u, cot, hx, hy, P, ngp, tau, sq=None, wscale=None, masks=(None, None), vals=(0.0, 0.0)):
+def eikonal_pullback_np(u, cot, hx, hy, P, ngp, tau, sq=None, wscale=None, masks=(None, None), vals=(0.0, 0.0), *, tables=None,
+                        dtype=np.float64, scale=False):
     """The VJP of the header: with the cotangent (zero on the Dirichlet nodes) evaluated like a field (L, L_x, L_y),
-    A' = tau (L_x u_x + L_y u_y), B' = 2 sq L u_x + tau u L_x, C' = 2 sq L u_y + tau u L_y on N | Nx | Ny, assembled, zero on the Dirichlet nodes"""
-    Bt, Dt, gw, sx, sy = _tables(P, ngp, hx, hy)
+    A' = tau (L_x u_x + L_y u_y), B' = 2 sq L u_x + tau u L_x, C' = 2 sq L u_y + tau u L_y on N | Nx | Ny, assembled, zero on the Dirichlet
+    nodes.  dtype: the same statements in that type, inputs, tables and constants cast once at entry; tables: see
+    test_strongform_host.elem_tables; scale: returns (out, S), S the magnitude field -- the same formula with every input, table entry
+    and constant replaced by its absolute value (there is no subtraction), after the Dirichlet substitutions; 0 on the Dirichlet nodes."""
+    dt = np.dtype(dtype).type
     sq = 1.0 + tau if sq is None else sq
     wscale = (0.5 * hx) * (0.5 * hy) if wscale is None else wscale
-    ny, nx = u.shape
+    ny, nx = np.shape(u)
     nely, nelx = (ny - 1) // P, (nx - 1) // P
-    ut, fixed = np.array(u, dtype=np.float64), np.zeros((ny, nx), dtype=bool)
+    nb = P + 1
+    fixed = np.zeros((ny, nx), dtype=bool)
     for k in (0, 1):
         if masks[k] is not None:
-            ut = np.where(masks[k], vals[k], ut)
             fixed |= np.asarray(masks[k], dtype=bool)
-    lt = np.where(fixed, 0.0, cot)
-    nb = P + 1
-    out = np.zeros((ny, nx))
-    for jg in range(ngp):
-        for ig in range(ngp):
-            W = wscale * gw[ig] * gw[jg]
-            N = {(jb, ib): Bt[ig, ib] * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
-            Nx = {(jb, ib): Dt[ig, ib] * sx * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
-            Ny = {(jb, ib): Bt[ig, ib] * Dt[jg, jb] * sy for jb in range(nb) for ib in range(nb)}
 
-            def at(t, tab):
-                return sum(tab[a] * t[_loc(P, nely, nelx, *a)] for a in tab)
+    def run(A):
+        c = lambda x: A(np.asarray(x, dtype=dt))                                # noqa: E731
+        Bt, Dt, Wt, sx, sy = (A(t) for t in _tables_kw(P, ngp, hx, hy, wscale, tables, dt))
+        tau_, sq_ = c(tau)[()], c(sq)[()]
+        ut = c(u)
+        for k in (0, 1):
+            if masks[k] is not None:
+                ut = np.where(masks[k], c(vals[k]), ut)
+        lt = np.where(fixed, dt(0), c(cot))
+        out = np.zeros((ny, nx), dtype=dt)
+        for jg in range(ngp):
+            for ig in range(ngp):
+                W = Wt[jg, ig]
+                N = {(jb, ib): Bt[ig, ib] * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
+                Nx = {(jb, ib): Dt[ig, ib] * sx * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
+                Ny = {(jb, ib): Bt[ig, ib] * Dt[jg, jb] * sy for jb in range(nb) for ib in range(nb)}
 
-            ug, ux, uy = at(ut, N), at(ut, Nx), at(ut, Ny)
-            L, Lx, Ly = at(lt, N), at(lt, Nx), at(lt, Ny)
-            A = tau * (Lx * ux + Ly * uy)
-            Bc = 2.0 * sq * L * ux + tau * ug * Lx
-            Cc = 2.0 * sq * L * uy + tau * ug * Ly
-            for a in N:
-                out[_loc(P, nely, nelx, *a)] += W * (N[a] * A + Nx[a] * Bc + Ny[a] * Cc)
-    return np.where(fixed, 0.0, out)
+                def at(t, tab):
+                    return sum(tab[a] * t[_loc(P, nely, nelx, *a)] for a in tab)
+
+                ug, ux, uy = at(ut, N), at(ut, Nx), at(ut, Ny)
+                L, Lx, Ly = at(lt, N), at(lt, Nx), at(lt, Ny)
+                Ac = tau_ * (Lx * ux + Ly * uy)
+                Bc = dt(2) * sq_ * L * ux + tau_ * ug * Lx
+                Cc = dt(2) * sq_ * L * uy + tau_ * ug * Ly
+                for a in N:
+                    out[_loc(P, nely, nelx, *a)] += W * (N[a] * Ac + Nx[a] * Bc + Ny[a] * Cc)
+        assert out.dtype == dt, out.dtype                                          # numpy promotes silently
+        return np.where(fixed, dt(0), out)
+
+    out = run(lambda x: x)
+    return (out, run(np.abs)) if scale else out
 
 
 def fixture_case(z):

@@ -177,60 +177,77 @@ def test_fosls_ops_refuse_cpu_tensors_and_bad_arguments():
 # ---------------------------------------------------------------------------------------------
 # float64 restatement of the operator (include/diffnet_hip.h, dn_fosls_args)
 # ---------------------------------------------------------------------------------------------
-def fosls_np(u, mx, my, masks, vals, hx, hy, P, ngp, nu=1.0, f=None, f_gp=None, weights=(1.0, 1.0), fs=1.0, wscale=1.0, out_scale=1.0):
+def fosls_np(u, mx, my, masks, vals, hx, hy, P, ngp, nu=1.0, f=None, f_gp=None, weights=(1.0, 1.0), fs=1.0, wscale=1.0, out_scale=1.0, *,
+             tables=None, dtype=np.float64, scale=False):
     """u, mx, my: (ny, nx) float64; masks[k]: bool arrays or None; vals[k]: float or (ny, nx); nu: float or nodal (ny, nx); f: nodal
     (ny, nx) or None; f_gp: (G, nely, nelx), a float or None, g = jg * ngp + ig.  The formulas of the header, term by term, with the
-    rule's truncated literals.  Returns (sum, (gu, gmx, gmy) each (ny, nx), (qx, qy, d) each (G, nely, nelx))."""
-    from diffnet_amd.tables import Basis1D, gauss_rule
-    gx, gw = gauss_rule(ngp)
-    Bt, Dt, _ = Basis1D(P).at_gauss(gx)             # (ngp, nbf)
-    wq, wd = weights
-    ny, nx = u.shape
+    rule's truncated literals.  Returns (sum, (gu, gmx, gmy) each (ny, nx), (qx, qy, d) each (G, nely, nelx)).  dtype: the same
+    statements in that type, inputs, tables and constants cast once at entry; tables: see test_strongform_host.elem_tables; scale: also
+    returns (S_sum, (S_gu, S_gmx, S_gmy)), the magnitude field -- the same formulas with every input, table entry and constant replaced
+    by its absolute value and every subtraction made an addition, after the Dirichlet substitutions; S_gu is 0 on the Dirichlet nodes."""
+    from test_strongform_host import elem_tables
+    dt = np.dtype(dtype).type
+    ny, nx = np.shape(u)
     nely, nelx = (ny - 1) // P, (nx - 1) // P
-    sx, sy = 2.0 / hx, 2.0 / hy
-    ut = np.array(u, dtype=np.float64)
-    mx, my = np.asarray(mx, dtype=np.float64), np.asarray(my, dtype=np.float64)
-    fixed = np.zeros((ny, nx), dtype=bool)
-    for k in (0, 1):                                # in order: where both hold, condition 2's value is the one used
-        if masks[k] is not None:
-            ut = np.where(masks[k], vals[k], ut)
-            fixed |= np.asarray(masks[k], dtype=bool)
     nb = P + 1
+    G = ngp * ngp
+    fixed = np.zeros((ny, nx), dtype=bool)
+    for k in (0, 1):
+        if masks[k] is not None:
+            fixed |= np.asarray(masks[k], dtype=bool)
 
     def loc(jb, ib):
         return (slice(jb, jb + P * (nely - 1) + 1, P), slice(ib, ib + P * (nelx - 1) + 1, P))
 
-    total = 0.0
-    gu, gmx, gmy = np.zeros((ny, nx)), np.zeros((ny, nx)), np.zeros((ny, nx))
-    G = ngp * ngp
-    qx_all, qy_all, d_all = np.zeros((G, nely, nelx)), np.zeros((G, nely, nelx)), np.zeros((G, nely, nelx))
-    for jg in range(ngp):
-        for ig in range(ngp):
-            g, W = jg * ngp + ig, wscale * gw[ig] * gw[jg]
-            N = {(jb, ib): Bt[ig, ib] * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
-            Nx = {(jb, ib): Dt[ig, ib] * sx * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
-            Ny = {(jb, ib): Bt[ig, ib] * Dt[jg, jb] * sy for jb in range(nb) for ib in range(nb)}
+    def run(A, minus):
+        c = lambda x: A(np.asarray(x, dtype=dt))                                # noqa: E731
+        Bt, Dt, _, Wt = (c(t) for t in elem_tables(P, ngp, tables, dt, wscale))
+        wq, wd = (c(x)[()] for x in weights)
+        fsc = c(fs)[()]
+        sx, sy = dt(2) / dt(hx), dt(2) / dt(hy)
+        ut, mxt, myt = c(u), c(mx), c(my)
+        for k in (0, 1):                            # in order: where both hold, condition 2's value is the one used
+            if masks[k] is not None:
+                ut = np.where(masks[k], c(vals[k]), ut)
+        total = dt(0)
+        gu, gmx, gmy = (np.zeros((ny, nx), dtype=dt) for _ in range(3))
+        qx_all, qy_all, d_all = (np.zeros((G, nely, nelx), dtype=dt) for _ in range(3))
+        for jg in range(ngp):
+            for ig in range(ngp):
+                g, W = jg * ngp + ig, Wt[jg, ig]
+                N = {(jb, ib): Bt[ig, ib] * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
+                Nx = {(jb, ib): Dt[ig, ib] * sx * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
+                Ny = {(jb, ib): Bt[ig, ib] * Dt[jg, jb] * sy for jb in range(nb) for ib in range(nb)}
 
-            def at(t, tab):
-                return sum(tab[a] * t[loc(*a)] for a in tab)
+                def at(t, tab):
+                    return sum(tab[a] * t[loc(*a)] for a in tab)
 
-            nug = at(np.asarray(nu, dtype=np.float64), N) if np.ndim(nu) else float(nu)
-            if f is not None:
-                fg = at(np.asarray(f, dtype=np.float64), N)
-            elif f_gp is None or np.ndim(f_gp) == 0:
-                fg = np.full((nely, nelx), 0.0 if f_gp is None else float(f_gp))
-            else:
-                fg = np.asarray(f_gp, dtype=np.float64)[g]
-            qx = at(mx, N) - nug * at(ut, Nx)
-            qy = at(my, N) - nug * at(ut, Ny)
-            d = at(mx, Nx) + at(my, Ny) + fs * fg
-            qx_all[g], qy_all[g], d_all[g] = qx, qy, d
-            total += W * np.sum(wq * (qx * qx + qy * qy) + wd * d * d)
-            for a in N:
-                gu[loc(*a)] += -2.0 * W * wq * nug * (qx * Nx[a] + qy * Ny[a])
-                gmx[loc(*a)] += 2.0 * W * (wq * qx * N[a] + wd * d * Nx[a])
-                gmy[loc(*a)] += 2.0 * W * (wq * qy * N[a] + wd * d * Ny[a])
-    return total, (np.where(fixed, 0.0, gu) * out_scale, gmx * out_scale, gmy * out_scale), (qx_all, qy_all, d_all)
+                nug = at(c(nu), N) if np.ndim(nu) else c(float(nu))[()]
+                if f is not None:
+                    fg = at(c(f), N)
+                elif f_gp is None or np.ndim(f_gp) == 0:
+                    fg = np.full((nely, nelx), c(0.0 if f_gp is None else float(f_gp)), dtype=dt)
+                else:
+                    fg = c(f_gp)[g]
+                qx = at(mxt, N) + minus * nug * at(ut, Nx)
+                qy = at(myt, N) + minus * nug * at(ut, Ny)
+                d = at(mxt, Nx) + at(myt, Ny) + fsc * fg
+                qx_all[g], qy_all[g], d_all[g] = qx, qy, d
+                total += W * np.sum(wq * (qx * qx + qy * qy) + wd * d * d)
+                for a in N:
+                    gu[loc(*a)] += minus * dt(2) * W * wq * nug * (qx * Nx[a] + qy * Ny[a])
+                    gmx[loc(*a)] += dt(2) * W * (wq * qx * N[a] + wd * d * Nx[a])
+                    gmy[loc(*a)] += dt(2) * W * (wq * qy * N[a] + wd * d * Ny[a])
+        os_ = c(out_scale)
+        grads = (np.where(fixed, dt(0), gu) * os_, gmx * os_, gmy * os_)
+        assert all(x.dtype == dt for x in grads), [x.dtype for x in grads]         # numpy promotes silently
+        return total, grads, (qx_all, qy_all, d_all)
+
+    total, grads, parts = run(lambda x: x, dt(-1))
+    if not scale:
+        return total, grads, parts
+    S_total, S_grads, _ = run(np.abs, dt(1))
+    return total, grads, parts, (S_total, S_grads)
 
 
 def fixture_case(z):

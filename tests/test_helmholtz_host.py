@@ -160,61 +160,75 @@ def test_helmholtz_ops_refuse_cpu_tensors_and_bad_arguments():
 # float64 restatement of the operator (include/diffnet_hip.h, dn_helmholtz_args)
 # ---------------------------------------------------------------------------------------------
 def helmholtz_np(u, masks, vals, hx, hy, P, ngp, nu=None, sigma=0.0, f=None, f_gp=None, ecoef=(0.5, 0.5, 1.0), ocoef=None, wscale=1.0,
-                 out_scale=1.0):
+                 out_scale=1.0, *, tables=None, dtype=np.float64, scale=False):
     """u: (ny, nx) float64; masks[k]: bool arrays or None; vals[k]: float or (ny, nx); nu: nodal (ny, nx) or None (1); sigma: float or
     nodal (ny, nx); f: nodal (ny, nx) or None; f_gp: (G, nely, nelx), a float or None, g = jg * ngp + ig; ecoef = (c, cr, fs); ocoef =
     (alpha, gamma, beta), None: (2c, 2cr, fs), the energy's gradient.  The formulas of the header, term by term, with the rule's
     truncated literals.  Returns dict(energy, out (ny, nx), sumsq, gross = (diffusion, reaction, forcing) sums of W c nu |grad u|^2,
-    W cr |sg| u^2, W |fs u f|)."""
-    from diffnet_amd.tables import Basis1D, gauss_rule
-    gx, gw = gauss_rule(ngp)
-    Bt, Dt = Basis1D(P).at_gauss(gx)[:2]            # (ngp, nbf)
-    c, cr, fs = ecoef
-    alpha, gamma, beta = (2.0 * c, 2.0 * cr, fs) if ocoef is None else ocoef
-    ny, nx = u.shape
+    W cr |sg| u^2, W |fs u f|).  dtype: the same statements in that type, inputs, tables and constants cast once at entry; tables: see
+    test_strongform_host.elem_tables; scale: the dict also holds S_energy, S_out and S_raw (S_out before out_scale), the magnitude field
+    -- the same formulas with every input, table entry and constant replaced by its absolute value and every subtraction made an
+    addition, after the Dirichlet substitutions; 0 on the Dirichlet nodes -- and `raw`, out before out_scale."""
+    from test_strongform_host import elem_tables
+    dt = np.dtype(dtype).type
+    ny, nx = np.shape(u)
     nely, nelx = (ny - 1) // P, (nx - 1) // P
-    sx, sy = 2.0 / hx, 2.0 / hy
-    ut = np.array(u, dtype=np.float64)
-    fixed = np.zeros((ny, nx), dtype=bool)
-    for k in (0, 1):                                # in order: where both hold, condition 2's value is the one used
-        if masks[k] is not None:
-            ut = np.where(masks[k], vals[k], ut)
-            fixed |= np.asarray(masks[k], dtype=bool)
     nb = P + 1
+    fixed = np.zeros((ny, nx), dtype=bool)
+    for k in (0, 1):
+        if masks[k] is not None:
+            fixed |= np.asarray(masks[k], dtype=bool)
 
     def loc(jb, ib):
         return (slice(jb, jb + P * (nely - 1) + 1, P), slice(ib, ib + P * (nelx - 1) + 1, P))
 
-    energy, out = 0.0, np.zeros((ny, nx))
-    gross = [0.0, 0.0, 0.0]
-    for jg in range(ngp):
-        for ig in range(ngp):
-            g, W = jg * ngp + ig, wscale * gw[ig] * gw[jg]
-            N = {(jb, ib): Bt[ig, ib] * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
-            Nx = {(jb, ib): Dt[ig, ib] * sx * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
-            Ny = {(jb, ib): Bt[ig, ib] * Dt[jg, jb] * sy for jb in range(nb) for ib in range(nb)}
+    def run(A, minus):
+        c = lambda x: A(np.asarray(x, dtype=dt))                                # noqa: E731
+        Bt, Dt, _, Wt = (c(t) for t in elem_tables(P, ngp, tables, dt, wscale))
+        cc, cr, fs = (c(x)[()] for x in ecoef)
+        alpha, gamma, beta = (dt(2) * cc, dt(2) * cr, fs) if ocoef is None else (c(x)[()] for x in ocoef)
+        sx, sy = dt(2) / dt(hx), dt(2) / dt(hy)
+        ut = c(u)
+        for k in (0, 1):                            # in order: where both hold, condition 2's value is the one used
+            if masks[k] is not None:
+                ut = np.where(masks[k], c(vals[k]), ut)
+        energy, out = dt(0), np.zeros((ny, nx), dtype=dt)
+        gross = [dt(0), dt(0), dt(0)]
+        for jg in range(ngp):
+            for ig in range(ngp):
+                g, W = jg * ngp + ig, Wt[jg, ig]
+                N = {(jb, ib): Bt[ig, ib] * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
+                Nx = {(jb, ib): Dt[ig, ib] * sx * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
+                Ny = {(jb, ib): Bt[ig, ib] * Dt[jg, jb] * sy for jb in range(nb) for ib in range(nb)}
 
-            def at(t, tab):
-                return sum(tab[a] * t[loc(*a)] for a in tab)
+                def at(t, tab):
+                    return sum(tab[a] * t[loc(*a)] for a in tab)
 
-            v, ux, uy = at(ut, N), at(ut, Nx), at(ut, Ny)
-            nug = np.ones((nely, nelx)) if nu is None else at(np.asarray(nu, dtype=np.float64), N)
-            sgg = np.full((nely, nelx), float(sigma)) if np.ndim(sigma) == 0 else at(np.asarray(sigma, dtype=np.float64), N)
-            if f is not None:
-                fg = at(np.asarray(f, dtype=np.float64), N)
-            elif f_gp is None or np.ndim(f_gp) == 0:
-                fg = np.full((nely, nelx), 0.0 if f_gp is None else float(f_gp))
-            else:
-                fg = np.asarray(f_gp, dtype=np.float64)[g]
-            diff, react, forc = c * nug * (ux * ux + uy * uy), cr * sgg * v * v, fs * v * fg
-            energy += W * np.sum(diff - react - forc)
-            gross[0] += W * np.sum(np.abs(diff))
-            gross[1] += W * np.sum(np.abs(react))
-            gross[2] += W * np.sum(np.abs(forc))
-            for a in N:
-                out[loc(*a)] += W * (alpha * nug * (Nx[a] * ux + Ny[a] * uy) - gamma * sgg * N[a] * v - beta * N[a] * fg)
-    out = np.where(fixed, 0.0, out)
-    return dict(energy=energy, out=out * out_scale, sumsq=float(np.sum(out * out)), gross=tuple(gross))
+                v, ux, uy = at(ut, N), at(ut, Nx), at(ut, Ny)
+                nug = np.ones((nely, nelx), dtype=dt) if nu is None else at(c(nu), N)
+                sgg = np.full((nely, nelx), c(float(sigma)), dtype=dt) if np.ndim(sigma) == 0 else at(c(sigma), N)
+                if f is not None:
+                    fg = at(c(f), N)
+                elif f_gp is None or np.ndim(f_gp) == 0:
+                    fg = np.full((nely, nelx), c(0.0 if f_gp is None else float(f_gp)), dtype=dt)
+                else:
+                    fg = c(f_gp)[g]
+                diff, react, forc = cc * nug * (ux * ux + uy * uy), cr * sgg * v * v, fs * v * fg
+                energy += W * np.sum(diff + minus * react + minus * forc)
+                gross[0] += W * np.sum(np.abs(diff))
+                gross[1] += W * np.sum(np.abs(react))
+                gross[2] += W * np.sum(np.abs(forc))
+                for a in N:
+                    out[loc(*a)] += W * (alpha * nug * (Nx[a] * ux + Ny[a] * uy) + minus * gamma * sgg * N[a] * v + minus * beta * N[a] * fg)
+        out = np.where(fixed, dt(0), out)
+        assert out.dtype == dt, out.dtype                                          # numpy promotes silently
+        return dict(energy=energy, out=out * c(out_scale), raw=out, sumsq=float(np.sum(out * out)), gross=tuple(gross))
+
+    res = run(lambda x: x, dt(-1))
+    if scale:
+        mag = run(np.abs, dt(1))
+        res.update(S_energy=mag["energy"], S_out=mag["out"], S_raw=mag["raw"])
+    return res
 
 
 def fixture_case(z):

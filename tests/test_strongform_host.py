@@ -141,55 +141,87 @@ def test_strongform_ops_refuse_cpu_tensors_and_bad_arguments():
 # ---------------------------------------------------------------------------------------------
 # float64 restatement of the operator (include/diffnet_hip.h, dn_strongform_args)
 # ---------------------------------------------------------------------------------------------
-def strongform_np(u, masks, vals, coef, hx, hy, P, ngp, f=None, f_gp=None, wscale=1.0, out_scale=1.0):
+def elem_tables(P, ngp, tables, dt, wscale):
+    """The 1-D tables (N, dN, d2N, each (ngp, P + 1)) and the 2-D weights W[jg][ig] of a restatement in the type dt.  tables None: the
+    rule's own, W = wscale w_ig w_jg; else the (N, dN, d2N, w) given -- the float32 values of the mesh struct -- with the weights formed
+    as the host forms them, w_jg * (w_ig * wscale) in float32 (elem2d_fill, csrc/elem2d_common.h)."""
+    from diffnet_amd.tables import Basis1D, gauss_rule
+    if tables is None:
+        gx, gw = gauss_rule(ngp)
+        Bt, Dt, D2t = Basis1D(P).at_gauss(gx)       # (ngp, nbf)
+        gw = np.asarray(gw, dtype=dt)
+        W = [[dt(wscale) * gw[ig] * gw[jg] for ig in range(ngp)] for jg in range(ngp)]
+    else:
+        Bt, Dt, D2t, gw = tables
+        w32 = np.asarray(gw, dtype=np.float32)
+        W = [[dt(w32[jg] * (w32[ig] * np.float32(wscale))) for ig in range(ngp)] for jg in range(ngp)]
+    return np.asarray(Bt, dtype=dt), np.asarray(Dt, dtype=dt), np.asarray(D2t, dtype=dt), np.asarray(W, dtype=dt)
+
+
+def strongform_np(u, masks, vals, coef, hx, hy, P, ngp, f=None, f_gp=None, wscale=1.0, out_scale=1.0, *, tables=None, dtype=np.float64,
+                  scale=False):
     """u: (ny, nx) float64; masks[k]: bool arrays or None; vals[k]: float or (ny, nx); f: nodal (ny, nx) or None; f_gp: (G, nely, nelx), a
     float or None, g = jg * ngp + ig.  The formulas of the header, term by term, with the rule's truncated literals.
-    Returns (sum, grad (ny, nx), r (G, nely, nelx))."""
-    from diffnet_amd.tables import Basis1D, gauss_rule
-    gx, gw = gauss_rule(ngp)
-    Bt, Dt, D2t = Basis1D(P).at_gauss(gx)           # (ngp, nbf)
-    ax, ay, b, dxx, dyy, fs = coef
-    ny, nx = u.shape
+    Returns (sum, grad (ny, nx), r (G, nely, nelx)).  dtype: the same statements in that type, inputs, tables and constants cast once at
+    entry; tables: see elem_tables; scale: also returns (S_sum, S_grad), the magnitude field -- the same formulas with every input,
+    table entry and constant replaced by its absolute value (there is no subtraction), after the Dirichlet substitutions; S_grad is 0 on
+    the Dirichlet nodes."""
+    dt = np.dtype(dtype).type
+    ny, nx = np.shape(u)
     nely, nelx = (ny - 1) // P, (nx - 1) // P
-    sx, sy = 2.0 / hx, 2.0 / hy
-    ut = np.array(u, dtype=np.float64)
-    fixed = np.zeros((ny, nx), dtype=bool)
-    for k in (0, 1):                                # in order: where both hold, condition 2's value is the one used
-        if masks[k] is not None:
-            ut = np.where(masks[k], vals[k], ut)
-            fixed |= np.asarray(masks[k], dtype=bool)
     nb = P + 1
+    fixed = np.zeros((ny, nx), dtype=bool)
+    for k in (0, 1):
+        if masks[k] is not None:
+            fixed |= np.asarray(masks[k], dtype=bool)
 
     def loc(jb, ib):
         return (slice(jb, jb + P * (nely - 1) + 1, P), slice(ib, ib + P * (nelx - 1) + 1, P))
 
-    total, grad = 0.0, np.zeros((ny, nx))
-    r_all = np.zeros((ngp * ngp, nely, nelx))
-    for jg in range(ngp):
-        for ig in range(ngp):
-            g, W = jg * ngp + ig, wscale * gw[ig] * gw[jg]
-            N = {(jb, ib): Bt[ig, ib] * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
-            Nx = {(jb, ib): Dt[ig, ib] * sx * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
-            Ny = {(jb, ib): Bt[ig, ib] * Dt[jg, jb] * sy for jb in range(nb) for ib in range(nb)}
-            Nxx = {(jb, ib): D2t[ig, ib] * sx * sx * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
-            Nyy = {(jb, ib): Bt[ig, ib] * D2t[jg, jb] * sy * sy for jb in range(nb) for ib in range(nb)}
+    def run(A):
+        c = lambda x: A(np.asarray(x, dtype=dt))                                # noqa: E731
+        Bt, Dt, D2t, Wt = (c(t) for t in elem_tables(P, ngp, tables, dt, wscale))
+        ax, ay, b, dxx, dyy, fs = (c(x)[()] for x in coef)
+        sx, sy = dt(2) / dt(hx), dt(2) / dt(hy)
+        ut = c(u)
+        for k in (0, 1):                            # in order: where both hold, condition 2's value is the one used
+            if masks[k] is not None:
+                ut = np.where(masks[k], c(vals[k]), ut)
+        total, grad = dt(0), np.zeros((ny, nx), dtype=dt)
+        r_all = np.zeros((ngp * ngp, nely, nelx), dtype=dt)
+        for jg in range(ngp):
+            for ig in range(ngp):
+                g, W = jg * ngp + ig, Wt[jg, ig]
+                N = {(jb, ib): Bt[ig, ib] * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
+                Nx = {(jb, ib): Dt[ig, ib] * sx * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
+                Ny = {(jb, ib): Bt[ig, ib] * Dt[jg, jb] * sy for jb in range(nb) for ib in range(nb)}
+                Nxx = {(jb, ib): D2t[ig, ib] * sx * sx * Bt[jg, jb] for jb in range(nb) for ib in range(nb)}
+                Nyy = {(jb, ib): Bt[ig, ib] * D2t[jg, jb] * sy * sy for jb in range(nb) for ib in range(nb)}
 
-            def at(t, tab):
-                return sum(tab[a] * t[loc(*a)] for a in tab)
+                def at(t, tab):
+                    return sum(tab[a] * t[loc(*a)] for a in tab)
 
-            v, ux, uy, uxx, uyy = at(ut, N), at(ut, Nx), at(ut, Ny), at(ut, Nxx), at(ut, Nyy)
-            if f is not None:
-                fg = at(np.asarray(f, dtype=np.float64), N)
-            elif f_gp is None or np.ndim(f_gp) == 0:
-                fg = np.full((nely, nelx), 0.0 if f_gp is None else float(f_gp))
-            else:
-                fg = np.asarray(f_gp, dtype=np.float64)[g]
-            r = ax * ux + ay * uy + b * v * ux + dxx * uxx + dyy * uyy + fs * fg
-            r_all[g] = r
-            total += W * np.sum(r * r)
-            for a in N:
-                grad[loc(*a)] += 2.0 * W * r * (ax * Nx[a] + ay * Ny[a] + b * (N[a] * ux + v * Nx[a]) + dxx * Nxx[a] + dyy * Nyy[a])
-    return total, np.where(fixed, 0.0, grad) * out_scale, r_all
+                v, ux, uy, uxx, uyy = at(ut, N), at(ut, Nx), at(ut, Ny), at(ut, Nxx), at(ut, Nyy)
+                if f is not None:
+                    fg = at(c(f), N)
+                elif f_gp is None or np.ndim(f_gp) == 0:
+                    fg = np.full((nely, nelx), c(0.0 if f_gp is None else float(f_gp)), dtype=dt)
+                else:
+                    fg = c(f_gp)[g]
+                r = ax * ux + ay * uy + b * v * ux + dxx * uxx + dyy * uyy + fs * fg
+                r_all[g] = r
+                total += W * np.sum(r * r)
+                for a in N:
+                    grad[loc(*a)] += dt(2) * W * r * (ax * Nx[a] + ay * Ny[a] + b * (N[a] * ux + v * Nx[a]) + dxx * Nxx[a] + dyy * Nyy[a])
+        grad = np.where(fixed, dt(0), grad) * c(out_scale)
+        assert grad.dtype == dt and r_all.dtype == dt, (grad.dtype, r_all.dtype)       # numpy promotes silently
+        return total, grad, r_all
+
+    total, grad, r_all = run(lambda x: x)
+    if not scale:
+        return total, grad, r_all
+    S_total, S_grad, _ = run(np.abs)
+    return total, grad, r_all, (S_total, S_grad)
 
 
 def fixture_case(z):
