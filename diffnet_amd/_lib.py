@@ -128,6 +128,28 @@ class DnCoefGradArgs(C.Structure):
                 ("in_scale", C.c_void_p), ("g_nu", C.c_void_p), ("g_f", C.c_void_p)]
 
 
+class DnPoissonDiagArgs(C.Structure):
+    _fields_ = [("nu", C.c_void_p), ("nu_batched", C.c_int32), ("bc", DnDirichlet * 2),
+                ("wscale", C.c_float), ("unit", C.c_int32), ("dinv", C.c_void_p)]
+
+
+class DnCgState(C.Structure):
+    _fields_ = [("rz", C.c_double), ("rr", C.c_double), ("rr0", C.c_double), ("pq", C.c_double),
+                ("alpha", C.c_float), ("beta", C.c_float),
+                ("active", C.c_int32), ("iterations", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class DnPoissonCgArgs(C.Structure):
+    _fields_ = [("phase", C.c_int32), ("batch", C.c_int32), ("n", C.c_int64),
+                ("x", C.c_void_p), ("r", C.c_void_p), ("p", C.c_void_p), ("q", C.c_void_p), ("dinv", C.c_void_p),
+                ("dinv_batched", C.c_int32), ("tol", C.c_float), ("atol", C.c_float),
+                ("state", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+CG_INIT, CG_DOT, CG_UPDATE, CG_DIRECTION = 0, 1, 2, 3
+CG_BREAKDOWN = 1
+
+
 class DnFdmPoissonArgs(C.Structure):
     _fields_ = [("B", C.c_int32), ("ny", C.c_int32), ("nx", C.c_int32),
                 ("u", C.c_void_p), ("nu", C.c_void_p), ("f", C.c_void_p), ("nu_batched", C.c_int32), ("f_batched", C.c_int32),
@@ -220,6 +242,9 @@ SYMBOLS = {
     "dn_eikonal3d_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),
     "dn_eikonal3d_apply": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnEikonalArgs), C.c_void_p]),
     "dn_poisson_coef_grad": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnCoefGradArgs), C.c_void_p]),
+    "dn_poisson_diag": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnPoissonDiagArgs), C.c_void_p]),
+    "dn_poisson_cg_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
+    "dn_poisson_cg": (C.c_int, [C.POINTER(DnPoissonCgArgs), C.c_void_p]),
     "dn_fdm_poisson_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "dn_fdm_poisson_apply": (C.c_int, [C.POINTER(DnFdmPoissonArgs), C.c_void_p]),
     "dn_points_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),

@@ -199,6 +199,13 @@ class DiffNetFEM(PDE):
         """sum(R^2) of `residual` (12_klsum.py:128-131) with fused reduction and single-kernel backward."""
         return ops.residual_loss(self.geom, u, nu, f, f_gp, dirichlet, jac)
 
+    def solve(self, nu=None, f=None, f_gp=None, dirichlet=(), u0=None, batch=None, **options):
+        """(u, info): the discrete solution of Z (K_nu u~ - F f) = 0 -- the minimiser of `energy_loss`, the zero of `residual` -- by
+        batched Jacobi-preconditioned CG on the fused operator (diffnet_amd/solve.py: poisson_solve); differentiable wrt nu and the
+        nodal f.  Q1 meshes only."""
+        from . import solve as _solve
+        return _solve.poisson_solve(self.geom, nu, f, f_gp, dirichlet, u0, batch, **options)
+
     def assemble(self, r_split, out=None):
         """Q1_2D/3D_vector_assembly of the reference scripts (any degree), deterministic."""
         return ops.assemble(r_split, self.nsd, self.nbf_1d, out)

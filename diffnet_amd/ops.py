@@ -11,7 +11,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from ._lib import DnCoefGradArgs, DnDirichlet, DnEikonalArgs, DnFdmPoissonArgs, DnFoslsArgs, DnFsdtArgs, DnHelmholtzArgs, DnMesh, DnNsArgs, DnPointsArgs, DnPoissonArgs, DnStokesArgs, DnStrongformArgs, DnTransportArgs, I32x3, DiffNetHipError
+from ._lib import DnCoefGradArgs, DnDirichlet, DnEikonalArgs, DnFdmPoissonArgs, DnFoslsArgs, DnFsdtArgs, DnHelmholtzArgs, DnMesh, DnNsArgs, DnPointsArgs, DnPoissonArgs, DnPoissonCgArgs, DnPoissonDiagArgs, DnStokesArgs, DnStrongformArgs, DnTransportArgs, I32x3, DiffNetHipError
 
 
 def _require(t, name, ndim=None, strict=False):
@@ -1157,6 +1157,105 @@ def poisson_coef_grad(geom, u, v=None, dirichlet=(), a_nu=1.0, a_f=1.0, wscale=1
         _lib.check(rc, "dn_poisson_coef_grad")
     _COEF_STATS["launch"] += 1
     return g_nu, g_f
+
+
+# ---- the vector side of the CG solve (dn_poisson_diag, dn_poisson_cg): raw wrappers; the host layer is diffnet_amd/solve.py -----------
+def poisson_diag(geom, batch, nu=None, dirichlet=(), wscale=1.0, unit=False, out=None, device=None):
+    """One launch of dn_poisson_diag (include/diffnet_hip.h): the inverse diagonal of K_nu as a (batch,1,*N) float32 tensor, 0 on the
+    Dirichlet nodes and where the diagonal is 0; unit=True: 1 on the other nodes.  PackedMask / BoxFaces conditions are expanded to
+    their images; the conditions' values are not read.  Outside autograd; Q1 meshes only."""
+    nsd, node_shape = geom.nsd, tuple(geom.node_shape)
+    if out is None:
+        if device is None:
+            device = nu.device if isinstance(nu, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty((int(batch), 1, *node_shape), dtype=torch.float32, device=device)
+    out = _require(out, "out", nsd + 2, True)
+    if tuple(out.shape) != (int(batch), 1, *node_shape):
+        raise ValueError(f"out has shape {tuple(out.shape)}, expected ({batch},1,{','.join(map(str, node_shape))})")
+    keep = [out]
+    args = DnPoissonDiagArgs()
+    if nu is not None:
+        nu = _require(nu.detach(), "nu", nsd + 2)
+        if tuple(nu.shape[1:]) != (1, *node_shape) or nu.shape[0] not in (1, batch) or nu.device != out.device:
+            raise ValueError("nu must be a nodal field (B|1,1,*N) on the output's device")
+        keep.append(nu)
+        args.nu, args.nu_batched = nu.data_ptr(), int(nu.shape[0] == batch)
+    for k, d in enumerate(_norm_dirichlet(dirichlet)):
+        _dirichlet_image(args.bc[k], d.mask, 0.0, out, node_shape, keep)
+    args.wscale, args.unit, args.dinv = float(wscale), int(bool(unit)), out.data_ptr()
+    mesh = geom.mesh_struct(int(batch))
+    rc = _lib.lib().dn_poisson_diag(C.byref(mesh), C.byref(args), _stream(out))
+    if rc:
+        _lib.check(rc, "dn_poisson_diag")
+    return out
+
+
+CG_PHASES = {"init": _lib.CG_INIT, "dot": _lib.CG_DOT, "update": _lib.CG_UPDATE, "direction": _lib.CG_DIRECTION}
+# one dn_cg_state as a numpy record (the device block is read back as bytes)
+CG_STATE_DTYPE = [("rz", "<f8"), ("rr", "<f8"), ("rr0", "<f8"), ("pq", "<f8"), ("alpha", "<f4"), ("beta", "<f4"),
+                  ("active", "<i4"), ("iterations", "<i4"), ("flags", "<i4"), ("reserved", "<i4", (3,))]
+
+
+def poisson_cg_workspace(n, batch, device):
+    """A zero-filled workspace for dn_poisson_cg launches on samples of n nodes (one per stream in use)."""
+    nbytes = int(_lib.lib().dn_poisson_cg_workspace_bytes(int(n), int(batch)))
+    if nbytes <= 0:
+        raise DiffNetHipError("dn_poisson_cg_workspace_bytes: n or batch out of range")
+    return torch.zeros(nbytes, dtype=torch.uint8, device=device)
+
+
+def poisson_cg_state(batch, device):
+    """A zeroed block of `batch` dn_cg_state records, (batch, 64) uint8."""
+    return torch.zeros((int(batch), C.sizeof(_lib.DnCgState)), dtype=torch.uint8, device=device)
+
+
+def poisson_cg_args(phase, x, r, p, q, dinv, state, workspace, tol=0.0, atol=0.0):
+    """The argument struct of one dn_poisson_cg phase on FIXED buffers: x, r, p, q (B,...) float32 of n = numel / B nodes per sample,
+    dinv the same or (1,...).  Returns (args, keep); launch it with poisson_cg_launch."""
+    B = p.shape[0]
+    n = p.numel() // B
+    a = DnPoissonCgArgs()
+    a.phase = CG_PHASES[phase] if isinstance(phase, str) else int(phase)
+    a.batch, a.n = B, n
+    keep = []
+    for name, t in (("x", x), ("r", r), ("p", p), ("q", q), ("dinv", dinv)):
+        if t is None:
+            continue
+        t = _require(t, name, None, True)
+        if t.numel() not in ((n, B * n) if name == "dinv" else (B * n,)) or t.device != p.device:
+            raise ValueError(f"{name} has shape {tuple(t.shape)}: expected {B} samples of {n} nodes on p's device")
+        setattr(a, name, t.data_ptr())
+        keep.append(t)
+    if dinv is not None:
+        a.dinv_batched = int(dinv.numel() == B * n)
+    a.tol, a.atol = float(tol), float(atol)
+    if state.dtype != torch.uint8 or state.numel() != B * C.sizeof(_lib.DnCgState) or not state.is_contiguous() or state.device != p.device:
+        raise ValueError("state must be the (B, 64) uint8 block of poisson_cg_state on p's device")
+    a.state = state.data_ptr()
+    keep.append(state)
+    if workspace is not None:
+        a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+        keep.append(workspace)
+    return a, keep
+
+
+def poisson_cg_launch(args, device):
+    """One dn_poisson_cg launch on the current stream of `device`."""
+    rc = _lib.lib().dn_poisson_cg(C.byref(args), C.c_void_p(_raw_stream(device)))
+    if rc:
+        _lib.check(rc, "dn_poisson_cg")
+
+
+def poisson_cg_phase(phase, x, r, p, q, dinv, state, workspace, tol=0.0, atol=0.0):
+    """One phase of the PCG iteration (include/diffnet_hip.h: dn_poisson_cg) in place on x, r, p and the state block."""
+    a, keep = poisson_cg_args(phase, x, r, p, q, dinv, state, workspace, tol, atol)
+    poisson_cg_launch(a, p.device)
+
+
+def poisson_cg_read_state(state):
+    """The state block as a numpy record array (one synchronising copy)."""
+    import numpy as np
+    return state.cpu().numpy().view(np.dtype(CG_STATE_DTYPE)).reshape(-1)
 
 
 class _CoefFn(torch.autograd.Function):

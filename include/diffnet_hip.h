@@ -831,6 +831,78 @@ typedef struct dn_coef_grad_args {
 } dn_coef_grad_args;
 int dn_poisson_coef_grad(const dn_mesh *mesh, const dn_coef_grad_args *args, void *stream);
 
+/* ---- batched matrix-free conjugate gradients for the Q1 Poisson problem: the vector side ------------------------------------
+ * The reference has no linear solve of its own: it trains on the loss, and where it wants the discrete solution it reaches for outside
+ * linear algebra (examples/poisson/single_instance/e8_2d_poisson_mms.py:60-67,143-146 loads an ILU factor from a .mat file).  Together
+ * with dn_poisson_apply (q = Z K_nu p: alpha = 1, f absent, homogeneous conditions) these entries are a Jacobi-preconditioned CG solve of
+ * Z (K_nu u~ - F f) = 0 for a whole batch without a host round trip per iteration; composed from torch ops an iteration is about a dozen
+ * launches and a synchronisation for its scalars.
+ *
+ * dn_poisson_diag: the inverse diagonal of K_nu, one launch, no workspace, every node written once with a fixed order of additions
+ * (bitwise reproducible and independent of the batch size):
+ *     diag_a = wscale * sum_{e contains a} sum_g gpw_g nu_g |grad N_a(g)|^2        nu_g = sum_b N_b(g) nu_b, as in dn_poisson_apply
+ *     dinv_a = 0           on a node of either condition's mask and wherever diag_a == 0 (a node surrounded by nu = 0: no equation)
+ *     dinv_a = 1 / diag_a  elsewhere (unit != 0: 1 elsewhere -- the unpreconditioned solve)
+ * nu: (B,1,*N), (1,1,*N) with nu_batched = 0, or NULL (nu = 1).  bc: only mask, mask_kind and mask_batched are read (DN_MASK_F32 /
+ * DN_MASK_U8 images, shared or per sample, the two may differ in format).  Mesh: nsd 2 or 3, degree 1, ngp 2..4.
+ * DN_E_UNSUPPORTED for degree > 1, ngp outside 2..4, nsd outside {2, 3}, samples of 2^30 nodes or more and DN_MASK_BITS / DN_MASK_BOX
+ * conditions (expand them: dn_unpack_mask_bits); DN_E_BADARG for a NULL mesh, args or dinv, fewer than 2 nodes on an axis, B outside
+ * 1..65535, an unknown mask kind or flags outside {0, 1}; nothing is launched then. */
+typedef struct dn_poisson_diag_args {
+    const float *nu;       /* (B,1,*N), (1,1,*N) or NULL (nu == 1)                      */
+    int32_t nu_batched;
+    dn_dirichlet bc[2];
+    float wscale;
+    int32_t unit;          /* 1: dinv = 1 on the free nodes                             */
+    float *dinv;           /* (B,1,*N)                                                  */
+} dn_poisson_diag_args;
+int dn_poisson_diag(const dn_mesh *mesh, const dn_poisson_diag_args *args, void *stream);
+
+/* dn_poisson_cg: the vector phases of one PCG iteration over flat arrays of `batch` samples of n floats (sample b starts at element
+ * b * n; array bases 16-byte aligned, a sample's base need not be).  Per-sample scalars live in one dn_cg_state per sample on the device.
+ *     DN_CG_INIT       (q = the operator's output Z (K x0~ - F f))   r = -q,  p = dinv r,  rz = sum r (dinv r),  rr0 = rr = sum r r,
+ *                      active = rr0 > atol^2,  iterations = 0,  flags = 0,  alpha = beta = 0          -- every sample
+ *     DN_CG_DOT        pq = sum p q;  alpha = rz / pq if active and pq > 0, else alpha = 0; an active sample with !(pq > 0) (an operator
+ *                      that is not positive definite, or a NaN) gets flags |= DN_CG_BREAKDOWN and active = 0
+ *     DN_CG_UPDATE     x += alpha p,  r -= alpha q,  rz' = sum r (dinv r),  rr = sum r r;  then beta = rz' / rz,  rz = rz',
+ *                      iterations += 1,  active = rr > max(tol^2 rr0, atol^2)  (a NaN rr: DN_CG_BREAKDOWN)   -- active samples only
+ *     DN_CG_DIRECTION  p = dinv r + beta p                                                             -- active samples only
+ * One iteration = the operator launch on p, then DOT, UPDATE, DIRECTION: 13 floats moved per node beside the operator's.
+ * No array of an inactive sample is read or written by any phase but INIT (its x, r, p stay bitwise as they are even when p or q hold
+ * NaN) and its scalars but alpha are left alone.  The sums are float64 sums of products of the float32 values, taken per workgroup in
+ * an order that depends on the in-sample index alone and added in a fixed order by the sample's last workgroup: a sample's scalars are
+ * reproducible run to run and do not depend on the batch it is solved in, on its place in it or on which samples are active.
+ * workspace: dn_poisson_cg_workspace_bytes(n, batch) bytes, 64-byte aligned, zero-filled ONCE before its first use; every launch leaves
+ * it ready for the next.  One workspace per concurrently used stream.  DIRECTION needs none.
+ * DN_E_BADARG for NULL args, an unknown phase, n < 1, batch outside 1..65535, a NULL or misaligned array the phase uses (x: UPDATE; r,
+ * dinv: all but DOT; q: all but DIRECTION; p, state: all), negative or NaN tol / atol, and a missing or too small workspace;
+ * DN_E_UNSUPPORTED for n >= 2^30.  Nothing is launched then. */
+enum { DN_CG_INIT = 0, DN_CG_DOT = 1, DN_CG_UPDATE = 2, DN_CG_DIRECTION = 3 };
+enum { DN_CG_BREAKDOWN = 1 };
+typedef struct dn_cg_state {
+    double rz, rr, rr0, pq;
+    float alpha, beta;
+    int32_t active, iterations, flags;
+    int32_t reserved[3];
+} dn_cg_state;
+typedef struct dn_poisson_cg_args {
+    int32_t phase;         /* DN_CG_*                                                   */
+    int32_t batch;
+    int64_t n;             /* nodes of one sample                                       */
+    float *x;              /* (B, n) the iterate                                        */
+    float *r;              /* (B, n) the residual of the recurrence                     */
+    float *p;              /* (B, n) the search direction                               */
+    const float *q;        /* (B, n) the operator's output: Z K p (INIT: Z (K x0~ - F f)) */
+    const float *dinv;     /* (B, n) or (1, n) with dinv_batched = 0                    */
+    int32_t dinv_batched;
+    float tol, atol;
+    dn_cg_state *state;    /* (B)                                                       */
+    void *workspace;
+    int64_t workspace_bytes;
+} dn_poisson_cg_args;
+int64_t dn_poisson_cg_workspace_bytes(int64_t n, int32_t batch);
+int dn_poisson_cg(const dn_poisson_cg_args *args, void *stream);
+
 /* ---- fused 2-D finite-difference Poisson residual, its sums of squares and its gradient ------------------------------------
  * Replaces the loss bodies of the three DiffNetFDM scripts of the reference under examples/poisson/single_instance/:
  * 12_fdm_mms.py:76-118, 12_klsum_fdm.py:69-111 and 12_klsum_fdm_nbc.py:69-158 -- the two Dirichlet substitutions, six valid 3x3
