@@ -58,6 +58,15 @@ __device__ __forceinline__ void block_sum2(double& a, double& b, double* scratch
     a = ra; b = rb;
 }
 
+// XCD-aware decode of a 1-D grid: logical index of workgroup `lid` of `nwg`.  Workgroups are dealt round-robin to the 8 XCDs, each with its
+// own L2.  In-plane neighbours share node rows and z-neighbours one plane, so every XCD gets a contiguous range of the logical order (chunk
+// fastest, then tile, strip, sample): the halo of a tile is then read from HBM once instead of once per XCD.  The remap is a bijection for
+// any grid size.
+__device__ __forceinline__ unsigned xcd_remap(unsigned lid, unsigned nwg) {
+    const unsigned xcd = lid & 7u, idx = lid >> 3, base = nwg >> 3, rem = nwg & 7u;
+    return xcd * base + min(xcd, rem) + idx;
+}
+
 template <int N>
 struct VecT;
 template <>

@@ -121,14 +121,7 @@ __global__ void __launch_bounds__(256, ek3_waves(NGP, MASK, BCF, FK, VJP)) eikon
     const int TX = (int)blockDim.x, TY = (int)blockDim.y;
     const int tx = (int)threadIdx.x, ty = (int)threadIdx.y;
     const int tid = ty * TX + tx;
-    // XCD-aware decode of the 1-D grid (workgroups are dealt round-robin to the 8 XCDs, each with its own L2): every XCD gets a
-    // contiguous range of the logical order chunk, tile, strip, sample, so that neighbours share their halo in one L2.  A bijection
-    // for any grid size.
-    unsigned lid = blockIdx.x;
-    {
-        const unsigned nwg = gridDim.x, xcd = lid & 7u, idx = lid >> 3, base = nwg >> 3, rem = nwg & 7u;
-        lid = xcd * base + min(xcd, rem) + idx;
-    }
+    unsigned lid = xcd_remap(blockIdx.x, gridDim.x);      // logical order chunk, tile, strip, sample: neighbours share their halo in one L2
     const int chunk = (int)(lid % (unsigned)p.chunks_x);
     lid /= (unsigned)p.chunks_x;
     const int tile = (int)(lid % (unsigned)p.tiles_y);

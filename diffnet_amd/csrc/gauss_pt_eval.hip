@@ -250,12 +250,9 @@ __global__ void __launch_bounds__(256) gpe_bwd_tiled_kernel(const float* __restr
     extern __shared__ float contrib[];                                          // [NBT][TZ][TY][TX]
     const int tx = SMALL ? (int)(threadIdx.x & 7) : (int)(threadIdx.x & 31), ty = SMALL ? (int)((threadIdx.x >> 3) & 7) : (int)(threadIdx.x >> 5);       // 32 x 8 threads (small: 8 x 8 x 4)
     const int tzs = (int)(threadIdx.x >> 6);                                    // small tiles: the thread's first element plane
-    unsigned t = blockIdx.x;
-    {   // XCD-aware decode: x-neighbouring tiles share cache lines of every element row (rows are not line-aligned); a contiguous range of
-        // the logical tile order per XCD lets them meet in one L2
-        const unsigned nwg = gridDim.x, xcd = t & 7u, idx = t >> 3, base = nwg >> 3, rem = nwg & 7u;
-        t = xcd * base + min(xcd, rem) + idx;
-    }
+    // XCD-aware decode: x-neighbouring tiles share cache lines of every element row (rows are not line-aligned); a contiguous range of
+    // the logical tile order per XCD lets them meet in one L2
+    unsigned t = xcd_remap(blockIdx.x, gridDim.x);
     const int tix = (int)(t % (unsigned)tiles_x); t /= (unsigned)tiles_x;
     const int tiy = (int)(t % (unsigned)tiles_y); t /= (unsigned)tiles_y;
     const int tiz = (int)(t % (unsigned)tiles_z);
@@ -362,12 +359,9 @@ __global__ void __launch_bounds__(256) gpe_bwd_march3d_q1_kernel(const float* __
                                                                   float* __restrict__ gin, const GpeGeom g, const int chunks_x,
                                                                   const int tiles_y, const int strips_z, const int R) {
     const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * 16 + tx;
-    unsigned lid = blockIdx.x;
-    {   // XCD-aware decode (workgroups are dealt round-robin to the 8 XCDs): every XCD gets a contiguous range of the logical order, so
-        // x-neighbouring tiles -- which share every 128-byte line of a 64-byte tile row -- meet in one L2
-        const unsigned nwg = gridDim.x, xcd = lid & 7u, idx = lid >> 3, base = nwg >> 3, rem = nwg & 7u;
-        lid = xcd * base + min(xcd, rem) + idx;
-    }
+    // XCD-aware decode: every XCD gets a contiguous range of the logical order, so x-neighbouring tiles -- which share every 128-byte line of
+    // a 64-byte tile row -- meet in one L2
+    unsigned lid = xcd_remap(blockIdx.x, gridDim.x);
     const int chunk = (int)(lid % (unsigned)chunks_x); lid /= (unsigned)chunks_x;
     const int tile = (int)(lid % (unsigned)tiles_y); lid /= (unsigned)tiles_y;
     const int strip = (int)(lid % (unsigned)strips_z), b = (int)(lid / (unsigned)strips_z);

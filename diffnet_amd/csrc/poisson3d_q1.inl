@@ -1,25 +1,17 @@
 // 3-D Q1 fused Poisson kernel, fully sum-factorised marching form.  Included by
 // poisson3d_q1_g{2,3,4}.hip with DN_NGP defined.
 //
-// grid = (chunks_x * tiles_y, strips_z, B), block = (TX, TY).  Thread (tx, ty) owns E consecutive elements of
-// element row ey and marches over element planes.  Carried per element: the in-plane stage of the lower node plane
+// grid = chunks_x * tiles_y * strips_z * B workgroups (strip3d_decode), block = (TX, TY).  Thread (tx, ty) owns one element of element
+// row ey (poisson3d_q1n2_kernel: two) and marches over element planes.  Carried per element: the in-plane stage of the lower node plane
 // (VU/VX/VY/VN/VF at the in-plane Gauss points) and the cotangents of that plane's stage values from the layer
 // below.  Per layer: load the two node rows of the new plane, x- and y-stage them, the O(NGP^2) layer arithmetic
-// (q1_layer_3d), then ONE in-plane transpose (y then x) per finished plane; contributions to nodes shared with the
+// (q1_layer_3d_w), then ONE in-plane transpose (y then x) per finished plane; contributions to nodes shared with the
 // neighbouring threads (right, up, up-right) go through a double-buffered LDS slot, one LDS-only barrier per layer.
 #include <cstdlib>
 
-#include "poisson_common.h"
+#include "poisson3d_q1_common.h"
 
 namespace dn {
-
-enum : int { FL3_NU = 1, FL3_F = 2, FL3_FGP = 4, FL3_BC = 8, FL3_BC_U8C = 16, FL3_BC_ONE = 32, FL3_E1G = 64, FL3_BC_F32 = 128, FL3_LOAD = 256, FL3_BOX = 512 };   // FL3_BOX (two-element node-owner form): at least one condition is given as faces of the domain box (DN_MASK_BOX): no array, no load   // FL3_LOAD (with FL3_F, two-element node-owner form): `f` holds the ASSEMBLED load vector b_a = sum_e sum_g W_g N_a f_g (dn_poisson_args.f_is_load) -- one FMA per node instead of the element's forcing arithmetic   // FL3_BC_F32 (node-owner form, with FL3_BC_U8C): the constant-value masks are fp32 images (> 0.5), the reference's format   // FL3_BC_U8C: uint8 masks with constant values only; FL3_BC_ONE (node-owner form): exactly one of them
-
-template <int NGP, int E>
-struct PlaneState3D {
-    float VU[E][NGP][NGP], VX[E][NGP], VY[E][NGP], VN[E][NGP][NGP], VF[E][NGP][NGP];
-    float keep[E];
-};
 
 // pure 1-D weight of Gauss point g (1 at compile time for the unit-weight rule)
 #define T_W(T, g, UW) ((UW) ? 1.f : (T).w[g])
@@ -33,12 +25,12 @@ struct PlaneState3D {
 //   * UW (exact 2-point rule, all weights 1): every weight multiplication vanishes at compile time;
 //   * every global access is SGPR base + 32-bit byte offset (ld_at / st_at): no 64-bit VALU address arithmetic.
 // =============================================================================================================
-template <int NGP, int E>
+template <int NGP>
 struct PlaneW {
-    float VU[E][NGP][NGP], VX[E][NGP], VY[E][NGP];
-    float VN[E][NGP][NGP];                            // weighted nu at the in-plane Gauss points
-    float VF[E][NGP][NGP];                            // weighted f
-    float keep[E];
+    float VU[NGP][NGP], VX[NGP], VY[NGP];
+    float VN[NGP][NGP];                               // weighted nu at the in-plane Gauss points
+    float VF[NGP][NGP];                               // weighted f
+    float keep;                                       // 0 where the thread's own node is a Dirichlet node
 };
 
 // in-plane stage of u for one element: nodal values r0[e], r0[e+1] (row ey) and r1[e], r1[e+1] (row ey + 1).
@@ -83,43 +75,21 @@ __device__ __forceinline__ void stage_w3(const ElemTab& T, V a0, V a1, V b0, V b
 struct __attribute__((packed, aligned(4))) F2U { float a, b; };
 struct __attribute__((packed, aligned(1))) B2U { uint8_t a, b; };
 
-// lane l <- lane l - 1 inside each row of 16 lanes, 0 for the first lane.  NOT a DPP move: on gfx950 every DPP / SDWA / v_readlane
-// instruction costs a SIMD ~33 cycles (about 14 plain VALU instructions) as soon as two or more waves share it, while a
-// ds_bpermute_b32 / ds_swizzle_b32 costs ~3 (tools/micro/valu_mem.hip, profiles/r2_valu_mem.txt).  `from` is the byte address of the
-// source lane ((lane - 1) & 63) * 4, `nf` is 0 for the first lane of a row and 1 elsewhere.
-__device__ __forceinline__ float lane_from_left(float v, int from, float nf) {
-    return nf * __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(from, __builtin_bit_cast(int, v)));
-}
-
-// Waves per SIMD asked of the compiler: 5 = the 16-wide one-element form with the next plane's loads in flight (<= 96 VGPRs), 6 = one element
-// per thread at 2 x 2 x 2 points (<= 80 VGPRs), 4 = the second-generation kernel (<= 128 VGPRs)
-template <int NGP, int E, bool VEC, int FL, bool UW, bool T16>
-__global__ void __launch_bounds__(256, NGP == 4 ? 2 : (T16 ? (NGP == 2 ? ((FL & (FL3_BC | FL3_FGP)) ? 4 : 5) : 3) : ((E == 1 && NGP == 2) ? ((FL & (FL3_BC | FL3_FGP)) ? 4 : 6) : 4))) poisson3d_q1w_kernel(const PoissonParams p, const int chunks_x, const int tiles_y,
+// One element per thread, tiles of any shape (generic) or exactly 16 threads wide (T16).
+// Waves per SIMD asked of the compiler: 5 = the 16-wide form with the next plane's loads in flight (<= 96 VGPRs), 6 = the generic form at
+// 2 x 2 x 2 points (<= 80 VGPRs), 4 = either with value fields, mixed masks or Gauss-point forcing (<= 128 VGPRs); 3 / 4 and 2 at 3 and 4 points
+template <int NGP, int FL, bool UW, bool T16>
+__global__ void __launch_bounds__(256, NGP == 4 ? 2 : (NGP == 3 ? (T16 ? 3 : 4) : ((FL & (FL3_BC | FL3_FGP)) ? 4 : (T16 ? 5 : 6)))) poisson3d_q1w_kernel(const PoissonParams p, const int chunks_x, const int tiles_y,
                                                                             const int strips_z) {
-    static_assert(!T16 || E == 1, "T16 is the one-element-per-thread form");
-    constexpr int NW = E;
     constexpr int G = NGP * NGP * NGP;
     constexpr bool HAS_NU = (FL & FL3_NU) != 0, HAS_F = (FL & FL3_F) != 0, FGP = (FL & FL3_FGP) != 0;
     constexpr bool BC_U8C = (FL & FL3_BC_U8C) != 0, BC_ANY = (FL & (FL3_BC | FL3_BC_U8C)) != 0;
     const int TX = blockDim.x, TY = blockDim.y;
     const int tx = threadIdx.x, ty = threadIdx.y;
     const int tid = ty * TX + tx;
-    // 1-D grid with an XCD-aware decode (cdna_hip_programming.md T1): workgroups are dealt round-robin to the 8 XCDs, each with its
-    // own L2.  In-plane neighbours share node rows and z-neighbours one plane, so every XCD gets a contiguous range of the logical
-    // order (chunk fastest, then tile, strip, sample): the halo of a tile is then read from HBM once instead of once per XCD.  The
-    // remap is a bijection for any grid size.
-    unsigned lid = blockIdx.x;
-    {
-        const unsigned nwg = gridDim.x, xcd = lid & 7u, idx = lid >> 3, base = nwg >> 3, rem = nwg & 7u;
-        lid = xcd * base + min(xcd, rem) + idx;
-    }
-    const int chunk = (int)(lid % (unsigned)chunks_x);
-    lid /= (unsigned)chunks_x;
-    const int tile = (int)(lid % (unsigned)tiles_y);
-    lid /= (unsigned)tiles_y;
-    const int strip = selected_strip(p, (int)(lid % (unsigned)strips_z)), b = (int)(lid / (unsigned)strips_z);
-    const int q = chunk * (TX - 1) + tx;
-    const int ex0 = q * E, x0 = ex0;
+    const Strip3D wg = strip3d_decode(xcd_remap(blockIdx.x, gridDim.x), chunks_x, tiles_y, strips_z, p.strip_sel, p.nstrips, p.rows_per_strip, p.nelz);
+    const int chunk = wg.chunk, tile = wg.tile, b = wg.b, ez_own = wg.ez_own, ez_begin = wg.ez_begin, ez_end = wg.ez_end;
+    const int x0 = chunk * (TX - 1) + tx;
     const int ey = tile * (TY - 1) + ty;
     const bool owner = !(chunk > 0 && tx == 0) && !(tile > 0 && ty == 0);
     const unsigned npl = (unsigned)(p.nx * p.ny);
@@ -128,36 +98,26 @@ __global__ void __launch_bounds__(256, NGP == 4 ? 2 : (T16 ? (NGP == 2 ? ((FL & 
     const unsigned eps = epl * (unsigned)p.nelz;
     const SampleBases sb = sample_bases(p, b, nps);
     const float* fgp = FGP ? p.fgp + (p.f_batched ? (int64_t)b * eps * G : 0) : nullptr;
-    const int R = p.rows_per_strip;
-    const int ez_own = strip * R;
-    const int ez_begin = ez_own > 0 ? ez_own - 1 : 0;
-    const int ez_end = min(ez_own + R, p.nelz);
-    const bool row_ok = ey < p.nely;
     const bool noderow_ok = ey < p.ny;
     // Elements beyond the mesh (ragged right / upper edge of the last chunk / tile) are computed like any other on clamped,
     // finite node values and their results multiplied by 0: no per-element branches, no exec-masked regions in the loop.
-    float okf[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) okf[e] = (row_ok && (ex0 + e < p.nelx)) ? 1.f : 0.f;
+    const float okf = (ey < p.nely && x0 < p.nelx) ? 1.f : 0.f;
 
-    __shared__ float xch[2][T16 ? 1 : NW + 2][256];
+    __shared__ float xch[2][T16 ? 1 : 3][256];      // hand-over slots: right, up, up-right (T16: up)
     __shared__ double red[2 * (256 / 64)];      // block_sum2: two sums per wave
     __shared__ int last_flag;
 
-    PlaneW<NGP, E> SA, SB;
-    float cU[E][NGP][NGP], cX[E][NGP], cY[E][NGP];
+    PlaneW<NGP> SA, SB;
+    float cU[NGP][NGP], cX[NGP], cY[NGP];
+    SA.keep = SB.keep = 1.f;
 #pragma unroll
-    for (int e = 0; e < E; ++e) {
-        SA.keep[e] = SB.keep[e] = 1.f;
+    for (int j = 0; j < NGP; ++j) {
+        cX[j] = cY[j] = 0.f;
 #pragma unroll
-        for (int j = 0; j < NGP; ++j) {
-            cX[e][j] = cY[e][j] = 0.f;
-#pragma unroll
-            for (int i = 0; i < NGP; ++i) {
-                cU[e][j][i] = 0.f;
-                SA.VN[e][j][i] = SB.VN[e][j][i] = T_W(p.T, j, UW) * T_W(p.T, i, UW);    // nu absent: the constant field 1
-                SA.VF[e][j][i] = SB.VF[e][j][i] = 0.f;
-            }
+        for (int i = 0; i < NGP; ++i) {
+            cU[j][i] = 0.f;
+            SA.VN[j][i] = SB.VN[j][i] = T_W(p.T, j, UW) * T_W(p.T, i, UW);    // nu absent: the constant field 1
+            SA.VF[j][i] = SB.VF[j][i] = 0.f;
         }
     }
 
@@ -171,24 +131,21 @@ __global__ void __launch_bounds__(256, NGP == 4 ? 2 : (T16 ? (NGP == 2 ? ((FL & 
     // applies the Dirichlet conditions and stages.  PF (T16 form): the loads of plane k + 2 are issued BEFORE the arithmetic of
     // layer k and consumed after it, so a wave does not sit on its memory latency once per layer (rocprofv3: 64 % of the wave
     // cycles were s_waitcnt / barrier waits without it); 14 more live VGPRs at one element per thread.
-    // uint8 masks with constant values: both mask slots are always loaded (see plane_issue)
-    const bool has_mask[2] = {sb.mask[0] != nullptr, sb.mask[1] != nullptr};
-    const uint8_t* mask8[2];
-    mask8[0] = reinterpret_cast<const uint8_t*>(has_mask[0] ? sb.mask[0] : sb.mask[1]);
-    mask8[1] = reinterpret_cast<const uint8_t*>(has_mask[1] ? sb.mask[1] : sb.mask[0]);
+    // uint8 masks with constant values: both mask slots are always loaded (mask_images)
+    const MaskImages mi = mask_images(sb.mask[0], sb.mask[1]);
     struct RawPlane {
-        float ru[2][NW + 1], rn[2][NW + 1], rf[2][NW + 1];
-        BcRaw<NW> braw[2];
-        uint8_t m8[2][2][NW + 1];
+        float ru[2][2], rn[2][2], rf[2][2];      // [node row][node column]
+        BcRaw<1> braw[2];
+        uint8_t m8[2][2][2];
     };
     auto plane_issue = [&](int zreq, RawPlane& W) {
         const unsigned zoff = (unsigned)min(zreq, p.nz - 1) * npl;
         const unsigned rowoff[2] = {zoff + row0, zoff + row1};
-        float (&ru)[2][NW + 1] = W.ru;
-        float (&rn)[2][NW + 1] = W.rn;
-        float (&rf)[2][NW + 1] = W.rf;
-        BcRaw<NW> (&braw)[2] = W.braw;
-        uint8_t (&m8)[2][2][NW + 1] = W.m8;
+        float (&ru)[2][2] = W.ru;
+        float (&rn)[2][2] = W.rn;
+        float (&rf)[2][2] = W.rf;
+        BcRaw<1> (&braw)[2] = W.braw;
+        uint8_t (&m8)[2][2][2] = W.m8;
 #pragma unroll
         for (int jb = 0; jb < 2; ++jb) {
             if constexpr (T16) {
@@ -201,72 +158,68 @@ __global__ void __launch_bounds__(256, NGP == 4 ? 2 : (T16 ? (NGP == 2 ? ((FL & 
                 if constexpr (HAS_NU) { const F2U t = ld_at<F2U>(sb.nu, o2); rn[jb][0] = t.a; rn[jb][1] = t.b; }
                 if constexpr (HAS_F) { const F2U t = ld_at<F2U>(sb.f, o2); rf[jb][0] = t.a; rf[jb][1] = t.b; }
                 if constexpr (BC_U8C) {
-                    // unconditional loads (an absent mask reads the other one and is ignored): a load inside a uniform branch makes
-                    // the compiler wait vmcnt(0) at the end of the branch, which serialises every load of the plane behind it
+                    // unconditional loads, no load inside a uniform branch (an absent mask reads the other one and is ignored: mask_images)
 #pragma unroll
                     for (int k = 0; k < 2; ++k) {
-                        const B2U t = ld_at<B2U>(mask8[k], o2);
+                        const B2U t = ld_at<B2U>(mi.m8[k], o2);
                         m8[jb][k][0] = t.a; m8[jb][k][1] = t.b;
                     }
                 } else if constexpr (BC_ANY) {
-                    bc_issue<NW, false>(p, sb, rowoff[jb], (int)x0c, braw[jb]);
+                    bc_issue<1, false>(p, sb, rowoff[jb], (int)x0c, braw[jb]);
                 }
             } else {
-                load_seg<NW, VEC>(sb.u, rowoff[jb], x0, p.nx, ru[jb]);
-                if constexpr (HAS_NU) load_seg<NW, VEC>(sb.nu, rowoff[jb], x0, p.nx, rn[jb]);
-                if constexpr (HAS_F) load_seg<NW, VEC>(sb.f, rowoff[jb], x0, p.nx, rf[jb]);
+                load_seg<1, false>(sb.u, rowoff[jb], x0, p.nx, ru[jb]);
+                if constexpr (HAS_NU) load_seg<1, false>(sb.nu, rowoff[jb], x0, p.nx, rn[jb]);
+                if constexpr (HAS_F) load_seg<1, false>(sb.f, rowoff[jb], x0, p.nx, rf[jb]);
                 if constexpr (BC_U8C) {
 #pragma unroll
-                    for (int k = 0; k < 2; ++k) load_seg<NW, VEC>(mask8[k], rowoff[jb], x0, p.nx, m8[jb][k]);
+                    for (int k = 0; k < 2; ++k) load_seg<1, false>(mi.m8[k], rowoff[jb], x0, p.nx, m8[jb][k]);
                 } else if constexpr (BC_ANY) {
-                    bc_issue<NW, VEC>(p, sb, rowoff[jb], x0, braw[jb]);
+                    bc_issue<1, false>(p, sb, rowoff[jb], x0, braw[jb]);
                 }
             }
         }
     };
-    auto plane_consume = [&](RawPlane& W, PlaneW<NGP, E>& S) {
-        float (&ru)[2][NW + 1] = W.ru;
-        float (&rn)[2][NW + 1] = W.rn;
-        float (&rf)[2][NW + 1] = W.rf;
-        BcRaw<NW> (&braw)[2] = W.braw;
-        uint8_t (&m8)[2][2][NW + 1] = W.m8;
-        float kall[NW + 1];                   // 0 on Dirichlet nodes of row ey (all NW + 1 loaded nodes)
+    auto plane_consume = [&](RawPlane& W, PlaneW<NGP>& S) {
+        float (&ru)[2][2] = W.ru;
+        float (&rn)[2][2] = W.rn;
+        float (&rf)[2][2] = W.rf;
+        BcRaw<1> (&braw)[2] = W.braw;
+        uint8_t (&m8)[2][2][2] = W.m8;
+        float kall[2] = {1.f, 1.f};           // 0 on Dirichlet nodes of row ey (both loaded nodes)
         if constexpr (BC_U8C) {
-#pragma unroll
-            for (int n = 0; n <= NW; ++n) kall[n] = 1.f;
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 const float val = p.bc[k].value;
 #pragma unroll
                 for (int jb = 0; jb < 2; ++jb)
 #pragma unroll
-                    for (int n = 0; n <= NW; ++n) {
-                        const bool set = has_mask[k] && m8[jb][k][n] != 0;
+                    for (int n = 0; n < 2; ++n) {
+                        const bool set = mi.has[k] && m8[jb][k][n] != 0;
                         ru[jb][n] = set ? val : ru[jb][n];
                         if (jb == 0) kall[n] = set ? 0.f : kall[n];
                     }
             }
         } else if constexpr (BC_ANY) {
-            float k1[NW + 1];
-            bc_apply_all<NW>(p, sb, braw[0], ru[0], kall);
-            bc_apply_all<NW>(p, sb, braw[1], ru[1], k1);
-        } else {
-#pragma unroll
-            for (int n = 0; n <= NW; ++n) kall[n] = 1.f;
+            float k1[2];
+            bc_apply_all<1>(p, sb, braw[0], ru[0], kall);
+            bc_apply_all<1>(p, sb, braw[1], ru[1], k1);
         }
         // T16: the thread of the last node column loads the pair (nx-2, nx-1); the node it owns is the second one
+        S.keep = (T16 && pair_shifted) ? kall[1] : kall[0];
+        // (A loop of one trip, on purpose: with the three calls written straight into the lambda the two 4-point generic kernels with nu and
+        // Gauss-point forcing spill 480 / 484 bytes per lane instead of 324 / 328 under ROCm 7.2's compiler (AMD clang 22.0.0git, roc-7.2.0) --
+        // profiles/poisson3d_refactor.txt.  Try the plain form again with a newer compiler.)
 #pragma unroll
-        for (int n = 0; n < NW; ++n) S.keep[n] = (T16 && pair_shifted) ? kall[n + 1] : kall[n];
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            stage_u3<NGP>(p.T, ru[0][e], ru[0][e + 1], ru[1][e], ru[1][e + 1], S.VU[e], S.VX[e], S.VY[e]);
-            if constexpr (HAS_NU) stage_w3<NGP, UW>(p.T, rn[0][e], rn[0][e + 1], rn[1][e], rn[1][e + 1], S.VN[e]);
-            if constexpr (HAS_F) stage_w3<NGP, UW>(p.T, rf[0][e], rf[0][e + 1], rf[1][e], rf[1][e + 1], S.VF[e]);
+        for (int e = 0; e < 1; ++e) {
+            stage_u3<NGP>(p.T, ru[0][e], ru[0][e + 1], ru[1][e], ru[1][e + 1], S.VU, S.VX, S.VY);
+            if constexpr (HAS_NU) stage_w3<NGP, UW>(p.T, rn[0][e], rn[0][e + 1], rn[1][e], rn[1][e + 1], S.VN);
+            if constexpr (HAS_F) stage_w3<NGP, UW>(p.T, rf[0][e], rf[0][e + 1], rf[1][e], rf[1][e + 1], S.VF);
         }
         __builtin_amdgcn_sched_barrier(0);
     };
 
-    auto plane_stage = [&](int zreq, PlaneW<NGP, E>& S) {
+    auto plane_stage = [&](int zreq, PlaneW<NGP>& S) {
         RawPlane W;
         plane_issue(zreq, W);
         plane_consume(W, S);
@@ -274,26 +227,6 @@ __global__ void __launch_bounds__(256, NGP == 4 ? 2 : (T16 ? (NGP == 2 ? ((FL & 
 
     float e1_acc = 0.f, e2_acc = 0.f, sq_acc = 0.f;
     int par = 0;
-
-    // adjoint of stage_u3: cotangents of one plane's stage values -> contributions to the element's 2 x 2 nodes
-    auto plane_transpose = [&](int e, const float (&tU)[NGP][NGP], const float (&tX)[NGP], const float (&tY)[NGP], float (&o)[2][NW + 1]) {
-        float s0 = 0.f, t0 = 0.f, s1 = 0.f, t1 = 0.f;
-#pragma unroll
-        for (int i = 0; i < NGP; ++i) {
-            float s = 0.f, t = 0.f;
-#pragma unroll
-            for (int j = 0; j < NGP; ++j) { s += tU[j][i]; t = fmaf(p.T.b[j][1], tU[j][i], t); }
-            const float c1 = t + tY[i], c0 = s - c1;
-            s0 += c0; t0 = fmaf(p.T.b[i][1], c0, t0);
-            s1 += c1; t1 = fmaf(p.T.b[i][1], c1, t1);
-        }
-        float sX = 0.f, d1 = 0.f;
-#pragma unroll
-        for (int j = 0; j < NGP; ++j) { sX += tX[j]; d1 = fmaf(p.T.b[j][1], tX[j], d1); }
-        const float g01 = t0 + (sX - d1), g11 = t1 + d1;
-        o[0][e + 1] = fmaf(okf[e], g01, o[0][e + 1]); o[0][e] = fmaf(okf[e], s0 - g01, o[0][e]);
-        o[1][e + 1] = fmaf(okf[e], g11, o[1][e + 1]); o[1][e] = fmaf(okf[e], s1 - g11, o[1][e]);
-    };
 
     const unsigned out_row = (unsigned)ey * (unsigned)p.nx;
     const int from_left = (int)(((unsigned)tid - 1u) & 63u) << 2;      // T16 hand-over: source lane of lane_from_left
@@ -305,7 +238,7 @@ __global__ void __launch_bounds__(256, NGP == 4 ? 2 : (T16 ? (NGP == 2 ? ((FL & 
         if (pend_st) st_at<float>(sb.out, pend_off, pend_v);
         pend_st = false;
     };
-    auto emit_plane = [&](const float (&o)[2][NW + 1], const float (&keep)[NW], int z, bool owned_plane) {
+    auto emit_plane = [&](const float (&o)[2][2], float keep, int z, bool owned_plane) {
         if constexpr (T16) {
             const float left = lane_from_left(o[0][1], from_left, nfirst);          // right-hand contribution of the thread to the left
             xch[par][0][tid] = o[1][0] + lane_from_left(o[1][1], from_left, nfirst);        // up slot with the up-right part of the left thread folded in
@@ -314,64 +247,48 @@ __global__ void __launch_bounds__(256, NGP == 4 ? 2 : (T16 ? (NGP == 2 ? ((FL & 
             // store issued here would be younger than those loads' consumer wait, which the compiler turns into vmcnt(0)
             float t = o[0][0] + left;
             if (ty > 0) t += xch[par][0][tid - 16];
-            t *= keep[0];
+            t *= keep;
             const bool st = owned_plane && owner && noderow_ok;
             sq_acc = st ? fmaf(t, t, sq_acc) : sq_acc;
             pend_v = t * p.out_scale;
             pend_off = (unsigned)z * npl + out_row + (unsigned)x0;
             pend_st = st && sb.out != nullptr && x0 < p.nx;
-            par ^= 1;
-            return;
-        }
-        xch[par][0][tid] = o[0][NW];
-#pragma unroll
-        for (int n = 0; n < NW; ++n) xch[par][(T16 ? 0 : 1 + n)][tid] = o[1][n];
-        xch[par][T16 ? 0 : NW + 1][tid] = o[1][NW];
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (owned_plane && owner && noderow_ok) {
-            float v[NW];
-#pragma unroll
-            for (int n = 0; n < NW; ++n) {
-                float t = o[0][n];
-                if (ty > 0) t += xch[par][T16 ? 0 : 1 + n][tid - TX];
-                if (n == 0) {
-                    if (tx > 0) t += xch[par][0][tid - 1];
-                    if (tx > 0 && ty > 0) t += xch[par][T16 ? 0 : NW + 1][tid - TX - 1];
-                }
-                t *= keep[n];
+        } else {
+            xch[par][0][tid] = o[0][1];
+            xch[par][1][tid] = o[1][0];
+            xch[par][2][tid] = o[1][1];
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            if (owned_plane && owner && noderow_ok) {
+                float t = o[0][0];
+                if (ty > 0) t += xch[par][1][tid - TX];
+                if (tx > 0) t += xch[par][0][tid - 1];
+                if (tx > 0 && ty > 0) t += xch[par][2][tid - TX - 1];
+                t *= keep;
                 sq_acc = fmaf(t, t, sq_acc);
-                v[n] = t * p.out_scale;
+                const float v[1] = {t * p.out_scale};
+                if (sb.out) store_seg<1, false>(sb.out, (unsigned)z * npl + out_row, x0, p.nx, v);
             }
-            if (sb.out) store_seg<NW, VEC>(sb.out, (unsigned)z * npl + out_row, x0, p.nx, v);
         }
         par ^= 1;
     };
 
-    auto layer = [&](int ez, const PlaneW<NGP, E>& L, const PlaneW<NGP, E>& U) {
+    auto layer = [&](int ez, const PlaneW<NGP>& L, const PlaneW<NGP>& U) {
         const bool own_layer = ez >= ez_own;
         const float cnt = (own_layer && owner) ? 1.f : 0.f;
-        float o[2][NW + 1], le1 = 0.f, le2 = 0.f;
+        float o[2][2] = {{0.f, 0.f}, {0.f, 0.f}}, fg[G];
+        if constexpr (FGP) {
+            const unsigned eo = (unsigned)ez * epl + (unsigned)min(ey, p.nely - 1) * (unsigned)p.nelx + (unsigned)min(x0, p.nelx - 1);
 #pragma unroll
-        for (int n = 0; n <= NW; ++n) o[0][n] = o[1][n] = 0.f;
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-            float fg[G];
-            if constexpr (FGP) {
-                const unsigned eo = (unsigned)ez * epl + (unsigned)min(ey, p.nely - 1) * (unsigned)p.nelx + (unsigned)min(ex0 + e, p.nelx - 1);
-#pragma unroll
-                for (int gi = 0; gi < G; ++gi) fg[gi] = ld_at<float>(fgp, eo + (unsigned)gi * eps);
-            }
-            float tU[NGP][NGP], tX[NGP], tY[NGP], e1, e2;
-            q1_layer_3d_w<NGP, FGP, HAS_F, UW>(p.T, L.VU[e], U.VU[e], L.VX[e], U.VX[e], L.VY[e], U.VY[e], L.VN[e], U.VN[e], L.VF[e], U.VF[e],
-                                               fg, cU[e], cX[e], cY[e], tU, tX, tY, e1, e2);
-            // pin the element's energy sums here: left alone, the compiler sinks their fused multiply-adds to the end of the loop
-            // body and keeps every Gauss-point factor alive until then (232 VGPRs instead of ~110)
-            asm volatile("" : "+v"(e1), "+v"(e2));
-            le1 = fmaf(okf[e], e1, le1);
-            le2 = fmaf(okf[e], e2, le2);
-            plane_transpose(e, tU, tX, tY, o);
-            __builtin_amdgcn_sched_barrier(0);      // keep the element streams apart: interleaving them doubles the live set
+            for (int gi = 0; gi < G; ++gi) fg[gi] = ld_at<float>(fgp, eo + (unsigned)gi * eps);
         }
+        float tU[NGP][NGP], tX[NGP], tY[NGP], e1, e2;
+        q1_layer_3d_w<NGP, FGP, HAS_F, UW>(p.T, L.VU, U.VU, L.VX, U.VX, L.VY, U.VY, L.VN, U.VN, L.VF, U.VF, fg, cU, cX, cY, tU, tX, tY, e1, e2);
+        // pin the element's energy sums here: left alone, the compiler sinks their fused multiply-adds to the end of the layer
+        // and keeps every Gauss-point factor alive until then (232 VGPRs instead of ~110)
+        asm volatile("" : "+v"(e1), "+v"(e2));
+        const float le1 = fmaf(okf, e1, 0.f), le2 = fmaf(okf, e2, 0.f);
+        plane_transpose<NGP, float, true>(p.T.b, okf, tU, tX, tY, o);
+        __builtin_amdgcn_sched_barrier(0);      // the element arithmetic stays ahead of the hand-over (the kernels were measured with this fence)
         e1_acc = fmaf(cnt, le1, e1_acc);
         e2_acc = fmaf(cnt, le2, e2_acc);
         emit_plane(o, L.keep, ez, own_layer);
@@ -418,11 +335,8 @@ __global__ void __launch_bounds__(256, NGP == 4 ? 2 : (T16 ? (NGP == 2 ? ((FL & 
         }
     }
     if (ez_end == p.nelz) {       // the last strip owns the top boundary plane: only the layer below contributes
-        float o[2][NW + 1];
-#pragma unroll
-        for (int n = 0; n <= NW; ++n) o[0][n] = o[1][n] = 0.f;
-#pragma unroll
-        for (int e = 0; e < E; ++e) plane_transpose(e, cU[e], cX[e], cY[e], o);
+        float o[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
+        plane_transpose<NGP, float, true>(p.T.b, okf, cU, cX, cY, o);
         emit_plane(o, SA.keep, p.nz - 1, true);
         if constexpr (T16) flush_store();
     }
@@ -451,29 +365,16 @@ __global__ void __launch_bounds__(256, NGP == 2 ? 5 : (NGP == 3 ? 3 : 2)) poisso
     // sum_a u_a out_a = alpha * sum W nu |grad u|^2 - beta * sum W f u  (u = sum_a u_a N_a), one FMA per node instead of 15 per element
     constexpr bool E1G = (FL & FL3_E1G) != 0;     // uint8 mask arrays read per node (compile-time: no load in a uniform branch)
     static_assert((FL & (FL3_FGP | FL3_BC)) == 0, "node-owner form: nodal forcing, uint8 constant-value conditions");
-    constexpr int E = 1, NW = 1;
     const int tx = threadIdx.x, ty = threadIdx.y;
     const int tid = ty * 16 + tx;
-    unsigned lid = blockIdx.x;                    // XCD-aware decode, see poisson3d_q1w_kernel
-    {
-        const unsigned nwg = gridDim.x, xcd = lid & 7u, idx = lid >> 3, base = nwg >> 3, rem = nwg & 7u;
-        lid = xcd * base + min(xcd, rem) + idx;
-    }
-    const int chunk = (int)(lid % (unsigned)chunks_x);
-    lid /= (unsigned)chunks_x;
-    const int tile = (int)(lid % (unsigned)tiles_y);
-    lid /= (unsigned)tiles_y;
-    const int strip = selected_strip(p, (int)(lid % (unsigned)strips_z)), b = (int)(lid / (unsigned)strips_z);
+    const Strip3D wg = strip3d_decode(xcd_remap(blockIdx.x, gridDim.x), chunks_x, tiles_y, strips_z, p.strip_sel, p.nstrips, p.rows_per_strip, p.nelz);
+    const int chunk = wg.chunk, tile = wg.tile, b = wg.b, ez_own = wg.ez_own, ez_begin = wg.ez_begin, ez_end = wg.ez_end;
     const int nx0 = chunk * 15, ny0 = tile * 15;               // first node of the tile
     const int x0 = nx0 + tx, ey = ny0 + ty;                    // the thread's node == lower-left node of its element
     const bool owner = !(chunk > 0 && tx == 0) && !(tile > 0 && ty == 0);
     const unsigned npl = (unsigned)(p.nx * p.ny);
     const int64_t nps = (int64_t)npl * p.nz;
     const SampleBases sb = sample_bases(p, b, nps);
-    const int R = p.rows_per_strip;
-    const int ez_own = strip * R;
-    const int ez_begin = ez_own > 0 ? ez_own - 1 : 0;
-    const int ez_end = min(ez_own + R, p.nelz);
     const bool noderow_ok = ey < p.ny;
     const float okf = (ey < p.nely && x0 < p.nelx) ? 1.f : 0.f;         // elements beyond the mesh: computed on clamped data, scaled by 0
 
@@ -499,14 +400,9 @@ __global__ void __launch_bounds__(256, NGP == 2 ? 5 : (NGP == 3 ? 3 : 2)) poisso
     const int own_rec = ty * 17 + tx, halo_rec = hrow * 17 + hcol;
     const float* const halo_src = (hgrp == 1 && HAS_NU) ? sb.nu : ((hgrp == 2 && HAS_F) ? sb.f : sb.u);       // per lane
 
-    const bool has_mask[2] = {sb.mask[0] != nullptr, sb.mask[1] != nullptr};
-    const uint8_t* mask8[2];
-    mask8[0] = reinterpret_cast<const uint8_t*>(has_mask[0] ? sb.mask[0] : sb.mask[1]);      // an absent condition re-reads the other one and is
-    mask8[1] = reinterpret_cast<const uint8_t*>(has_mask[1] ? sb.mask[1] : sb.mask[0]);      // ignored: no load inside a wave-uniform branch
-    const float* mask32[2] = {reinterpret_cast<const float*>(mask8[0]), reinterpret_cast<const float*>(mask8[1])};
-
-    // with one condition, slot 0 of mask8 / bcval is the one that is present
-    const float bcval[2] = {NMASK == 1 ? (has_mask[0] ? p.bc[0].value : p.bc[1].value) : p.bc[0].value, p.bc[1].value};
+    const MaskImages mi = mask_images(sb.mask[0], sb.mask[1]);
+    // with one condition, slot 0 of mi.m8 / bcval is the one that is present
+    const float bcval[2] = {NMASK == 1 ? (mi.has[0] ? p.bc[0].value : p.bc[1].value) : p.bc[0].value, p.bc[1].value};
     struct RawNodes { float u, n, f, h; uint8_t m[2][2]; float mf[2][2]; };       // own node: u, n, f; halo node: h (u, nu or f by lane group); masks [0] own, [1] halo
     auto plane_request = [&](int zreq, RawNodes& W) {
         const unsigned zoff = (unsigned)min(zreq, p.nz - 1) * npl;
@@ -520,8 +416,8 @@ __global__ void __launch_bounds__(256, NGP == 2 ? 5 : (NGP == 3 ? 3 : 2)) poisso
             if constexpr (BC_U8C) {
 #pragma unroll
                 for (int k = 0; k < NMASK; ++k) {
-                    if constexpr (MASK_F32) W.mf[h][k] = ld_at<float>(mask32[k], o[h]);
-                    else W.m[h][k] = ld_at<uint8_t>(mask8[k], o[h]);
+                    if constexpr (MASK_F32) W.mf[h][k] = ld_at<float>(mi.m32[k], o[h]);
+                    else W.m[h][k] = ld_at<uint8_t>(mi.m8[k], o[h]);
                 }
             }
         }
@@ -531,10 +427,10 @@ __global__ void __launch_bounds__(256, NGP == 2 ? 5 : (NGP == 3 ? 3 : 2)) poisso
         if constexpr (BC_U8C) {
 #pragma unroll
             for (int k = 0; k < NMASK; ++k) {
-                const bool set = (NMASK == 1 || has_mask[k]) && (MASK_F32 ? W.mf[0][k] > 0.5f : W.m[0][k] != 0);
+                const bool set = (NMASK == 1 || mi.has[k]) && (MASK_F32 ? W.mf[0][k] > 0.5f : W.m[0][k] != 0);
                 uu = set ? bcval[k] : uu;
                 keep = set ? 0.f : keep;
-                const bool seth = hgrp == 0 && (NMASK == 1 || has_mask[k]) && (MASK_F32 ? W.mf[1][k] > 0.5f : W.m[1][k] != 0);
+                const bool seth = hgrp == 0 && (NMASK == 1 || mi.has[k]) && (MASK_F32 ? W.mf[1][k] > 0.5f : W.m[1][k] != 0);
                 hv = seth ? bcval[k] : hv;
             }
         }
@@ -542,54 +438,36 @@ __global__ void __launch_bounds__(256, NGP == 2 ? 5 : (NGP == 3 ? 3 : 2)) poisso
         // (the .w of a halo record is never read; absent nu / f keep the 1 / 0 the prologue put there)
         if (halo_lane) reinterpret_cast<float*>(&rec[zpl & 1][halo_rec])[hgrp] = hv;
     };
-    float keep_lo = 1.f, keep_up = 1.f;           // keep of the own node in the lower / upper plane of the current layer
-    float u_lo = 0.f, u_up = 0.f, ut_acc = 0.f;   // E1G: the own node's value after the Dirichlet conditions, sum of u * out over the owned nodes
-    auto plane_gather = [&](int zpl, PlaneW<NGP, 1>& S, float& keep, float& uown) {
+    float ut_acc = 0.f;                           // E1G: sum of u * out over the owned nodes
+    struct PlaneN : PlaneW<NGP> { float uown; };      // uown: the own node's value after the Dirichlet conditions (E1G)
+    auto plane_gather = [&](int zpl, PlaneN& S) {
         const float4* t = &rec[zpl & 1][own_rec];
         const float4 a0 = t[0], a1 = t[1], b0 = t[17], b1 = t[18];
-        keep = a0.w;
-        uown = a0.x;
-        stage_u3<NGP>(TV, a0.x, a1.x, b0.x, b1.x, S.VU[0], S.VX[0], S.VY[0]);
-        if constexpr (HAS_NU) stage_w3<NGP, UW>(TV, a0.y, a1.y, b0.y, b1.y, S.VN[0]);
-        if constexpr (HAS_F) stage_w3<NGP, UW>(TV, a0.z, a1.z, b0.z, b1.z, S.VF[0]);
+        S.keep = a0.w;
+        S.uown = a0.x;
+        stage_u3<NGP>(TV, a0.x, a1.x, b0.x, b1.x, S.VU, S.VX, S.VY);
+        if constexpr (HAS_NU) stage_w3<NGP, UW>(TV, a0.y, a1.y, b0.y, b1.y, S.VN);
+        if constexpr (HAS_F) stage_w3<NGP, UW>(TV, a0.z, a1.z, b0.z, b1.z, S.VF);
         __builtin_amdgcn_sched_barrier(0);
     };
 
-    PlaneW<NGP, 1> SA, SB;
+    PlaneN SA, SB;
     float cU[NGP][NGP], cX[NGP], cY[NGP];
+    SA.keep = SB.keep = 1.f;
+    SA.uown = SB.uown = 0.f;
 #pragma unroll
     for (int j = 0; j < NGP; ++j) {
         cX[j] = cY[j] = 0.f;
 #pragma unroll
         for (int i = 0; i < NGP; ++i) {
             cU[j][i] = 0.f;
-            SA.VN[0][j][i] = SB.VN[0][j][i] = T_W(TV, j, UW) * T_W(TV, i, UW);    // nu absent: the constant field 1
-            SA.VF[0][j][i] = SB.VF[0][j][i] = 0.f;
+            SA.VN[j][i] = SB.VN[j][i] = T_W(TV, j, UW) * T_W(TV, i, UW);    // nu absent: the constant field 1
+            SA.VF[j][i] = SB.VF[j][i] = 0.f;
         }
     }
 
     float e1_acc = 0.f, e2_acc = 0.f, sq_acc = 0.f;
     int par = 0;
-
-    // adjoint of stage_u3: cotangents of one plane's stage values -> contributions to the element's 2 x 2 nodes
-    auto plane_transpose = [&](const float (&tU)[NGP][NGP], const float (&tX)[NGP], const float (&tY)[NGP], float (&o)[2][2]) {
-        float s0 = 0.f, t0 = 0.f, s1 = 0.f, t1 = 0.f;
-#pragma unroll
-        for (int i = 0; i < NGP; ++i) {
-            float sv = 0.f, t = 0.f;
-#pragma unroll
-            for (int j = 0; j < NGP; ++j) { sv += tU[j][i]; t = fmaf(TV.b[j][1], tU[j][i], t); }
-            const float c1 = t + tY[i], c0 = sv - c1;
-            s0 += c0; t0 = fmaf(TV.b[i][1], c0, t0);
-            s1 += c1; t1 = fmaf(TV.b[i][1], c1, t1);
-        }
-        float sX = 0.f, d1 = 0.f;
-#pragma unroll
-        for (int j = 0; j < NGP; ++j) { sX += tX[j]; d1 = fmaf(TV.b[j][1], tX[j], d1); }
-        const float g01 = t0 + (sX - d1), g11 = t1 + d1;
-        o[0][1] = okf * g01; o[0][0] = okf * (s0 - g01);
-        o[1][1] = okf * g11; o[1][0] = okf * (s1 - g11);
-    };
 
     const unsigned out_row = (unsigned)ey * (unsigned)p.nx;
     const int from_left = (int)(((unsigned)tid - 1u) & 63u) << 2;
@@ -618,13 +496,12 @@ __global__ void __launch_bounds__(256, NGP == 2 ? 5 : (NGP == 3 ? 3 : 2)) poisso
         pend_st = st && sb.out != nullptr && x0 < p.nx;
         par ^= 1;
     };
-    auto layer = [&](int ez, const PlaneW<NGP, 1>& L, const PlaneW<NGP, 1>& U, float keep, float uown, const RawNodes* W) {
+    auto layer = [&](int ez, const PlaneN& L, const PlaneN& U, const RawNodes* W) {
         const bool own_layer = ez >= ez_own;
         const float cnt = (own_layer && owner) ? 1.f : 0.f;
         float o[2][2], fg[1] = {0.f};
         float tU[NGP][NGP], tX[NGP], tY[NGP], e1, e2;
-        q1_layer_3d_w<NGP, false, HAS_F, UW>(TV, L.VU[0], U.VU[0], L.VX[0], U.VX[0], L.VY[0], U.VY[0], L.VN[0], U.VN[0], L.VF[0], U.VF[0],
-                                             fg, cU, cX, cY, tU, tX, tY, e1, e2);
+        q1_layer_3d_w<NGP, false, HAS_F, UW>(TV, L.VU, U.VU, L.VX, U.VX, L.VY, U.VY, L.VN, U.VN, L.VF, U.VF, fg, cU, cX, cY, tU, tX, tY, e1, e2);
         if constexpr (E1G) {
             asm volatile("" : "+v"(e2));
         } else {
@@ -632,56 +509,22 @@ __global__ void __launch_bounds__(256, NGP == 2 ? 5 : (NGP == 3 ? 3 : 2)) poisso
             e1_acc = fmaf(cnt * okf, e1, e1_acc);
         }
         e2_acc = fmaf(cnt * okf, e2, e2_acc);
-        plane_transpose(tU, tX, tY, o);
+        plane_transpose<NGP, float>(TV.b, okf, tU, tX, tY, o);
         __builtin_amdgcn_sched_barrier(0);
-        emit_plane(o, keep, uown, ez, own_layer, W, ez + 2);
+        emit_plane(o, L.keep, L.uown, ez, own_layer, W, ez + 2);
+    };
+    auto top_plane = [&](bool odd) {
+        float o[2][2];
+        plane_transpose<NGP, float>(TV.b, okf, cU, cX, cY, o);
+        emit_plane(o, odd ? SB.keep : SA.keep, odd ? SB.uown : SA.uown, p.nz - 1, true, nullptr, 0);
     };
 
-    // prologue: planes ez_begin and ez_begin + 1 into LDS (both requested before the first is consumed: one memory latency and one barrier
-    // instead of two -- a workgroup of a 128^3 launch marches only ~10 layers), the lower one staged
     if (lane < 9 && wave * 9 + lane < 33) {          // the constant components of the halo records (both parities): nu = 1, f = 0, keep = 1
         rec[0][halo_rec] = make_float4(0.f, 1.f, 0.f, 1.f);
         rec[1][halo_rec] = make_float4(0.f, 1.f, 0.f, 1.f);
     }
     __syncthreads();
-    RawNodes W;
-    {
-        RawNodes W0;
-        plane_request(ez_begin, W0);
-        plane_request(ez_begin + 1, W);
-        plane_publish(W0, ez_begin);
-        plane_publish(W, ez_begin + 1);
-    }
-    __syncthreads();
-    plane_gather(ez_begin, SA, keep_lo, u_lo);
-    __syncthreads();              // every thread has read plane ez_begin before the first layer publishes plane ez_begin + 2 into its slot
-    int ez = ez_begin;
-    // (Static or rotating wave priorities per workgroup, against workgroups falling into lock-step, measured equal: profiles/r2_prio3d.txt.)
-#pragma nounroll
-    for (; ez + 1 < ez_end; ez += 2) {
-        plane_request(ez + 2, W);                 // lands while this layer is computed; published before the layer's barrier
-        flush_store();
-        plane_gather(ez + 1, SB, keep_up, u_up);
-        layer(ez, SA, SB, keep_lo, u_lo, &W);
-        plane_request(ez + 3, W);
-        flush_store();
-        plane_gather(ez + 2, SA, keep_lo, u_lo);
-        layer(ez + 1, SB, SA, keep_up, u_up, &W);
-    }
-    bool odd = false;
-    if (ez < ez_end) {
-        flush_store();
-        plane_gather(ez + 1, SB, keep_up, u_up);
-        layer(ez, SA, SB, keep_lo, u_lo, nullptr);
-        odd = true;
-    }
-    flush_store();
-    if (ez_end == p.nelz) {       // the last strip owns the top boundary plane: only the layer below contributes
-        float o[2][2];
-        plane_transpose(cU, cX, cY, o);
-        emit_plane(o, odd ? keep_up : keep_lo, odd ? u_up : u_lo, p.nz - 1, true, nullptr, 0);
-        flush_store();
-    }
+#include "poisson3d_q1_march.inl"
 
     if constexpr (E1G) e1_acc = (ut_acc / p.T.esc + p.T.beta * e2_acc) / p.T.alpha;       // per-thread share of sum W nu |grad u|^2 (the identity holds for the total)
     if (p.want_sums) finish_sums(p, e1_acc, e2_acc, sq_acc, tid, 256, red, &last_flag, (double)p.T.esc);
@@ -711,26 +554,14 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1n2_kernel(const PoissonPar
     static_assert((FL & (FL3_FGP | FL3_BC)) == 0, "node-owner form: nodal forcing, constant-value conditions");
     const int tx = threadIdx.x, ty = threadIdx.y;
     const int tid = ty * 16 + tx;
-    unsigned lid = blockIdx.x;                    // XCD-aware decode, see poisson3d_q1w_kernel
-    {
-        const unsigned nwg = gridDim.x, xcd = lid & 7u, idx = lid >> 3, base = nwg >> 3, rem = nwg & 7u;
-        lid = xcd * base + min(xcd, rem) + idx;
-    }
-    const int chunk = (int)(lid % (unsigned)chunks_x);
-    lid /= (unsigned)chunks_x;
-    const int tile = (int)(lid % (unsigned)tiles_y);
-    lid /= (unsigned)tiles_y;
-    const int strip = selected_strip(p, (int)(lid % (unsigned)strips_z)), b = (int)(lid / (unsigned)strips_z);
+    const Strip3D wg = strip3d_decode(xcd_remap(blockIdx.x, gridDim.x), chunks_x, tiles_y, strips_z, p.strip_sel, p.nstrips, p.rows_per_strip, p.nelz);
+    const int chunk = wg.chunk, tile = wg.tile, b = wg.b, ez_own = wg.ez_own, ez_begin = wg.ez_begin, ez_end = wg.ez_end;
     const int nx0 = chunk * 30, ny0 = tile * 15;               // first node of the tile (chunks overlap by one thread column = two elements)
     const int x0 = nx0 + 2 * tx, ey = ny0 + ty;                // the thread's first node == lower-left node of its first element
     const bool owner = !(chunk > 0 && tx == 0) && !(tile > 0 && ty == 0);
     const unsigned npl = (unsigned)(p.nx * p.ny);
     const int64_t nps = (int64_t)npl * p.nz;
     const SampleBases sb = sample_bases(p, b, nps);
-    const int R = p.rows_per_strip;
-    const int ez_own = strip * R;
-    const int ez_begin = ez_own > 0 ? ez_own - 1 : 0;
-    const int ez_end = min(ez_own + R, p.nelz);
     const bool noderow_ok = ey < p.ny;
     const float okf[2] = {(ey < p.nely && x0 < p.nelx) ? 1.f : 0.f, (ey < p.nely && x0 + 1 < p.nelx) ? 1.f : 0.f};
     const ElemTab& TV = p.T;
@@ -757,11 +588,7 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1n2_kernel(const PoissonPar
     const unsigned halo_par_stride = 4u * ((hcol & 1) ? 17u * 16u : 17u * 17u);                                                        // floats
     const float* const halo_src = (hgrp == 1 && HAS_NU) ? sb.nu : ((hgrp == 2 && HAS_F) ? sb.f : sb.u);                               // per lane
 
-    const bool has_mask[2] = {sb.mask[0] != nullptr, sb.mask[1] != nullptr};
-    const uint8_t* mask8[2];
-    mask8[0] = reinterpret_cast<const uint8_t*>(has_mask[0] ? sb.mask[0] : sb.mask[1]);
-    mask8[1] = reinterpret_cast<const uint8_t*>(has_mask[1] ? sb.mask[1] : sb.mask[0]);
-    const float* mask32[2] = {reinterpret_cast<const float*>(mask8[0]), reinterpret_cast<const float*>(mask8[1])};
+    const MaskImages mi = mask_images(sb.mask[0], sb.mask[1]);
     // BOX: per condition the faces of the domain box it fixes (0: not a box condition).  In-plane part per node (this thread's pair, its halo
     // node), constant over the march; the two faces across the marched axis per plane (wave-uniform)
     const int bfaces[2] = {BOX && p.bc[0].kind == DN_MASK_BOX ? p.bc[0].box_faces : 0, BOX && p.bc[1].kind == DN_MASK_BOX ? p.bc[1].box_faces : 0};
@@ -772,28 +599,19 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1n2_kernel(const PoissonPar
     const bool bxy0[2] = {box_xy(0, x0, ey), box_xy(1, x0, ey)}, bxy1[2] = {box_xy(0, x0 + 1, ey), box_xy(1, x0 + 1, ey)};
     const bool bxyh[2] = {box_xy(0, nx0 + hcol, ny0 + hrow), box_xy(1, nx0 + hcol, ny0 + hrow)};
 
-    struct RawNodes2 {
+    struct RawNodes {
         float2 u, n, f;               // own pair
         float h;                      // halo node: u, nu or f by lane group
-        uint16_t m[2];                // uint8 masks of the own pair (two bytes), per condition
-        float2 mf[2];                 // fp32 masks of the own pair
-        uint8_t hm[2];
-        float hmf[2];
+        PairMasks mk;
     };
-    auto plane_request = [&](int zreq, RawNodes2& W) {
+    auto plane_request = [&](int zreq, RawNodes& W) {
         const unsigned zoff = (unsigned)min(zreq, p.nz - 1) * npl;
         const unsigned oo = zoff + own_off, oh = zoff + halo_off;
         W.u = ld_at<float2>(sb.u, oo);
         if constexpr (HAS_NU) W.n = ld_at<float2>(sb.nu, oo);
         if constexpr (F_ARR) W.f = ld_at<float2>(sb.f, oo);
         W.h = halo_src[oh];
-        if constexpr (BC_U8C) {
-#pragma unroll
-            for (int k = 0; k < NMASK; ++k) {
-                if constexpr (MASK_F32) { W.mf[k] = ld_at<float2>(mask32[k], oo); W.hmf[k] = ld_at<float>(mask32[k], oh); }
-                else { W.m[k] = ld_at<uint16_t>(mask8[k], oo); W.hm[k] = ld_at<uint8_t>(mask8[k], oh); }
-            }
-        }
+        pair_masks_request<NMASK, MASK_F32>(mi, oo, oh, W.mk);
     };
     // img[j]: the node is set in the j-th LOADED mask image (NMASK == 1: the one image is whichever condition has it); box[k]: by condition k's faces.
     // The conditions are applied in their order (the reference's torch.where lines, e.g. IBN_3D.py:119-122)
@@ -803,8 +621,8 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1n2_kernel(const PoissonPar
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 bool s = false;
-                if constexpr (NMASK == 2) s = has_mask[k] && img[k];
-                if constexpr (NMASK == 1) s = has_mask[k] && img[0];
+                if constexpr (NMASK == 2) s = mi.has[k] && img[k];
+                if constexpr (NMASK == 1) s = mi.has[k] && img[0];
                 if constexpr (BOX) s = s || box[k];
                 uu = s ? p.bc[k].value : uu;
                 keep = s ? 0.f : keep;
@@ -812,15 +630,9 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1n2_kernel(const PoissonPar
         }
         return make_float4(uu, HAS_NU ? nn : 1.f, F_ARR ? ff : 0.f, keep);
     };
-    auto plane_publish = [&](const RawNodes2& W, int zpl) {
-        bool s0[2] = {false, false}, s1[2] = {false, false}, sh[2] = {false, false};
-        if constexpr (BC_U8C) {
-#pragma unroll
-            for (int k = 0; k < NMASK; ++k) {
-                if constexpr (MASK_F32) { s0[k] = W.mf[k].x > 0.5f; s1[k] = W.mf[k].y > 0.5f; sh[k] = W.hmf[k] > 0.5f; }
-                else { s0[k] = (W.m[k] & 0xffu) != 0; s1[k] = (W.m[k] >> 8) != 0; sh[k] = W.hm[k] != 0; }
-            }
-        }
+    auto plane_publish = [&](const RawNodes& W, int zpl) {
+        bool s0[2], s1[2], sh[2];
+        pair_masks_decode<NMASK, MASK_F32>(W.mk, s0, s1, sh);
         const int par = zpl & 1;
         bool b0[2] = {false, false}, b1[2] = {false, false}, bh[2] = {false, false};
         if constexpr (BOX) {
@@ -872,26 +684,6 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1n2_kernel(const PoissonPar
     const v2f okv = {okf[0], okf[1]};
     int par = 0;
 
-    // adjoint of stage_u3: cotangents of a plane's stage values -> contributions to each element's 2 x 2 nodes
-    auto plane_transpose = [&](const v2f (&tU)[NGP][NGP], const v2f (&tX)[NGP], const v2f (&tY)[NGP], v2f (&o)[2][2]) {
-        v2f s0 = 0.f, t0 = 0.f, s1 = 0.f, t1 = 0.f;
-#pragma unroll
-        for (int i = 0; i < NGP; ++i) {
-            v2f sv = 0.f, t = 0.f;
-#pragma unroll
-            for (int j = 0; j < NGP; ++j) { sv += tU[j][i]; t = vfma(TV.b[j][1], tU[j][i], t); }
-            const v2f c1 = t + tY[i], c0 = sv - c1;
-            s0 += c0; t0 = vfma(TV.b[i][1], c0, t0);
-            s1 += c1; t1 = vfma(TV.b[i][1], c1, t1);
-        }
-        v2f sX = 0.f, d1 = 0.f;
-#pragma unroll
-        for (int j = 0; j < NGP; ++j) { sX += tX[j]; d1 = vfma(TV.b[j][1], tX[j], d1); }
-        const v2f g01 = t0 + (sX - d1), g11 = t1 + d1;
-        o[0][1] = okv * g01; o[0][0] = okv * (s0 - g01);
-        o[1][1] = okv * g11; o[1][0] = okv * (s1 - g11);
-    };
-
     const unsigned out_row = (unsigned)ey * (unsigned)p.nx;
     const int from_left = (int)(((unsigned)tid - 1u) & 63u) << 2;
     const float nfirst = tx > 0 ? 1.f : 0.f;
@@ -904,7 +696,7 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1n2_kernel(const PoissonPar
     };
     // o[node row][node column of the element]: contributions of the thread's two elements (.x, .y) to their 2 x 2 nodes in the plane being
     // finished.  The thread's node columns: c0 = o[.][0].x (+ the left thread's o[.][1].y), c1 = o[.][1].x + o[.][0].y; o[.][1].y goes right.
-    auto emit_plane = [&](const v2f (&o)[2][2], int z, bool owned_plane, const RawNodes2* W, int zpub) {
+    auto emit_plane = [&](const v2f (&o)[2][2], int z, bool owned_plane, const RawNodes* W, int zpub) {
         // keep and (E1G) the value of the own node pair in the plane being finished: re-read from the thread's own records rather than carried in
         // eight registers through the layer (the kernel sits at its register cap).  The reads are issued BEFORE this call's publish overwrites the
         // records of the same parity (a wave's LDS accesses execute in order) and land under the barrier.
@@ -936,7 +728,7 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1n2_kernel(const PoissonPar
         pend_st = st && sb.out != nullptr && x0 < p.nx;
         par ^= 1;
     };
-    auto layer = [&](int ez, const PlaneP& L, const PlaneP& U, const RawNodes2* W) {
+    auto layer = [&](int ez, const PlaneP& L, const PlaneP& U, const RawNodes* W) {
         const bool own_layer = ez >= ez_own;
         const v2f cnt = ((own_layer && owner) ? 1.f : 0.f) * okv;
         v2f o[2][2], tU[NGP][NGP], tX[NGP], tY[NGP], e1, e2;
@@ -949,12 +741,16 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1n2_kernel(const PoissonPar
             e1_acc2 = vfma(cnt, e1, e1_acc2);
         }
         e2_acc2 = vfma(cnt, e2, e2_acc2);
-        plane_transpose(tU, tX, tY, o);
+        plane_transpose<NGP, v2f>(TV.b, okv, tU, tX, tY, o);
         __builtin_amdgcn_sched_barrier(0);
         emit_plane(o, ez, own_layer, W, ez + 2);
     };
+    auto top_plane = [&](bool) {
+        v2f o[2][2];
+        plane_transpose<NGP, v2f>(TV.b, okv, cU, cX, cY, o);
+        emit_plane(o, p.nz - 1, true, nullptr, 0);
+    };
 
-    // prologue: planes ez_begin and ez_begin + 1 into LDS (requested together), the lower one staged
     if (lane < 13 && wave * 13 + lane < 49) {          // the constant components of the halo records (both parities): nu = 1, f = 0, keep = 1
         float4* const r0 = (hcol & 1) ? &recO[0][hrow][hcol >> 1] : &recE[0][hrow][hcol >> 1];
         const unsigned st4 = (hcol & 1) ? 17u * 16u : 17u * 17u;
@@ -962,43 +758,8 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1n2_kernel(const PoissonPar
         r0[st4] = make_float4(0.f, 1.f, 0.f, 1.f);
     }
     __syncthreads();
-    RawNodes2 W;
-    {
-        RawNodes2 W0;
-        plane_request(ez_begin, W0);
-        plane_request(ez_begin + 1, W);
-        plane_publish(W0, ez_begin);
-        plane_publish(W, ez_begin + 1);
-    }
-    __syncthreads();
-    plane_gather(ez_begin, SA);
-    __syncthreads();
-    int ez = ez_begin;
-#pragma nounroll
-    for (; ez + 1 < ez_end; ez += 2) {
-        plane_request(ez + 2, W);                 // lands while this layer is computed; published before the layer's barrier
-        flush_store();
-        plane_gather(ez + 1, SB);
-        layer(ez, SA, SB, &W);
-        plane_request(ez + 3, W);
-        flush_store();
-        plane_gather(ez + 2, SA);
-        layer(ez + 1, SB, SA, &W);
-    }
-    bool odd = false;
-    if (ez < ez_end) {
-        flush_store();
-        plane_gather(ez + 1, SB);
-        layer(ez, SA, SB, nullptr);
-        odd = true;
-    }
-    flush_store();
-    if (ez_end == p.nelz) {       // the last strip owns the top boundary plane: only the layer below contributes
-        v2f o[2][2];
-        plane_transpose(cU, cX, cY, o);
-        emit_plane(o, p.nz - 1, true, nullptr, 0);
-        flush_store();
-    }
+#include "poisson3d_q1_march.inl"
+
     float e1_acc = e1_acc2.x + e1_acc2.y;
     const float e2_acc = e2_acc2.x + e2_acc2.y, sq_acc = sq_acc2.x + sq_acc2.y;
     if constexpr (E1G) e1_acc = ((ut_acc.x + ut_acc.y) / p.T.esc + p.T.beta * e2_acc) / p.T.alpha;
@@ -1007,79 +768,75 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1n2_kernel(const PoissonPar
 #endif
 
 // ---- dispatch ---------------------------------------------------------------------------------------------
-template <int NGP, int E, bool VEC, int FL>
+// unit: the exact 2-point rule's weights, all 1 (UW kernels exist for 2 points only)
+template <int NGP>
+static bool unit_weights(const PoissonParams& pp) {
+    bool unit = NGP == 2;
+    for (int i = 0; i < NGP; ++i) unit = unit && pp.T.w[i] == 1.0f;
+    return unit;
+}
+
+// node-owner form (every node requested once) with FL's mask images, or (one) with exactly one of them
+template <int NGP, int FL, bool UW>
+static void launch3_n1(const PoissonParams& pp, const Geom3D& g, const dim3& grid, bool one, hipStream_t s) {
+    constexpr int FL1 = (FL & FL3_BC_U8C) ? (FL | FL3_BC_ONE) : FL;
+    const dim3 block(16, 16);
+    if (one) hipLaunchKernelGGL((poisson3d_q1n_kernel<NGP, FL1, UW>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
+    else hipLaunchKernelGGL((poisson3d_q1n_kernel<NGP, FL, UW>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
+}
+
+template <int NGP, int FL>
 static void launch3_one(const PoissonParams& pp, const Geom3D& g, int family, int batch, hipStream_t s) {
     const dim3 grid((unsigned)((long long)g.chunks * g.tiles * g.strips * batch)), block(g.TX, g.TY);
-    bool unit = true;                                   // the exact 2-point rule: all weights 1
-    for (int i = 0; i < NGP; ++i) unit = unit && pp.T.w[i] == 1.0f;
-    if constexpr (E == 1 && (FL & (FL3_FGP | FL3_BC)) == 0) {
-        if (family == DN_POISSON_3D_Q1_N1) {      // node-owner form (every node requested once)
-            constexpr int FL1 = (FL & FL3_BC_U8C) ? (FL | FL3_BC_ONE) : FL;
+    const bool unit = unit_weights<NGP>(pp);
+    if constexpr ((FL & (FL3_FGP | FL3_BC)) == 0) {
+        if (family == DN_POISSON_3D_Q1_N1) {
             const bool one = (FL & FL3_BC_U8C) && ((pp.bc[0].mask != nullptr) != (pp.bc[1].mask != nullptr));
             if constexpr (NGP == 2) {
                 if (unit) {
                     // energy from the nodal values (FL3_E1G) whenever the launch has a stiffness part and sums are wanted
-                    const bool e1g = pp.T.alpha != 0.f && pp.want_sums && config(CFG_Q1_3D_E1SUM) == nullptr;
-                    if (e1g) {
-                        if (one) hipLaunchKernelGGL((poisson3d_q1n_kernel<NGP, FL1 | FL3_E1G, true>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
-                        else hipLaunchKernelGGL((poisson3d_q1n_kernel<NGP, FL | FL3_E1G, true>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
-                        return;
-                    }
-                    if (one) hipLaunchKernelGGL((poisson3d_q1n_kernel<NGP, FL1, true>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
-                    else hipLaunchKernelGGL((poisson3d_q1n_kernel<NGP, FL, true>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
+                    if (pp.T.alpha != 0.f && pp.want_sums && config(CFG_Q1_3D_E1SUM) == nullptr) launch3_n1<NGP, FL | FL3_E1G, true>(pp, g, grid, one, s);
+                    else launch3_n1<NGP, FL, true>(pp, g, grid, one, s);
                     return;
                 }
             }
-            if (one) hipLaunchKernelGGL((poisson3d_q1n_kernel<NGP, FL1, false>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
-            else hipLaunchKernelGGL((poisson3d_q1n_kernel<NGP, FL, false>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
+            launch3_n1<NGP, FL, false>(pp, g, grid, one, s);
             return;
         }
     }
-    if constexpr (E == 1) {
-        if (family == DN_POISSON_3D_Q1_T16) {          // 16-wide tiles, one element per thread: DPP hand-over, paired loads
-            if constexpr (NGP == 2) {
-                if (unit) {
-                    hipLaunchKernelGGL((poisson3d_q1w_kernel<NGP, 1, false, FL, true, true>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
-                    return;
-                }
-            }
-            hipLaunchKernelGGL((poisson3d_q1w_kernel<NGP, 1, false, FL, false, true>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
-            return;
-        }
-    }
+    const bool t16 = family == DN_POISSON_3D_Q1_T16;          // 16-wide tiles: lane-exchange hand-over, paired loads
+#define DN_W3(UW, T16) hipLaunchKernelGGL((poisson3d_q1w_kernel<NGP, FL, UW, T16>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips)
     if constexpr (NGP == 2) {
         if (unit) {
-            hipLaunchKernelGGL((poisson3d_q1w_kernel<NGP, E, VEC, FL, true, false>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
+            if (t16) DN_W3(true, true);
+            else DN_W3(true, false);
             return;
         }
     }
-    hipLaunchKernelGGL((poisson3d_q1w_kernel<NGP, E, VEC, FL, false, false>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
+    if (t16) DN_W3(false, true);
+    else DN_W3(false, false);
+#undef DN_W3
 }
 
-// node-owner form with fp32 mask images (constant values); only instantiated for one element per thread and nodal / absent forcing
-template <int NGP, int E, bool VEC, int FL>
+// node-owner form with fp32 mask images (constant values); only instantiated for nodal / absent forcing
+template <int NGP, int FL>
 static void launch3_f32n(const PoissonParams& pp, const Geom3D& g, int family, int batch, hipStream_t s) {
-    if constexpr (E == 1 && (FL & FL3_FGP) == 0) {
-        const dim3 grid((unsigned)((long long)g.chunks * g.tiles * g.strips * batch)), block(16, 16);
-        constexpr int F2 = FL | FL3_BC_U8C | FL3_BC_F32, F1 = F2 | FL3_BC_ONE;
+    if constexpr ((FL & FL3_FGP) == 0) {
+        const dim3 grid((unsigned)((long long)g.chunks * g.tiles * g.strips * batch));
         const bool one = (pp.bc[0].mask != nullptr) != (pp.bc[1].mask != nullptr);
-        bool unit = NGP == 2;
-        for (int i = 0; i < NGP; ++i) unit = unit && pp.T.w[i] == 1.0f;
         if constexpr (NGP == 2) {
-            if (unit) {
-                if (one) hipLaunchKernelGGL((poisson3d_q1n_kernel<NGP, F1, true>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
-                else hipLaunchKernelGGL((poisson3d_q1n_kernel<NGP, F2, true>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
+            if (unit_weights<NGP>(pp)) {
+                launch3_n1<NGP, FL | FL3_BC_U8C | FL3_BC_F32, true>(pp, g, grid, one, s);
                 return;
             }
         }
-        if (one) hipLaunchKernelGGL((poisson3d_q1n_kernel<NGP, F1, false>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
-        else hipLaunchKernelGGL((poisson3d_q1n_kernel<NGP, F2, false>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips);
+        launch3_n1<NGP, FL | FL3_BC_U8C | FL3_BC_F32, false>(pp, g, grid, one, s);
     } else {
-        launch3_one<NGP, E, VEC, FL | FL3_BC>(pp, g, family, batch, s);
+        launch3_one<NGP, FL | FL3_BC>(pp, g, family, batch, s);
     }
 }
 
-template <int NGP, int E, bool VEC>
+template <int NGP>
 static void launch3_flags(const PoissonParams& pp, const Geom3D& g, int family, int batch, hipStream_t s) {
     const int f = pp.fgp ? 2 : (pp.f ? 1 : 0);
     const bool bc = pp.bc[0].mask || pp.bc[1].mask;
@@ -1091,11 +848,11 @@ static void launch3_flags(const PoissonParams& pp, const Geom3D& g, int family, 
     // fp32 images with constant values (the reference's masks): the node-owner form reads them as one dword per node; everything else
     // with fp32 masks or value fields goes through the generic form of the T16 kernel
     const bool f32n = f32c && family == DN_POISSON_3D_Q1_N1;
-#define DN_L3(FLAGS)                                                                   \
-    (!bc ? launch3_one<NGP, E, VEC, (FLAGS)>(pp, g, family, batch, s)                    \
-         : u8c ? launch3_one<NGP, E, VEC, (FLAGS) | FL3_BC_U8C>(pp, g, family, batch, s) \
-         : f32n ? launch3_f32n<NGP, E, VEC, (FLAGS)>(pp, g, family, batch, s)            \
-               : launch3_one<NGP, E, VEC, (FLAGS) | FL3_BC>(pp, g, family, batch, s))
+#define DN_L3(FLAGS)                                                           \
+    (!bc ? launch3_one<NGP, (FLAGS)>(pp, g, family, batch, s)                    \
+         : u8c ? launch3_one<NGP, (FLAGS) | FL3_BC_U8C>(pp, g, family, batch, s) \
+         : f32n ? launch3_f32n<NGP, (FLAGS)>(pp, g, family, batch, s)            \
+               : launch3_one<NGP, (FLAGS) | FL3_BC>(pp, g, family, batch, s))
     if (pp.nu) {
         if (f == 0) DN_L3(FL3_NU);
         else if (f == 1) DN_L3(FL3_NU | FL3_F);
@@ -1111,25 +868,9 @@ static void launch3_flags(const PoissonParams& pp, const Geom3D& g, int family, 
 #if DN_NGP == 2
 template <int FLB>
 static void launch3_n2_bc(const PoissonParams& pp, const dim3& grid, const Geom3D& g, hipStream_t s) {
-    const bool any = pp.bc[0].mask || pp.bc[1].mask;
-    const bool one = (pp.bc[0].mask != nullptr) != (pp.bc[1].mask != nullptr);
-    bool f32 = false;
-    for (int k = 0; k < 2; ++k)
-        if (pp.bc[k].mask && !pp.bc[k].mask_is_u8) f32 = true;
-    const dim3 block(16, 16);
-#define DN_N2(FLAGS) hipLaunchKernelGGL((poisson3d_q1n2_kernel<(FLAGS)>), grid, block, 0, s, pp, g.chunks, g.tiles, g.strips)
-    if (pp.bc[0].kind == DN_MASK_BOX || pp.bc[1].kind == DN_MASK_BOX) {       // box faces (no array), alone or beside ONE mask image
-        if (!any) DN_N2(FLB | FL3_BOX);
-        else if (!f32) DN_N2(FLB | FL3_BOX | FL3_BC_U8C | FL3_BC_ONE);
-        else DN_N2(FLB | FL3_BOX | FL3_BC_U8C | FL3_BC_F32 | FL3_BC_ONE);
-        return;
-    }
-    if (!any) DN_N2(FLB);
-    else if (!f32 && one) DN_N2(FLB | FL3_BC_U8C | FL3_BC_ONE);
-    else if (!f32) DN_N2(FLB | FL3_BC_U8C);
-    else if (one) DN_N2(FLB | FL3_BC_U8C | FL3_BC_F32 | FL3_BC_ONE);
-    else DN_N2(FLB | FL3_BC_U8C | FL3_BC_F32);
-#undef DN_N2
+    launch_mask_form(pp.bc, [&](auto form) {
+        hipLaunchKernelGGL((poisson3d_q1n2_kernel<FLB | decltype(form)::value>), grid, dim3(16, 16), 0, s, pp, g.chunks, g.tiles, g.strips);
+    });
 }
 
 static int launch3_n2(const PoissonParams& pp, const Geom3D& g, int batch, hipStream_t s) {
@@ -1164,7 +905,7 @@ static int launch3_n2(const PoissonParams& pp, const Geom3D& g, int batch, hipSt
 #define DN_CAT(a, b) DN_CAT2(a, b)
 int DN_CAT(launch_poisson3d_q1_g, DN_NGP)(const PoissonParams& pp, const Geom3D& g, int family, int batch, bool vec, hipStream_t s) {
     if (pp.f && pp.f_is_load && !(DN_NGP == 2 && g.E == 2 && g.TX == 16 && g.TY == 16)) return DN_E_UNSUPPORTED;      // load vectors: two-element node-owner form only
-    if (g.E == 1) { launch3_flags<DN_NGP, 1, false>(pp, g, family, batch, s); return 0; }
+    if (g.E == 1) { launch3_flags<DN_NGP>(pp, g, family, batch, s); return 0; }
 #if DN_NGP == 2
     if (g.E == 2 && g.TX == 16 && g.TY == 16) {
         // node-owner forms, two elements per thread (poisson_choose checked their preconditions): closed form in z (poisson3d_q1_cf.hip) or marching

@@ -31,13 +31,9 @@
 // construction) and a per-phase cycle budget of the loop (profiles/r4_stamp3d_cf.txt) showed it; they were removed from the source.
 #include <cmath>
 
-#include "poisson_common.h"
+#include "poisson3d_q1_common.h"
 
 namespace dn {
-
-enum : int { CF3_NU = 1, CF3_F = 2, CF3_LOAD = 4, CF3_IMG = 8, CF3_ONE = 16, CF3_F32 = 32, CF3_BOX = 64 };
-// CF3_LOAD (with CF3_F): `f` holds the assembled load vector (dn_poisson_args.f_is_load); CF3_IMG: mask images, uint8 or (CF3_F32) fp32, two or
-// (CF3_ONE) one of them; CF3_BOX: at least one condition is given as faces of the domain box
 
 struct Cf3Consts {
     float t0, t1;                      // lerp weights of the two Gauss points
@@ -52,12 +48,6 @@ struct Cf3Consts {
     float inv_esc, beta, inv_alpha;
 };
 
-// lane l <- lane l - 1 of the wave, 0 for the first lane of a row of 16.  ds_bpermute, not DPP: on gfx950 a DPP move costs a shared SIMD ~33
-// cycles, a ds_bpermute ~3 (tools/micro/valu_mem.hip, profiles/r2_valu_mem.txt).
-__device__ __forceinline__ float cf3_from_left(float v, int from, float nf) {
-    return nf * __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(from, __builtin_bit_cast(int, v)));
-}
-
 // wave-uniform float select on the scalar unit: (a < b) ? x : y for wave-uniform integers a, b.  Inline asm: written in C++ (with floats or with
 // their bit patterns) the compiler moves both values into vector registers, selects there and reads the result back (4 VALU instructions)
 __device__ __forceinline__ float cf3_usel_lt(int a, int b, float x, float y) {
@@ -70,21 +60,16 @@ __device__ __forceinline__ float cf3_usel_lt(int a, int b, float x, float y) {
     return __builtin_bit_cast(float, r);
 }
 
-template <int FL>     // 3 waves per SIMD asked of the compiler (<= 168 VGPRs)
+template <int FL>     // FL3_NU, FL3_F, FL3_LOAD, FL3_BC_U8C (IMG), FL3_BC_ONE, FL3_BC_F32, FL3_BOX;  3 waves per SIMD asked of the compiler (<= 168 VGPRs)
 __global__ void __launch_bounds__(256, 3) poisson3d_q1_cf_kernel(const PoissonParams p, const Cf3Consts k, const int chunks_x, const int tiles_y, const int strips_z) {
-    constexpr bool HAS_NU = (FL & CF3_NU) != 0, F_ARR = (FL & CF3_F) != 0, LOADV = F_ARR && (FL & CF3_LOAD) != 0, HAS_F = F_ARR && !LOADV;
-    constexpr bool IMG = (FL & CF3_IMG) != 0, BOX = (FL & CF3_BOX) != 0;
-    constexpr int NMASK = !IMG ? 0 : ((FL & CF3_ONE) ? 1 : 2);
-    constexpr bool MASK_F32 = (FL & CF3_F32) != 0;
+    constexpr bool HAS_NU = (FL & FL3_NU) != 0, F_ARR = (FL & FL3_F) != 0, LOADV = F_ARR && (FL & FL3_LOAD) != 0, HAS_F = F_ARR && !LOADV;
+    constexpr bool IMG = (FL & FL3_BC_U8C) != 0, BOX = (FL & FL3_BOX) != 0;
+    constexpr int NMASK = !IMG ? 0 : ((FL & FL3_BC_ONE) ? 1 : 2);
+    constexpr bool MASK_F32 = (FL & FL3_BC_F32) != 0;
+    static_assert((FL & (FL3_FGP | FL3_BC | FL3_E1G)) == 0, "closed form in z: nodal forcing, constant-value conditions, energy from the nodal values");
     const int tx = threadIdx.x, ty = threadIdx.y;
     const int tid = ty * 16 + tx;
-    // 1-D grid with an XCD-aware decode: workgroups are dealt round-robin to the 8 XCDs, each with its own L2; every XCD gets a contiguous range of
-    // the logical order (chunk fastest, then tile, strip, sample), so a tile's halo is read from HBM once instead of once per XCD
-    unsigned lid = blockIdx.x;
-    {
-        const unsigned nwg = gridDim.x, xcd = lid & 7u, idx = lid >> 3, base = nwg >> 3, rem = nwg & 7u;
-        lid = xcd * base + min(xcd, rem) + idx;
-    }
+    unsigned lid = xcd_remap(blockIdx.x, gridDim.x);      // logical order: chunk fastest, then tile, strip, sample
     const int chunk = (int)(lid % (unsigned)chunks_x);
     lid /= (unsigned)chunks_x;
     const int tile = (int)(lid % (unsigned)tiles_y);
@@ -149,12 +134,12 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1_cf_kernel(const PoissonPa
     const unsigned halo_fmask = halo_is_f ? 0xffffffffu : 0u;
     const float halo_mul = (HAS_NU && hgrp == 1) ? k.snu : 1.f;
 
-    const bool has_mask[2] = {sb.mask[0] != nullptr, sb.mask[1] != nullptr};
-    const uint8_t* mask8[2];
-    mask8[0] = reinterpret_cast<const uint8_t*>(has_mask[0] ? sb.mask[0] : sb.mask[1]);      // an absent condition re-reads the other one and is
-    mask8[1] = reinterpret_cast<const uint8_t*>(has_mask[1] ? sb.mask[1] : sb.mask[0]);      // ignored: no load inside a wave-uniform branch
-    const float* mask32[2] = {reinterpret_cast<const float*>(mask8[0]), reinterpret_cast<const float*>(mask8[1])};
-    // BOX: per condition the faces of the domain box it fixes (0: not a box condition); in-plane part per node, constant over the march
+    const MaskImages mi = mask_images(sb.mask[0], sb.mask[1]);
+    // BOX: per condition the faces of the domain box it fixes (0: not a box condition); in-plane part per node, constant over the march.
+    // (This kernel keeps its own spelling, in its own statement order, of the decode, the tile origin, the halo assignment, the box-face tests and
+    // the in-order application of the conditions: on shared helpers its prologue came out in another order and the 128^3 box + load-vector launch,
+    // one wave of workgroups of ten layers each, ran 1 % slower in five rounds of five, twice -- profiles/poisson3d_refactor.txt.  As written the
+    // machine code of that instantiation is the one it had before the shared header.)
     const int bfaces[2] = {BOX && p.bc[0].kind == DN_MASK_BOX ? p.bc[0].box_faces : 0, BOX && p.bc[1].kind == DN_MASK_BOX ? p.bc[1].box_faces : 0};
     auto box_xy = [&](int kk, int x, int y) {
         return ((bfaces[kk] & DN_FACE_XLO) && x == 0) || ((bfaces[kk] & DN_FACE_XHI) && x == p.nx - 1) || ((bfaces[kk] & DN_FACE_YLO) && y == 0) ||
@@ -175,10 +160,7 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1_cf_kernel(const PoissonPa
     struct RawNodes {
         v2f u, n, f;                  // own pair (f: one plane AHEAD of u and nu when it is nodal forcing)
         float h;                      // halo node: u, nu or f by lane group
-        uint16_t m[2];                // uint8 masks of the own pair (two bytes), per condition
-        v2f mf[2];                    // fp32 masks of the own pair
-        uint8_t hm[2];
-        float hmf[2];
+        PairMasks mk;
     };
     auto ld_pair = [&](const float* base, unsigned off) {
         const float2 t = ld_at<float2>(base, off);
@@ -193,21 +175,12 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1_cf_kernel(const PoissonPa
         if constexpr (HAS_NU) W.n = ld_pair(sb.nu, oo);
         if constexpr (F_ARR) W.f = ld_pair(sb.f, zoff_f + own_off);
         W.h = halo_src[oh];
-        if constexpr (IMG) {
-            const unsigned ohm = zoff + halo_off;
-#pragma unroll
-            for (int kk = 0; kk < NMASK; ++kk) {
-                if constexpr (MASK_F32) W.mf[kk] = ld_pair(mask32[kk], oo);
-                else W.m[kk] = ld_at<uint16_t>(mask8[kk], oo);
-                if constexpr (MASK_F32) W.hmf[kk] = ld_at<float>(mask32[kk], ohm);
-                else W.hm[kk] = ld_at<uint8_t>(mask8[kk], ohm);
-            }
-        }
+        pair_masks_request<NMASK, MASK_F32>(mi, oo, zoff + halo_off, W.mk);
     };
     // Dirichlet conditions of one node: set[k]: the node is fixed by condition k (its mask image and / or its box faces).  Applied in their order
     // (the reference's torch.where lines, IBN_3D.py:119-122): uu <- value, keep <- 0
-    const float bcv1 = has_mask[0] ? p.bc[0].value : p.bc[1].value;      // NMASK == 1, no box faces: the value of the one condition
-    auto fix_node = [&](float& uu, float& keep, const bool (&img)[2], const bool (&box)[2]) {
+    const float bcv1 = mi.has[0] ? p.bc[0].value : p.bc[1].value;      // NMASK == 1, no box faces: the value of the one condition
+    auto fix = [&](float& uu, float& keep, const bool (&img)[2], const bool (&box)[2]) {
         keep = 1.f;
         if constexpr (NMASK == 1 && !BOX) {
             uu = img[0] ? bcv1 : uu;
@@ -216,8 +189,8 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1_cf_kernel(const PoissonPa
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) {
                 bool sset = false;
-                if constexpr (NMASK == 2) sset = has_mask[kk] && img[kk];
-                if constexpr (NMASK == 1) sset = has_mask[kk] && img[0];
+                if constexpr (NMASK == 2) sset = mi.has[kk] && img[kk];
+                if constexpr (NMASK == 1) sset = mi.has[kk] && img[0];
                 if constexpr (BOX) sset = sset || box[kk];
                 uu = sset ? p.bc[kk].value : uu;
                 keep = sset ? 0.f : keep;
@@ -229,14 +202,8 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1_cf_kernel(const PoissonPa
     v2f fh0 = 0.f, fh1 = 0.f;
     float hh0 = 0.f, hh1 = 0.f;
     auto plane_publish = [&](const RawNodes& W, int zpl, int slot) {
-        bool s0[2] = {false, false}, s1[2] = {false, false}, sh[2] = {false, false};
-        if constexpr (IMG) {
-#pragma unroll
-            for (int kk = 0; kk < NMASK; ++kk) {
-                if constexpr (MASK_F32) { s0[kk] = W.mf[kk].x > 0.5f; s1[kk] = W.mf[kk].y > 0.5f; sh[kk] = W.hmf[kk] > 0.5f; }
-                else { s0[kk] = (W.m[kk] & 0xffu) != 0; s1[kk] = (W.m[kk] >> 8) != 0; sh[kk] = W.hm[kk] != 0; }
-            }
-        }
+        bool s0[2], s1[2], sh[2];
+        pair_masks_decode<NMASK, MASK_F32>(W.mk, s0, s1, sh);
         bool b0[2] = {false, false}, b1[2] = {false, false}, bh[2] = {false, false};
         const int zc = min(zpl, p.nz - 1);
         if constexpr (BOX) {
@@ -270,8 +237,8 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1_cf_kernel(const PoissonPa
             u0 = bfix0 ? bval0 : u0; k0 = bkeep0;
             u1 = bfix1 ? bval1 : u1; k1 = bkeep1;
         } else {
-            fix_node(u0, k0, s0, b0);
-            fix_node(u1, k1, s1, b1);
+            fix(u0, k0, s0, b0);
+            fix(u1, k1, s1, b1);
         }
         lds_wr2(lds_own, slot * PLANE + OFF_U, slot * PLANE + OFF_U + HALF, u0, u1);
         if constexpr (HAS_NU) {
@@ -285,7 +252,7 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1_cf_kernel(const PoissonPa
                 float kh;
                 float hu = hv;
                 if (box_fast) hu = bfixh ? bvalh : hu;
-                else fix_node(hu, kh, sh, bh);
+                else fix(hu, kh, sh, bh);
                 hv = hgrp == 0 ? hu : hv;
             }
             halo_lds[slot * PLANE] = hv;
@@ -407,8 +374,8 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1_cf_kernel(const PoissonPa
     };
     // steps 5-8
     auto emit_plane = [&](const v2f (&o)[2][2], const v2f uown, const OwnVals& ov, int z, int zslot, bool owned_plane) {
-        const float left0 = cf3_from_left(o[0][1].y, from_left, nfirst);
-        lds_st2(lds_pair, OFF_X + zslot * 512, o[1][0].x + cf3_from_left(o[1][1].y, from_left, nfirst), o[1][1].x + o[1][0].y);
+        const float left0 = lane_from_left(o[0][1].y, from_left, nfirst);
+        lds_st2(lds_pair, OFF_X + zslot * 512, o[1][0].x + lane_from_left(o[1][1].y, from_left, nfirst), o[1][1].x + o[1][0].y);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         v2f up = {0.f, 0.f};
         if (ty > 0) up = lds_ld2(lds_pair, OFF_X + zslot * 512 - 32);       // the hand-over of the thread one node row below (tid - 16)
@@ -574,25 +541,9 @@ __global__ void __launch_bounds__(256, 3) poisson3d_q1_cf_kernel(const PoissonPa
 // ---- dispatch ---------------------------------------------------------------------------------------------
 template <int FLB>
 static void launch_cf3_bc(const PoissonParams& pp, const Cf3Consts& kc, const dim3& grid, const Geom3D& g, hipStream_t s) {
-    const bool any = pp.bc[0].mask || pp.bc[1].mask;
-    const bool one = (pp.bc[0].mask != nullptr) != (pp.bc[1].mask != nullptr);
-    bool f32 = false;
-    for (int kk = 0; kk < 2; ++kk)
-        if (pp.bc[kk].mask && !pp.bc[kk].mask_is_u8) f32 = true;
-    const dim3 block(16, 16);
-#define DN_CF3(FLAGS) hipLaunchKernelGGL((poisson3d_q1_cf_kernel<(FLAGS)>), grid, block, 0, s, pp, kc, g.chunks, g.tiles, g.strips)
-    if (pp.bc[0].kind == DN_MASK_BOX || pp.bc[1].kind == DN_MASK_BOX) {       // box faces (no array), alone or beside ONE mask image
-        if (!any) DN_CF3(FLB | CF3_BOX);
-        else if (!f32) DN_CF3(FLB | CF3_BOX | CF3_IMG | CF3_ONE);
-        else DN_CF3(FLB | CF3_BOX | CF3_IMG | CF3_F32 | CF3_ONE);
-        return;
-    }
-    if (!any) DN_CF3(FLB);
-    else if (!f32 && one) DN_CF3(FLB | CF3_IMG | CF3_ONE);
-    else if (!f32) DN_CF3(FLB | CF3_IMG);
-    else if (one) DN_CF3(FLB | CF3_IMG | CF3_F32 | CF3_ONE);
-    else DN_CF3(FLB | CF3_IMG | CF3_F32);
-#undef DN_CF3
+    launch_mask_form(pp.bc, [&](auto form) {
+        hipLaunchKernelGGL((poisson3d_q1_cf_kernel<FLB | decltype(form)::value>), grid, dim3(16, 16), 0, s, pp, kc, g.chunks, g.tiles, g.strips);
+    });
 }
 
 // poisson_choose (poisson_fused.hip) sends a launch here when it has a stiffness part (the scales of the records divide by alpha), the rule is
@@ -621,15 +572,15 @@ int launch_poisson3d_q1_cf(const PoissonParams& pp, const Geom3D& g, int batch, 
     const dim3 grid((unsigned)((long long)g.chunks * g.tiles * g.strips * batch));
     const int sel = (pp.nu ? 1 : 0) | (pp.f ? 2 : 0);
     if (pp.f && pp.f_is_load) {                    // the forcing as the assembled load vector (dn_poisson_args.f_is_load)
-        if (sel == 2) launch_cf3_bc<CF3_F | CF3_LOAD>(pp, kc, grid, g, s);
-        else launch_cf3_bc<CF3_NU | CF3_F | CF3_LOAD>(pp, kc, grid, g, s);
+        if (sel == 2) launch_cf3_bc<FL3_F | FL3_LOAD>(pp, kc, grid, g, s);
+        else launch_cf3_bc<FL3_NU | FL3_F | FL3_LOAD>(pp, kc, grid, g, s);
         return 0;
     }
     switch (sel) {
         case 0: launch_cf3_bc<0>(pp, kc, grid, g, s); break;
-        case 1: launch_cf3_bc<CF3_NU>(pp, kc, grid, g, s); break;
-        case 2: launch_cf3_bc<CF3_F>(pp, kc, grid, g, s); break;
-        default: launch_cf3_bc<CF3_NU | CF3_F>(pp, kc, grid, g, s); break;
+        case 1: launch_cf3_bc<FL3_NU>(pp, kc, grid, g, s); break;
+        case 2: launch_cf3_bc<FL3_F>(pp, kc, grid, g, s); break;
+        default: launch_cf3_bc<FL3_NU | FL3_F>(pp, kc, grid, g, s); break;
     }
     return 0;
 }

@@ -63,9 +63,10 @@ __device__ __forceinline__ void write_sums(double e, double s, int acc, double* 
 }
 
 // strip index of the idx-th launched strip (split evaluations launch a subset of the strips: PoissonParams::strip_sel)
-__device__ __forceinline__ int selected_strip(const PoissonParams& p, int idx) {
-    return p.strip_sel == 1 ? (idx == 0 ? 0 : p.nstrips - 1) : (p.strip_sel == 2 ? idx + 1 : idx);
+__device__ __forceinline__ int selected_strip(int strip_sel, int nstrips, int idx) {
+    return strip_sel == 1 ? (idx == 0 ? 0 : nstrips - 1) : (strip_sel == 2 ? idx + 1 : idx);
 }
+__device__ __forceinline__ int selected_strip(const PoissonParams& p, int idx) { return selected_strip(p.strip_sel, p.nstrips, idx); }
 
 // Per-sample base pointers (wave-uniform): all in-kernel indexing is a 32-bit offset from these.
 struct SampleBases {

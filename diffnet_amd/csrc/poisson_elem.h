@@ -49,7 +49,7 @@ struct ElemTab {
     float mxs[4];        // m[r] * wscale (the x axis carries the Jacobian / user scale): closed-form 2-D Q1 kernel
     float kx[3][4];
     float q1c[4];        // alpha*hs0^2, alpha*hs1^2, hs0^2, hs1^2  (2-D Q1 layer: derivative scales applied once per element)
-    // 3-D Q1 marching kernel, second form (q1_layer_3d_w): the in-plane weights live in the staged coefficient planes, the
+    // 3-D Q1 marching kernels (q1_layer_3d_w): the in-plane weights live in the staged coefficient planes, the
     // user scale (wscale) in kap[] and in the final energy scale, the 1/h factors are applied once per element.
     float wb[4];         // w[g] * b[g]           (pure 1-D weights: no wscale)
     float kap[3];        // alpha * wscale * hs[d]^2   cotangent scale of direction d
@@ -76,7 +76,7 @@ __device__ __forceinline__ void elem2d(const ElemTab& T, const float (&u)[P + 1]
                                        float& e1, float& e2) {
     constexpr int NB = P + 1;
     float a1 = 0.f, a2 = 0.f;
-    static_assert(P >= 2, "Q1 elements run through the marching kernels (q1_layer_2d / q1_layer_3d)");
+    static_assert(P >= 2, "Q1 elements run through the marching kernels (q1_layer_2d / q1_layer_3d_w)");
     // Table-driven sum factorisation, one x-Gauss point at a time: x-stage of u / nu / f for that point (per node row),
     // its NGP y-points (energy density, cotangents, y-transpose), then the x-transpose of that point straight into g.
     // The live set is one point's stage values and cotangents instead of all points'.
@@ -238,103 +238,11 @@ __host__ __device__ __forceinline__ void q1cf_elem(const float (&xm)[4], const f
 // ---------------------------------------------------------------------------------------------
 // 3-D Q1, marching form.  One element between node planes k (L) and k+1 (U), given each plane's in-plane stage at
 // the element's in-plane Gauss points m = (jg, ig):
-//   VU[jg][ig] value of u, VX[jg] = lerp_y of the x-differences, VY[ig] = y-difference of the x-lerped rows,
-//   VN / VF values of nu / f.
-// As in 2-D every sum over the z-Gauss points collapses onto the moments m[0..2] of the 1-D rule, and the sums over
-// one in-plane index onto the small vectors A0/A1 (per jg) and B0/B1 (per ig): O(NGP^2) work per element.
-// Outputs: cotangents of both planes' stage values (…L / …U) and the two energy parts.
-// ---------------------------------------------------------------------------------------------
-template <int NGP, bool FGP>
-__device__ __forceinline__ void q1_layer_3d(const ElemTab& T, const float (&LU)[NGP][NGP], const float (&UU)[NGP][NGP],
-                                            const float (&LX)[NGP], const float (&UX)[NGP], const float (&LY)[NGP],
-                                            const float (&UY)[NGP], const float (&LN)[NGP][NGP], const float (&UN)[NGP][NGP],
-                                            const float (&LF)[NGP][NGP], const float (&UF)[NGP][NGP], const float* fg,
-                                            float (&cUL)[NGP][NGP], float (&cUU)[NGP][NGP], float (&cXL)[NGP], float (&cXU)[NGP],
-                                            float (&cYL)[NGP], float (&cYU)[NGP], float& e1, float& e2) {
-    float a1 = 0.f, a2 = 0.f;
-    float A0[NGP], A1[NGP], B0[NGP], B1[NGP];
-#pragma unroll
-    for (int i = 0; i < NGP; ++i) A0[i] = A1[i] = B0[i] = B1[i] = 0.f;
-    const float nb = -T.beta;
-#pragma unroll
-    for (int jg = 0; jg < NGP; ++jg) {
-#pragma unroll
-        for (int ig = 0; ig < NGP; ++ig) {
-            const float w2 = T.w2[jg][ig];
-            const float dzu = UU[jg][ig] - LU[jg][ig];
-            const float uz = T.hs[2] * dzu;
-            const float dzn = UN[jg][ig] - LN[jg][ig];
-            const float wn0 = w2 * LN[jg][ig], wn1 = w2 * dzn;
-            A0[jg] += wn0; A1[jg] += wn1; B0[ig] += wn0; B1[ig] += wn1;
-            const float Qz = fmaf(T.m[1], wn1, T.m[0] * wn0);
-            const float qzu = Qz * uz;
-            a1 = fmaf(qzu, uz, a1);
-            const float cz = T.ahs[2] * qzu;
-            float cs, c1;
-            if constexpr (FGP) {
-                cs = 0.f; c1 = 0.f;
-#pragma unroll
-                for (int kg = 0; kg < NGP; ++kg) {
-                    const float wf = T.w[kg] * w2 * fg[(kg * NGP + jg) * NGP + ig];
-                    cs += wf;
-                    c1 = fmaf(T.b[kg][1], wf, c1);
-                }
-            } else {
-                const float dzf = UF[jg][ig] - LF[jg][ig];
-                const float wf0 = w2 * LF[jg][ig], wf1 = w2 * dzf;
-                cs = fmaf(T.m[1], wf1, T.m[0] * wf0);
-                c1 = fmaf(T.m[2], wf1, T.m[1] * wf0);
-            }
-            a2 = fmaf(cs, LU[jg][ig], a2);
-            a2 = fmaf(c1, dzu, a2);
-            cUU[jg][ig] = fmaf(nb, c1, cz);
-            cUL[jg][ig] = fmaf(nb, cs, -cUU[jg][ig]);
-        }
-    }
-#pragma unroll
-    for (int jg = 0; jg < NGP; ++jg) {
-        const float dv = UX[jg] - LX[jg];
-        float sx = 0.f, tx = 0.f;
-#pragma unroll
-        for (int kg = 0; kg < NGP; ++kg) {
-            const float ux = T.hs[0] * fmaf(T.b[kg][1], dv, LX[jg]);
-            const float Qx = T.w[kg] * fmaf(T.b[kg][1], A1[jg], A0[jg]);
-            const float qxu = Qx * ux;
-            a1 = fmaf(qxu, ux, a1);
-            const float cx = T.ahs[0] * qxu;
-            sx += cx;
-            tx = fmaf(T.b[kg][1], cx, tx);
-        }
-        cXU[jg] = tx;
-        cXL[jg] = sx - tx;
-    }
-#pragma unroll
-    for (int ig = 0; ig < NGP; ++ig) {
-        const float dv = UY[ig] - LY[ig];
-        float sy = 0.f, ty = 0.f;
-#pragma unroll
-        for (int kg = 0; kg < NGP; ++kg) {
-            const float uy = T.hs[1] * fmaf(T.b[kg][1], dv, LY[ig]);
-            const float Qy = T.w[kg] * fmaf(T.b[kg][1], B1[ig], B0[ig]);
-            const float qyu = Qy * uy;
-            a1 = fmaf(qyu, uy, a1);
-            const float cy = T.ahs[1] * qyu;
-            sy += cy;
-            ty = fmaf(T.b[kg][1], cy, ty);
-        }
-        cYU[ig] = ty;
-        cYL[ig] = sy - ty;
-    }
-    e1 = a1;
-    e2 = a2;
-}
-
-// ---------------------------------------------------------------------------------------------
-// 3-D Q1, marching form, second version (fewer instructions).  Differences to q1_layer_3d:
-//   * the coefficient planes arrive WEIGHTED: VNw = w_j w_i nu, VFw = w_j w_i f at the in-plane Gauss points (weights applied
-//     once per plane instead of once per layer, plane and term);
-//   * raw differences are used throughout; 1/h^2, alpha and the user scale are applied once per element (T.kap, T.hs2);
-//   * the cotangents of the lower plane are returned already summed with the carried cotangents of the layer below.
+//   VU[jg][ig] value of u, VX[jg] = lerp_y of the x-differences, VY[ig] = y-difference of the x-lerped rows (all three as raw
+//   differences: 1/h^2, alpha and the user scale are applied once per element, T.kap, T.hs2),
+//   VNw = w_j w_i nu and VFw = w_j w_i f, the coefficient planes WEIGHTED (once per plane instead of once per layer, plane and term).
+// As in 2-D every sum over the z-Gauss points collapses onto the moments of the 1-D rule, and the sums over one in-plane index
+// onto small vectors (per jg and per ig): O(NGP^2) work per element.
 // UW: all weights of the rule are 1 (the exact 2-point rule): weight multiplications vanish at compile time.
 // Outputs: tU/tX/tY = complete cotangents of the LOWER plane's stage values (carry included), cU/cX/cY (in/out) = carried
 // cotangents: in = from the layer below, out = this layer's contribution to the UPPER plane.  e1, e2 without wscale.

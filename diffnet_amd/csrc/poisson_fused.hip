@@ -221,6 +221,21 @@ static Geom2D plan2d(const dn_mesh* m, int P, bool allow_e4 = true, bool chain_o
     return g;
 }
 
+// Strip height of the 16-wide forms: fewest (half-)rounds of resident workgroups (`cap` of them fit the chip) x layers per workgroup -- a
+// workgroup costs its R layers + 1 recomputed seam layer + ~1.5 layers of start-up.  Ties: shorter strips (smaller tail).
+static int strip_height3d(double cap, long long wg_per_strip, int nelz) {
+    double bestc = 1e300;
+    int best = nelz < 1 ? 1 : nelz;
+    for (int R = 4; R <= 64 && R <= (nelz < 4 ? 4 : nelz); ++R) {
+        const int strips = ceil_div(nelz, R);
+        const double rounds = std::max(1.0, std::ceil(2.0 * (double)(wg_per_strip * strips) / cap) / 2.0);
+        const double layers = (strips == 1 ? nelz : R + 1) + 1.5;
+        const double cost = rounds * layers * (1.0 + 0.002 * R);
+        if (cost < bestc) { bestc = cost; best = R; }
+    }
+    return best > nelz ? (nelz < 1 ? 1 : nelz) : best;
+}
+
 static Geom3D plan3d(const dn_mesh* m, bool allow_e2 = false) {
     Geom3D g;
     const int nx = m->nx, ny = m->ny, nelz = m->nz - 1;
@@ -229,26 +244,14 @@ static Geom3D plan3d(const dn_mesh* m, bool allow_e2 = false) {
         g.TX = 16; g.TY = 16; g.E = 2;
         g.chunks = chunks_for(nx / 2, 16);
         g.tiles = chunks_for(ny, 16);
-        const double cap = 256.0 * 3.0;
-        const long long wg_per_strip = (long long)g.chunks * g.tiles * m->batch;
-        double bestc = 1e300;
-        g.R = nelz < 1 ? 1 : nelz;
-        for (int R = 4; R <= 64 && R <= (nelz < 4 ? 4 : nelz); ++R) {
-            const int strips = ceil_div(nelz, R);
-            const double rounds = std::max(1.0, std::ceil(2.0 * (double)(wg_per_strip * strips) / cap) / 2.0);
-            const double layers = (strips == 1 ? nelz : R + 1) + 1.5;
-            const double cost = rounds * layers * (1.0 + 0.002 * R);
-            if (cost < bestc) { bestc = cost; g.R = R; }
-        }
-        if (g.R > nelz) g.R = nelz < 1 ? 1 : nelz;
+        g.R = strip_height3d(256.0 * 3.0, (long long)g.chunks * g.tiles * m->batch, nelz);
         g.strips = ceil_div(nelz, g.R);
         return g;
     }
     if (m->ngp == 2) {
-        // 2 x 2 x 2 points: one element per thread in tiles 16 threads wide (the T16 form of poisson3d_q1w_kernel: DPP hand-over
+        // 2 x 2 x 2 points: one element per thread in tiles 16 threads wide (the T16 form of poisson3d_q1w_kernel: lane-exchange hand-over
         // along x, paired loads, next plane's loads in flight).  Tile height: the multiple of 4 rows (whole waves) that wastes
-        // the fewest thread rows; strip height: fewest (half-)rounds of resident workgroups x layers per workgroup -- a
-        // workgroup costs its R layers + 1 recomputed seam layer + ~1.5 layers of start-up, and 256 CUs hold 5 workgroups each.
+        // the fewest thread rows; 256 CUs hold 5 workgroups of 256 threads each.
         g.TX = 16; g.E = 1;
         g.chunks = chunks_for(nx, 16);
         double best = -1.0;
@@ -259,38 +262,25 @@ static Geom3D plan3d(const dn_mesh* m, bool allow_e2 = false) {
             if (util > best) { best = util; g.TY = TY; g.tiles = tiles; }
         }
         const double cap = 256.0 * 5.0 * (256.0 / (16.0 * g.TY)) ;          // resident workgroups (waves per SIMD bound)
-        const long long wg_per_strip = (long long)g.chunks * g.tiles * m->batch;
-        double bestc = 1e300;
-        g.R = nelz < 1 ? 1 : nelz;
-        for (int R = 4; R <= 64 && R <= (nelz < 4 ? 4 : nelz); ++R) {
-            const int strips = ceil_div(nelz, R);
-            const double rounds = std::max(1.0, std::ceil(2.0 * (double)(wg_per_strip * strips) / cap) / 2.0);
-            const double layers = (strips == 1 ? nelz : R + 1) + 1.5;
-            const double cost = rounds * layers * (1.0 + 0.002 * R);              // ties: shorter strips (smaller tail)
-            if (cost < bestc) { bestc = cost; g.R = R; }
-        }
-        if (g.R > nelz) g.R = nelz < 1 ? 1 : nelz;
+        g.R = strip_height3d(cap, (long long)g.chunks * g.tiles * m->batch, nelz);
         g.strips = ceil_div(nelz, g.R);
         return g;
     }
-    const int maxE = 1;                                  // larger rules: one element per thread (register budget)
+    // larger rules: one element per thread (register budget)
     double best = -1.0;
     g.TX = 16; g.TY = 16; g.E = 1; g.chunks = 1; g.tiles = 1;
     // Tile shape: what counts is the fraction of thread slots doing useful work -- chunks and tiles overlap by one thread
     // column / row and the last ones are partly empty.  Any TX is legal (a wave may span rows); powers of two get a small
     // bonus (measured: equal utilisation runs a few per cent faster with aligned rows).
-    for (int E = 1; E <= maxE; E *= 2) {
-        const int Q = (nx - 1) / E + 1;
-        for (int TX = 8; TX <= 128; ++TX) {
-            const int TY = 256 / TX;
-            if (TX * TY < 192 || TY < 2) continue;
-            const int chunks = chunks_for(Q, TX);
-            const int tiles = chunks_for(ny, TY);
-            const double util = ((double)Q / ((double)chunks * TX)) * ((double)ny / ((double)tiles * TY));
-            const bool pow2 = (TX & (TX - 1)) == 0;
-            const double score = util + 0.05 * E + (pow2 ? 0.04 + 0.0005 * TX : 0.0);
-            if (score > best) { best = score; g.TX = TX; g.TY = TY; g.E = E; g.chunks = chunks; g.tiles = tiles; }
-        }
+    for (int TX = 8; TX <= 128; ++TX) {
+        const int TY = 256 / TX;
+        if (TX * TY < 192 || TY < 2) continue;
+        const int chunks = chunks_for(nx, TX);
+        const int tiles = chunks_for(ny, TY);
+        const double util = ((double)nx / ((double)chunks * TX)) * ((double)ny / ((double)tiles * TY));
+        const bool pow2 = (TX & (TX - 1)) == 0;
+        const double score = util + 0.05 + (pow2 ? 0.04 + 0.0005 * TX : 0.0);      // (0.05: a constant share every candidate has always carried; kept, so that ties round as before)
+        if (score > best) { best = score; g.TX = TX; g.TY = TY; g.chunks = chunks; g.tiles = tiles; }
     }
     // Strip height: >= 2048 workgroups when the mesh allows it, but never fewer than 8 layers per strip (one layer is
     // recomputed per strip, and a workgroup's start-up costs about as much as a layer).

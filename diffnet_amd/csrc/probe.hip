@@ -174,10 +174,7 @@ __global__ void __launch_bounds__(NT) tile_probe_kernel(const float* __restrict_
     constexpr int V = ROWS * 128 / NT + ((ROWS * 128) % NT ? 1 : 0);       // 16-byte vectors per thread and array
     extern __shared__ v4f lds[];                                           // [3][ROWS][128]
     unsigned lid = blockIdx.x;
-    if constexpr (XCD) {        // consecutive tiles (which share halo rows) on the same XCD
-        const unsigned nwg = gridDim.x, xcd = lid & 7u, idx = lid >> 3, base = nwg >> 3, rem = nwg & 7u;
-        lid = xcd * base + min(xcd, rem) + idx;
-    }
+    if constexpr (XCD) lid = xcd_remap(lid, gridDim.x);        // consecutive tiles (which share halo rows) on the same XCD
     const int tile = (int)(lid % (unsigned)tiles), smp = (int)(lid / (unsigned)tiles);
     const long long sbase = (long long)smp * ny * 512;
     const float *pa = a + sbase, *pb = b + sbase, *pc = c + sbase;
