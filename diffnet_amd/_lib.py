@@ -150,6 +150,25 @@ CG_INIT, CG_DOT, CG_UPDATE, CG_DIRECTION = 0, 1, 2, 3
 CG_BREAKDOWN = 1
 
 
+class DnPoissonPcgArgs(C.Structure):
+    _fields_ = [("phase", C.c_int32), ("batch", C.c_int32), ("n", C.c_int64),
+                ("x", C.c_void_p), ("r", C.c_void_p), ("p", C.c_void_p), ("q", C.c_void_p), ("z", C.c_void_p),
+                ("tol", C.c_float), ("atol", C.c_float),
+                ("state", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+PCG_RESID0, PCG_UPDATE, PCG_RZ, PCG_DIRECTION = 0, 1, 2, 3
+
+
+class DnPoissonMgArgs(C.Structure):
+    _fields_ = [("op", C.c_int32), ("nsd", C.c_int32), ("batch", C.c_int32), ("fine", C.c_int32 * 3), ("coarse", C.c_int32 * 3),
+                ("x", C.c_void_p), ("b", C.c_void_p), ("q", C.c_void_p), ("dinv", C.c_void_p), ("dinv_batched", C.c_int32),
+                ("c", C.c_void_p), ("mask", C.c_void_p), ("mask_batched", C.c_int32), ("omega", C.c_float)]
+
+
+MG_RESTRICT, MG_PROLONG, MG_SMOOTH, MG_SMOOTH0 = 0, 1, 2, 3
+
+
 class DnFdmPoissonArgs(C.Structure):
     _fields_ = [("B", C.c_int32), ("ny", C.c_int32), ("nx", C.c_int32),
                 ("u", C.c_void_p), ("nu", C.c_void_p), ("f", C.c_void_p), ("nu_batched", C.c_int32), ("f_batched", C.c_int32),
@@ -245,6 +264,8 @@ SYMBOLS = {
     "dn_poisson_diag": (C.c_int, [C.POINTER(DnMesh), C.POINTER(DnPoissonDiagArgs), C.c_void_p]),
     "dn_poisson_cg_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
     "dn_poisson_cg": (C.c_int, [C.POINTER(DnPoissonCgArgs), C.c_void_p]),
+    "dn_poisson_pcg": (C.c_int, [C.POINTER(DnPoissonPcgArgs), C.c_void_p]),
+    "dn_poisson_mg": (C.c_int, [C.POINTER(DnPoissonMgArgs), C.c_void_p]),
     "dn_fdm_poisson_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "dn_fdm_poisson_apply": (C.c_int, [C.POINTER(DnFdmPoissonArgs), C.c_void_p]),
     "dn_points_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),

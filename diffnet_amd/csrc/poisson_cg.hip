@@ -40,6 +40,16 @@
 // Accesses: 16 bytes per lane in the body.  A sample's base is only 4-byte aligned when n is odd; the quads are then read and written as
 // 4-byte-aligned dwordx4 accesses (the hardware takes them; as in the closed-form kernel's rows of 4 k + 1 nodes), the last < 4 nodes of a
 // sample one by one.  At n = 512^2, B = 1 the launch has 256 workgroups (one per CU); the chunk grows only past 2048 workgroups a sample.
+//
+// dn_poisson_pcg -- the same template for a preconditioner that is a PROCEDURE (z = M r from a multigrid V-cycle, csrc/poisson_mg.hip)
+// rather than a diagonal: the phases above form dinv r inline, these read z from memory.
+//     RESID0     r = -out, rr0 = rr = sum r r, rz = 0, active = rr0 > atol^2, iterations = 0, flags = 0
+//     UPDATE     x += alpha p, r -= alpha q, rr = sum r r, iterations += 1, active = rr > max(tol^2 rr0, atol^2), a NaN rr: BREAKDOWN
+//     RZ         rz' = sum r z, beta = rz' / rz (0 where rz is not positive: the first call after RESID0), rz = rz'
+//     DIRECTION  p = z + beta p (p = z where beta == 0: the first direction does not depend on what p held)
+// between them: the V-cycle on r, and dn_poisson_cg's DOT unchanged.  One sum per phase; the same state block, workspace, chunks,
+// reduction and inactive-sample rule.  Floats per node and iteration beside the operator and the V-cycle: DOT 2, UPDATE 6, RZ 2,
+// DIRECTION 3.
 #include "dn_reduce.h"
 
 namespace dn {
@@ -158,6 +168,7 @@ struct CgParams {
     float* p;
     const float* q;
     const float* dinv;
+    const float* z;                        // the dn_poisson_pcg phases: the preconditioned residual
     int dinv_batched;
     CgState* st;
     unsigned* counter;
@@ -167,16 +178,20 @@ struct CgParams {
     float tol, atol;
 };
 
+// phases of dn_poisson_pcg as values of the same template parameter
+constexpr int PCG_RESID0 = 4, PCG_UPDATE = 5, PCG_RZ = 6, PCG_DIRECTION = 7;
+
 template <int PHASE>
 __global__ void __launch_bounds__(CG_THREADS) poisson_cg_kernel(const CgParams p) {
-    constexpr int NS = PHASE == DN_CG_DOT ? 1 : 2;            // sums of the phase (DIRECTION: none)
+    constexpr int NS = (PHASE == DN_CG_DOT || PHASE >= PCG_RESID0) ? 1 : 2;            // sums of the phase (DIRECTION: none)
     const int tid = threadIdx.x, g = blockIdx.x, b = blockIdx.y;
     __shared__ double red[2 * CG_THREADS / DN_WAVE];
     __shared__ int flag;
 
     CgState* stb = p.st + b;
-    const bool act = PHASE == DN_CG_INIT ? true : stb->active != 0;
-    const float alpha = PHASE == DN_CG_UPDATE ? stb->alpha : 0.f, beta = PHASE == DN_CG_DIRECTION ? stb->beta : 0.f;
+    const bool act = (PHASE == DN_CG_INIT || PHASE == PCG_RESID0) ? true : stb->active != 0;
+    const float alpha = (PHASE == DN_CG_UPDATE || PHASE == PCG_UPDATE) ? stb->alpha : 0.f;
+    const float beta = (PHASE == DN_CG_DIRECTION || PHASE == PCG_DIRECTION) ? stb->beta : 0.f;
     double s0 = 0.0, s1 = 0.0;
 
     if (act) {
@@ -185,7 +200,7 @@ __global__ void __launch_bounds__(CG_THREADS) poisson_cg_kernel(const CgParams p
         float* rb = p.r + base;
         float* pb = p.p + base;
         const float* qb = p.q + base;
-        const float* db = p.dinv + (p.dinv_batched ? base : 0);
+        const float* db = PHASE >= PCG_RESID0 ? p.z + base : p.dinv + (p.dinv_batched ? base : 0);      // the pcg phases read z in dinv's place
         const unsigned c0 = (unsigned)g * (unsigned)p.chunk, c1 = min(c0 + (unsigned)p.chunk, p.n);
 
         // one node of the phase: the same arithmetic in the quads and in the tail
@@ -203,14 +218,27 @@ __global__ void __launch_bounds__(CG_THREADS) poisson_cg_kernel(const CgParams p
                 const float zv = dv * rv;
                 s0 += (double)rv * (double)zv;
                 s1 += (double)rv * (double)rv;
-            } else {
+            } else if constexpr (PHASE == DN_CG_DIRECTION) {
                 pv = fmaf(beta, pv, dv * rv);
+            } else if constexpr (PHASE == PCG_RESID0) {
+                rv = -qv;
+                s0 += (double)rv * (double)rv;
+            } else if constexpr (PHASE == PCG_UPDATE) {
+                xv = fmaf(alpha, pv, xv);
+                rv = fmaf(-alpha, qv, rv);
+                s0 += (double)rv * (double)rv;
+            } else if constexpr (PHASE == PCG_RZ) {
+                s0 += (double)rv * (double)dv;
+            } else {
+                pv = beta == 0.f ? dv : fmaf(beta, pv, dv);
             }
         };
-        constexpr bool RX = PHASE == DN_CG_UPDATE, WX = RX;
-        constexpr bool RR = PHASE == DN_CG_UPDATE || PHASE == DN_CG_DIRECTION, WR = PHASE == DN_CG_INIT || PHASE == DN_CG_UPDATE;
-        constexpr bool RP = PHASE != DN_CG_INIT, WP = PHASE == DN_CG_INIT || PHASE == DN_CG_DIRECTION;
-        constexpr bool RQ = PHASE != DN_CG_DIRECTION, RD = PHASE != DN_CG_DOT;
+        constexpr bool RX = PHASE == DN_CG_UPDATE || PHASE == PCG_UPDATE, WX = RX;
+        constexpr bool RR = RX || PHASE == DN_CG_DIRECTION || PHASE == PCG_RZ, WR = PHASE == DN_CG_INIT || PHASE == PCG_RESID0 || RX;
+        constexpr bool RP = PHASE != DN_CG_INIT && PHASE != PCG_RESID0 && PHASE != PCG_RZ;
+        constexpr bool WP = PHASE == DN_CG_INIT || PHASE == DN_CG_DIRECTION || PHASE == PCG_DIRECTION;
+        constexpr bool RQ = PHASE != DN_CG_DIRECTION && PHASE != PCG_RZ && PHASE != PCG_DIRECTION;
+        constexpr bool RD = PHASE != DN_CG_DOT && PHASE != PCG_RESID0 && PHASE != PCG_UPDATE;      // dinv, or z in the pcg phases
 
         for (unsigned i = c0 + 4u * (unsigned)tid; i < c1; i += CG_QUANTUM) {
             if (i + 4u <= c1) {
@@ -241,7 +269,7 @@ __global__ void __launch_bounds__(CG_THREADS) poisson_cg_kernel(const CgParams p
             }
         }
     }
-    if constexpr (PHASE == DN_CG_DIRECTION) return;
+    if constexpr (PHASE == DN_CG_DIRECTION || PHASE == PCG_DIRECTION) return;
 
     // workgroup sums -> workspace, arrival at the SAMPLE's counters; the sample's last arriver adds its G partials and updates its scalars
     // (the tails of the samples of a batch run side by side, each one memory round trip long)
@@ -304,6 +332,32 @@ __global__ void __launch_bounds__(CG_THREADS) poisson_cg_kernel(const CgParams p
             }
         }
         s->alpha = al;
+    } else if constexpr (PHASE == PCG_RESID0) {
+        const double rr = a[0], at = (double)p.atol * (double)p.atol;
+        s->rz = 0.0;
+        s->rr = rr;
+        s->rr0 = rr;
+        s->pq = 0.0;
+        s->alpha = 0.f;
+        s->beta = 0.f;
+        s->active = rr > at ? 1 : 0;
+        s->iterations = 0;
+        s->flags = rr == rr ? 0 : DN_CG_BREAKDOWN;
+    } else if constexpr (PHASE == PCG_UPDATE) {
+        if (act) {
+            const double rr = a[0];
+            const double tt = (double)p.tol * (double)p.tol * s->rr0, at = (double)p.atol * (double)p.atol;
+            s->rr = rr;
+            s->iterations += 1;
+            s->active = rr > (tt > at ? tt : at) ? 1 : 0;
+            if (!(rr == rr)) s->flags |= DN_CG_BREAKDOWN;
+        }
+    } else if constexpr (PHASE == PCG_RZ) {
+        if (act) {
+            const double rzn = a[0], rz = s->rz;
+            s->beta = rz > 0.0 ? (float)(rzn / rz) : 0.f;
+            s->rz = rzn;
+        }
     } else {
         if (act) {
             const double rzn = a[0], rr = a[NS - 1], rz = s->rz;
@@ -414,6 +468,47 @@ extern "C" int dn_poisson_cg(const dn_poisson_cg_args* a, void* stream) {
         case DN_CG_DOT: hipLaunchKernelGGL(poisson_cg_kernel<DN_CG_DOT>, grid, block, 0, s, pp); break;
         case DN_CG_UPDATE: hipLaunchKernelGGL(poisson_cg_kernel<DN_CG_UPDATE>, grid, block, 0, s, pp); break;
         default: hipLaunchKernelGGL(poisson_cg_kernel<DN_CG_DIRECTION>, grid, block, 0, s, pp); break;
+    }
+    DN_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dn_poisson_pcg(const dn_poisson_pcg_args* a, void* stream) {
+    if (!a) return DN_E_BADARG;
+    if (a->phase < DN_PCG_RESID0 || a->phase > DN_PCG_DIRECTION) return DN_E_BADARG;
+    if (a->n < 1 || a->batch < 1 || a->batch > 65535) return DN_E_BADARG;
+    if (a->n >= (1ll << 30)) return DN_E_UNSUPPORTED;
+    const int ph = a->phase;
+    if (!a->state) return DN_E_BADARG;
+    if ((ph == DN_PCG_RESID0 || ph == DN_PCG_UPDATE) && (!a->r || !a->q)) return DN_E_BADARG;
+    if (ph == DN_PCG_UPDATE && (!a->x || !a->p)) return DN_E_BADARG;
+    if (ph == DN_PCG_RZ && (!a->r || !a->z)) return DN_E_BADARG;
+    if (ph == DN_PCG_DIRECTION && (!a->p || !a->z)) return DN_E_BADARG;
+    if (!(a->tol >= 0.f) || !(a->atol >= 0.f)) return DN_E_BADARG;
+    for (const void* q : {(const void*)a->x, (const void*)a->r, (const void*)a->p, (const void*)a->q, (const void*)a->z})
+        if (reinterpret_cast<uintptr_t>(q) & 15) return DN_E_BADARG;
+    if (reinterpret_cast<uintptr_t>(a->state) & 7) return DN_E_BADARG;
+    if (ph != DN_PCG_DIRECTION) {
+        if (!a->workspace || (reinterpret_cast<uintptr_t>(a->workspace) & 63)) return DN_E_BADARG;
+        if (a->workspace_bytes < dn_poisson_cg_workspace_bytes(a->n, a->batch)) return DN_E_BADARG;
+    }
+
+    CgParams pp = {};
+    pp.x = a->x; pp.r = a->r; pp.p = a->p; pp.q = a->q; pp.z = a->z;
+    pp.st = reinterpret_cast<CgState*>(a->state);
+    pp.counter = reinterpret_cast<unsigned*>(a->workspace);
+    pp.part = a->workspace ? reinterpret_cast<double*>(reinterpret_cast<char*>(a->workspace) + DN_WS_HEADER * a->batch) : nullptr;
+    pp.n = (unsigned)a->n;
+    cg_geometry(a->n, pp.chunk, pp.G);
+    pp.batch = a->batch;
+    pp.tol = a->tol; pp.atol = a->atol;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(pp.G, a->batch), block(CG_THREADS);
+    switch (ph) {
+        case DN_PCG_RESID0: hipLaunchKernelGGL(poisson_cg_kernel<PCG_RESID0>, grid, block, 0, s, pp); break;
+        case DN_PCG_UPDATE: hipLaunchKernelGGL(poisson_cg_kernel<PCG_UPDATE>, grid, block, 0, s, pp); break;
+        case DN_PCG_RZ: hipLaunchKernelGGL(poisson_cg_kernel<PCG_RZ>, grid, block, 0, s, pp); break;
+        default: hipLaunchKernelGGL(poisson_cg_kernel<PCG_DIRECTION>, grid, block, 0, s, pp); break;
     }
     DN_LAUNCH_CHECK();
     return 0;

@@ -1258,6 +1258,103 @@ def poisson_cg_read_state(state):
     return state.cpu().numpy().view(np.dtype(CG_STATE_DTYPE)).reshape(-1)
 
 
+# ---- PCG with a preconditioner that is a procedure (dn_poisson_pcg) and the multigrid transfers / smoother (dn_poisson_mg): raw wrappers
+PCG_PHASES = {"resid0": _lib.PCG_RESID0, "update": _lib.PCG_UPDATE, "rz": _lib.PCG_RZ, "direction": _lib.PCG_DIRECTION}
+MG_OPS = {"restrict": _lib.MG_RESTRICT, "prolong": _lib.MG_PROLONG, "smooth": _lib.MG_SMOOTH, "smooth0": _lib.MG_SMOOTH0}
+
+
+def _flat_f32(t, name, numel, device):
+    t = _require(t, name, None, True)
+    if t.numel() not in (numel if isinstance(numel, tuple) else (numel,)) or t.device != device:
+        raise ValueError(f"{name} has shape {tuple(t.shape)} on {t.device}: expected {numel} float32 values on {device}")
+    return t
+
+
+def poisson_pcg_args(phase, x, r, p, q, z, state, workspace, tol=0.0, atol=0.0):
+    """The argument struct of one dn_poisson_pcg phase on FIXED buffers (include/diffnet_hip.h): the arrays the phase does not use may be
+    None.  state: the (B, 64) block of poisson_cg_state, workspace: poisson_cg_workspace.  Returns (args, keep)."""
+    B = int(state.shape[0])
+    first = next(t for t in (r, p, x, q, z) if t is not None)
+    n = first.numel() // B
+    a = _lib.DnPoissonPcgArgs()
+    a.phase = PCG_PHASES[phase] if isinstance(phase, str) else int(phase)
+    a.batch, a.n = B, n
+    keep = []
+    for name, t in (("x", x), ("r", r), ("p", p), ("q", q), ("z", z)):
+        if t is None:
+            continue
+        setattr(a, name, _flat_f32(t, name, B * n, first.device).data_ptr())
+        keep.append(t)
+    a.tol, a.atol = float(tol), float(atol)
+    if state.dtype != torch.uint8 or state.numel() != B * C.sizeof(_lib.DnCgState) or not state.is_contiguous() or state.device != first.device:
+        raise ValueError("state must be the (B, 64) uint8 block of poisson_cg_state on the arrays' device")
+    a.state = state.data_ptr()
+    keep.append(state)
+    if workspace is not None:
+        a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel()
+        keep.append(workspace)
+    return a, keep
+
+
+def poisson_pcg_launch(args, device):
+    rc = _lib.lib().dn_poisson_pcg(C.byref(args), C.c_void_p(_raw_stream(device)))
+    if rc:
+        _lib.check(rc, "dn_poisson_pcg")
+
+
+def poisson_pcg_phase(phase, x, r, p, q, z, state, workspace, tol=0.0, atol=0.0):
+    """One dn_poisson_pcg phase in place on x, r, p and the state block."""
+    a, keep = poisson_pcg_args(phase, x, r, p, q, z, state, workspace, tol, atol)
+    poisson_pcg_launch(a, state.device)
+
+
+def poisson_mg_args(op, fine_shape, batch, x=None, b=None, q=None, dinv=None, c=None, mask=None, omega=1.0):
+    """The argument struct of one dn_poisson_mg launch on FIXED buffers (include/diffnet_hip.h).  fine_shape: the node shape (memory
+    order, z slowest) of the fine level -- of the only level for "smooth" / "smooth0".  x, b, q, dinv: (B,..) float32 of the fine level
+    (dinv may be (1,..)); c: (B,..) of the coarse level; mask: uint8 image (B|1,..) of the coarse level for "restrict", of the fine
+    level for "prolong".  Returns (args, keep)."""
+    fine_shape = tuple(int(s) for s in fine_shape)
+    nsd, B = len(fine_shape), int(batch)
+    a = _lib.DnPoissonMgArgs()
+    a.op = MG_OPS[op] if isinstance(op, str) else int(op)
+    a.nsd, a.batch = nsd, B
+    coarse_shape = tuple((s - 1) // 2 + 1 for s in fine_shape)
+    for d, (sf, sc) in enumerate(zip(fine_shape[::-1], coarse_shape[::-1])):
+        a.fine[d], a.coarse[d] = sf, sc
+    for d in range(nsd, 3):
+        a.fine[d] = a.coarse[d] = 1
+    nf, nc = math.prod(fine_shape), math.prod(coarse_shape)
+    first = next(t for t in (x, b, c) if t is not None)
+    keep = []
+    for name, t, numel in (("x", x, B * nf), ("b", b, B * nf), ("q", q, B * nf), ("dinv", dinv, (nf, B * nf)), ("c", c, B * nc)):
+        if t is None:
+            continue
+        setattr(a, name, _flat_f32(t, name, numel, first.device).data_ptr())
+        keep.append(t)
+    if dinv is not None:
+        a.dinv_batched = int(dinv.numel() == B * nf and B > 1)
+    if mask is not None:
+        nm = nc if a.op == _lib.MG_RESTRICT else nf
+        if mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() not in (nm, B * nm) or mask.device != first.device:
+            raise ValueError(f"mask must be a contiguous uint8 image of {nm} nodes, shared or per sample, on the arrays' device")
+        a.mask, a.mask_batched = mask.data_ptr(), int(mask.numel() == B * nm and B > 1)
+        keep.append(mask)
+    a.omega = float(omega)
+    return a, keep
+
+
+def poisson_mg_launch(args, device):
+    rc = _lib.lib().dn_poisson_mg(C.byref(args), C.c_void_p(_raw_stream(device)))
+    if rc:
+        _lib.check(rc, "dn_poisson_mg")
+
+
+def poisson_mg(op, fine_shape, batch, **arrays):
+    """One dn_poisson_mg launch (arguments as poisson_mg_args), in place on x (prolong, smooth, smooth0) or c (restrict)."""
+    a, keep = poisson_mg_args(op, fine_shape, batch, **arrays)
+    poisson_mg_launch(a, keep[0].device)
+
+
 class _CoefFn(torch.autograd.Function):
     """(g_nu, g_f) of one dn_poisson_coef_grad launch, differentiable wrt u and v -- the composed route it replaces can be differentiated
     twice, so this one can.  For cotangents (mu, mu_f):  <mu, g_nu> = a_nu <v, K_mu u~>  and  <mu_f, g_f> = a_f <v, M mu_f>  (K_mu the

@@ -6,17 +6,27 @@ One iteration is the fused operator (q = Z K_nu p through a prepared `ops.Poisso
 batch stand still, and nothing of an iteration touches the host but the launches themselves: a chunk of iterations can be captured
 with torch.cuda.graph.
 
-Limits, stated plainly: Q1 meshes only (degree 1, rules of 2 to 4 points), Jacobi preconditioning only (or none).  Float32 CG stalls at
-a relative residual that grows with the condition number of the mesh (README.md quotes measured levels); ask for a `tol` it can reach.
+precondition="multigrid" replaces the diagonal by one geometric multigrid V-cycle per iteration (`_Multigrid` below): the levels are the
+same operator rediscretised on nested meshes of halved element counts (`multigrid_levels`), each a prepared `ops.PoissonPlan` and a
+`dn_poisson_diag`; the transfers and the damped-Jacobi update are `dn_poisson_mg`, and because z = M r now comes from memory the vector
+phases are those of `dn_poisson_pcg`.  The iteration count becomes roughly independent of the mesh; one iteration costs several
+operator launches per level (DESIGN.md section 6 and profiles/poisson_multigrid.txt say where that pays).
+
+Limits, stated plainly: Q1 meshes only (degree 1, rules of 2 to 4 points); Jacobi, multigrid or no preconditioning; multigrid on nested
+meshes only (node counts k 2^(L-1) + 1 per axis with L >= 2: no non-nested coarsening), with a point smoother, so strongly anisotropic
+spacings or coefficient jumps that the coarse meshes cannot see still cost iterations.  Float32 CG stalls at a relative residual that
+grows with the condition number of the mesh (README.md quotes measured levels); ask for a `tol` it can reach.
 """
 import types
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
 from . import _lib, ops
 from ._lib import DiffNetHipError
+from .fem import FemGeometry
 from .ops import Dirichlet, PackedMask
 
 
@@ -26,6 +36,59 @@ def _check_geom(geom):
                               "Jacobi diagonal are written for the Q1 operator")
     if not 2 <= geom.ngp_1d <= 4:
         raise DiffNetHipError(f"PoissonSolver: rules of 2 to 4 points per axis, got {geom.ngp_1d}")
+
+
+def multigrid_levels(geom, max_levels=None):
+    """[(node_shape, hs), ...] of the multigrid levels of a mesh, fine first: node_shape in memory order (as geom.node_shape), hs the
+    spacings (as geom.hs).  A level is coarsened -- element counts halved, spacings doubled -- while every axis has an even element count
+    and the coarse mesh keeps at least 2 elements per axis; at most `max_levels` levels.  Pure: needs no GPU."""
+    if max_levels is not None and int(max_levels) < 1:
+        raise ValueError("mg_max_levels must be at least 1")
+    levels = [(tuple(geom.node_shape), tuple(geom.hs))]
+    while max_levels is None or len(levels) < int(max_levels):
+        shape, hs = levels[-1]
+        nel = [s - 1 for s in shape]
+        if any(e % 2 or e // 2 < 2 for e in nel):
+            break
+        levels.append((tuple(e // 2 + 1 for e in nel), tuple(2.0 * h for h in hs)))
+    return levels
+
+
+def _level_geometry(geom, shape, hs):
+    return FemGeometry(geom.nsd, shape[::-1], hs, geom.deg, geom.ngp_1d, geom.gpx_1d, geom.gpw_1d)
+
+
+def _multigrid_levels_or_raise(geom, max_levels):
+    levels = multigrid_levels(geom, max_levels)
+    if len(levels) < 2:
+        raise DiffNetHipError(f'precondition="multigrid": the mesh of {"x".join(map(str, geom.node_shape))} nodes cannot be coarsened (every axis needs an '
+                              "even element count and 2 elements left on the coarse mesh; non-nested coarsening is not implemented).  Node counts "
+                              'that work: k 2^(L-1) + 1 per axis with k >= 2 and L >= 2 levels, e.g. 129, 257, 385, 513; or use precondition="jacobi"')
+    return levels
+
+
+def element_lambda_max(geom):
+    """lambda_max(D_e^-1 K_e) of one element of the mesh with nu = 1, in float64: an upper bound of lambda_max(D^-1 K) of the assembled
+    constant-coefficient operator (1.5 for square and cubic elements, up to 3 / 4 for stretched ones in 2-D / 3-D) that a variable nu
+    moves by a few per cent (DESIGN.md section 6 lists measured values)."""
+    B = np.asarray(geom.basis, np.float64)[:, :2]
+    D = np.asarray(geom.dbasis, np.float64)[:, :2]
+    w = np.asarray(geom.gpw_1d, np.float64)
+    M1 = np.einsum("g,ga,gc->ac", w, B, B)
+    K = 0.0
+    for d in range(geom.nsd):
+        term = np.ones((1, 1))
+        for ax in range(geom.nsd):
+            term = np.kron(term, np.einsum("g,ga,gc->ac", w, D, D) * (2.0 / geom.hs[d]) ** 2 if ax == d else M1)
+        K = K + term
+    dg = np.diag(K)
+    return float(np.linalg.eigvalsh(K / np.sqrt(np.outer(dg, dg)))[-1])
+
+
+def default_mg_omega(geom):
+    """The damping of the Jacobi smoother when mg_omega is None: (4 / 3) / element_lambda_max -- 8 / 9 on square and cubic elements --
+    so that omega lambda_max(D^-1 K) stays near 4 / 3, well inside the < 2 that keeps the V-cycle positive definite."""
+    return (4.0 / 3.0) / element_lambda_max(geom)
 
 
 def _tensors_of(nu, f, f_gp, u0, dl, load=None):
@@ -39,7 +102,8 @@ class PoissonSolver:
     """Preconditioned CG on FIXED buffers for `batch` samples of one mesh.
 
         solver = PoissonSolver(geom, batch, nu=None, f=None, f_gp=None, dirichlet=(), u0=None, jac=1.0, tol=1e-5, atol=0.0,
-                               maxiter=None, check_every=32, precondition="jacobi")
+                               maxiter=None, check_every=None, precondition="jacobi", mg_sweeps=1, mg_omega=None,
+                               mg_coarse_sweeps=4, mg_max_levels=None)
         solver.setup()        # diagonal + initial residual + INIT; call again after changing nu / f / masks / u0 in place
         solver.iterate(k)     # k iterations: no allocation, no device-to-host copy, no synchronisation (capturable)
         solver.status()       # one synchronising read of the per-sample scalars
@@ -51,16 +115,25 @@ class PoissonSolver:
     The tensors are read in place by every launch (as with `ops.PoissonPlan`): they must be usable as they are.
     u0: the initial guess (B|1,1,*N), zero when None.  tol: relative residual |r| / |r0| at which a sample stops; atol: absolute |r|.
     maxiter: 20 * max(node_shape) when None -- a heuristic for coefficient contrast near 1 (Jacobi-CG needs O(n) iterations on an
-    n-node-wide mesh); `poisson_solve` stops there.  precondition: "jacobi" or None (dinv = 1 on the free nodes).
+    n-node-wide mesh); `poisson_solve` stops there.  precondition: "jacobi", None (dinv = 1 on the free nodes) or "multigrid": one
+    V-cycle per iteration with mg_sweeps damped-Jacobi sweeps before and after each coarse correction (equal, so that M stays symmetric),
+    damping mg_omega (None: `default_mg_omega(geom)`), mg_coarse_sweeps sweeps on the coarsest level, at most mg_max_levels levels; a mesh
+    that `multigrid_levels` cannot coarsen raises DiffNetHipError.  check_every: iterations between the status reads of `solve()`, 32
+    when None (2 with "multigrid", whose iterations are few and dear).
     load: an ASSEMBLED right-hand side (B,1,*N) added to F f (read as zero on the Dirichlet nodes): what the adjoint solve needs.
     phases: "fused" (the dn_poisson_cg kernels) or "composed" (the same recurrences from torch ops on `ops.residual`: a measuring
     stick, about a dozen launches per iteration)."""
 
     def __init__(self, geom, batch, nu=None, f=None, f_gp=None, dirichlet=(), u0=None, jac=1.0, tol=1e-5, atol=0.0, maxiter=None,
-                 check_every=32, precondition="jacobi", load=None, phases="fused", device=None):
+                 check_every=None, precondition="jacobi", load=None, phases="fused", device=None, mg_sweeps=1, mg_omega=None,
+                 mg_coarse_sweeps=4, mg_max_levels=None):
         _check_geom(geom)
-        if precondition not in ("jacobi", None):
-            raise ValueError('precondition must be "jacobi" or None')
+        if precondition not in ("jacobi", "multigrid", None):
+            raise ValueError('precondition must be "jacobi", "multigrid" or None')
+        if precondition == "multigrid":
+            if int(mg_sweeps) < 1 or int(mg_coarse_sweeps) < 1:
+                raise ValueError("mg_sweeps and mg_coarse_sweeps must be at least 1")
+            mg_levels = _multigrid_levels_or_raise(geom, mg_max_levels)
         if phases not in ("fused", "composed"):
             raise ValueError('phases must be "fused" or "composed"')
         self.geom, self.B = geom, int(batch)
@@ -75,7 +148,9 @@ class PoissonSolver:
         self.device = torch.device(device)
         self.jac, self.tol, self.atol = float(jac), float(tol), float(atol)
         self.maxiter = int(maxiter) if maxiter is not None else 20 * max(geom.node_shape)
-        self.check_every = max(1, int(check_every))
+        # iterations between two status() reads of solve(): a read costs about one multigrid iteration on a small mesh and every iteration past
+        # convergence still runs its operator launches and V-cycle on the batch, so multigrid looks often
+        self.check_every = max(1, int(check_every)) if check_every is not None else (2 if precondition == "multigrid" else 32)
         self.precondition, self.phases = precondition, phases
         shape = (self.B, 1, *geom.node_shape)
         self.n = int(np.prod(geom.node_shape))
@@ -87,6 +162,10 @@ class PoissonSolver:
                                       want_sums=False, out=self.q)
         self._plan = ops.PoissonPlan(geom, self.p, nu, None, None, self.homog, alpha=1.0, beta=0.0, c=0.0, wscale=self.jac, want_out=True,
                                      want_sums=False, out=self.q)
+        self.mg = None
+        if precondition == "multigrid":
+            self.z = new()
+            self.mg = _Multigrid(self, mg_levels, int(mg_sweeps), default_mg_omega(geom) if mg_omega is None else float(mg_omega), int(mg_coarse_sweeps))
         if phases == "fused":
             self.state = ops.poisson_cg_state(self.B, self.device)
             self.workspace = ops.poisson_cg_workspace(self.n, self.B, self.device)
@@ -95,6 +174,12 @@ class PoissonSolver:
             fn = _lib.lib().dn_poisson_cg
             refs = [ops.C.byref(self._args[ph][0]) for ph in ("dot", "update", "direction")]
             self._fn, self._refs = fn, refs
+            if self.mg is not None:
+                # z = M r comes from memory: the phases of dn_poisson_pcg around the V-cycle, DOT unchanged
+                pk = lambda ph: ops.poisson_pcg_args(ph, self.x, self.r, self.p, self.q, self.z, self.state, self.workspace, self.tol, self.atol)
+                self._pargs = {ph: pk(ph) for ph in ("resid0", "update", "rz", "direction")}
+                self._pfn = _lib.lib().dn_poisson_pcg
+                self._prefs = {ph: ops.C.byref(a[0]) for ph, a in self._pargs.items()}
         self._ready = False
 
     # -- setup -------------------------------------------------------------------------------------------------------------------
@@ -115,15 +200,21 @@ class PoissonSolver:
             if self.dl:
                 self.x.copy_(ops._apply_dirichlet(self.x, self.dl))
             ops.poisson_diag(self.geom, self.B, self.nu, self.dl, wscale=self.jac, unit=self.precondition is None, out=self.dinv)
+            if self.mg is not None:
+                self.mg.setup()
             self._plan0.launch()
             if self.load is not None:
                 fx = self._fixed()
                 ld = self.load.to(self.device).expand_as(self.q)
                 self.q.sub_(ld if fx is None else torch.where(fx, torch.zeros_like(ld), ld))
-            if self.phases == "fused":
+            if self.phases == "composed":
+                self._composed_init()
+            elif self.mg is None:
                 ops.poisson_cg_launch(self._args["init"][0], self.device)
             else:
-                self._composed_init()
+                s = ops.C.c_void_p(ops._raw_stream(self.device))
+                self._pcg("resid0", s)
+                self._precondition_and_direct(s)
         self._ready = True
         return self
 
@@ -138,6 +229,15 @@ class PoissonSolver:
             return self
         plan, fn, refs = self._plan, self._fn, self._refs
         s = ops.C.c_void_p(ops._raw_stream(self.device))
+        if self.mg is not None:
+            for _ in range(int(k)):
+                plan.launch()
+                rc = fn(refs[0], s)               # DOT
+                if rc:
+                    _lib.check(rc, "dn_poisson_cg")
+                self._pcg("update", s)
+                self._precondition_and_direct(s)
+            return self
         for _ in range(int(k)):
             plan.launch()
             for ref in refs:
@@ -145,6 +245,32 @@ class PoissonSolver:
                 if rc:
                     _lib.check(rc, "dn_poisson_cg")
         return self
+
+    def _pcg(self, phase, s):
+        rc = self._pfn(self._prefs[phase], s)
+        if rc:
+            _lib.check(rc, "dn_poisson_pcg")
+
+    def _precondition_and_direct(self, s):
+        """z = M r (one V-cycle), rz and beta, p = z + beta p."""
+        self.mg.launch(s)
+        self._pcg("rz", s)
+        self._pcg("direction", s)
+
+    def apply_preconditioner(self, r):
+        """z = M r for a (B,1,*N) float32 field r, as a new tensor: dinv r, or one V-cycle.  For inspection and tests; needs setup() and
+        (with "multigrid") overwrites the solver's r, z and q -- call setup() again before iterating."""
+        if not self._ready:
+            raise DiffNetHipError("PoissonSolver.apply_preconditioner: call setup() first")
+        with torch.no_grad():
+            r = r.to(self.device, torch.float32).expand_as(self.x)
+            if self.mg is None:
+                return self.dinv * r
+            if self.phases == "composed":
+                return self.mg.composed(r.contiguous())
+            self.r.copy_(r)
+            self.mg.launch(ops.C.c_void_p(ops._raw_stream(self.device)))
+            return self.z.clone()
 
     def status(self):
         """Per-sample scalars after one synchronising read: iterations (int32), rel_residual = sqrt(rr / rr0), converged, breakdown,
@@ -186,10 +312,13 @@ class PoissonSolver:
     def _dots(self, a, b):
         return (a.double() * b.double()).flatten(1).sum(1)
 
+    def _composed_precondition(self, r):
+        return self.dinv * r if self.mg is None else self.mg.composed(r)
+
     def _composed_init(self):
         r = -self.q
         self.r.copy_(r)
-        self.p.copy_(self.dinv * r)
+        self.p.copy_(self._composed_precondition(r))
         rr = self._dots(r, r)
         at = float(np.float32(self.atol)) ** 2
         z = torch.zeros(self.B, dtype=torch.int32, device=self.device)
@@ -207,7 +336,7 @@ class PoissonSolver:
         okc = col(ok)
         x = torch.where(okc, torch.addcmul(self.x, col(alpha), self.p), self.x)
         r = torch.where(okc, torch.addcmul(self.r, col(-alpha), q), self.r)
-        z = self.dinv * r
+        z = self._composed_precondition(r)
         rzn, rr = self._dots(r, z), self._dots(r, r)
         beta = torch.where(ok, rzn / torch.where(ok, c["rz"], torch.ones_like(pq)), torch.zeros_like(pq)).float()
         thr = torch.clamp(float(np.float32(self.tol)) ** 2 * c["rr0"], min=float(np.float32(self.atol)) ** 2)
@@ -219,6 +348,113 @@ class PoissonSolver:
         self.x.copy_(x)
         self.r.copy_(r)
         self.p.copy_(torch.where(col(still), torch.addcmul(z, col(beta), self.p), self.p))
+
+
+class _Multigrid:
+    """The V-cycle z = M r of a PoissonSolver on FIXED buffers.  Level l is the same operator rediscretised: a FemGeometry with the same
+    rule, element counts halved and spacings doubled l times, wscale = jac 2^(nsd l) (for a constant coefficient that IS the Galerkin
+    product P^T K P), nu injected (every second node; a shared field stays shared, None stays None), the Dirichlet nodes the injection of
+    the union of the fine conditions (one uint8 image per level, shared unless a mask is per sample; the values are homogeneous), dinv
+    from dn_poisson_diag.  Level 0 works on the solver's own r (right-hand side), z (the result), q and dinv.  Everything is prepared here;
+    `launch` only launches; `setup` rebuilds what depends on nu and the masks."""
+
+    def __init__(self, solver, levels, sweeps, omega, coarse_sweeps):
+        s = self.solver = solver
+        geom, B, dev = s.geom, s.B, s.device
+        self.sweeps, self.omega, self.coarse_sweeps = sweeps, omega, coarse_sweeps
+        if not omega > 0:
+            raise ValueError("mg_omega must be positive")
+        nb = 1                                              # batch extent of the Dirichlet images
+        for d in s.dl:
+            m = d.mask
+            nb = max(nb, 1 if isinstance(m, ops.BoxFaces) else int(m.shape[0]))
+        self.levels = []
+        for l, (shape, hs) in enumerate(levels):
+            g = geom if l == 0 else _level_geometry(geom, shape, hs)
+            new = lambda: torch.zeros((B, 1, *shape), dtype=torch.float32, device=dev)
+            L = types.SimpleNamespace(geom=g, shape=shape, wscale=s.jac * 2.0 ** (geom.nsd * l))
+            L.x, L.b, L.q, L.dinv = (s.z, s.r, s.q, s.dinv) if l == 0 else (new(), new(), new(), new())
+            L.img = torch.zeros((nb, 1, *shape), dtype=torch.uint8, device=dev) if s.dl else None
+            L.nu = s.nu if l == 0 or s.nu is None else torch.zeros((s.nu.shape[0], 1, *shape), dtype=torch.float32, device=dev)
+            L.dl = s.homog if l == 0 else ([Dirichlet(L.img, 0.0)] if s.dl else [])
+            L.plan = ops.PoissonPlan(g, L.x, L.nu, None, None, L.dl, alpha=1.0, beta=0.0, c=0.0, wscale=L.wscale, want_out=True,
+                                     want_sums=False, out=L.q)
+            self.levels.append(L)
+        self._fn = _lib.lib().dn_poisson_mg
+        self._keep, self._seq = [], []
+        self._build(0)
+        k1 = torch.tensor([0.5, 1.0, 0.5], device=dev)                 # the composed cycle's transfers: P^T as a stride-2 convolution
+        k2 = k1[:, None] * k1[None, :]
+        self._stencil = (k2 if geom.nsd == 2 else k1[:, None, None] * k2[None])[None, None]
+
+    def _mg(self, op, l, **arrays):
+        L = self.levels[l]
+        a, keep = ops.poisson_mg_args(op, L.shape, self.solver.B, omega=self.omega, **arrays)
+        self._keep.append((a, keep))
+        self._seq.append((1, ops.C.byref(a)))
+
+    def _build(self, l):
+        """The launches of level l and below, in order."""
+        L, last = self.levels[l], l + 1 == len(self.levels)
+        sweep = lambda: (self._seq.append((0, L.plan)), self._mg("smooth", l, x=L.x, b=L.b, q=L.q, dinv=L.dinv))
+        self._mg("smooth0", l, x=L.x, b=L.b, dinv=L.dinv)
+        for _ in range((self.coarse_sweeps if last else self.sweeps) - 1):
+            sweep()
+        if last:
+            return
+        C = self.levels[l + 1]
+        self._seq.append((0, L.plan))
+        self._mg("restrict", l, b=L.b, q=L.q, c=C.b, mask=C.img)
+        self._build(l + 1)
+        self._mg("prolong", l, x=L.x, c=C.x, mask=L.img)
+        for _ in range(self.sweeps):
+            sweep()
+
+    def setup(self):
+        s = self.solver
+        every_second = (slice(None), slice(None)) + (slice(None, None, 2),) * s.geom.nsd
+        for l, L in enumerate(self.levels):
+            if L.img is not None:
+                if l == 0:
+                    fx = s._fixed()
+                    L.img.copy_(fx.to(torch.uint8).expand_as(L.img))
+                else:
+                    L.img.copy_(self.levels[l - 1].img[every_second])
+            if l > 0:
+                if L.nu is not None:
+                    L.nu.copy_(self.levels[l - 1].nu[every_second])
+                ops.poisson_diag(L.geom, s.B, L.nu, L.dl, wscale=L.wscale, out=L.dinv)
+
+    def launch(self, stream):
+        fn = self._fn
+        for kind, what in self._seq:
+            if kind == 0:
+                what.launch()
+            else:
+                rc = fn(what, stream)
+                if rc:
+                    _lib.check(rc, "dn_poisson_mg")
+
+    # -- the same cycle from torch ops (phases="composed"): the measuring stick -------------------------------------------------------
+    def composed(self, r, l=0):
+        L, last = self.levels[l], l + 1 == len(self.levels)
+        s = self.solver
+        free = 1.0 if L.img is None else (L.img == 0).to(torch.float32)
+        conv, convT = (F.conv2d, F.conv_transpose2d) if s.geom.nsd == 2 else (F.conv3d, F.conv_transpose3d)
+        op = lambda x: ops.residual(L.geom, x, L.nu, None, None, L.dl, L.wscale)
+        wd = self.omega * L.dinv
+        x = wd * r
+        for _ in range((self.coarse_sweeps if last else self.sweeps) - 1):
+            x = x + wd * (r - op(x))
+        if last:
+            return x
+        C = self.levels[l + 1]
+        cfree = 1.0 if C.img is None else (C.img == 0).to(torch.float32)
+        bc = cfree * conv(r - op(x), self._stencil, stride=2, padding=1)
+        x = x + free * convT(self.composed(bc, l + 1), self._stencil, stride=2, padding=1)
+        for _ in range(self.sweeps):
+            x = x + wd * (r - op(x))
+        return x
 
 
 def _infer_batch(geom, batch, nu, f, f_gp, u0, dl):
@@ -292,10 +528,11 @@ class _SolveFn(torch.autograd.Function):
 
 
 def poisson_solve(geom, nu=None, f=None, f_gp=None, dirichlet=(), u0=None, batch=None, **options):
-    """(u, info): the discrete solution of the Q1 Poisson problem for a batch, by Jacobi-preconditioned CG on the fused operator.
+    """(u, info): the discrete solution of the Q1 Poisson problem for a batch, by preconditioned CG on the fused operator (Jacobi unless
+    precondition="multigrid").
 
-    Arguments as `PoissonSolver` (options: jac, tol, atol, maxiter, check_every, precondition, phases); batch: taken from the tensors when
-    None.  info: `PoissonSolver.status()` of the last check plus `maxiter` -- look at info.converged: reaching maxiter does not raise.
+    Arguments as `PoissonSolver` (options: jac, tol, atol, maxiter, check_every, precondition, phases, mg_sweeps, mg_omega,
+    mg_coarse_sweeps, mg_max_levels); batch: taken from the tensors when None.  info: `PoissonSolver.status()` of the last check plus `maxiter` -- look at info.converged: reaching maxiter does not raise.
     u is differentiable wrt `nu` and nodal `f` when they require a gradient (implicit differentiation: one more solve with the same
     options and a zero initial guess, then one dn_poisson_coef_grad launch; a shared (1,1,*N) field receives the sum over the
     samples).  There is NO gradient for f_gp, Dirichlet value fields or u0: a DiffNetHipError is raised if one of them requires one."""

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""The discrete solution the Poisson losses converge to, solved directly: batched Jacobi-preconditioned CG on the fused operator
-(diffnet_amd/solve.py, dn_poisson_diag + dn_poisson_cg) instead of an optimiser on the loss.  Q1 meshes only.
+"""The discrete solution the Poisson losses converge to, solved directly: batched preconditioned CG on the fused operator
+(diffnet_amd/solve.py, dn_poisson_diag + dn_poisson_cg; --precondition multigrid: a geometric multigrid V-cycle per iteration,
+dn_poisson_mg + dn_poisson_pcg, on meshes of k 2^(L-1) + 1 nodes per axis) instead of an optimiser on the loss.  Q1 meshes only.
 
-    python examples/poisson_solve.py --case mms [--n 129] [--nsd 2|3] [--precondition jacobi|none] [--tol 1e-5] [--compare lbfgs]
-    python examples/poisson_solve.py --case ibn [--n 33] [--points 2000]
-    python examples/poisson_solve.py --case compliance [--n 65] [--steps 8] [--mode fused|composed]
+    python examples/poisson_solve.py --case mms [--n 129] [--nsd 2|3] [--precondition jacobi|multigrid|none] [--tol 1e-5] [--compare lbfgs]
+    python examples/poisson_solve.py --case ibn [--n 33] [--points 2000] [--precondition jacobi|multigrid]
+    python examples/poisson_solve.py --case compliance [--n 65] [--steps 8] [--mode fused|composed] [--precondition jacobi|multigrid]
 
 mms         the manufactured problems of the reference's e8_2d_poisson_mms.py / e8_3d_poisson_mms.py (u = prod sin(pi x_d), f = nsd pi^2 u,
             u = 0 on the boundary): iterations, relative residual, the calc_l2_err figures, wall time.  --compare lbfgs also runs the
@@ -47,7 +48,7 @@ def run_mms(n=129, nsd=2, precondition="jacobi", tol=1e-5, compare=None, verbose
     f = (nsd * math.pi ** 2 * u_exact)[None, None].float().contiguous().to(dev)
     jac = float(np.prod([0.5 * h for h in m.geom.hs]))
     bc = [(BoxFaces("all"), 0.0)]
-    m.solve(f=f, dirichlet=bc, jac=jac, tol=tol, maxiter=8)              # first-call set-up (kernel load) outside the timing
+    m.solve(f=f, dirichlet=bc, jac=jac, tol=tol, maxiter=8, precondition=precondition)      # first-call set-up (kernel load) outside the timing
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     u, info = m.solve(f=f, dirichlet=bc, jac=jac, tol=tol, precondition=precondition)
@@ -92,7 +93,7 @@ def run_mms(n=129, nsd=2, precondition="jacobi", tol=1e-5, compare=None, verbose
     return out
 
 
-def run_ibn(n=33, npts=2000, tol=1e-5, verbose=True):
+def run_ibn(n=33, npts=2000, tol=1e-5, verbose=True, precondition="jacobi"):
     from ibn_3d_pointcloud import ellipsoid_cloud
     from diffnet_amd.winding import winding_mask
     dev = torch.device("cuda")
@@ -102,7 +103,7 @@ def run_ibn(n=33, npts=2000, tol=1e-5, verbose=True):
     f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))[None].to(dev)      # noqa: E731
     source = winding_mask(f32(pts), f32(nrm), f32(area), nodes)                 # uint8 (1, 1, n, n, n)
     t0 = time.perf_counter()
-    u, info = m.solve(dirichlet=[(source, 1.0), (BoxFaces("all"), 0.0)], tol=tol)
+    u, info = m.solve(dirichlet=[(source, 1.0), (BoxFaces("all"), 0.0)], tol=tol, precondition=precondition)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     energy = float(m.energy_loss(u, None, None, dirichlet=[(source, 1.0), (BoxFaces("all"), 0.0)], c=0.5))
@@ -113,7 +114,7 @@ def run_ibn(n=33, npts=2000, tol=1e-5, verbose=True):
     return dict(converged=bool(info.converged[0]), iterations=int(info.iterations[0]), energy=energy, umin=float(u.min()), umax=float(u.max()))
 
 
-def run_compliance(n=65, steps=8, mode="fused", lr=0.5, verbose=True):
+def run_compliance(n=65, steps=8, mode="fused", lr=0.5, verbose=True, precondition="jacobi"):
     dev = torch.device("cuda")
     m = DiffNet2DFEM(None, None, domain_size=n)
     jac = float(np.prod([0.5 * h for h in m.geom.hs]))
@@ -128,17 +129,19 @@ def run_compliance(n=65, steps=8, mode="fused", lr=0.5, verbose=True):
         opt.zero_grad(set_to_none=True)
         dens = torch.sigmoid(rho)
         nu = 0.001 + dens ** 3
-        u, info = m.solve(nu=nu, f=f, dirichlet=[(sink, 0.0)], jac=jac, tol=1e-5, maxiter=100 * n, phases=mode)
+        u, info = m.solve(nu=nu, f=f, dirichlet=[(sink, 0.0)], jac=jac, tol=1e-5, maxiter=100 * n, phases=mode,
+                          precondition=precondition)
         compliance = (f * u).sum()
         compliance.backward()
         opt.step()
-        hist.append((float(compliance.detach()), float(dens.detach().mean()), int(info.iterations[0]), bool(info.converged[0])))
+        hist.append((float(compliance.detach()), float(dens.detach().mean()), int(info.iterations[0]), bool(info.converged[0]),
+                     int(info.adjoint.iterations[0])))
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     if verbose:
-        for k, (cval, vol, its, ok) in enumerate(hist):
-            print(f"compliance [{mode}] step {k}: sum f u* = {cval:.6f}  volume {vol:.3f}  {its} iterations  converged {ok}")
-        print(f"compliance [{mode}]: {hist[0][0]:.6f} -> {hist[-1][0]:.6f} in {steps} steps, {dt:.2f} s")
+        for k, (cval, vol, its, ok, adj) in enumerate(hist):
+            print(f"compliance [{mode}, {precondition}] step {k}: sum f u* = {cval:.6f}  volume {vol:.3f}  {its} iterations (adjoint {adj})  converged {ok}")
+        print(f"compliance [{mode}, {precondition}]: {hist[0][0]:.6f} -> {hist[-1][0]:.6f} in {steps} steps, {dt:.2f} s")
     return hist
 
 
@@ -147,7 +150,7 @@ if __name__ == "__main__":
     ap.add_argument("--case", choices=("mms", "ibn", "compliance"), default="mms")
     ap.add_argument("--n", type=int, default=None)
     ap.add_argument("--nsd", type=int, default=2)
-    ap.add_argument("--precondition", choices=("jacobi", "none"), default="jacobi")
+    ap.add_argument("--precondition", choices=("jacobi", "multigrid", "none"), default="jacobi")
     ap.add_argument("--tol", type=float, default=1e-5)
     ap.add_argument("--compare", choices=("lbfgs",), default=None)
     ap.add_argument("--points", type=int, default=2000)
@@ -155,8 +158,8 @@ if __name__ == "__main__":
     ap.add_argument("--mode", choices=("fused", "composed"), default="fused")
     a = ap.parse_args()
     if a.case == "mms":
-        run_mms(a.n or 129, a.nsd, None if a.precondition == "none" else "jacobi", a.tol, a.compare)
+        run_mms(a.n or 129, a.nsd, None if a.precondition == "none" else a.precondition, a.tol, a.compare)
     elif a.case == "ibn":
-        run_ibn(a.n or 33, a.points, a.tol)
+        run_ibn(a.n or 33, a.points, a.tol, precondition=None if a.precondition == "none" else a.precondition)
     else:
-        run_compliance(a.n or 65, a.steps, a.mode)
+        run_compliance(a.n or 65, a.steps, a.mode, precondition=None if a.precondition == "none" else a.precondition)

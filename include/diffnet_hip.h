@@ -834,7 +834,8 @@ int dn_poisson_coef_grad(const dn_mesh *mesh, const dn_coef_grad_args *args, voi
 /* ---- batched matrix-free conjugate gradients for the Q1 Poisson problem: the vector side ------------------------------------
  * The reference has no linear solve of its own: it trains on the loss, and where it wants the discrete solution it reaches for outside
  * linear algebra (examples/poisson/single_instance/e8_2d_poisson_mms.py:60-67,143-146 loads an ILU factor from a .mat file).  Together
- * with dn_poisson_apply (q = Z K_nu p: alpha = 1, f absent, homogeneous conditions) these entries are a Jacobi-preconditioned CG solve of
+ * with dn_poisson_apply (q = Z K_nu p: alpha = 1, f absent, homogeneous conditions) these entries are a Jacobi-preconditioned CG solve (with
+ * dn_poisson_pcg and dn_poisson_mg further down: a multigrid-preconditioned one) of
  * Z (K_nu u~ - F f) = 0 for a whole batch without a host round trip per iteration; composed from torch ops an iteration is about a dozen
  * launches and a synchronisation for its scalars.
  *
@@ -902,6 +903,73 @@ typedef struct dn_poisson_cg_args {
 } dn_poisson_cg_args;
 int64_t dn_poisson_cg_workspace_bytes(int64_t n, int32_t batch);
 int dn_poisson_cg(const dn_poisson_cg_args *args, void *stream);
+
+/* dn_poisson_pcg: the vector phases of a PCG iteration whose preconditioner is a PROCEDURE -- z = M r comes from memory (a multigrid
+ * V-cycle, dn_poisson_mg below) where dn_poisson_cg forms dinv r inline.  Same arrays, same dn_cg_state block, same workspace
+ * (dn_poisson_cg_workspace_bytes) and the same reduction and reproducibility rules as dn_poisson_cg.
+ *     DN_PCG_RESID0     (q = the operator's output Z (K x0~ - F f))   r = -q,  rr0 = rr = sum r r,  rz = 0,  active = rr0 > atol^2,
+ *                       iterations = 0,  flags = 0,  alpha = beta = 0                                  -- every sample
+ *     DN_PCG_UPDATE     x += alpha p,  r -= alpha q,  rr = sum r r,  iterations += 1,  active = rr > max(tol^2 rr0, atol^2)
+ *                       (a NaN rr: DN_CG_BREAKDOWN)                                                    -- active samples only
+ *     DN_PCG_RZ         rz' = sum r z,  beta = rz' / rz (0 where rz is not positive: the first call after RESID0),  rz = rz'
+ *     DN_PCG_DIRECTION  p = z + beta p  (p = z where beta == 0, whatever p held)                        -- active samples only
+ * A solve: RESID0, then [z = M r, RZ, DIRECTION] and per iteration the operator launch on p, DN_CG_DOT of dn_poisson_cg (unchanged),
+ * UPDATE, [z = M r, RZ, DIRECTION].  Beside the operator and the preconditioner 13 floats move per node and iteration.
+ * No array of an inactive sample is read or written by any phase but RESID0 and its scalars are left alone; it adds zeros to the sums.
+ * DN_E_BADARG for NULL args, an unknown phase, n < 1, batch outside 1..65535, a NULL or misaligned array the phase uses (r, q: RESID0,
+ * UPDATE; x, p: UPDATE; r, z: RZ; p, z: DIRECTION; state: all), negative or NaN tol / atol, and a missing or too small workspace
+ * (DIRECTION needs none); DN_E_UNSUPPORTED for n >= 2^30.  Nothing is launched then. */
+enum { DN_PCG_RESID0 = 0, DN_PCG_UPDATE = 1, DN_PCG_RZ = 2, DN_PCG_DIRECTION = 3 };
+typedef struct dn_poisson_pcg_args {
+    int32_t phase;         /* DN_PCG_*                                                  */
+    int32_t batch;
+    int64_t n;             /* nodes of one sample                                       */
+    float *x;              /* (B, n) the iterate                                        */
+    float *r;              /* (B, n) the residual of the recurrence                     */
+    float *p;              /* (B, n) the search direction                               */
+    const float *q;        /* (B, n) the operator's output: Z K p (RESID0: Z (K x0~ - F f)) */
+    const float *z;        /* (B, n) the preconditioned residual M r                    */
+    float tol, atol;
+    dn_cg_state *state;    /* (B)                                                       */
+    void *workspace;
+    int64_t workspace_bytes;
+} dn_poisson_pcg_args;
+int dn_poisson_pcg(const dn_poisson_pcg_args *args, void *stream);
+
+/* dn_poisson_mg: the grid transfers and the smoother update of a geometric multigrid V-cycle on nested Q1 meshes, over flat batched
+ * float32 nodal arrays (sample b of a level starts at element b * n_level; array bases 16-byte aligned, a sample's base need not be).
+ * The operator of a level is dn_poisson_apply on that level's mesh, its inverse diagonal dn_poisson_diag.  The fine mesh has
+ * fine[0..2] = (nx, ny, nz) nodes (nz = 1 in 2-D), the coarse mesh coarse[d] = (fine[d] - 1) / 2 + 1 with every fine[d] odd.  P is the
+ * multilinear interpolation coarse -> fine (per axis: a fine node 2 i takes coarse node i, a fine node 2 i + 1 half of i and of i + 1),
+ * Z zeroes the nodes of a level's Dirichlet image (uint8, (B,*N) or (1,*N) with mask_batched = 0, NULL: none).
+ *     DN_MG_RESTRICT  c = Z_c P^T (b - q)    c: coarse (written), b, q: fine, mask: the COARSE level's image.  The fine residual is
+ *                     formed on the fly; per axis the weights are 1/2, 1, 1/2, a neighbour beyond a mesh face is absent (no renormalising)
+ *     DN_MG_PROLONG   x += Z_f P c           x: fine (updated), c: coarse (read), mask: the FINE level's image
+ *     DN_MG_SMOOTH    x += omega dinv (b - q)      x, b, q, dinv: arrays of fine[] nodes; coarse[], c and mask are not read
+ *     DN_MG_SMOOTH0   x  = omega dinv b            the first sweep from a zero guess
+ * Every output node is written by exactly one thread with additions in an order that depends on the node alone, no atomics: the
+ * results are bitwise reproducible and bitwise independent of the batch size and of a sample's place in the batch.
+ * DN_E_BADARG for NULL args, an unknown op, nsd outside {2, 3}, batch outside 1..65535, fewer than 2 nodes on an axis (3 on a fine axis
+ * of a transfer), a coarse shape that does not match the fine one, a NULL or misaligned array the op uses, flags outside {0, 1} and a
+ * NaN omega; DN_E_UNSUPPORTED for samples of 2^30 nodes or more.  Nothing is launched then. */
+enum { DN_MG_RESTRICT = 0, DN_MG_PROLONG = 1, DN_MG_SMOOTH = 2, DN_MG_SMOOTH0 = 3 };
+typedef struct dn_poisson_mg_args {
+    int32_t op;            /* DN_MG_*                                                   */
+    int32_t nsd;           /* 2 or 3                                                    */
+    int32_t batch;
+    int32_t fine[3];       /* nx, ny, nz of the fine (SMOOTH*: the only) level          */
+    int32_t coarse[3];     /* nx, ny, nz of the coarse level (transfers)                */
+    float *x;              /* (B, n_f)  PROLONG, SMOOTH: updated; SMOOTH0: written      */
+    const float *b;        /* (B, n_f)  RESTRICT, SMOOTH, SMOOTH0: the right-hand side  */
+    const float *q;        /* (B, n_f)  RESTRICT, SMOOTH: the operator's output Z K x   */
+    const float *dinv;     /* (B, n_f) or (1, n_f) with dinv_batched = 0: SMOOTH*       */
+    int32_t dinv_batched;
+    float *c;              /* (B, n_c)  RESTRICT: written; PROLONG: read                */
+    const uint8_t *mask;   /* RESTRICT: (B|1, n_c); PROLONG: (B|1, n_f); or NULL        */
+    int32_t mask_batched;
+    float omega;
+} dn_poisson_mg_args;
+int dn_poisson_mg(const dn_poisson_mg_args *args, void *stream);
 
 /* ---- fused 2-D finite-difference Poisson residual, its sums of squares and its gradient ------------------------------------
  * Replaces the loss bodies of the three DiffNetFDM scripts of the reference under examples/poisson/single_instance/:

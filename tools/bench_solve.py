@@ -4,6 +4,10 @@
     python tools/bench_solve.py [--shapes 512x512x1,512x512x16,1025x1025x1,128x128x128x1,256x256x256x1] [--iters 16] [--replays 30]
     python tools/bench_solve.py --trace 512x512x16        # a bare loop of iterations, for `rocprofv3 --kernel-trace --stats -- ...`
     python tools/bench_solve.py --convergence              # time to tol = 1e-5 (mms, CG against L-BFGS), Jacobi on a klsum field, stall level
+    python tools/bench_solve.py --precondition multigrid [--shapes 513x513x16,1025x1025x1,129x129x129x1] [--trace ...] [--convergence]
+                                                           # the same three modes for the multigrid preconditioner (profiles/poisson_multigrid.txt):
+                                                           # one V-cycle and one preconditioned iteration, eager and as a HIP graph, beside one
+                                                           # Jacobi iteration on the same shape; iterations and wall time to tol = 1e-5 against Jacobi
 
 Per shape (nx x ny [x nz] x B; random nu in [0.5, 1.5], random f, u = 0 on the box faces, samples kept active with tol = 0):
   * device time per iteration: `--iters` iterations captured in one HIP graph, replayed `--replays` times after warm-up, timed by device events,
@@ -123,8 +127,85 @@ def bench_shape(sizes, B, iters, replays):
           f"composed eager {comp:8.1f} us = {comp / it[0]:.1f} x", flush=True)
 
 
-def trace(sizes, B, iters=200):
-    s = make_solver(sizes, B).setup()
+def eager_us(body, k=8, reps=5):
+    """median host-clock time of one `body()` out of k in a synchronised loop"""
+    body()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        for _ in range(k):
+            body()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) / k * 1e6)
+    return statistics.median(out)
+
+
+def bench_shape_multigrid(sizes, B, iters, replays):
+    """One V-cycle and one multigrid-preconditioned iteration, eager and captured, beside one Jacobi iteration on the same shape."""
+    name = "x".join(map(str, sizes)) + f" B={B}"
+    s = make_solver(sizes, B, precondition="multigrid").setup()
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    nl, launches = len(s.mg.levels), len(s.mg._seq)
+    s.iterate(2)
+    it_e = eager_us(lambda: s.iterate(1))
+    s.setup()
+    it = graph_median_us(lambda: s.iterate(1), iters, replays)
+    assert s.status().active.all(), "the samples must stay active while they are timed"
+    s.setup()
+    vc_e = eager_us(lambda: s.mg.launch(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    vc = graph_median_us(lambda: s.mg.launch(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), iters, replays)
+    j = make_solver(sizes, B).setup()
+    j.iterate(2)
+    jt_e = eager_us(lambda: j.iterate(1))
+    j.setup()
+    jt = graph_median_us(lambda: j.iterate(1), iters, replays)
+    print(f"{name:>22}: {nl} levels, {launches} launches per V-cycle | V-cycle graph {vc[0]:8.1f} us (min {vc[1]:.1f}, max {vc[2]:.1f}) eager {vc_e:8.1f} | "
+          f"multigrid iteration graph {it[0]:8.1f} us (min {it[1]:.1f}, max {it[2]:.1f}) eager {it_e:8.1f} | "
+          f"Jacobi iteration graph {jt[0]:7.1f} us eager {jt_e:7.1f} | one multigrid iteration = {it[0] / jt[0]:.1f} Jacobi iterations (graph), {it_e / jt_e:.1f} (eager)",
+          flush=True)
+
+
+def timed_solve(label, geom, precondition, **kw):
+    """iterations and wall time of one solve to tol = 1e-5 (after an untimed first call) and the true relative residual at the end"""
+    solve.poisson_solve(geom, precondition=precondition, tol=1e-5, **{**kw, "maxiter": 4})
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    u, info = solve.poisson_solve(geom, precondition=precondition, tol=1e-5, **kw)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    R = ops.residual(geom, u, kw.get("nu"), kw.get("f"), None, kw["dirichlet"], kw["jac"]).double()
+    print(f"  {label} precondition {precondition}: {int(info.iterations[0])} iterations, converged {bool(info.converged[0])}, recurrence "
+          f"{float(info.rel_residual[0]):.3e}, true |R| / |r0| {float(R.norm()) / float(np.sqrt(info.rr0[0])):.3e}, wall {dt * 1e3:.1f} ms", flush=True)
+
+
+def convergence_multigrid():
+    """Iterations and wall time to tol = 1e-5, multigrid against Jacobi: the klsum 257^2 case and the 1025^2 random-coefficient case of
+    profiles/poisson_solve.txt, break-even over the mesh size, the compliance example."""
+    import poisson_solve as ex
+    from diffnet_amd.gen_input_calc import generate_diffusivity_tensor
+    n = 257
+    geom = geometry((n, n))
+    nu = torch.from_numpy(np.ascontiguousarray(generate_diffusivity_tensor([1.2, -0.8, 1.5, 0.6, -1.1, 0.9], n), dtype=np.float32))[None].cuda()
+    jac = float(np.prod([0.5 * h for h in geom.hs]))
+    dl = [(BoxFaces("xlo"), 1.0), (BoxFaces("xhi"), 0.0)]
+    print(f"klsum {n}^2: nu in [{float(nu.min()):.3f}, {float(nu.max()):.3f}]")
+    for pre in ("multigrid", "jacobi"):
+        timed_solve(f"klsum {n}^2", geom, pre, nu=nu, dirichlet=dl, jac=jac, maxiter=40 * n)
+    for n in (33, 65, 129, 257, 513, 1025):
+        geom = geometry((n, n))
+        g = torch.Generator().manual_seed(1)
+        shape = (1, 1, n, n)
+        nu, f = (0.5 + torch.rand(shape, generator=g)).cuda(), torch.randn(shape, generator=g).cuda()
+        jac = float(np.prod([0.5 * h for h in geom.hs]))
+        for pre in ("multigrid", "jacobi"):
+            timed_solve(f"random nu {n}^2", geom, pre, nu=nu, f=f, dirichlet=[(BoxFaces("all"), 0.0)], jac=jac, maxiter=6000)
+    for pre in ("multigrid", "jacobi"):
+        ex.run_compliance(65, 8, "fused", precondition=pre)
+
+
+def trace(sizes, B, iters=200, precondition="jacobi"):
+    s = make_solver(sizes, B, precondition=precondition).setup()
     s.iterate(iters)
     torch.cuda.synchronize()
     print("trace loop done:", "x".join(map(str, sizes)), "B", B, "iterations", iters)
@@ -171,14 +252,16 @@ if __name__ == "__main__":
     ap.add_argument("--replays", type=int, default=30)
     ap.add_argument("--trace", default=None)
     ap.add_argument("--convergence", action="store_true")
+    ap.add_argument("--precondition", choices=("jacobi", "multigrid"), default="jacobi")
     a = ap.parse_args()
+    mg = a.precondition == "multigrid"
     if not torch.cuda.is_available():
         raise SystemExit("bench_solve.py measures on the GPU: no device visible")
     if a.trace:
-        trace(*parse_shape(a.trace))
+        trace(*parse_shape(a.trace), iters=40 if mg else 200, precondition=a.precondition)
     elif a.convergence:
-        convergence()
+        convergence_multigrid() if mg else convergence()
     else:
         print(torch.cuda.get_device_name(0), _lib.lib().dn_build_info().decode())
         for sh in a.shapes.split(","):
-            bench_shape(*parse_shape(sh), a.iters, a.replays)
+            (bench_shape_multigrid if mg else bench_shape)(*parse_shape(sh), a.iters, a.replays)
