@@ -169,6 +169,20 @@ class DnPoissonMgArgs(C.Structure):
 MG_RESTRICT, MG_PROLONG, MG_SMOOTH, MG_SMOOTH0 = 0, 1, 2, 3
 
 
+class DnMgParent(C.Structure):
+    _fields_ = [("j", C.c_int32), ("w0", C.c_float), ("w1", C.c_float), ("pad", C.c_int32)]
+
+
+class DnMgChildren(C.Structure):
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("pad", C.c_int32 * 2), ("w", C.c_float * 4)]
+
+
+class DnPoissonMgTransferArgs(C.Structure):
+    _fields_ = [("op", C.c_int32), ("nsd", C.c_int32), ("batch", C.c_int32), ("fine", C.c_int32 * 3), ("coarse", C.c_int32 * 3),
+                ("x", C.c_void_p), ("b", C.c_void_p), ("q", C.c_void_p), ("c", C.c_void_p), ("mask", C.c_void_p),
+                ("mask_batched", C.c_int32), ("parents", C.c_void_p * 3), ("children", C.c_void_p * 3)]
+
+
 class DnFdmPoissonArgs(C.Structure):
     _fields_ = [("B", C.c_int32), ("ny", C.c_int32), ("nx", C.c_int32),
                 ("u", C.c_void_p), ("nu", C.c_void_p), ("f", C.c_void_p), ("nu_batched", C.c_int32), ("f_batched", C.c_int32),
@@ -266,6 +280,7 @@ SYMBOLS = {
     "dn_poisson_cg": (C.c_int, [C.POINTER(DnPoissonCgArgs), C.c_void_p]),
     "dn_poisson_pcg": (C.c_int, [C.POINTER(DnPoissonPcgArgs), C.c_void_p]),
     "dn_poisson_mg": (C.c_int, [C.POINTER(DnPoissonMgArgs), C.c_void_p]),
+    "dn_poisson_mg_transfer": (C.c_int, [C.POINTER(DnPoissonMgTransferArgs), C.c_void_p]),
     "dn_fdm_poisson_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "dn_fdm_poisson_apply": (C.c_int, [C.POINTER(DnFdmPoissonArgs), C.c_void_p]),
     "dn_points_workspace_bytes": (C.c_int64, [C.POINTER(DnMesh)]),

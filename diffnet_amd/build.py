@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdiffnet_hip.so")
 STAMP = os.path.join(HERE, ".libdiffnet_hip.stamp")
 ARCH = "gfx950"
-SOURCES = ["dn_api.hip", "probe.hip", "poisson_fused.hip", "poisson2d_q1_cf.hip", "poisson2d_q1_g2.hip", "poisson2d_q1_g3.hip", "poisson2d_q1_g4.hip", "poisson3d_q1_g2.hip", "poisson3d_q1_g3.hip", "poisson3d_q1_g4.hip", "poisson3d_q1_cf.hip", "poisson3d_gen.hip", "gauss_pt_eval.hip", "winding.hip", "winding_field.hip", "winding_vjp.hip", "fdm.hip", "instnorm_act.hip", "fsdt.hip", "fsdt_st.hip", "stokes.hip", "navier_stokes.hip", "transport.hip", "strongform.hip", "strongform_q2.hip", "strongform_q3.hip", "fosls.hip", "fosls_q2.hip", "fosls_q3.hip", "helmholtz.hip", "helmholtz_q2.hip", "helmholtz_q3.hip", "eikonal.hip", "eikonal_q2.hip", "eikonal_q3.hip", "eikonal3d.hip", "eikonal3d_g3.hip", "eikonal3d_g4.hip", "poisson_coef_grad.hip", "poisson_cg.hip", "poisson_mg.hip", "fdm_poisson.hip", "point_terms.hip", "upconv_out.hip", "upconv3d_out.hip", "conv3d_wrw.hip", "conv2d_k4s2.hip", "conv2d_k4s2_v2.hip", "conv3d_k4s2.hip", "conv2d_direct.hip"]
+SOURCES = ["dn_api.hip", "probe.hip", "poisson_fused.hip", "poisson2d_q1_cf.hip", "poisson2d_q1_g2.hip", "poisson2d_q1_g3.hip", "poisson2d_q1_g4.hip", "poisson3d_q1_g2.hip", "poisson3d_q1_g3.hip", "poisson3d_q1_g4.hip", "poisson3d_q1_cf.hip", "poisson3d_gen.hip", "gauss_pt_eval.hip", "winding.hip", "winding_field.hip", "winding_vjp.hip", "fdm.hip", "instnorm_act.hip", "fsdt.hip", "fsdt_st.hip", "stokes.hip", "navier_stokes.hip", "transport.hip", "strongform.hip", "strongform_q2.hip", "strongform_q3.hip", "fosls.hip", "fosls_q2.hip", "fosls_q3.hip", "helmholtz.hip", "helmholtz_q2.hip", "helmholtz_q3.hip", "eikonal.hip", "eikonal_q2.hip", "eikonal_q3.hip", "eikonal3d.hip", "eikonal3d_g3.hip", "eikonal3d_g4.hip", "poisson_coef_grad.hip", "poisson_cg.hip", "poisson_mg.hip", "poisson_mg_general.hip", "fdm_poisson.hip", "point_terms.hip", "upconv_out.hip", "upconv3d_out.hip", "conv3d_wrw.hip", "conv2d_k4s2.hip", "conv2d_k4s2_v2.hip", "conv3d_k4s2.hip", "conv2d_direct.hip"]
 HEADERS = ["dn_common.h", "dn_reduce.h", "fsdt_common.h", "flow2d_common.h", "q1_owner_march.h", "q1_owner_march.inl", "elem2d_common.h", "elem2d_march.inl", "elem_args.h", "poisson_elem.h", "poisson_common.h", "poisson2d_q1.inl", "poisson3d_q1.inl", "poisson3d_q1_common.h", "poisson3d_q1_march.inl", os.path.join("..", "..", "include", "diffnet_hip.h")]
 # -amdgpu-sdwa-peephole=0: on gfx950 an SDWA (like a DPP or v_readlane) instruction costs a SIMD ~33 cycles once two or more waves
 # share it -- 14 plain VALU instructions -- so the byte-select forms the peephole creates for mask tests are a large net loss

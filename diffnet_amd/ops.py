@@ -1355,6 +1355,139 @@ def poisson_mg(op, fine_shape, batch, **arrays):
     poisson_mg_launch(a, keep[0].device)
 
 
+# ---- the transfers between meshes that need not be nested (dn_poisson_mg_transfer): the per-axis tables and the raw wrappers
+def mg_general_coarse_shape(fine_shape):
+    """The coarse node shape of dn_poisson_mg_transfer: an axis of e elements keeps ceil(e / 2)."""
+    return tuple(int(s) // 2 + 1 for s in fine_shape)
+
+
+def mg_axis_interpolation(n_src, n_dst):
+    """Linear interpolation from a 1-D mesh of n_src nodes to one of n_dst nodes over the same length, from integers alone: node i of the
+    target lies at the source coordinate i (n_src - 1) / (n_dst - 1) = j + rem / (n_dst - 1) and takes w0 = (n_dst - 1 - rem) / (n_dst - 1)
+    of source node j and w1 = rem / (n_dst - 1) of node j + 1 (the last node: j = n_src - 2, w0 = 0, w1 = 1).  Returns (j int64 (n_dst,),
+    w float32 (n_dst, 2)): each weight is a quotient of integers rounded to float32.  Pure: needs no GPU."""
+    import numpy as np
+    n_src, n_dst = int(n_src), int(n_dst)
+    if n_src < 2 or n_dst < 2:
+        raise ValueError("mg_axis_interpolation: both meshes need at least 2 nodes")
+    num = np.arange(n_dst, dtype=np.int64) * (n_src - 1)
+    j = num // (n_dst - 1)
+    rem = num - j * (n_dst - 1)
+    end = j > n_src - 2
+    j, rem = np.where(end, n_src - 2, j), np.where(end, n_dst - 1, rem)
+    w = np.stack([(n_dst - 1 - rem) / np.float64(n_dst - 1), rem / np.float64(n_dst - 1)], axis=1)
+    return j, w.astype(np.float32)
+
+
+MG_PARENT_DTYPE = [("j", "<i4"), ("w0", "<f4"), ("w1", "<f4"), ("pad", "<i4")]
+MG_CHILDREN_DTYPE = [("first", "<i4"), ("count", "<i4"), ("pad", "<i4", (2,)), ("w", "<f4", (4,))]
+
+
+def mg_axis_tables(nf, nc):
+    """(parents, children) of one axis of dn_poisson_mg_transfer as numpy record arrays (include/diffnet_hip.h: dn_mg_parent,
+    dn_mg_children): the rows and the columns of the same float32 1-D interpolation matrix.  Pure: needs no GPU."""
+    import numpy as np
+    nf, nc = int(nf), int(nc)
+    if nf < 4 or nc != nf // 2 + 1:
+        raise ValueError(f"mg_axis_tables: a fine axis of {nf} nodes (at least 4) has a coarse axis of {nf // 2 + 1} nodes, got {nc}")
+    j, w = mg_axis_interpolation(nc, nf)
+    parents = np.zeros(nf, MG_PARENT_DTYPE)
+    parents["j"], parents["w0"], parents["w1"] = j, w[:, 0], w[:, 1]
+    kids = [[] for _ in range(nc)]
+    for i in range(nf):
+        for t in (0, 1):
+            if w[i, t] != 0:
+                kids[j[i] + t].append((i, w[i, t]))
+    children = np.zeros(nc, MG_CHILDREN_DTYPE)
+    for jc, ks in enumerate(kids):
+        # the children of coarse node jc lie strictly between its coarse neighbours: an open interval of 2 (nf - 1) / (nc - 1) <= 4 fine
+        # spacings (nc - 1 = ceil((nf - 1) / 2)), which holds at most 4 integers -- and they are consecutive
+        first = ks[0][0]
+        assert 1 <= len(ks) <= 4 and [i for i, _ in ks] == list(range(first, first + len(ks))), (nf, nc, jc, ks)
+        children["first"][jc], children["count"][jc] = first, len(ks)
+        children["w"][jc, : len(ks)] = [wt for _, wt in ks]
+    return parents, children
+
+
+def mg_axis_matrix(parents, nc):
+    """The float32 1-D interpolation matrix (nf, nc) that a parents table stands for (numpy)."""
+    import numpy as np
+    P = np.zeros((len(parents), nc), np.float32)
+    rows = np.arange(len(parents))
+    P[rows, parents["j"]] = parents["w0"]
+    P[rows, parents["j"] + 1] += parents["w1"]
+    return P
+
+
+class MgTransferTables:
+    """The per-axis device tables of dn_poisson_mg_transfer for one pair of levels.  fine_shape: node shape in memory order (z slowest);
+    parents / children: lists of uint8 device tensors in the order x, y[, z]; matrices: the float32 1-D interpolation matrices
+    (nf_d, nc_d) in MEMORY order of the axes, as device tensors (what the composed route multiplies by)."""
+
+    def __init__(self, fine_shape, device):
+        import numpy as np
+        self.fine_shape = tuple(int(s) for s in fine_shape)
+        self.coarse_shape = mg_general_coarse_shape(self.fine_shape)
+        self.parents, self.children, mats = [], [], []
+        for nf, nc in zip(self.fine_shape[::-1], self.coarse_shape[::-1]):
+            p, c = mg_axis_tables(nf, nc)
+            self.parents.append(torch.from_numpy(p.view(np.uint8).copy()).to(device))
+            self.children.append(torch.from_numpy(c.view(np.uint8).copy()).to(device))
+            mats.append(torch.from_numpy(mg_axis_matrix(p, nc)).to(device))
+        self.matrices = mats[::-1]
+
+
+def poisson_mg_transfer_args(op, fine_shape, batch, tables, x=None, b=None, q=None, c=None, mask=None):
+    """The argument struct of one dn_poisson_mg_transfer launch on FIXED buffers (include/diffnet_hip.h).  fine_shape: the node shape
+    (memory order, z slowest) of the fine level; tables: the `MgTransferTables` of it; arrays and mask as poisson_mg_args.  Returns
+    (args, keep)."""
+    fine_shape = tuple(int(s) for s in fine_shape)
+    if tables.fine_shape != fine_shape:
+        raise ValueError(f"the tables are those of a fine mesh of {tables.fine_shape} nodes, not {fine_shape}")
+    nsd, B = len(fine_shape), int(batch)
+    coarse_shape = tables.coarse_shape
+    a = _lib.DnPoissonMgTransferArgs()
+    a.op = MG_OPS[op] if isinstance(op, str) else int(op)
+    a.nsd, a.batch = nsd, B
+    for d, (sf, sc) in enumerate(zip(fine_shape[::-1], coarse_shape[::-1])):
+        a.fine[d], a.coarse[d] = sf, sc
+        a.parents[d], a.children[d] = tables.parents[d].data_ptr(), tables.children[d].data_ptr()
+    for d in range(nsd, 3):
+        a.fine[d] = a.coarse[d] = 1
+    nf, nc = math.prod(fine_shape), math.prod(coarse_shape)
+    first = next(t for t in (x, b, c) if t is not None)
+    if tables.parents[0].device != first.device:
+        raise ValueError("the tables live on another device than the arrays")
+    keep = []
+    for name, t, numel in (("x", x, B * nf), ("b", b, B * nf), ("q", q, B * nf), ("c", c, B * nc)):
+        if t is None:
+            continue
+        setattr(a, name, _flat_f32(t, name, numel, first.device).data_ptr())
+        keep.append(t)
+    if mask is not None:
+        nm = nc if a.op == _lib.MG_RESTRICT else nf
+        if mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() not in (nm, B * nm) or mask.device != first.device:
+            raise ValueError(f"mask must be a contiguous uint8 image of {nm} nodes, shared or per sample, on the arrays' device")
+        a.mask, a.mask_batched = mask.data_ptr(), int(mask.numel() == B * nm and B > 1)
+        keep.append(mask)
+    keep.append(tables)
+    return a, keep
+
+
+def poisson_mg_transfer_launch(args, device):
+    rc = _lib.lib().dn_poisson_mg_transfer(C.byref(args), C.c_void_p(_raw_stream(device)))
+    if rc:
+        _lib.check(rc, "dn_poisson_mg_transfer")
+
+
+def poisson_mg_transfer(op, fine_shape, batch, tables=None, **arrays):
+    """One dn_poisson_mg_transfer launch ("restrict" into c, "prolong" onto x); the tables are built when none are given."""
+    first = next(t for t in (arrays.get(k) for k in ("x", "b", "c")) if t is not None)
+    tables = MgTransferTables(fine_shape, first.device) if tables is None else tables
+    a, keep = poisson_mg_transfer_args(op, fine_shape, batch, tables, **arrays)
+    poisson_mg_transfer_launch(a, first.device)
+
+
 class _CoefFn(torch.autograd.Function):
     """(g_nu, g_f) of one dn_poisson_coef_grad launch, differentiable wrt u and v -- the composed route it replaces can be differentiated
     twice, so this one can.  For cotangents (mu, mu_f):  <mu, g_nu> = a_nu <v, K_mu u~>  and  <mu_f, g_f> = a_f <v, M mu_f>  (K_mu the

@@ -9,12 +9,14 @@ with torch.cuda.graph.
 precondition="multigrid" replaces the diagonal by one geometric multigrid V-cycle per iteration (`_Multigrid` below): the levels are the
 same operator rediscretised on nested meshes of halved element counts (`multigrid_levels`), each a prepared `ops.PoissonPlan` and a
 `dn_poisson_diag`; the transfers and the damped-Jacobi update are `dn_poisson_mg`, and because z = M r now comes from memory the vector
-phases are those of `dn_poisson_pcg`.  The iteration count becomes roughly independent of the mesh; one iteration costs several
+phases are those of `dn_poisson_pcg`.  mg_coarsening="general" coarsens meshes that are not nested as well (an axis of e elements keeps
+ceil(e / 2) over the same length); on a level with such an axis the transfers are `dn_poisson_mg_transfer`, which reads the per-axis
+interpolation weights from small tables built here on the host.  The iteration count becomes roughly independent of the mesh; one iteration costs several
 operator launches per level (DESIGN.md section 6 and profiles/poisson_multigrid.txt say where that pays).
 
-Limits, stated plainly: Q1 meshes only (degree 1, rules of 2 to 4 points); Jacobi, multigrid or no preconditioning; multigrid on nested
-meshes only (node counts k 2^(L-1) + 1 per axis with L >= 2: no non-nested coarsening), with a point smoother, so strongly anisotropic
-spacings or coefficient jumps that the coarse meshes cannot see still cost iterations.  Float32 CG stalls at a relative residual that
+Limits, stated plainly: Q1 meshes only (degree 1, rules of 2 to 4 points); Jacobi, multigrid or no preconditioning; multigrid by default
+on nested meshes only (node counts k 2^(L-1) + 1 per axis with L >= 2), with mg_coarsening="general" on any mesh with at least 3 elements
+per axis; a point smoother, so strongly anisotropic spacings or coefficient jumps that the coarse meshes cannot see still cost iterations.  Float32 CG stalls at a relative residual that
 grows with the condition number of the mesh (README.md quotes measured levels); ask for a `tol` it can reach.
 """
 import types
@@ -38,16 +40,30 @@ def _check_geom(geom):
         raise DiffNetHipError(f"PoissonSolver: rules of 2 to 4 points per axis, got {geom.ngp_1d}")
 
 
-def multigrid_levels(geom, max_levels=None):
+def _check_coarsening(coarsening):
+    if coarsening not in ("nested", "general"):
+        raise ValueError('mg_coarsening must be "nested" or "general"')
+
+
+def multigrid_levels(geom, max_levels=None, coarsening="nested"):
     """[(node_shape, hs), ...] of the multigrid levels of a mesh, fine first: node_shape in memory order (as geom.node_shape), hs the
-    spacings (as geom.hs).  A level is coarsened -- element counts halved, spacings doubled -- while every axis has an even element count
-    and the coarse mesh keeps at least 2 elements per axis; at most `max_levels` levels.  Pure: needs no GPU."""
+    spacings (as geom.hs).  coarsening="nested": a level is coarsened -- element counts halved, spacings doubled -- while every axis has
+    an even element count and the coarse mesh keeps at least 2 elements per axis.  "general": while every axis has at least 3 elements;
+    an axis of e elements keeps ceil(e / 2) over the same length (spacing h e / ceil(e / 2)), so an axis with an even count is coarsened
+    exactly as under "nested" and an odd one loses its nesting on that level alone.  At most `max_levels` levels.  Pure: needs no GPU."""
+    _check_coarsening(coarsening)
     if max_levels is not None and int(max_levels) < 1:
         raise ValueError("mg_max_levels must be at least 1")
     levels = [(tuple(geom.node_shape), tuple(geom.hs))]
     while max_levels is None or len(levels) < int(max_levels):
         shape, hs = levels[-1]
         nel = [s - 1 for s in shape]
+        if coarsening == "general":
+            if any(e < 3 for e in nel):
+                break
+            # hs is in the order x, y[, z], the shape in memory order; e / ceil(e / 2) is exactly 2.0 for an even e
+            levels.append((tuple((e + 1) // 2 + 1 for e in nel), tuple(h * (e / ((e + 1) // 2)) for h, e in zip(hs, nel[::-1]))))
+            continue
         if any(e % 2 or e // 2 < 2 for e in nel):
             break
         levels.append((tuple(e // 2 + 1 for e in nel), tuple(2.0 * h for h in hs)))
@@ -58,12 +74,17 @@ def _level_geometry(geom, shape, hs):
     return FemGeometry(geom.nsd, shape[::-1], hs, geom.deg, geom.ngp_1d, geom.gpx_1d, geom.gpw_1d)
 
 
-def _multigrid_levels_or_raise(geom, max_levels):
-    levels = multigrid_levels(geom, max_levels)
+def _multigrid_levels_or_raise(geom, max_levels, coarsening="nested"):
+    levels = multigrid_levels(geom, max_levels, coarsening)
+    if len(levels) < 2 and coarsening == "general":
+        raise DiffNetHipError(f'precondition="multigrid": the mesh of {"x".join(map(str, geom.node_shape))} nodes cannot be coarsened (mg_coarsening="general" '
+                              "needs at least 3 elements on every axis, and mg_max_levels at least 2).  Under the default "
+                              'mg_coarsening="nested" the node counts that work are k 2^(L-1) + 1 per axis; or use precondition="jacobi"')
     if len(levels) < 2:
         raise DiffNetHipError(f'precondition="multigrid": the mesh of {"x".join(map(str, geom.node_shape))} nodes cannot be coarsened (every axis needs an '
-                              "even element count and 2 elements left on the coarse mesh; non-nested coarsening is not implemented).  Node counts "
-                              'that work: k 2^(L-1) + 1 per axis with k >= 2 and L >= 2 levels, e.g. 129, 257, 385, 513; or use precondition="jacobi"')
+                              'even element count and 2 elements left on the coarse mesh under mg_coarsening="nested").  Node counts that work: '
+                              'k 2^(L-1) + 1 per axis with k >= 2 and L >= 2 levels, e.g. 129, 257, 385, 513; mg_coarsening="general" coarsens any '
+                              'mesh with at least 3 elements per axis; or use precondition="jacobi"')
     return levels
 
 
@@ -103,7 +124,7 @@ class PoissonSolver:
 
         solver = PoissonSolver(geom, batch, nu=None, f=None, f_gp=None, dirichlet=(), u0=None, jac=1.0, tol=1e-5, atol=0.0,
                                maxiter=None, check_every=None, precondition="jacobi", mg_sweeps=1, mg_omega=None,
-                               mg_coarse_sweeps=4, mg_max_levels=None)
+                               mg_coarse_sweeps=4, mg_max_levels=None, mg_coarsening="nested")
         solver.setup()        # diagonal + initial residual + INIT; call again after changing nu / f / masks / u0 in place
         solver.iterate(k)     # k iterations: no allocation, no device-to-host copy, no synchronisation (capturable)
         solver.status()       # one synchronising read of the per-sample scalars
@@ -118,7 +139,8 @@ class PoissonSolver:
     n-node-wide mesh); `poisson_solve` stops there.  precondition: "jacobi", None (dinv = 1 on the free nodes) or "multigrid": one
     V-cycle per iteration with mg_sweeps damped-Jacobi sweeps before and after each coarse correction (equal, so that M stays symmetric),
     damping mg_omega (None: `default_mg_omega(geom)`), mg_coarse_sweeps sweeps on the coarsest level, at most mg_max_levels levels; a mesh
-    that `multigrid_levels` cannot coarsen raises DiffNetHipError.  check_every: iterations between the status reads of `solve()`, 32
+    that `multigrid_levels` cannot coarsen raises DiffNetHipError; mg_coarsening: "nested" (node counts k 2^(L-1) + 1 per axis) or "general"
+    (any mesh with at least 3 elements per axis: `multigrid_levels`, `_Multigrid`).  check_every: iterations between the status reads of `solve()`, 32
     when None (2 with "multigrid", whose iterations are few and dear).
     load: an ASSEMBLED right-hand side (B,1,*N) added to F f (read as zero on the Dirichlet nodes): what the adjoint solve needs.
     phases: "fused" (the dn_poisson_cg kernels) or "composed" (the same recurrences from torch ops on `ops.residual`: a measuring
@@ -126,14 +148,15 @@ class PoissonSolver:
 
     def __init__(self, geom, batch, nu=None, f=None, f_gp=None, dirichlet=(), u0=None, jac=1.0, tol=1e-5, atol=0.0, maxiter=None,
                  check_every=None, precondition="jacobi", load=None, phases="fused", device=None, mg_sweeps=1, mg_omega=None,
-                 mg_coarse_sweeps=4, mg_max_levels=None):
+                 mg_coarse_sweeps=4, mg_max_levels=None, mg_coarsening="nested"):
         _check_geom(geom)
+        _check_coarsening(mg_coarsening)
         if precondition not in ("jacobi", "multigrid", None):
             raise ValueError('precondition must be "jacobi", "multigrid" or None')
         if precondition == "multigrid":
             if int(mg_sweeps) < 1 or int(mg_coarse_sweeps) < 1:
                 raise ValueError("mg_sweeps and mg_coarse_sweeps must be at least 1")
-            mg_levels = _multigrid_levels_or_raise(geom, mg_max_levels)
+            mg_levels = _multigrid_levels_or_raise(geom, mg_max_levels, mg_coarsening)
         if phases not in ("fused", "composed"):
             raise ValueError('phases must be "fused" or "composed"')
         self.geom, self.B = geom, int(batch)
@@ -355,7 +378,11 @@ class _Multigrid:
     rule, element counts halved and spacings doubled l times, wscale = jac 2^(nsd l) (for a constant coefficient that IS the Galerkin
     product P^T K P), nu injected (every second node; a shared field stays shared, None stays None), the Dirichlet nodes the injection of
     the union of the fine conditions (one uint8 image per level, shared unless a mask is per sample; the values are homogeneous), dinv
-    from dn_poisson_diag.  Level 0 works on the solver's own r (right-hand side), z (the result), q and dinv.  Everything is prepared here;
+    from dn_poisson_diag.  Under mg_coarsening="general" a level's shape and spacings are those of `multigrid_levels`, wscale =
+    jac prod(hs_l / hs_0), and below a level with an axis of odd element count (`L.tables` is set: the per-axis float32 weights of
+    `ops.MgTransferTables`, read by dn_poisson_mg_transfer and, as dense 1-D matrices, by the composed route) nu is interpolated
+    multilinearly at the coarse nodes and a coarse node is a Dirichlet node where its nearest fine node is one -- both are injection on
+    an axis that is nested; levels whose axes are all nested keep the dn_poisson_mg transfers.  Level 0 works on the solver's own r (right-hand side), z (the result), q and dinv.  Everything is prepared here;
     `launch` only launches; `setup` rebuilds what depends on nu and the masks."""
 
     def __init__(self, solver, levels, sweeps, omega, coarse_sweeps):
@@ -372,7 +399,13 @@ class _Multigrid:
         for l, (shape, hs) in enumerate(levels):
             g = geom if l == 0 else _level_geometry(geom, shape, hs)
             new = lambda: torch.zeros((B, 1, *shape), dtype=torch.float32, device=dev)
-            L = types.SimpleNamespace(geom=g, shape=shape, wscale=s.jac * 2.0 ** (geom.nsd * l))
+            # the level's own Jacobian over the fine one: 2^(nsd l), exactly, while every coarsening so far was nested
+            L = types.SimpleNamespace(geom=g, shape=shape, wscale=s.jac * float(np.prod([hl / h0 for hl, h0 in zip(hs, geom.hs)])))
+            # the transfers to the next level: dn_poisson_mg while every axis is nested, else dn_poisson_mg_transfer and its tables
+            L.tables = None
+            if l + 1 < len(levels) and any((n - 1) % 2 for n in shape):
+                L.tables = ops.MgTransferTables(shape, dev)
+                assert L.tables.coarse_shape == tuple(levels[l + 1][0])
             L.x, L.b, L.q, L.dinv = (s.z, s.r, s.q, s.dinv) if l == 0 else (new(), new(), new(), new())
             L.img = torch.zeros((nb, 1, *shape), dtype=torch.uint8, device=dev) if s.dl else None
             L.nu = s.nu if l == 0 or s.nu is None else torch.zeros((s.nu.shape[0], 1, *shape), dtype=torch.float32, device=dev)
@@ -380,7 +413,7 @@ class _Multigrid:
             L.plan = ops.PoissonPlan(g, L.x, L.nu, None, None, L.dl, alpha=1.0, beta=0.0, c=0.0, wscale=L.wscale, want_out=True,
                                      want_sums=False, out=L.q)
             self.levels.append(L)
-        self._fn = _lib.lib().dn_poisson_mg
+        self._fn, self._tfn = _lib.lib().dn_poisson_mg, _lib.lib().dn_poisson_mg_transfer
         self._keep, self._seq = [], []
         self._build(0)
         k1 = torch.tensor([0.5, 1.0, 0.5], device=dev)                 # the composed cycle's transfers: P^T as a stride-2 convolution
@@ -393,6 +426,15 @@ class _Multigrid:
         self._keep.append((a, keep))
         self._seq.append((1, ops.C.byref(a)))
 
+    def _transfer(self, op, l, **arrays):
+        """RESTRICT from / PROLONG onto level l: the nested kernels, or the general ones where an axis of the level is not nested."""
+        L = self.levels[l]
+        if L.tables is None:
+            return self._mg(op, l, **arrays)
+        a, keep = ops.poisson_mg_transfer_args(op, L.shape, self.solver.B, L.tables, **arrays)
+        self._keep.append((a, keep))
+        self._seq.append((2, ops.C.byref(a)))
+
     def _build(self, l):
         """The launches of level l and below, in order."""
         L, last = self.levels[l], l + 1 == len(self.levels)
@@ -404,9 +446,9 @@ class _Multigrid:
             return
         C = self.levels[l + 1]
         self._seq.append((0, L.plan))
-        self._mg("restrict", l, b=L.b, q=L.q, c=C.b, mask=C.img)
+        self._transfer("restrict", l, b=L.b, q=L.q, c=C.b, mask=C.img)
         self._build(l + 1)
-        self._mg("prolong", l, x=L.x, c=C.x, mask=L.img)
+        self._transfer("prolong", l, x=L.x, c=C.x, mask=L.img)
         for _ in range(self.sweeps):
             sweep()
 
@@ -418,22 +460,52 @@ class _Multigrid:
                 if l == 0:
                     fx = s._fixed()
                     L.img.copy_(fx.to(torch.uint8).expand_as(L.img))
-                else:
+                elif self.levels[l - 1].tables is None:
                     L.img.copy_(self.levels[l - 1].img[every_second])
+                else:
+                    L.img.copy_(self._coarse_image(self.levels[l - 1].img, L.shape))
             if l > 0:
-                if L.nu is not None:
+                if L.nu is not None and self.levels[l - 1].tables is None:
                     L.nu.copy_(self.levels[l - 1].nu[every_second])
+                elif L.nu is not None:
+                    L.nu.copy_(self._coarse_field(self.levels[l - 1].nu, L.shape))
                 ops.poisson_diag(L.geom, s.B, L.nu, L.dl, wscale=L.wscale, out=L.dinv)
 
+    @staticmethod
+    def _coarse_image(img, coarse_shape):
+        """The Dirichlet image of the next level: on each axis the fine node nearest to the coarse node (the lower one of a tie) --
+        injection on a nested axis, and faces map to faces."""
+        for d, nc in enumerate(coarse_shape):
+            nf = img.shape[2 + d]
+            j = torch.arange(nc, device=img.device)
+            img = img.index_select(2 + d, (2 * j * (nf - 1) + (nc - 1)) // (2 * (nc - 1)))
+        return img
+
+    @staticmethod
+    def _coarse_field(nu, coarse_shape):
+        """A nodal coefficient interpolated multilinearly at the nodes of the next level (`ops.mg_axis_interpolation` from the fine to
+        the coarse mesh): injection on a nested axis."""
+        for d, nc in enumerate(coarse_shape):
+            j, w = ops.mg_axis_interpolation(nu.shape[2 + d], nc)
+            j, w = torch.from_numpy(j).to(nu.device), torch.from_numpy(w).to(nu.device)
+            bshape = [1] * nu.dim()
+            bshape[2 + d] = nc
+            nu = w[:, 0].reshape(bshape) * nu.index_select(2 + d, j) + w[:, 1].reshape(bshape) * nu.index_select(2 + d, j + 1)
+        return nu
+
     def launch(self, stream):
-        fn = self._fn
+        fn, tfn = self._fn, self._tfn
         for kind, what in self._seq:
             if kind == 0:
                 what.launch()
-            else:
+            elif kind == 1:
                 rc = fn(what, stream)
                 if rc:
                     _lib.check(rc, "dn_poisson_mg")
+            else:
+                rc = tfn(what, stream)
+                if rc:
+                    _lib.check(rc, "dn_poisson_mg_transfer")
 
     # -- the same cycle from torch ops (phases="composed"): the measuring stick -------------------------------------------------------
     def composed(self, r, l=0):
@@ -450,8 +522,17 @@ class _Multigrid:
             return x
         C = self.levels[l + 1]
         cfree = 1.0 if C.img is None else (C.img == 0).to(torch.float32)
-        bc = cfree * conv(r - op(x), self._stencil, stride=2, padding=1)
-        x = x + free * convT(self.composed(bc, l + 1), self._stencil, stride=2, padding=1)
+        if L.tables is None:
+            bc = cfree * conv(r - op(x), self._stencil, stride=2, padding=1)
+            x = x + free * convT(self.composed(bc, l + 1), self._stencil, stride=2, padding=1)
+        else:
+            # a level that is not nested: the dense 1-D matrices of the kernels' own float32 tables, axis by axis
+            def along_axes(t, transpose):
+                for d, P in enumerate(L.tables.matrices):
+                    t = torch.movedim(torch.tensordot(t, P, dims=([2 + d], [0 if transpose else 1])), -1, 2 + d)
+                return t
+            bc = cfree * along_axes(r - op(x), True)
+            x = x + free * along_axes(self.composed(bc, l + 1), False)
         for _ in range(self.sweeps):
             x = x + wd * (r - op(x))
         return x
@@ -532,7 +613,7 @@ def poisson_solve(geom, nu=None, f=None, f_gp=None, dirichlet=(), u0=None, batch
     precondition="multigrid").
 
     Arguments as `PoissonSolver` (options: jac, tol, atol, maxiter, check_every, precondition, phases, mg_sweeps, mg_omega,
-    mg_coarse_sweeps, mg_max_levels); batch: taken from the tensors when None.  info: `PoissonSolver.status()` of the last check plus `maxiter` -- look at info.converged: reaching maxiter does not raise.
+    mg_coarse_sweeps, mg_max_levels, mg_coarsening); batch: taken from the tensors when None.  info: `PoissonSolver.status()` of the last check plus `maxiter` -- look at info.converged: reaching maxiter does not raise.
     u is differentiable wrt `nu` and nodal `f` when they require a gradient (implicit differentiation: one more solve with the same
     options and a zero initial guess, then one dn_poisson_coef_grad launch; a shared (1,1,*N) field receives the sum over the
     samples).  There is NO gradient for f_gp, Dirichlet value fields or u0: a DiffNetHipError is raised if one of them requires one."""

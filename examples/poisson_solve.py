@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """The discrete solution the Poisson losses converge to, solved directly: batched preconditioned CG on the fused operator
 (diffnet_amd/solve.py, dn_poisson_diag + dn_poisson_cg; --precondition multigrid: a geometric multigrid V-cycle per iteration,
-dn_poisson_mg + dn_poisson_pcg, on meshes of k 2^(L-1) + 1 nodes per axis) instead of an optimiser on the loss.  Q1 meshes only.
+dn_poisson_mg + dn_poisson_pcg, on meshes of k 2^(L-1) + 1 nodes per axis; --coarsening general: on any mesh with at least 3 elements per
+axis, dn_poisson_mg_transfer where a level is not nested) instead of an optimiser on the loss.  Q1 meshes only.
 
-    python examples/poisson_solve.py --case mms [--n 129] [--nsd 2|3] [--precondition jacobi|multigrid|none] [--tol 1e-5] [--compare lbfgs]
+    python examples/poisson_solve.py --case mms [--n 129] [--nsd 2|3] [--precondition jacobi|multigrid|none] [--coarsening nested|general] [--tol 1e-5] [--compare lbfgs]
     python examples/poisson_solve.py --case ibn [--n 33] [--points 2000] [--precondition jacobi|multigrid]
     python examples/poisson_solve.py --case compliance [--n 65] [--steps 8] [--mode fused|composed] [--precondition jacobi|multigrid]
 
@@ -40,7 +41,7 @@ class Mms3D(DiffNet3DFEM):
         return torch.sin(math.pi * x) * torch.sin(math.pi * y) * torch.sin(math.pi * z)
 
 
-def run_mms(n=129, nsd=2, precondition="jacobi", tol=1e-5, compare=None, verbose=True):
+def run_mms(n=129, nsd=2, precondition="jacobi", tol=1e-5, compare=None, verbose=True, coarsening="nested"):
     dev = torch.device("cuda")
     m = (Mms2D if nsd == 2 else Mms3D)(None, None, domain_size=n, nsd=nsd)
     coords = (m.xx, m.yy) if nsd == 2 else (m.xx, m.yy, m.zz)
@@ -48,10 +49,10 @@ def run_mms(n=129, nsd=2, precondition="jacobi", tol=1e-5, compare=None, verbose
     f = (nsd * math.pi ** 2 * u_exact)[None, None].float().contiguous().to(dev)
     jac = float(np.prod([0.5 * h for h in m.geom.hs]))
     bc = [(BoxFaces("all"), 0.0)]
-    m.solve(f=f, dirichlet=bc, jac=jac, tol=tol, maxiter=8, precondition=precondition)      # first-call set-up (kernel load) outside the timing
+    m.solve(f=f, dirichlet=bc, jac=jac, tol=tol, maxiter=8, precondition=precondition, mg_coarsening=coarsening)      # first-call set-up (kernel load) outside the timing
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    u, info = m.solve(f=f, dirichlet=bc, jac=jac, tol=tol, precondition=precondition)
+    u, info = m.solve(f=f, dirichlet=bc, jac=jac, tol=tol, precondition=precondition, mg_coarsening=coarsening)
     torch.cuda.synchronize()
     t_cg = time.perf_counter() - t0
     eL2, uL2, exL2 = (float(v) for v in m._l2_terms(u))                  # the sums of calc_l2_err, without its prints
@@ -93,7 +94,7 @@ def run_mms(n=129, nsd=2, precondition="jacobi", tol=1e-5, compare=None, verbose
     return out
 
 
-def run_ibn(n=33, npts=2000, tol=1e-5, verbose=True, precondition="jacobi"):
+def run_ibn(n=33, npts=2000, tol=1e-5, verbose=True, precondition="jacobi", coarsening="nested"):
     from ibn_3d_pointcloud import ellipsoid_cloud
     from diffnet_amd.winding import winding_mask
     dev = torch.device("cuda")
@@ -103,7 +104,7 @@ def run_ibn(n=33, npts=2000, tol=1e-5, verbose=True, precondition="jacobi"):
     f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))[None].to(dev)      # noqa: E731
     source = winding_mask(f32(pts), f32(nrm), f32(area), nodes)                 # uint8 (1, 1, n, n, n)
     t0 = time.perf_counter()
-    u, info = m.solve(dirichlet=[(source, 1.0), (BoxFaces("all"), 0.0)], tol=tol, precondition=precondition)
+    u, info = m.solve(dirichlet=[(source, 1.0), (BoxFaces("all"), 0.0)], tol=tol, precondition=precondition, mg_coarsening=coarsening)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     energy = float(m.energy_loss(u, None, None, dirichlet=[(source, 1.0), (BoxFaces("all"), 0.0)], c=0.5))
@@ -114,7 +115,7 @@ def run_ibn(n=33, npts=2000, tol=1e-5, verbose=True, precondition="jacobi"):
     return dict(converged=bool(info.converged[0]), iterations=int(info.iterations[0]), energy=energy, umin=float(u.min()), umax=float(u.max()))
 
 
-def run_compliance(n=65, steps=8, mode="fused", lr=0.5, verbose=True, precondition="jacobi"):
+def run_compliance(n=65, steps=8, mode="fused", lr=0.5, verbose=True, precondition="jacobi", coarsening="nested"):
     dev = torch.device("cuda")
     m = DiffNet2DFEM(None, None, domain_size=n)
     jac = float(np.prod([0.5 * h for h in m.geom.hs]))
@@ -130,7 +131,7 @@ def run_compliance(n=65, steps=8, mode="fused", lr=0.5, verbose=True, preconditi
         dens = torch.sigmoid(rho)
         nu = 0.001 + dens ** 3
         u, info = m.solve(nu=nu, f=f, dirichlet=[(sink, 0.0)], jac=jac, tol=1e-5, maxiter=100 * n, phases=mode,
-                          precondition=precondition)
+                          precondition=precondition, mg_coarsening=coarsening)
         compliance = (f * u).sum()
         compliance.backward()
         opt.step()
@@ -151,6 +152,7 @@ if __name__ == "__main__":
     ap.add_argument("--n", type=int, default=None)
     ap.add_argument("--nsd", type=int, default=2)
     ap.add_argument("--precondition", choices=("jacobi", "multigrid", "none"), default="jacobi")
+    ap.add_argument("--coarsening", choices=("nested", "general"), default="nested")
     ap.add_argument("--tol", type=float, default=1e-5)
     ap.add_argument("--compare", choices=("lbfgs",), default=None)
     ap.add_argument("--points", type=int, default=2000)
@@ -158,8 +160,8 @@ if __name__ == "__main__":
     ap.add_argument("--mode", choices=("fused", "composed"), default="fused")
     a = ap.parse_args()
     if a.case == "mms":
-        run_mms(a.n or 129, a.nsd, None if a.precondition == "none" else a.precondition, a.tol, a.compare)
+        run_mms(a.n or 129, a.nsd, None if a.precondition == "none" else a.precondition, a.tol, a.compare, coarsening=a.coarsening)
     elif a.case == "ibn":
-        run_ibn(a.n or 33, a.points, a.tol, precondition=None if a.precondition == "none" else a.precondition)
+        run_ibn(a.n or 33, a.points, a.tol, precondition=None if a.precondition == "none" else a.precondition, coarsening=a.coarsening)
     else:
-        run_compliance(a.n or 65, a.steps, a.mode, precondition=None if a.precondition == "none" else a.precondition)
+        run_compliance(a.n or 65, a.steps, a.mode, precondition=None if a.precondition == "none" else a.precondition, coarsening=a.coarsening)

@@ -971,6 +971,50 @@ typedef struct dn_poisson_mg_args {
 } dn_poisson_mg_args;
 int dn_poisson_mg(const dn_poisson_mg_args *args, void *stream);
 
+/* dn_poisson_mg_transfer: DN_MG_RESTRICT and DN_MG_PROLONG of dn_poisson_mg between meshes that need not be nested -- an axis of e
+ * elements is coarsened to ceil(e / 2) elements over the same length: coarse[d] = ceil((fine[d] - 1) / 2) + 1, which is fine[d] / 2 + 1 in
+ * integers, every fine[d] >= 4. Arrays, masks and the two operations' meaning as in dn_poisson_mg; P is the multilinear interpolation between the
+ * two meshes, the tensor product of per-axis matrices that the CALLER supplies as device tables (16-byte aligned), both views of the
+ * same float32 numbers so that RESTRICT is the transpose of PROLONG exactly:
+ *     parents[d]   fine[d] entries: fine node i of axis d takes w0 of coarse node j and w1 of coarse node j + 1 (0 <= j <= coarse[d] - 2)
+ *     children[d]  coarse[d] entries: coarse node j receives w[t] of fine node first + t for t < count (count <= 4; w[t] = 0 beyond)
+ * With n_f = fine[d] and n_c = coarse[d], fine node i lies at the coarse coordinate i (n_c - 1) / (n_f - 1): j = floor of it,
+ * rem = i (n_c - 1) - j (n_f - 1), w0 = (n_f - 1 - rem) / (n_f - 1), w1 = rem / (n_f - 1), each rounded once to float32 on the host
+ * (the last fine node: j = n_c - 2, w0 = 0, w1 = 1).  On an axis with an even element count these are the weights of dn_poisson_mg;
+ * one launch may mix such axes with others.  The kernels clamp every index they read from a table into the mesh, so a wrong table
+ * gives wrong numbers, not a wrong address -- but the tables must have fine[d] and coarse[d] entries.
+ * Same guarantees: one thread per written node, additions in an order that depends on the node alone (z, then y, then x), no atomics,
+ * no workspace; bitwise reproducible and independent of the batch size.
+ * DN_E_BADARG for NULL args, an op other than the two transfers, nsd outside {2, 3}, batch outside 1..65535, a fine axis of fewer than
+ * 4 nodes, a coarse extent other than fine[d] / 2 + 1, a NULL or misaligned table or array the op uses, mask_batched outside {0, 1}
+ * and samples of 2^30 nodes or more.  Nothing is launched then. */
+typedef struct dn_mg_parent {
+    int32_t j;             /* the first parent; the second is j + 1                     */
+    float w0, w1;
+    int32_t pad;
+} dn_mg_parent;
+typedef struct dn_mg_children {
+    int32_t first, count;  /* fine nodes first .. first + count - 1                     */
+    int32_t pad[2];
+    float w[4];
+} dn_mg_children;
+typedef struct dn_poisson_mg_transfer_args {
+    int32_t op;            /* DN_MG_RESTRICT or DN_MG_PROLONG                           */
+    int32_t nsd;           /* 2 or 3                                                    */
+    int32_t batch;
+    int32_t fine[3];       /* nx, ny, nz of the fine level                              */
+    int32_t coarse[3];     /* nx, ny, nz of the coarse level                            */
+    float *x;              /* (B, n_f)  PROLONG: updated                                */
+    const float *b;        /* (B, n_f)  RESTRICT: the right-hand side                   */
+    const float *q;        /* (B, n_f)  RESTRICT: the operator's output Z K x           */
+    float *c;              /* (B, n_c)  RESTRICT: written; PROLONG: read                */
+    const uint8_t *mask;   /* RESTRICT: (B|1, n_c); PROLONG: (B|1, n_f); or NULL        */
+    int32_t mask_batched;
+    const dn_mg_parent *parents[3];      /* per axis x, y, z: fine[d] entries           */
+    const dn_mg_children *children[3];   /* per axis x, y, z: coarse[d] entries         */
+} dn_poisson_mg_transfer_args;
+int dn_poisson_mg_transfer(const dn_poisson_mg_transfer_args *args, void *stream);
+
 /* ---- fused 2-D finite-difference Poisson residual, its sums of squares and its gradient ------------------------------------
  * Replaces the loss bodies of the three DiffNetFDM scripts of the reference under examples/poisson/single_instance/:
  * 12_fdm_mms.py:76-118, 12_klsum_fdm.py:69-111 and 12_klsum_fdm_nbc.py:69-158 -- the two Dirichlet substitutions, six valid 3x3
